@@ -74,8 +74,14 @@ __device__ __forceinline__ f2 fma2(f2 a, f2 b, f2 c)   // per-component fused mu
 #endif
 }
 
-// ggrad record (12 floats / Gaussian): gx gy gA gB gC gop gr gg gb gz - -
-constexpr int kGG = 12;
+// ggrad record (10 doubles / Gaussian): gx gy gA gB gC gop gr gg gb gz.  The blend backward adds every tile's float32 part with a
+// float64 atomic, and the per-Gaussian kernel reads the sums back as float32.  A float64 sum of k float32 parts is exact -- the same
+// for every order the tiles arrive in -- while the parts' exponent span plus log2(k) fits in 29 bits.  When it does not (a large
+// splat over many tiles, parts of opposite sign cancelling), two orders can give float64 sums a few float64 ulps of the summed
+// magnitudes apart, and their float32 roundings differ only when a float32 rounding boundary falls between the two: rare (about
+// 2^-29 relative), not impossible.  With float32 atomics every order-dependent sum differed in its last bits.
+constexpr int kGG = 10;
 constexpr int kDetStride = 10;   // floats per (tile, instance) slot of the deterministic backward
+static_assert(kDetStride <= kGG, "the deterministic reduce writes kDetStride values of a ggrad row");
 
 }  // namespace gsr

@@ -2481,7 +2481,7 @@ __global__ __launch_bounds__(256) void k_bwd_prologue(float4* __restrict__ gg4, 
 // K8: backward blend.  Same staging as the forward; front-to-back replay from the stored totals.  The per-(pixel, Gaussian)
 // contributions are summed over the lane's pixels, reduced across the wave (transposed DPP butterfly), combined across the
 // tile's two waves in LDS and flushed with ONE set of float atomics per (tile, Gaussian) record.
-// ggrad record (12 floats / Gaussian): gx gy gA gB gC gop gr gg gb gz - -   (kGG, blend_common.h)
+// ggrad record (10 doubles / Gaussian): gx gy gA gB gC gop gr gg gb gz   (kGG, blend_common.h)
 // Packed math:  Each lane owns the two vertically adjacent pixels (x, y0) and (x, y0+1);
 // everything per pixel is a float2 so the arithmetic maps to v_pk_mul/add/fma_f32 (two pixels per VALU issue
 // slot).  HAS_DA = false drops the depth / alpha-output terms when those upstream gradients are absent (the
@@ -2494,7 +2494,7 @@ struct BlendBwdArgs {
     const uint32_t* list;
     const Splat* splat;
     const float *bg, *img, *g_color, *g_depth, *g_alpha;
-    float* ggrad;
+    double* ggrad;
     const float* ckpt;
     float* det_part;
     BwdItemHdr* hdr;
@@ -2573,7 +2573,7 @@ __global__ __launch_bounds__(128) void k_blend_bwd2(BlendBwdArgs args_)
     const float* const __restrict__ g_color = ka->g_color;
     const float* const __restrict__ g_depth = ka->g_depth;
     const float* const __restrict__ g_alpha = ka->g_alpha;
-    float* const __restrict__ ggrad = ka->ggrad;
+    double* const __restrict__ ggrad = ka->ggrad;
     const float* const __restrict__ ckpt = ka->ckpt;
     float* const __restrict__ det_part = ka->det_part;
     // ---- next item -------------------------------------------------------------------------------------------------------
@@ -2853,7 +2853,7 @@ __global__ __launch_bounds__(128) void k_blend_bwd2(BlendBwdArgs args_)
                     // deterministic debug mode: the (tile, instance) partial goes to its own slot, k_det_reduce sums a
                     // Gaussian's slots in list order afterwards; default: one coalesced atomic per record row
                     if (det_part) det_part[((size_t)rg.x + (size_t)b * NT + jj) * kDetStride + r] = r < 2 ? v * kLn2 : v;
-                    else if (v != 0.f) atomicAdd(ggrad + (size_t)s_gid[buf][jj] * kGG + r, r < 2 ? v * kLn2 : v);
+                    else if (v != 0.f) atomicAdd(ggrad + (size_t)s_gid[buf][jj] * kGG + r, (double)(r < 2 ? v * kLn2 : v));
                 }
             }
         }
@@ -2924,7 +2924,7 @@ __global__ __launch_bounds__(256) void k_blend_bwd1(BlendBwdArgs args_)
     const float* const __restrict__ g_color = ka->g_color;
     const float* const __restrict__ g_depth = ka->g_depth;
     const float* const __restrict__ g_alpha = ka->g_alpha;
-    float* const __restrict__ ggrad = ka->ggrad;
+    double* const __restrict__ ggrad = ka->ggrad;
     const float* const __restrict__ ckpt = ka->ckpt;
     float* const __restrict__ det_part = ka->det_part;
     // ---- next item -------------------------------------------------------------------------------------------------------
@@ -3161,7 +3161,7 @@ __global__ __launch_bounds__(256) void k_blend_bwd1(BlendBwdArgs args_)
                     // deterministic debug mode: the (tile, instance) partial goes to its own slot, k_det_reduce sums a
                     // Gaussian's slots in list order afterwards; default: one coalesced atomic per record row
                     if (det_part) det_part[((size_t)rg.x + (size_t)b * NT + jj) * kDetStride + r] = r < 2 ? v * kLn2 : v;
-                    else if (v != 0.f) atomicAdd(ggrad + (size_t)s_gid[buf][jj] * kGG + r, r < 2 ? v * kLn2 : v);
+                    else if (v != 0.f) atomicAdd(ggrad + (size_t)s_gid[buf][jj] * kGG + r, (double)(r < 2 ? v * kLn2 : v));
                 }
             }
         }
@@ -3455,12 +3455,22 @@ constexpr int kCamVals = 47;   // viewmatrix 16 + projmatrix 16 + campos 3 + poi
 // PREP >= 0 (with ADAM): "prepare in backward" -- the block also runs the NEXT render's preprocess, at SH degree PREP (the degree
 // this render used, or one above it: `oneupSHdegree` between two steps, /root/reference/scene/gaussian_model_ht.py:193-195), on the
 // parameters it has just updated.  -1 = off.
+// one Gaussian's ggrad row (80 bytes, 16-byte aligned) as the three float4 the derivative chain works on (the last two lanes zero)
+__device__ __forceinline__ void load_ggrad(const double* __restrict__ row, float4& g0, float4& g1, float4& g2)
+{
+    const double2* p = reinterpret_cast<const double2*>(row);
+    const double2 a0 = p[0], a1 = p[1], a2 = p[2], a3 = p[3], a4 = p[4];
+    g0 = make_float4((float)a0.x, (float)a0.y, (float)a1.x, (float)a1.y);
+    g1 = make_float4((float)a2.x, (float)a2.y, (float)a3.x, (float)a3.y);
+    g2 = make_float4((float)a4.x, (float)a4.y, 0.f, 0.f);
+}
+
 template <int DEG, bool RAW, bool CAM, bool ADAM, int PREP>
 __global__ __launch_bounds__(kPreThreads) void k_preprocess_bwd(CamParams cp, int N, const float* means,
                                                                 const float* scales, const float* rots,
                                                                 const float* __restrict__ cov_pre, const float* shs,
                                                                 const float* shs_rest, const float* opac_raw, AdamDev ad,
-                                                                const Splat* __restrict__ splat, const float* __restrict__ ggrad,
+                                                                const Splat* __restrict__ splat, const double* __restrict__ ggrad,
                                                                 float* __restrict__ d_means, float* __restrict__ d_means2d,
                                                                 float* __restrict__ d_opac, float* __restrict__ d_colors,
                                                                 float* __restrict__ d_shs, float* __restrict__ d_shs_rest,
@@ -3527,8 +3537,7 @@ __global__ __launch_bounds__(kPreThreads) void k_preprocess_bwd(CamParams cp, in
     float e_ds[3] = {0.f, 0.f, 0.f}, e_m2dn = 0.f;
     if constexpr (ADAM) {
         if (i < N) {
-            const float4* gp = reinterpret_cast<const float4*>(ggrad + (size_t)i * kGG);
-            e_g0 = gp[0]; e_g1 = gp[1]; e_g2 = gp[2];
+            load_ggrad(ggrad + (size_t)i * kGG, e_g0, e_g1, e_g2);
 #pragma unroll
             for (int k = 0; k < 3; k++) { e_mean[k] = means[3 * (size_t)i + k]; e_sc[k] = scales[3 * (size_t)i + k]; }
 #pragma unroll
@@ -3590,8 +3599,8 @@ __global__ __launch_bounds__(kPreThreads) void k_preprocess_bwd(CamParams cp, in
         // the zeros of the memset and every gradient below would come out zero -- so "row is non-zero" replaces the
         // radius > 0 test, and the 48-byte splat record is not read by this kernel at all (the activated opacity the
         // sigmoid chain needs is recomputed from the logit exactly as the forward computed it).
-        const float4* gp = reinterpret_cast<const float4*>(ggrad + (size_t)i * kGG);
-        const float4 g0 = ADAM ? e_g0 : gp[0], g1 = ADAM ? e_g1 : gp[1], g2 = ADAM ? e_g2 : gp[2];   // gx gy gA gB | gC gop gr gg | gb gz - -
+        float4 g0 = e_g0, g1 = e_g1, g2 = e_g2;   // gx gy gA gB | gC gop gr gg | gb gz - -
+        if constexpr (!ADAM) load_ggrad(ggrad + (size_t)i * kGG, g0, g1, g2);
         const bool live = g0.x != 0.f || g0.y != 0.f || g0.z != 0.f || g0.w != 0.f || g1.x != 0.f || g1.y != 0.f || g1.z != 0.f ||
                           g1.w != 0.f || g2.x != 0.f || g2.y != 0.f;
         if (live) {
@@ -3939,7 +3948,7 @@ __global__ __launch_bounds__(256) void k_det_iota(uint32_t R, uint32_t* __restri
     if (i < R) { pos[i] = i; ids[i] = min(list[i], n_gaussians - 1u); }
 }
 __global__ __launch_bounds__(256) void k_det_reduce(uint32_t R, const uint32_t* __restrict__ gid_sorted, const uint32_t* __restrict__ pos_sorted,
-                                                    const float* __restrict__ part, float* __restrict__ ggrad)
+                                                    const float* __restrict__ part, double* __restrict__ ggrad)
 {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     if (i >= R) return;
@@ -3956,7 +3965,7 @@ __global__ __launch_bounds__(256) void k_det_reduce(uint32_t R, const uint32_t* 
         for (int r = 0; r < kDetStride; r++) acc[r] += (double)p[r];
     }
 #pragma unroll
-    for (int r = 0; r < kDetStride; r++) ggrad[(size_t)g * kGG + r] = (float)acc[r];
+    for (int r = 0; r < kDetStride; r++) ggrad[(size_t)g * kGG + r] = acc[r];
 }
 
 // one block per camera entry (and, batched, per model: blockIdx.y, over that model's blocks): deterministic sum of the partials
@@ -4274,7 +4283,7 @@ size_t gsr_binning_scratch_bytes(int64_t R) { return bin_scratch_layout(R).bytes
 size_t gsr_backward_scratch_bytes(int32_t N)
 {
     const size_t n = (size_t)(N > 0 ? N : 1);
-    return align256(n * kGG * 4) + align256(((n + kPreThreads - 1) / kPreThreads) * kCamVals * 4);
+    return align256(n * kGG * sizeof(double)) + align256(((n + kPreThreads - 1) / kPreThreads) * kCamVals * 4);
 }
 size_t gsr_sort_scratch_bytes(uint32_t n) { return radix_scratch_bytes(n); }
 size_t gsr_prepared_bytes(int32_t N) { return prep_layout(N).bytes; }
@@ -5061,7 +5070,7 @@ int gsr_backward(const GsrBackwardArgs* a, void* stream_)
     const uint8_t* bin = static_cast<const uint8_t*>(a->binning);
     const uint2* ranges = reinterpret_cast<const uint2*>(bin + B.ranges);
     const uint32_t* list = reinterpret_cast<const uint32_t*>(bin + B.list);
-    float* gg = static_cast<float*>(a->scratch);
+    double* gg = static_cast<double*>(a->scratch);
     // (round 3, measured and dropped: the extension allocating this scratch in the FORWARD and clearing it on a side stream behind
     //  an event, so that the 8 us fill runs next to the forward's kernels instead of in front of the backward's -- 0.863-0.873 ms per
     //  step against 0.847-0.855 with the fill here, same box: the concurrent fill takes more from the sorts than it saves)
@@ -5083,7 +5092,7 @@ int gsr_backward(const GsrBackwardArgs* a, void* stream_)
         const int tpad = 8 * slots_per_xcd(f_map, T, tiles_x);
         const int want_split = g_bwd_split ? g_bwd_split : 16;
         const int split_ok = (want_split > 1 && f_ppt >= 5) ? 1 : 0;
-        const size_t n4 = (size_t)N * kGG / 4;
+        const size_t n4 = (size_t)N * kGG * sizeof(double) / sizeof(float4);
         int fill_blocks = (int)std::min<size_t>(4096, (n4 + 255) / 256);
         if (blend_items) {
             // (the binning buffer is this library's workspace: the item lists live behind the checkpoints, see bin_layout)
@@ -5150,7 +5159,7 @@ int gsr_backward(const GsrBackwardArgs* a, void* stream_)
     CamParams cp = {a->viewmatrix, a->projmatrix, a->campos, a->tanfovx, a->tanfovy, a->scale_modifier, W, H, a->D, a->M, a->points_transform, bt};
     const int grid = (N + kPreThreads - 1) / kPreThreads;
     const bool want_cam = a->d_viewmatrix || a->d_projmatrix || a->d_campos || a->d_points_transform;
-    float* cam_partial = reinterpret_cast<float*>(static_cast<uint8_t*>(a->scratch) + align256((size_t)N * kGG * 4));
+    float* cam_partial = reinterpret_cast<float*>(static_cast<uint8_t*>(a->scratch) + align256((size_t)N * kGG * sizeof(double)));
     AdamDev ad = {};
     const GsrFusedAdam* fa = a->fused_adam;
     if (fa) {

@@ -4,8 +4,7 @@ The reference's `CF3DGS_Render` / `HTGaussianModel` / `Camera` (/root/reference/
 /root/reference/scene/cameras.py:17-98) import lietorch, plyfile and the dataset stack, none of which exists in this image or on the
 GPU box; these classes carry exactly the ATTRIBUTES the render wrapper and the train step read from them -- no behaviour of their own
 beyond the reference's one-line activations -- so that the patched method can be driven the way the unmodified trainer drives it
-(/root/reference/trainer/ht3dgs_trainer.py:102-166).  tests/helpers/ref_render_driver.py runs the same method on the real classes
-in the authoring container.
+(/root/reference/trainer/ht3dgs_trainer.py:102-166).
 """
 import math
 

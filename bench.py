@@ -112,7 +112,51 @@ def parse():
     ap.add_argument("--tile-map", type=int, default=-1, help="2 = 2x2 tile blocks interleaved over the XCDs (default), 1 = single tiles "
                     "interleaved, 0 = one band of tiles per XCD")
     ap.add_argument("--sort-algo", type=int, default=-1, help="2 = onesweep for both sorts (default), 1 = onesweep depth sort only, 0 = hist+scan+scatter per pass")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last timed step computed "
+                    "(loss, render, depth, alpha, radii and the updated parameters; fixed seeded samples of the large ones) as DIR/<name>.npy "
+                    "(rank 0; float32 / float64, at most 64 MB in all)")
     return ap.parse_args()
+
+
+DUMP_MAX_ROWS = 1 << 16        # per-Gaussian arrays: a fixed seeded sample of this many Gaussians
+DUMP_MAX_PIXELS = 1 << 21      # per-pixel arrays: the whole image up to 2 Mpixel (1920x1080 included), a fixed seeded sample above
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, pkg, params, densifier):
+    """What the last timed step handed its caller -- train_step's package (loss, raw render, depth, alpha, radii) and the model it
+    updated in place (the six raw parameter tensors after the fused Adam step; the densification statistics when they are
+    collected) -- as float32 / float64 .npy files.  Large arrays are cut to a fixed sample drawn from a seeded generator, so that two
+    runs with the same arguments write the same elements."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+
+    def sample(n, k, seed):
+        if n <= k:
+            return None
+        return torch.randperm(n, generator=torch.Generator().manual_seed(seed))[:k].sort().values
+
+    n = int(params._xyz.shape[0])
+    rows = sample(n, DUMP_MAX_ROWS, 0)
+    H, W = int(pkg["raw_image"].shape[-2]), int(pkg["raw_image"].shape[-1])
+    pix = sample(H * W, DUMP_MAX_PIXELS, 1)
+    arrays = {"loss": pkg["loss"].reshape(1)}
+    for k in ("raw_image", "depth", "alpha"):
+        a = pkg[k].detach()
+        arrays[k] = a if pix is None else a.reshape(a.shape[0], H * W)[:, pix.to(a.device)]
+    per_gaussian = {"radii": pkg["radii"], **{"param" + k: v for k, v in params.raw().items()}}
+    if densifier is not None:
+        per_gaussian.update(xyz_gradient_accum=densifier.xyz_gradient_accum, denom=densifier.denom, max_radii2D=densifier.max_radii2D)
+    for k, v in per_gaussian.items():
+        arrays[k] = v.detach() if rows is None else v.detach()[rows.to(v.device)]
+    host = {k: v.cpu().numpy() for k, v in arrays.items()}
+    host = {k: a.astype(np.float64 if a.dtype in (np.float64, np.int64) else np.float32) for k, a in host.items()}
+    total = sum(a.nbytes for a in host.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes, more than {DUMP_MAX_BYTES >> 20} MB")
+    for k, a in host.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+    return sorted(host)
 
 
 def read_profile(lib, names):
@@ -940,6 +984,7 @@ def main():
             torch.cuda.synchronize(dev)
 
     it_count = [0]
+    last_pkg = [None]      # --dump-outputs: what the latest step returned (kept only then)
 
     def one_step():
         i = it_count[0]
@@ -947,7 +992,9 @@ def main():
         st, tgt = views[i % V]
         # the next step's camera is known (frames are drawn ahead): its preprocess rides in this step's backward
         nxt = None if args.no_prepare_next else views[(i + 1) % V][0]
-        ts.train_step(params, st, tgt, next_settings=nxt, densifier=den, iteration=i + 1)
+        pkg = ts.train_step(params, st, tgt, next_settings=nxt, densifier=den, iteration=i + 1)
+        if args.dump_outputs:
+            last_pkg[0] = pkg
 
     for _ in range(args.warmup):
         one_step()
@@ -980,6 +1027,10 @@ def main():
     lc1 = cut_stats()
     lib.gsr_set_option(b"profile", 0)
     prof_blend = read_profile(lib, ["blend_fwd"])["blend_fwd"]
+    dumped = None
+    if args.dump_outputs and rank == 0:      # before any further step or render changes the model
+        dumped = dump_outputs(args.dump_outputs, last_pkg[0], params, den)
+    last_pkg[0] = None
     # R_eff of every view (the roofline's algorithmic bytes are the mean over the views the timed launches rendered)
     r_eff_views, r_views = [], []
     with torch.no_grad():
@@ -1148,7 +1199,7 @@ def main():
     blend_bwd_ms, preb_ms = stage_ms["blend_bwd"], stage_ms["preprocess_bwd"]
     others = []
     if blend_bwd_ms:
-        ab = 44.0 * R_eff + 36.0 * P + 40.0 * n_vis
+        ab = 44.0 * R_eff + 36.0 * P + 80.0 * n_vis     # (the ggrad row a visible Gaussian ends with: ten float64 sums)
         tr_b, tr_b_why = counted_traffic("k_blend_bwd2", blend_bwd_ms)
         others.append({"kernel": "gsr::k_blend_bwd2<false>", "bound": "valu", "achieved": ab / (blend_bwd_ms * 1e-3) / 1e9, "peak": HBM_PEAK_GBS,
                        "unit": "GB/s", "frac": ab / (blend_bwd_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, "algorithmic_bytes_per_launch": ab,
@@ -1156,10 +1207,10 @@ def main():
                        "note": "frac = algorithmic bytes against the HBM peak (the figure SURVEY 8d asks for); the roof that binds is the "
                                "vector pipe: see `valu` (packed f32 math + DPP butterfly: mostly double-pass instructions)"})
     if preb_ms:
-        # params 236 + ggrad 48 + moments 472 in; params + moments 708 + means2D grad 12 out; + 68 out for the next render's
-        # splat / radii / key / id / tile records when that render's preprocess rides along ("prepare in backward"); + 4 in (radii)
-        # and 12 in / 12 out for the densification statistics of the visible Gaussians
-        ab = (1476.0 + (0.0 if args.no_prepare_next else 68.0)) * N + (0.0 if den is None else 4.0 * N + 24.0 * n_vis)
+        # params 236 + ggrad 80 (ten float64 sums) + moments 472 in; params + moments 708 + means2D grad 12 out; + 68 out for the next
+        # render's splat / radii / key / id / tile records when that render's preprocess rides along ("prepare in backward"); + 4 in
+        # (radii) and 12 in / 12 out for the densification statistics of the visible Gaussians
+        ab = (1508.0 + (0.0 if args.no_prepare_next else 68.0)) * N + (0.0 if den is None else 4.0 * N + 24.0 * n_vis)
         tr_p, tr_p_why = counted_traffic("k_preprocess_bwd", preb_ms)
         others.append({"kernel": "gsr::k_preprocess_bwd<3, true, false, true, 3> (per-Gaussian backward + in-kernel Adam + next preprocess)", "bound": "hbm",
                        "achieved": ab / (preb_ms * 1e-3) / 1e9, "peak": HBM_PEAK_GBS, "unit": "GB/s",
@@ -1212,6 +1263,8 @@ def main():
     if per_rank_ms is not None:
         res["per_rank_ms_per_step"] = per_rank_ms
         res["rank_time_max_over_min"] = max(per_rank_ms) / min(per_rank_ms)
+    if dumped is not None:
+        res["dump_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
     state["res"] = res
     if dog is not None:
         dog.start()

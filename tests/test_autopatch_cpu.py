@@ -1,6 +1,5 @@
 """gsr_autopatch (opt-in fast path for the unmodified reference trainer): the dispatch and import-hook logic, on CPU."""
 import importlib
-import os
 import sys
 
 import pytest
@@ -38,11 +37,16 @@ def test_remove_restores_torch(autopatch):
     autopatch.apply()
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/trainer"), reason="the reference tree only exists in the authoring container")
-def test_import_hook_patches_the_reference_loss_module(autopatch):
+def test_import_hook_patches_the_reference_loss_module(autopatch, tmp_path):
     """`trainer.losses` imported AFTER gsr_autopatch gets its Loss.forward replaced, with no reference file edited; remove() puts
-    the original back."""
-    sys.path.insert(0, "/root/reference")
+    the original back.  The module is a stand-in with the reference's module path and class name (all the hook keys on), written
+    here so that the test needs nothing outside the repository."""
+    pkg = tmp_path / "trainer"
+    pkg.mkdir()
+    (pkg / "__init__.py").write_text("")
+    (pkg / "losses.py").write_text("import torch\n\n\nclass Loss(torch.nn.Module):\n    def forward(self, *args, **kwargs):\n"
+                                   "        raise NotImplementedError\n")
+    sys.path.insert(0, str(tmp_path))
     try:
         sys.modules.pop("trainer.losses", None)
         sys.modules.pop("trainer", None)
@@ -53,6 +57,6 @@ def test_import_hook_patches_the_reference_loss_module(autopatch):
         autopatch.apply()
         assert TL.Loss.forward is autopatch.loss_forward      # already imported: patched in place
     finally:
-        sys.path.remove("/root/reference")
+        sys.path.remove(str(tmp_path))
         sys.modules.pop("trainer.losses", None)
         sys.modules.pop("trainer", None)

@@ -4,9 +4,7 @@ the DISPATCH logic, on CPU.  The kernels' numbers are checked on the GPU (tests/
 The HIP ops cannot run here, so `gsr_autopatch._ops` is replaced by a recorder whose `pose_matrix` is pose.py's torch statement
 of Exp(delta) * base (test infrastructure, the same closed forms tests/test_gpu_pose.py holds the kernel to)."""
 import importlib
-import json
 import os
-import subprocess
 import sys
 
 import numpy as np
@@ -249,22 +247,3 @@ def test_zero_points_buffer_is_not_shared_after_a_write(autopatch):
         assert len(autopatch._ZERO_POINTS) <= 2
     finally:
         R.rasterize_gaussians_raw = orig
-
-
-@pytest.mark.skipif(not os.path.isdir("/root/reference/scene"), reason="authoring container only: imports the real reference classes")
-def test_pose_route_on_the_real_reference_classes():
-    """The REAL `HTGaussianModel.init_RT_seq` / `training_setup(fit_pose=True)` / `training_setup_fix_position` / `update_RT_seq` /
-    `get_RT` and `CF3DGS_Render.render` (imported under the CPU shim, lietorch replaced by refstub's stand-ins of its public API)
-    with `import gsr_autopatch` first: the optimizers they build are FusedPoseAdam objects, their renders take the pose node."""
-    out = subprocess.run([sys.executable, os.path.join(HERE, "helpers", "ref_pose_driver.py")], capture_output=True, text=True, timeout=600)
-    line = next((l for l in out.stdout.splitlines() if l.startswith("RESULT ")), None)
-    assert line is not None, out.stdout[-2000:] + out.stderr[-4000:]
-    res = json.loads(line[7:])
-    assert res["camera_optimizers"] == ["FusedPoseAdam"] * 3 and res["camera_optimizer_is_adam"]
-    assert res["model_optimizer"] == "FusedAdam" or res["model_optimizer"] == "Adam"         # (CPU tensors: the six-group optimizer stays stock)
-    assert res["fix_position_optimizer"] == "FusedPoseAdam" and res["fix_position_with_rotation"] == "Adam"
-    assert res["seq_transform_shape"] == [3, 4] and res["seq_node_calls"] == 1 and res["seq_node_param_is_P2"]
-    assert res["seq_transform_error"] < 1e-6 and res["seq_grad_error"] < 1e-5 and res["seq_other_grads_none"]
-    assert res["get_RT_matches"] < 1e-6
-    assert res["after_update_RT_seq_error"] < 1e-6
-    assert res["lr_statement_ok"]

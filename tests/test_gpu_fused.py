@@ -394,8 +394,13 @@ def test_extension_ops_run_under_torch_compile():
     g0 = [a.grad.clone() for a in args]
     for a in args:
         a.grad = None
-    l1 = torch.compile(f)(*args, gt)
-    l1.backward()
+    # compile in this process: inductor's default pool of compile workers (one per core, up to 32) would inherit this process's open
+    # GPU device file, and that many processes holding the GPU is more than a shared machine allows.  (The backward graph compiles
+    # inside backward(), so both stay under the setting.)
+    import torch._inductor.config as inductor_config
+    with inductor_config.patch(compile_threads=1):
+        l1 = torch.compile(f)(*args, gt)
+        l1.backward()
     assert abs(float(l0.detach()) - float(l1.detach())) < 1e-6
     for a, b in zip(g0, [a.grad for a in args]):
         assert (a - b).abs().max().item() <= 2e-5 * a.abs().max().item() + 1e-12
@@ -983,3 +988,33 @@ def test_view_cache_keeps_frames_apart_that_are_farther_than_the_tolerance():
         render(tx)
     s1 = _view_cache_stats(lib, W, H)
     assert s1["lookups"] - s0["lookups"] == 7 and s1["hits"] - s0["hits"] == 5 and s1["entries"] - s0["entries"] == 2, (s0, s1)
+
+
+def test_training_steps_are_reproducible_bit_for_bit():
+    """The same scene, cameras and targets give the same model every run: bench.py's step (fused activations, loss and Adam, the
+    next view prepared in the backward, densification statistics) run twice from the same start ends in identical parameters,
+    statistics, render and loss.  The blend backward adds a Gaussian's per-tile parts with float64 atomics, so the order the tiles
+    arrive in -- which differs from run to run -- reaches a float32 gradient only when a float32 rounding boundary falls between
+    two orders' float64 sums (blend_common.h: about 2^-29 relative of an inexact sum).  With the float32 atomics this replaced,
+    every Gaussian whose sum took three or more parts could differ in its last bits, and Adam carried that into the model."""
+    dev = torch.device("cuda:0")
+    dm = importlib.import_module("3dgs_hierarchical_training_amd.densify")
+    W, H = 640, 360
+    sc = parity.syn.make_scene(200000, W, H, sh_degree=3, seed=12)
+    views = [(ts.make_settings(sc, dev, 3), parity.syn.target_image(W, H, seed=1).to(dev))]
+    gen = torch.Generator().manual_seed(4)
+    for k in (2, 3):
+        cam = parity.syn.make_camera(W, H, R=parity.syn.random_rotation(gen, 0.05), t=0.05 * torch.randn(3, generator=gen))
+        views.append((ts.make_settings({**sc, **cam}, dev, 3), parity.syn.target_image(W, H, seed=k).to(dev)))
+    runs = []
+    for _ in range(2):
+        p = ts.GaussianParams(sc, dev)
+        den = dm.Densifier(p, scene_extent=5.0, cfg=dm.DensifyConfig(densify_from_iter=10 ** 9, opacity_reset_interval=10 ** 9,
+                                                                       densify_until_iter=10 ** 9))
+        for i in range(12):
+            pkg = ts.train_step(p, views[i % 3][0], views[i % 3][1], next_settings=views[(i + 1) % 3][0], densifier=den, iteration=i + 1)
+        torch.cuda.synchronize(dev)
+        runs.append({**{k: v.clone() for k, v in p.raw().items()}, "loss": pkg["loss"].clone(), "image": pkg["raw_image"].detach().clone(),
+                     "xyz_gradient_accum": den.xyz_gradient_accum.clone(), "max_radii2D": den.max_radii2D.clone()})
+    for k in runs[0]:
+        assert torch.equal(runs[0][k], runs[1][k]), (k, (runs[0][k] - runs[1][k]).abs().max().item())

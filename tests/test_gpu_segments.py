@@ -154,7 +154,9 @@ def test_tree_walked_by_four_processes_sharing_the_gpu():
            "--one-device", "--frames", "20", "--width", "320", "--height", "240", "--gt-gaussians", "60000", "--leaf-gaussians", "30000",
            "--leaf-iters", "20", "--phase1-iters", "3", "--phase2-iters", "6", "--stage-a", "20000", "150", "100"]
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
-    env.update(HSA_ENABLE_IPC_MODE_LEGACY="0")
+    # PYTORCH_NVML_BASED_CUDA_CHECK: torch.distributed.run's agent asks torch.cuda.is_available(), which would otherwise open the GPU
+    # in the agent too -- with it the device is counted through amd-smi, and only this process and the four ranks hold the GPU
+    env.update(HSA_ENABLE_IPC_MODE_LEGACY="0", PYTORCH_NVML_BASED_CUDA_CHECK="1")
     out = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-3000:]
     recs = [json.loads(l) for l in out.stdout.splitlines() if l.startswith("{")]
@@ -194,7 +196,7 @@ def test_bench_line_at_two_ranks_on_one_gpu():
     # (tests/test_launch_cpu.py covers the launcher's refusals; the explicit torch.distributed.run form is what the 4-process walk uses)
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "2", "--gaussians", "200000"]
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
-    env.update(HSA_ENABLE_IPC_MODE_LEGACY="0", GSR_BENCH_BACKEND="gloo", GSR_BENCH_ONE_DEVICE="1")
+    env.update(HSA_ENABLE_IPC_MODE_LEGACY="0", GSR_BENCH_BACKEND="gloo", GSR_BENCH_ONE_DEVICE="1", PYTORCH_NVML_BASED_CUDA_CHECK="1")  # (see above)
     out = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]

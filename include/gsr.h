@@ -345,9 +345,12 @@ size_t gsr_struct_bytes(int32_t which); /* 0 GsrForwardArgs, 1 GsrBackwardArgs, 
  *                          counts, the list cut's remembered depths, the counters of gsr_debug_view_cache_stats /
  *                          gsr_debug_list_cut_stats (synchronises the device)
  *   "deterministic_backward" 1 = debug mode: the blend backward writes every (tile, Gaussian) partial gradient to its own slot and
- *                          a second kernel sums each Gaussian's slots in list order -- no float atomics, bit-identical gradients
- *                          from run to run (the default accumulates with atomics in arrival order); several times slower
- *                          (always through the two-pixel kernel: the four waves of "blend_bwd_ppt" 1 add into a tile's LDS row in arrival order)
+ *                          a second kernel sums each Gaussian's slots in list order, in float64; several times slower.  The
+ *                          default adds the same float32 parts with float64 atomics in arrival order, and those sums are exact
+ *                          (order-independent) while the parts' exponent span plus log2(count) fits in 29 bits: the default gives
+ *                          the same bits as this mode apart from rare rounding-boundary flips of inexact sums.  "blend_bwd_ppt" 1
+ *                          does not: its four waves add a tile's part into LDS in float32, in arrival order (this mode always runs
+ *                          the two-pixel kernel)
  *   "profile"              1 = HIP events around every stage on the caller's stream (an event pair costs ~10 us of stream
  *                          bubble per stage), 2 = only the forward blend kernel is timed, through the start / stop timestamps of
  *                          its own dispatch (hipExtLaunchKernelGGL: still ~11 us of idle queue around the launch), 3 = as 2 on

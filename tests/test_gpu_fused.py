@@ -83,13 +83,12 @@ def test_train_step_variants_agree():
 @pytest.mark.parametrize("n,deg", [(30000, 3), (30001, 3), (20011, 1), (4099, 0)])
 def test_optimizer_in_backward_equals_backward_then_step(n, deg):
     """GsrFusedAdam (Adam applied inside the per-Gaussian backward kernel) == backward() + gsr_adam_step: same
-    gradient arithmetic, same update arithmetic, only the HBM round trip of the gradient is gone.  Two runs of the
-    blend backward differ in the last bits (float atomics across tiles commit in any order), and Adam with eps = 1e-15
-    turns the relative noise of a nearly cancelled gradient into a visible fraction of an lr step, so the comparison
-    is: all but 1e-3 of the elements agree to 5% of one learning-rate step + 4 ulp (parameters; a wrong group, column
-    or learning rate moves most elements by a whole step) / 1e-3 relative (moments).  Covers the 16-byte streams (n
-    multiple of 128), the ragged last block, and SH bands above the active degree (deg < 3 with 16 stored
-    coefficients: zero gradient, moments still decay)."""
+    gradient arithmetic, same update arithmetic (adam_one, adam_math.h), only the HBM round trip of the gradient is gone.
+    The blend backward's float64 cross-tile sums repeat their bits from run to run, so parameters, both moments and the
+    screen-space gradient are EQUAL, up to rounding-boundary flips of inexact sums (parity.same_accumulation: at most 4
+    entries per tensor; Adam with eps = 1e-15 would turn any other difference of a nearly cancelled gradient into a
+    visible fraction of an lr step).  Covers the 16-byte streams (n multiple of 128), the ragged last block, and SH bands
+    above the active degree (deg < 3 with 16 stored coefficients: zero gradient, moments still decay)."""
     dev = torch.device("cuda:0")
     sc = parity.syn.make_scene(n, 320, 240, sh_degree=3, seed=9)
     sc["sh_degree"] = deg
@@ -97,25 +96,18 @@ def test_optimizer_in_backward_equals_backward_then_step(n, deg):
     settings = ts.make_settings(sc, dev, deg)
     pa, pb = ts.GaussianParams(sc, dev, optimizer="hip"), ts.GaussianParams(sc, dev, optimizer="hip")
     names = ["_xyz", "_features_dc", "_features_rest", "_opacity", "_scaling", "_rotation"]
-    lrs = {id(g["params"][0]): g["lr"] for g in pa.optimizer.param_groups}
-
-    def bad_frac(a, b, rtol, atol):
-        return ((a - b).abs() > atol + rtol * b.abs()).float().mean().item()
 
     for it in range(3):
         ka = ts.train_step(pa, settings, gt, fused_optimizer=True)
         kb = ts.train_step(pb, settings, gt, fused_optimizer=False)
         assert all(getattr(pa, k).grad is None for k in names)
-        ga, gb = ka["viewspace_points"].grad, kb["viewspace_points"].grad
-        assert bad_frac(ga, gb, 1e-3, 1e-3 * gb.abs().max().item() * 1e-3) < 1e-4
+        got, want = {"viewspace_points": ka["viewspace_points"].grad}, {"viewspace_points": kb["viewspace_points"].grad}
         for k in names:
-            a, b = getattr(pa, k).detach(), getattr(pb, k).detach()
-            assert bad_frac(a, b, 5e-7, 0.05 * lrs[id(getattr(pa, k))]) < 1e-3, (it, k, (a - b).abs().max().item())
-            assert (a - b).abs().max().item() <= 2.5 * (it + 1) * lrs[id(getattr(pa, k))] + 1e-6 * b.abs().max().item()
+            got[k], want[k] = getattr(pa, k).detach(), getattr(pb, k).detach()
             sa, sb = pa.optimizer.state[getattr(pa, k)], pb.optimizer.state[getattr(pb, k)]
             for mom in ("exp_avg", "exp_avg_sq"):
-                scale = sb[mom].abs().max().item()
-                assert bad_frac(sa[mom], sb[mom], 1e-3, 1e-6 * scale) < 1e-3, (it, k, mom)
+                got[k + "/" + mom], want[k + "/" + mom] = sa[mom], sb[mom]
+        parity.same_accumulation(got, want, f"in-backward vs step, {n}/deg{deg}, step {it}", verbose=False)
     assert pa.optimizer.step_count == pb.optimizer.step_count == 3
     if deg < 3:   # bands above the active degree: no gradient, so both routes must agree exactly (and stay put)
         hi = 3 * ((deg + 1) ** 2 - 1) // 3
@@ -406,17 +398,20 @@ def test_extension_ops_run_under_torch_compile():
         assert (a - b).abs().max().item() <= 2e-5 * a.abs().max().item() + 1e-12
 
 
+PREPARE_SHAPES = [(12800, 3), (10007, 3), (4098, 3), (101, 3), (130, 3), (12800, 0), (10007, 0), (4098, 1), (12800, 2), (130, 0),
+                  (12800, "up"), (10007, "up")]
+PREPARE_IDS = ["whole-blocks", "ragged-odd", "ragged-mod4", "one-ragged-block", "two-blocks-ragged", "deg0-whole", "deg0-ragged-odd",
+               "deg1-ragged-mod4", "deg2-whole", "deg0-two-blocks-ragged", "degree-steps-up-whole", "degree-steps-up-ragged"]
+
+
 @pytest.mark.parametrize("digits_in_backward", [True, False], ids=["digits-counted-in-backward", "histogram-launch"])
-@pytest.mark.parametrize("N,deg", [(12800, 3), (10007, 3), (4098, 3), (101, 3), (130, 3), (12800, 0), (10007, 0), (4098, 1), (12800, 2), (130, 0),
-                                   (12800, "up"), (10007, "up")],
-                         ids=["whole-blocks", "ragged-odd", "ragged-mod4", "one-ragged-block", "two-blocks-ragged", "deg0-whole", "deg0-ragged-odd",
-                              "deg1-ragged-mod4", "deg2-whole", "deg0-two-blocks-ragged", "degree-steps-up-whole", "degree-steps-up-ragged"])
+@pytest.mark.parametrize("N,deg", PREPARE_SHAPES, ids=PREPARE_IDS)
 def test_prepare_in_backward_is_bit_identical(N, deg, digits_in_backward):
     """"Prepare in backward" (GsrNextView): with `next_settings` the backward that applies the Adam step also runs the NEXT
     render's preprocess on the updated parameters, and that render skips k_preprocess.  Two copies of one model trained on
     two alternating cameras, one with and one without the hand-over, must stay EQUAL: images, radii, parameters, moments --
     bit for bit, on whole blocks and on ragged last blocks (N not a multiple of 128 / of 4).  (The blend backward runs in its
-    deterministic debug mode here: with float atomics two runs of the SAME path already differ in the last bits.)
+    fixed-order mode here, "deterministic_backward"; the default accumulation: the test below.)
     The hand-over buffer also carries the next depth sort's scratch: its counters are cleared by the blend backward, and up
     to 262 144 Gaussians the per-Gaussian kernel counts the sort's digits too (no histogram launch in the forward); both
     sides of that threshold are run here ("prep_hist_max_n").
@@ -424,21 +419,33 @@ def test_prepare_in_backward_is_bit_identical(N, deg, digits_in_backward):
     reference's models start at degree 0 and step up once per 1 000 iterations (gaussian_model_ht.py:68,193-195); "up" walks
     0 -> 1 -> 2 -> 3 with an `oneup_sh_degree()` after every second step, announced through `next_sh_degree` so that the
     hand-over survives the change."""
+    _prepare_in_backward_test(N, deg, digits_in_backward, fixed_order=True)
+
+
+@pytest.mark.parametrize("N,deg", [PREPARE_SHAPES[i] for i in (0, 1, 3, 5, 11)], ids=[PREPARE_IDS[i] for i in (0, 1, 3, 5, 11)])
+def test_prepare_in_backward_is_bit_identical_on_the_default_accumulation(N, deg):
+    """The same on the default backward (float64 atomics across a Gaussian's tiles): equal up to rounding-boundary flips of inexact
+    sums (parity.same_accumulation: at most 4 entries per tensor).  A representative subset of the shapes above -- whole blocks,
+    ragged blocks, one ragged block, degree 0, the degree steps -- with the digits counted in the backward."""
+    _prepare_in_backward_test(N, deg, True, fixed_order=False)
+
+
+def _prepare_in_backward_test(N, deg, digits_in_backward, fixed_order):
     L = importlib.import_module("3dgs_hierarchical_training_amd._lib")
     lib = L.load()
-    assert lib.gsr_set_option(b"deterministic_backward", 1) == 0
+    assert lib.gsr_set_option(b"deterministic_backward", 1 if fixed_order else 0) == 0
     assert lib.gsr_set_option(b"prep_hist_max_n", 262144 if digits_in_backward else 0) == 0
     for D in range(4):
         assert lib.gsr_prepare_supported(16, D, 1) == 1
     assert lib.gsr_prepare_supported(9, 2, 1) == 0 and lib.gsr_prepare_supported(16, 3, 0) == 0
     try:
-        _prepare_in_backward_case(N, deg)
+        _prepare_in_backward_case(N, deg, fixed_order)
     finally:
         lib.gsr_set_option(b"deterministic_backward", 0)
         lib.gsr_set_option(b"prep_hist_max_n", 262144)
 
 
-def _prepare_in_backward_case(N, deg=3):
+def _prepare_in_backward_case(N, deg=3, fixed_order=True):
     dev = torch.device("cuda:0")
     W, H = 320, 240
     up = deg == "up"
@@ -465,15 +472,18 @@ def _prepare_in_backward_case(N, deg=3):
         if raise_after:
             pa.oneup_sh_degree(); pb.oneup_sh_degree()
         used += int(had)
-        assert torch.equal(ka["raw_image"], kb["raw_image"]) and torch.equal(ka["radii"], kb["radii"]), it
-        assert torch.equal(ka["depth"], kb["depth"]) and torch.equal(ka["alpha"], kb["alpha"]), it
-        assert torch.equal(ka["viewspace_points"].grad, kb["viewspace_points"].grad), it
+        got = {k: ka[k] for k in ("raw_image", "radii", "depth", "alpha")}
+        want = {k: kb[k] for k in ("raw_image", "radii", "depth", "alpha")}
+        got["viewspace_points"], want["viewspace_points"] = ka["viewspace_points"].grad, kb["viewspace_points"].grad
         for k in names:
-            assert torch.equal(getattr(pa, k), getattr(pb, k)), (it, k)
+            got[k], want[k] = getattr(pa, k).detach(), getattr(pb, k).detach()
         # the moments too (bands above the active degree decay with a zero gradient, as dense Adam has it)
         for ga, gb in zip(pa.optimizer.param_groups, pb.optimizer.param_groups):
             sa, sb = pa.optimizer.state[ga["params"][0]], pb.optimizer.state[gb["params"][0]]
-            assert torch.equal(sa["exp_avg"], sb["exp_avg"]) and torch.equal(sa["exp_avg_sq"], sb["exp_avg_sq"]), (it, ga["name"])
+            for mom in ("exp_avg", "exp_avg_sq"):
+                got[ga["name"] + "/" + mom], want[gb["name"] + "/" + mom] = sa[mom], sb[mom]
+        # fixed order: equal bits; default accumulation: equal up to rounding-boundary flips of inexact cross-tile sums
+        parity.same_accumulation(got, want, f"prepare in backward, step {it}", max_entries=0 if fixed_order else None, verbose=False)
     assert used == steps - 1              # every step after the first rendered from a hand-over buffer -- across the degree changes too
     if up:
         assert pa.active_sh_degree == 3
@@ -525,14 +535,16 @@ def test_a_render_that_never_reaches_backward_leaves_the_optimizer_untouched():
     for _ in range(2):
         ts.train_step(pa, st, gt); ts.train_step(pb, st, gt, fused_optimizer=False)
     assert pa.optimizer.step_count == 3 and pb.optimizer.step_count == 3
-    # (tolerance as in test_optimizer_in_backward_equals_backward_then_step: float atomics + eps 1e-15 turn the rounding noise of a
-    #  nearly cancelled gradient into a fraction of an lr step on a few elements; a step count off by one -- a wrong bias correction
-    #  1 / (1 - 0.9^t) at t = 2 instead of 3 -- would move EVERY element by 30 % of a step)
-    lrs = {g["name"]: g["lr"] for g in pa.optimizer.param_groups}
+    # (equal, as in test_optimizer_in_backward_equals_backward_then_step, up to rounding-boundary flips of the blend backward's
+    #  float64 cross-tile sums; a step count off by one -- a wrong bias correction 1 / (1 - 0.9^t) at t = 2 instead of 3 -- would move
+    #  EVERY element by 30 % of a step)
+    got, want = {}, {}
     for name, k in ts.GaussianParams._GROUP_ATTR.items():
-        a, b = getattr(pa, k).detach(), getattr(pb, k).detach()
-        bad = ((a - b).abs() > 0.05 * lrs[name] + 5e-7 * b.abs()).float().mean().item()
-        assert bad < 1e-3, (k, bad)
+        got[k], want[k] = getattr(pa, k).detach(), getattr(pb, k).detach()
+        sa, sb = pa.optimizer.state[getattr(pa, k)], pb.optimizer.state[getattr(pb, k)]
+        for mom in ("exp_avg", "exp_avg_sq"):
+            got[k + "/" + mom], want[k + "/" + mom] = sa[mom], sb[mom]
+    parity.same_accumulation(got, want, "fused step after renders without a backward vs plain steps")
     # state_dict reports the reconciled count in torch's layout
     sd = pa.optimizer.state_dict()
     assert all(int(v["step"]) == 3 for v in sd["state"].values())

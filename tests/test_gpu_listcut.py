@@ -7,7 +7,9 @@ for the flagged tiles, blend of the flagged tiles on their full lists).  So ever
 radii, R, the tiles' range starts, the list's valid prefixes, and -- with the backward's fixed-order accumulation
 ("deterministic_backward") -- every gradient, bit for bit, between `list_cut` 1 and 0; on a scene that does not change (no repair),
 on one that changes under the same frame so that tiles need MORE than they kept (repairs), with large rects, with a speculative
-capacity that overflows, with another model under the same frame.  Plus: the oracle parity of a cut render."""
+capacity that overflows, with another model under the same frame.  On the default backward (float64 atomics across a Gaussian's
+tiles) the gradients are equal up to rounding-boundary flips of inexact sums (tests/parity.py same_accumulation): the
+`..._on_the_default_accumulation` tests.  Plus: the oracle parity of a cut render."""
 import ctypes as C
 import importlib
 
@@ -37,7 +39,7 @@ def _render(kw, grads=None):
     return out, ranges.cpu().numpy(), lst.cpu().numpy(), info["num_rendered"], info["staged"]
 
 
-def _equal_renders(a, b, what):
+def _equal_renders(a, b, what, fixed_order=True):
     (oa, ra, la, Ra, sa), (ob, rb, lb, Rb, sb) = a, b
     assert Ra == Rb and sa == sb, (what, Ra, Rb, sa, sb)
     for x, y, name in zip(oa["fwd"], ob["fwd"], ("color", "radii", "depth", "alpha")):
@@ -50,16 +52,20 @@ def _equal_renders(a, b, what):
         x, y = int(cut_r[t, 0]), int(cut_r[t, 1])
         assert np.array_equal(cut_l[x:y], full_l[x:y]), (what, int(t))
     if "grads" in oa:
+        if not fixed_order:
+            parity.same_accumulation(oa["grads"], ob["grads"], what, verbose=False)
+            return
         for k in oa["grads"]:
             assert np.array_equal(oa["grads"][k], ob["grads"][k]), (what, k, float(np.abs(oa["grads"][k] - ob["grads"][k]).max()))
 
 
-def _two_ways(lib, kws, W, H, grads, margin=None, hint=None):
+def _two_ways(lib, kws, W, H, grads, margin=None, hint=None, fixed_order=True):
     """Render the sequence of scenes `kws` (the same frame: same camera, same image size) with the cut on and off, from a clean cache;
-    returns ([cut renders], [full renders], stats of the cut run)."""
+    returns ([cut renders], [full renders], stats of the cut run).  fixed_order: the backward's "deterministic_backward" mode;
+    False: its default accumulation."""
     res = {}
     st = None
-    assert lib.gsr_set_option(b"deterministic_backward", 1) == 0
+    assert lib.gsr_set_option(b"deterministic_backward", 1 if fixed_order else 0) == 0
     # (models of these sizes take the tile-sort route by default, which has no global depth order to cut along: the cut serves the
     #  depth-sort route that large models take -- forced here, so that the seconds-sized scenes of a test exercise it)
     assert lib.gsr_set_option(b"tile_sort", 0) == 0
@@ -94,15 +100,25 @@ def test_cut_lists_render_what_full_lists_render(case):
     """A frame rendered four times (the first sight of it is never cut): with the cut on, the later renders write shorter lists --
     chunks of the depth order are skipped -- and everything a caller can observe is what full lists give, bit for bit; no tile
     needs a repair on a scene that does not change."""
+    _cut_vs_full_case(case, fixed_order=True)
+
+
+@pytest.mark.parametrize("case", CASES, ids=[f"{c[0]}@{c[1]}x{c[2]}-deg{c[3]}-x{c[4]}" for c in CASES])
+def test_cut_lists_render_what_full_lists_render_on_the_default_accumulation(case):
+    """The same on the default backward: gradients equal up to rounding-boundary flips of inexact cross-tile sums."""
+    _cut_vs_full_case(case, fixed_order=False)
+
+
+def _cut_vs_full_case(case, fixed_order):
     N, W, H, deg, smod = case
     lib = L.load()
     sc = parity.syn.make_scene(N, W, H, sh_degree=deg, seed=N % 89, posed=True)
     sc["scale_modifier"] = smod                     # (x6: rects of more than 32 tiles, walked by whole waves)
     kw = parity.scene_kwargs(sc, "sh", bg=(0.1, 0.2, 0.3))
     gc, gd, ga = parity.upstream_grads(H, W, seed=5)
-    cut, full, st = _two_ways(lib, [kw] * 4, W, H, (gc, gd, ga))
+    cut, full, st = _two_ways(lib, [kw] * 4, W, H, (gc, gd, ga), fixed_order=fixed_order)
     for i, (a, b) in enumerate(zip(cut, full)):
-        _equal_renders(a, b, f"render {i}")
+        _equal_renders(a, b, f"render {i}", fixed_order)
     assert st[0] == 4 and st[1] == 0 and st[2] == 0, st
     kept = [(r[1][:, 1] - r[1][:, 0]).sum() for r in cut]
     assert kept[0] == cut[0][3]                       # the first render of a frame: full lists (R)
@@ -117,6 +133,15 @@ def test_tiles_that_need_more_than_they_kept_are_repaired_on_the_device():
     far more of their lists than they kept -- with NO margin.  The waves that run out of
     their cut lists flag their tiles and the repair pass re-blends those on full lists: everything equals the full-list render,
     the counters say that repairs happened, and the render after that keeps what the repaired tiles needed (no repair again)."""
+    _repair_case(fixed_order=True)
+
+
+def test_repaired_tiles_give_the_full_lists_gradients_on_the_default_accumulation():
+    """The repair scene on the default backward: gradients equal up to rounding-boundary flips of inexact cross-tile sums."""
+    _repair_case(fixed_order=False)
+
+
+def _repair_case(fixed_order):
     lib = L.load()
     N, W, H = 80_000, 640, 360
     sc = parity.syn.make_scene(N, W, H, sh_degree=1, seed=31, posed=True)
@@ -126,11 +151,13 @@ def test_tiles_that_need_more_than_they_kept_are_repaired_on_the_device():
     sc1["opacities"] = sc["opacities"] * 0.15
     kw1 = parity.scene_kwargs(sc1, "sh", bg=(0.0, 0.1, 0.0))
     gc, gd, ga = parity.upstream_grads(H, W, seed=6)
-    cut, full, st = _two_ways(lib, [kw0, kw0, kw1, kw1, kw1], W, H, (gc, gd, ga), margin=0)
+    cut, full, st = _two_ways(lib, [kw0, kw0, kw1, kw1, kw1], W, H, (gc, gd, ga), margin=0, fixed_order=fixed_order)
     for i, (a, b) in enumerate(zip(cut, full)):
-        _equal_renders(a, b, f"render {i}")
+        _equal_renders(a, b, f"render {i}", fixed_order)
     assert st[0] == 5 and st[1] >= 1 and st[2] > 50, st          # render 2 ran into its cuts all over the frame
     assert cut[2][4] > 1.5 * cut[1][4]                             # (the transparent model stages far deeper)
+    if not fixed_order:
+        return
     cut2, full2, st2 = _two_ways(lib, [kw0, kw0, kw1, kw1], W, H, None, margin=0)
     cut3, full3, st3 = _two_ways(lib, [kw0, kw0, kw1], W, H, None, margin=0)
     assert st2[1] == st3[1] and st2[2] == st3[2], (st2, st3)      # the render AFTER the repaired one needed no repair
@@ -140,14 +167,23 @@ def test_tiles_that_need_more_than_they_kept_are_repaired_on_the_device():
 def test_cut_with_an_overflowing_speculative_capacity():
     """A cut render whose speculative binning capacity is too small is run again on the exact size -- the cut tables are the same,
     the flags of the truncated first attempt must not leak into the result."""
+    _overflow_case(fixed_order=True)
+
+
+def test_cut_with_an_overflowing_speculative_capacity_on_the_default_accumulation():
+    """The same on the default backward: gradients equal up to rounding-boundary flips of inexact cross-tile sums."""
+    _overflow_case(fixed_order=False)
+
+
+def _overflow_case(fixed_order):
     lib = L.load()
     N, W, H = 50_000, 480, 320
     sc = parity.syn.make_scene(N, W, H, sh_degree=0, seed=7, posed=True)
     kw = parity.scene_kwargs(sc, "sh")
     gc, gd, ga = parity.upstream_grads(H, W, seed=1)
-    cut, full, st = _two_ways(lib, [kw] * 4, W, H, (gc, gd, ga), hint=(2, 20_000))
+    cut, full, st = _two_ways(lib, [kw] * 4, W, H, (gc, gd, ga), hint=(2, 20_000), fixed_order=fixed_order)
     for i, (a, b) in enumerate(zip(cut, full)):
-        _equal_renders(a, b, f"render {i}")
+        _equal_renders(a, b, f"render {i}", fixed_order)
     assert lib.gsr_get_counter(b"spec_overflows") >= 1
 
 

@@ -41,7 +41,7 @@ def _register_fakes():
     @torch.library.register_fake("gsr::rasterize_forward")
     def _(means3D, sh, colors_precomp, opacities, scales, rotations, cov3D_precomp, sh_rest, viewmatrix, projmatrix, campos, bg,
           points_transform, image_height, image_width, tanfovx, tanfovy, scale_modifier, sh_degree, raw_params, prefiltered, debug,
-          prepared, batch_first_block, view_id=0, extras=0):
+          prepared, batch_first_block, view_id=0, extras=0, sh_origin=None):
         N, H, W = means3D.shape[0], image_height, image_width
         f = lambda *s: means3D.new_empty(s, dtype=torch.float32)
         b = lambda n: means3D.new_empty((n,), dtype=torch.uint8)
@@ -57,7 +57,8 @@ def _register_fakes():
     def _(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3D_precomp, sh_rest, viewmatrix, projmatrix, campos,
           bg, points_transform, image_height, image_width, tanfovx, tanfovy, scale_modifier, sh_degree, raw_params, prefiltered, debug,
           cam_grad, adam_m, adam_v, adam_lr, beta1, beta2, eps, step, prepared, next_viewmatrix, next_projmatrix, next_campos,
-          next_height, next_width, next_tanfovx, next_tanfovy, next_points_transform, next_sh_degree, adam_commit, densify_stats, batch_first_block, view_id=0, extras=0):
+          next_height, next_width, next_tanfovx, next_tanfovy, next_points_transform, next_sh_degree, adam_commit, densify_stats, batch_first_block, view_id=0, extras=0,
+          sh_origin=None):
         N, H, W = means3D.shape[0], image_height, image_width
         f = lambda *s: means3D.new_empty(s, dtype=torch.float32)
         nprep = lib.gsr_prepared_bytes(int(N)) if next_viewmatrix.numel() else 0
@@ -71,7 +72,7 @@ def _register_fakes():
     def _(means3D, sh, colors_precomp, opacities, scales, rotations, cov3D_precomp, sh_rest, viewmatrix, projmatrix, campos, bg,
           points_transform, geom, image, binning, meta, grad_color, grad_depth, grad_alpha, image_height, image_width, tanfovx, tanfovy,
           scale_modifier, sh_degree, raw_params, need_viewmatrix, need_projmatrix, need_campos, need_points_transform, densify_stats, radii,
-          batch_first_block):
+          batch_first_block, sh_origin=None):
         N = means3D.shape[0]
         f = lambda *s: means3D.new_empty(s, dtype=torch.float32)
         has = lambda t: t.numel() > 0
@@ -90,7 +91,7 @@ def _register_fakes():
           meta, grad_color, grad_depth, grad_alpha, image_height, image_width, tanfovx, tanfovy, scale_modifier, sh_degree,
           need_viewmatrix, need_projmatrix, need_campos, need_points_transform, adam_m, adam_v, adam_lr, beta1, beta2, eps, step,
           next_viewmatrix, next_projmatrix, next_campos, next_height, next_width, next_tanfovx, next_tanfovy, prepared_out,
-          next_points_transform, next_sh_degree, densify_stats, radii, batch_first_block):
+          next_points_transform, next_sh_degree, densify_stats, radii, batch_first_block, sh_origin=None):
         f = lambda *s: means3D.new_empty(s, dtype=torch.float32)
         none = f(0)
         B = len(batch_first_block) - 1 if len(batch_first_block) >= 3 else 1

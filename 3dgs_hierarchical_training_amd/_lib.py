@@ -26,6 +26,7 @@ class GsrForwardArgs(C.Structure):
         ("shs_rest", C.c_void_p), ("raw_params", C.c_int32),
         ("points_transform", C.c_void_p), ("prepared", C.c_void_p), ("batch", C.c_void_p),
         ("view_id", C.c_int64), ("out_color_clamped", C.c_void_p), ("visible", C.c_void_p),
+        ("sh_origin", C.c_void_p),
     ]
 
 
@@ -52,6 +53,7 @@ class GsrBackwardArgs(C.Structure):
         ("points_transform", C.c_void_p), ("d_points_transform", C.c_void_p),
         ("binning_capacity", C.c_int64), ("forward_flags", C.c_int64),
         ("next_view", C.c_void_p), ("prepared_out", C.c_void_p), ("densify_stats", C.c_void_p), ("batch", C.c_void_p),
+        ("sh_origin", C.c_void_p),
     ]
 
 

@@ -453,7 +453,9 @@ struct DepthHist {
                               // their status clear; 0 = none do, the single-block k_preprocess launch clears instead
 };
 
-template <int DEG, bool RAW>
+// SHO (GsrForwardArgs::sh_origin): the SH view direction is normalize(untransformed mean - sh_origin) instead of
+// normalize(posed mean - campos) -- the reference's convert_SHs_python route.  A template flag: the default instantiations are untouched.
+template <int DEG, bool RAW, bool SHO = false>
 __global__ __launch_bounds__(kPreThreads) void k_preprocess(CamParams cp, int N, const float* __restrict__ means,
                                                             const float* __restrict__ scales, const float* __restrict__ rots,
                                                             const float* __restrict__ cov_pre, const float* __restrict__ opac,
@@ -463,7 +465,8 @@ __global__ __launch_bounds__(kPreThreads) void k_preprocess(CamParams cp, int N,
                                                             uint32_t* __restrict__ dkey, uint32_t* __restrict__ gid,
                                                             TileRec* __restrict__ tilerec, uint32_t* __restrict__ zero_words,
                                                             int zero_count, int block0, DepthHist dh, uint2* __restrict__ early_parts = nullptr,
-                                                            uint32_t window_max = 0xffffffffu, uint8_t* __restrict__ visible = nullptr)
+                                                            uint32_t window_max = 0xffffffffu, uint8_t* __restrict__ visible = nullptr,
+                                                            const float* __restrict__ sh_origin = nullptr)
 {
     constexpr int NC3 = 3 * (DEG + 1) * (DEG + 1);
     __shared__ float s_sh[kPreThreads * kShStride];
@@ -512,11 +515,13 @@ __global__ __launch_bounds__(kPreThreads) void k_preprocess(CamParams cp, int N,
     Camera cam = load_camera(cp);
     cam.D = DEG;
     float mean[3] = {0.f, 0.f, 0.f};
+    float mraw[3] = {0.f, 0.f, 0.f};   // SHO: the untransformed mean, for the SH direction
     Splat s;
     TileRec rec;
     uint32_t lo_pack = 0u;   // sub-ulp remainders of the pixel-space mean (gsr_math.h pixel_lo_pack): stored in the record's `tiles` word
     if (act) {
         mean[0] = means[3 * (size_t)i]; mean[1] = means[3 * (size_t)i + 1]; mean[2] = means[3 * (size_t)i + 2];
+        if constexpr (SHO) { mraw[0] = mean[0]; mraw[1] = mean[1]; mraw[2] = mean[2]; }
         apply_points_transform(cp.xf, mean);
         float sc[3] = {0, 0, 0}, rq[4] = {1, 0, 0, 0}, cv[6], colp[3];
         if (cov_pre) {
@@ -581,6 +586,10 @@ __global__ __launch_bounds__(kPreThreads) void k_preprocess(CamParams cp, int N,
         __syncthreads();
         if (act && s.radius > 0) {
             float col[3];
+            if constexpr (SHO) {   // (the geometry is done with both: the colour sees the origin and the raw mean from here on)
+#pragma unroll
+                for (int k = 0; k < 3; k++) { cam.cam[k] = sh_origin[k]; mean[k] = mraw[k]; }
+            }
             if (lin) splat_sh_color(cam, mean, s_rest + tid * NR - 3, 3, 1, col, s_dc + tid * 3);
             else splat_sh_color(cam, mean, &s_sh[tid * kShStride], 3, 1, col);
             s.r = col[0]; s.g = col[1]; s.b = col[2];
@@ -3465,7 +3474,9 @@ __device__ __forceinline__ void load_ggrad(const double* __restrict__ row, float
     g2 = make_float4((float)a4.x, (float)a4.y, 0.f, 0.f);
 }
 
-template <int DEG, bool RAW, bool CAM, bool ADAM, int PREP>
+// SHO (GsrBackwardArgs::sh_origin; not with PREP): the colour's direction is normalize(untransformed mean - sh_origin), so its share of
+// dL/dmean is added to d_means3D AFTER the R^T chain of points_transform and reaches neither d_points_transform nor d_campos.
+template <int DEG, bool RAW, bool CAM, bool ADAM, int PREP, bool SHO = false>
 __global__ __launch_bounds__(kPreThreads) void k_preprocess_bwd(CamParams cp, int N, const float* means,
                                                                 const float* scales, const float* rots,
                                                                 const float* __restrict__ cov_pre, const float* shs,
@@ -3476,8 +3487,10 @@ __global__ __launch_bounds__(kPreThreads) void k_preprocess_bwd(CamParams cp, in
                                                                 float* __restrict__ d_shs, float* __restrict__ d_shs_rest,
                                                                 float* __restrict__ d_scales,
                                                                 float* __restrict__ d_rots, float* __restrict__ d_cov,
-                                                                float* __restrict__ cam_partial, PrepOut po, DensDev ds)
+                                                                float* __restrict__ cam_partial, PrepOut po, DensDev ds,
+                                                                const float* __restrict__ sh_origin = nullptr)
 {
+    static_assert(!SHO || PREP < 0, "sh_origin is not served together with a next view");
     constexpr int NC3 = 3 * (DEG + 1) * (DEG + 1);
     __shared__ float s_sh[kPreThreads * kShStride];
     __shared__ float s_cam[CAM ? (kPreThreads / 64) * kCamVals : 1];
@@ -3647,11 +3660,19 @@ __global__ __launch_bounds__(kPreThreads) void k_preprocess_bwd(CamParams cp, in
             for (int k = 0; k < 4; k++) drq[k] = o.rot[k];
 #pragma unroll
             for (int k = 0; k < 6; k++) dcv[k] = o.cov[k];
+            float dsho[3] = {0.f, 0.f, 0.f};   // SHO: the colour's share of dL/d(untransformed mean)
             if (shs) {
+                if constexpr (SHO) {   // direction (raw mean - sh_origin)/|.|: the camera takes no part (cam is not read below)
+#pragma unroll
+                    for (int k = 0; k < 3; k++) cam.cam[k] = sh_origin[k];
+                    if (lin) sh_backward(cam, mraw, s_rest + tid * NRL - 3, 3, 1, grgb, s_rest + tid * NRL - 3, 3, 1, dsho, s_dc + tid * 3, s_dc + tid * 3);
+                    else sh_backward(cam, mraw, &s_sh[tid * kShStride], 3, 1, grgb, &s_sh[tid * kShStride], 3, 1, dsho);
+                } else {
                 if (lin) sh_backward(cam, mean, s_rest + tid * NRL - 3, 3, 1, grgb, s_rest + tid * NRL - 3, 3, 1, dmean, s_dc + tid * 3, s_dc + tid * 3);
                 else sh_backward(cam, mean, &s_sh[tid * kShStride], 3, 1, grgb, &s_sh[tid * kShStride], 3, 1, dmean);
                 if (CAM) {   // the view direction is (p - campos)/|.|: d/dcampos = -(its share of d/dp)
                     cg.cam[0] = o.mean[0] - dmean[0]; cg.cam[1] = o.mean[1] - dmean[1]; cg.cam[2] = o.mean[2] - dmean[2];
+                }
                 }
             }
             if (cp.xf) {   // chain through p' = M [p; 1]: dL/dM = dL/dp' [p; 1]^T, dL/dp = R^T dL/dp'
@@ -3665,6 +3686,10 @@ __global__ __launch_bounds__(kPreThreads) void k_preprocess_bwd(CamParams cp, in
                 const float d0 = dmean[0], d1 = dmean[1], d2 = dmean[2];
 #pragma unroll
                 for (int c = 0; c < 3; c++) dmean[c] = fmaf(cp.xf[c], d0, fmaf(cp.xf[4 + c], d1, cp.xf[8 + c] * d2));
+            }
+            if constexpr (SHO) {
+#pragma unroll
+                for (int k = 0; k < 3; k++) dmean[k] += dsho[k];
             }
         } else if (lin) {
             for (int e = 0; e < 3; e++) s_dc[tid * 3 + e] = 0.f;
@@ -4290,7 +4315,7 @@ size_t gsr_prepared_bytes(int32_t N) { return prep_layout(N).bytes; }
 size_t gsr_prepared_radii_offset(int32_t N) { return prep_layout(N).radii; }
 int gsr_prepare_supported(int32_t M, int32_t D, int32_t raw_params) { return (raw_params && M == 16 && D >= 0 && D <= 3) ? 1 : 0; }
 const char* gsr_last_error(void) { return g_err; }
-int gsr_version(void) { return 110; }
+int gsr_version(void) { return 111; }
 size_t gsr_struct_bytes(int32_t which)
 {
     return which == 0 ? sizeof(GsrForwardArgs) : which == 1 ? sizeof(GsrBackwardArgs) : which == 2 ? sizeof(GsrForwardOut) : 0;
@@ -4466,6 +4491,8 @@ int gsr_forward(const GsrForwardArgs* a, GsrForwardOut* out, void* stream_)
     const int tiles_x = (W + kTile - 1) / kTile, tiles_y = (H + kTile - 1) / kTile, T = tiles_x * tiles_y * NB;
     if (NB > 1 && opt_ppt < 6) return fail(GSR_ERR_ARG, "batch: served by the default forward blend kernel only%s");
     if (a->out_color_clamped && opt_ppt < 6) return fail(GSR_ERR_ARG, "out_color_clamped: served by the default forward blend kernel only%s");
+    if (a->sh_origin && (!a->shs || NB > 1 || a->prepared))
+        return fail(GSR_ERR_ARG, "sh_origin needs shs and is not served with a batch of B > 1 or a prepared buffer%s");
     out->num_rendered = 0; out->binning = nullptr; out->binning_bytes = 0; out->binning_capacity = 0;
     out->forward_flags = pack_fwd_flags(opt_ppt, opt_map, opt_ckpt);
     uint64_t R = 0;
@@ -4740,20 +4767,32 @@ int gsr_forward(const GsrForwardArgs* a, GsrForwardOut* out, void* stream_)
             hipLaunchKernelGGL(k_prepared_begin, dim3((N + 255) / 256), dim3(256), 0, st, N, reinterpret_cast<const int32_t*>(pb + PL.radii),
                                a->radii, (uint32_t*)nullptr, 0);
     } else {
-#define GSR_PRE_(DEG, RAW)                                                                                                          \
-    hipLaunchKernelGGL((k_preprocess<DEG, RAW>), dim3(grid), dim3(kPreThreads), 0, st, cp, N, a->means3D, a->scales, a->rotations, \
-                       a->cov3D_precomp, a->opacities, a->shs, a->shs_rest, a->colors_precomp, splat, a->radii, dkey, gid, ntiles,  \
-                       zero_words, zero_count, 0, DepthHist{}, early_parts, early_window, a->visible)
-#define GSR_PRE(DEG) do { if (a->raw_params) GSR_PRE_(DEG, true); else GSR_PRE_(DEG, false); } while (0)
+#define GSR_PRE_(DEG, RAW, SHO)                                                                                                     \
+    hipLaunchKernelGGL((k_preprocess<DEG, RAW, SHO>), dim3(grid), dim3(kPreThreads), 0, st, cp, N, a->means3D, a->scales,           \
+                       a->rotations, a->cov3D_precomp, a->opacities, a->shs, a->shs_rest, a->colors_precomp, splat, a->radii, dkey, gid, \
+                       ntiles, zero_words, zero_count, 0, DepthHist{}, early_parts, early_window, a->visible, a->sh_origin)
+#define GSR_PRE(DEG) do { if (a->raw_params) GSR_PRE_(DEG, true, false); else GSR_PRE_(DEG, false, false); } while (0)
+    // sh_origin: degree 0 takes the default kernel (the colour does not depend on the direction)
+#define GSR_PRE_SHO(DEG) do { if (a->raw_params) GSR_PRE_(DEG, true, true); else GSR_PRE_(DEG, false, true); } while (0)
     {
         ProfScope ps(P_PRE_FWD, st);
+        if (a->sh_origin) {
+            switch (a->D) {
+                case 0: GSR_PRE(0); break;
+                case 1: GSR_PRE_SHO(1); break;
+                case 2: GSR_PRE_SHO(2); break;
+                default: GSR_PRE_SHO(3); break;
+            }
+        } else {
         switch (a->shs ? a->D : 0) {
             case 0: GSR_PRE(0); break;
             case 1: GSR_PRE(1); break;
             case 2: GSR_PRE(2); break;
             default: GSR_PRE(3); break;
         }
+        }
     }
+#undef GSR_PRE_SHO
 #undef GSR_PRE
 #undef GSR_PRE_
     }
@@ -5029,6 +5068,8 @@ int gsr_backward(const GsrBackwardArgs* a, void* stream_)
     rc = batch_dev(a->batch, N, H, bt);
     if (rc) return rc;
     const int NB = bt.B;
+    if (a->sh_origin && (!a->shs || NB > 1 || a->next_view))
+        return fail(GSR_ERR_ARG, "sh_origin needs shs and is not served with a batch of B > 1 or a next_view%s");
     {   // early R: a forward's count is held against its scan's own report as soon as that has arrived (no waiting here)
         int dev_id = 0;
         (void)hipGetDevice(&dev_id);
@@ -5230,17 +5271,19 @@ int gsr_backward(const GsrBackwardArgs* a, void* stream_)
             po.dh.clear_threads = (uint32_t)tail_blocks * kPreThreads;
         }
     }
-#define GSR_PREB_(DEG, RAW, CAM, ADAM, PREP)                                                                                                \
-    hipLaunchKernelGGL((k_preprocess_bwd<DEG, RAW, CAM, ADAM, PREP>), dim3(grid), dim3(kPreThreads), 0, st, cp, N, a->means3D, a->scales,  \
-                       a->rotations, a->cov3D_precomp, a->shs, a->shs_rest, a->opacities, ad, splat, gg, a->d_means3D, a->d_means2D,        \
-                       a->d_opacities, a->d_colors_precomp, a->d_shs, a->d_shs_rest, a->d_scales, a->d_rotations, a->d_cov3D_precomp,      \
-                       cam_partial, po, ds)
-#define GSR_PREB(DEG)                                                     \
-    do {                                                                  \
-        if (fa) { if (want_cam) GSR_PREB_(DEG, true, true, true, -1); else GSR_PREB_(DEG, true, false, true, -1); }                 \
-        else if (a->raw_params) { if (want_cam) GSR_PREB_(DEG, true, true, false, -1); else GSR_PREB_(DEG, true, false, false, -1); }   \
-        else { if (want_cam) GSR_PREB_(DEG, false, true, false, -1); else GSR_PREB_(DEG, false, false, false, -1); }               \
+#define GSR_PREB_S(DEG, RAW, CAM, ADAM, PREP, SHO)                                                                                          \
+    hipLaunchKernelGGL((k_preprocess_bwd<DEG, RAW, CAM, ADAM, PREP, SHO>), dim3(grid), dim3(kPreThreads), 0, st, cp, N, a->means3D,         \
+                       a->scales, a->rotations, a->cov3D_precomp, a->shs, a->shs_rest, a->opacities, ad, splat, gg, a->d_means3D,           \
+                       a->d_means2D, a->d_opacities, a->d_colors_precomp, a->d_shs, a->d_shs_rest, a->d_scales, a->d_rotations,             \
+                       a->d_cov3D_precomp, cam_partial, po, ds, a->sh_origin)
+#define GSR_PREB_(DEG, RAW, CAM, ADAM, PREP) GSR_PREB_S(DEG, RAW, CAM, ADAM, PREP, false)
+#define GSR_PREB_SO(DEG, SHO)                                                                                                               \
+    do {                                                                                                                                    \
+        if (fa) { if (want_cam) GSR_PREB_S(DEG, true, true, true, -1, SHO); else GSR_PREB_S(DEG, true, false, true, -1, SHO); }             \
+        else if (a->raw_params) { if (want_cam) GSR_PREB_S(DEG, true, true, false, -1, SHO); else GSR_PREB_S(DEG, true, false, false, -1, SHO); } \
+        else { if (want_cam) GSR_PREB_S(DEG, false, true, false, -1, SHO); else GSR_PREB_S(DEG, false, false, false, -1, SHO); }           \
     } while (0)
+#define GSR_PREB(DEG) GSR_PREB_SO(DEG, false)
 #define GSR_PREB_NEXT(DEG, NDEG) do { if (want_cam) GSR_PREB_(DEG, true, true, true, NDEG); else GSR_PREB_(DEG, true, false, true, NDEG); } while (0)
 #define GSR_PRE_TAIL(NDEG)                                                                                                               \
     hipLaunchKernelGGL((k_preprocess<NDEG, true>), dim3(1), dim3(kPreThreads), 0, st, po.cp, N, a->means3D, a->scales, a->rotations,       \
@@ -5270,6 +5313,13 @@ int gsr_backward(const GsrBackwardArgs* a, void* stream_)
                     default: GSR_PRE_TAIL(3); break;
                 }
             }
+        } else if (a->sh_origin) {   // (degree 0: the default kernel -- the colour does not depend on the direction)
+        switch (a->D) {
+            case 0: GSR_PREB(0); break;
+            case 1: GSR_PREB_SO(1, true); break;
+            case 2: GSR_PREB_SO(2, true); break;
+            default: GSR_PREB_SO(3, true); break;
+        }
         } else {
         switch (a->shs ? a->D : 0) {
             case 0: GSR_PREB(0); break;
@@ -5282,7 +5332,9 @@ int gsr_backward(const GsrBackwardArgs* a, void* stream_)
 #undef GSR_PRE_TAIL
 #undef GSR_PREB_NEXT
 #undef GSR_PREB
+#undef GSR_PREB_SO
 #undef GSR_PREB_
+#undef GSR_PREB_S
     if (want_cam)
         hipLaunchKernelGGL(k_cam_reduce, dim3(kCamVals, NB), dim3(256), 0, st, cam_partial, grid, a->d_viewmatrix, a->d_projmatrix, a->d_campos,
                            a->d_points_transform, bt);

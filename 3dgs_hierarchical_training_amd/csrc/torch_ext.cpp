@@ -96,12 +96,20 @@ std::vector<Tensor> debug_last()
 }
 
 // ---------------------------------------------------------------------------------------------------------------
+// GsrForwardArgs::sh_origin as a contiguous float32 [3] tensor (undefined = none)
+Tensor sh_origin_arg(const c10::optional<Tensor>& o)
+{
+    if (!o.has_value() || !o->defined()) return Tensor();
+    TORCH_CHECK(o->numel() == 3 && o->is_cuda(), "sh_origin: three numbers on the device of the model expected");
+    return f32c(o->reshape({3}));
+}
+
 std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> rasterize_forward(
     const Tensor& means3D_, const Tensor& sh_, const Tensor& colors_, const Tensor& opacities_, const Tensor& scales_,
     const Tensor& rotations_, const Tensor& cov3D_, const Tensor& sh_rest_, const Tensor& viewmatrix_, const Tensor& projmatrix_,
     const Tensor& campos_, const Tensor& bg_, const Tensor& xf_, int64_t H, int64_t W, double tanfovx, double tanfovy,
     double scale_modifier, int64_t sh_degree, bool raw_params, bool prefiltered, bool debug, const Tensor& prepared,
-    at::IntArrayRef batch_first_block, int64_t view_id, int64_t extras)
+    at::IntArrayRef batch_first_block, int64_t view_id, int64_t extras, const c10::optional<Tensor>& sh_origin_)
 {
     TORCH_CHECK(means3D_.is_cuda(), "GaussianRasterizer: tensors must be on a ROCm/HIP device (no CPU fallback)");
     const BatchArg batch(batch_first_block);
@@ -110,6 +118,7 @@ std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tenso
     const Tensor means3D = f32c(means3D_), sh = f32c(sh_), colors = f32c(colors_), opac = f32c(opacities_), scales = f32c(scales_),
                  rots = f32c(rotations_), cov = f32c(cov3D_), rest = f32c(sh_rest_), vm = f32c(viewmatrix_), pm = f32c(projmatrix_),
                  campos = f32c(campos_), bg = f32c(bg_), xf = f32c(xf_);
+    const Tensor sh_origin = sh_origin_arg(sh_origin_);
     const int64_t N = means3D.size(0);
     const int64_t M = has(sh) ? sh.size(1) + (has(rest) ? rest.size(1) : 0) : 0;
     const auto fo = means3D.options().dtype(at::kFloat);
@@ -149,6 +158,7 @@ std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tenso
     a.prepared = has(prepared) ? prepared.data_ptr() : nullptr;
     a.batch = batch.ptr();
     a.view_id = view_id;
+    a.sh_origin = fp(sh_origin);
     // extras: bit 0 = the clamped colour image (written by the blend kernel), bit 1 = the visibility bytes radii > 0 (written by the
     // preprocess; not available from a prepared buffer) -- what the reference's wrapper derives with one torch launch each
     Tensor clamped = (extras & 1) ? at::empty_like(color) : at::empty({0}, fo);
@@ -215,7 +225,7 @@ std::vector<Tensor> rasterize_backward(
     const Tensor& geom, const Tensor& image, const Tensor& binning, const Tensor& meta, const Tensor& grad_color, const Tensor& grad_depth,
     const Tensor& grad_alpha, int64_t H, int64_t W, double tanfovx, double tanfovy, double scale_modifier, int64_t sh_degree,
     bool raw_params, bool need_vm, bool need_pm, bool need_campos, bool need_xf, at::TensorList densify_stats, const Tensor& radii,
-    at::IntArrayRef batch_first_block)
+    at::IntArrayRef batch_first_block, const c10::optional<Tensor>& sh_origin_)
 {
     const c10::hip::HIPGuardMasqueradingAsCUDA guard(means3D.device());
     const BatchArg batch(batch_first_block);
@@ -239,6 +249,8 @@ std::vector<Tensor> rasterize_backward(
     GsrBackwardArgs a{};
     fill_backward_args(a, b, geom, image, binning, meta, H, W, tanfovx, tanfovy, scale_modifier, sh_degree, raw_params);
     a.batch = batch.ptr();
+    const Tensor sh_origin = sh_origin_arg(sh_origin_);
+    a.sh_origin = fp(sh_origin);
     a.d_means3D = fpm(d_means3D); a.d_means2D = fpm(d_means2D); a.d_opacities = fpm(d_opac);
     a.d_colors_precomp = fpm(d_col); a.d_shs = fpm(d_sh); a.d_scales = fpm(d_scales); a.d_rotations = fpm(d_rot);
     a.d_cov3D_precomp = fpm(d_cov); a.d_shs_rest = fpm(d_rest);
@@ -260,7 +272,7 @@ std::vector<Tensor> rasterize_backward_fused(
     at::TensorList adam_v, at::ArrayRef<double> adam_lr, double beta1, double beta2, double eps, int64_t step, const Tensor& next_vm,
     const Tensor& next_pm, const Tensor& next_campos, int64_t next_H, int64_t next_W, double next_tanfovx, double next_tanfovy,
     Tensor prepared_out, const Tensor& next_xf, int64_t next_sh_degree, at::TensorList densify_stats, const Tensor& radii,
-    at::IntArrayRef batch_first_block)
+    at::IntArrayRef batch_first_block, const c10::optional<Tensor>& sh_origin_)
 {
     const c10::hip::HIPGuardMasqueradingAsCUDA guard(means3D.device());
     const BatchArg batch(batch_first_block);
@@ -303,6 +315,8 @@ std::vector<Tensor> rasterize_backward_fused(
     a.scratch = scratch.data_ptr();
     a.fused_adam = &fa;
     a.batch = batch.ptr();
+    const Tensor sh_origin = sh_origin_arg(sh_origin_);
+    a.sh_origin = fp(sh_origin);
     GsrNextView nv{};
     // (the next render's own pose transform when its frame has one; otherwise it shares this render's)
     const Tensor nvm = f32c(next_vm), npm = f32c(next_pm), ncp = f32c(next_campos),
@@ -343,6 +357,7 @@ struct Cfg {
     int64_t next_H = 0, next_W = 0, next_D = -1;   // next_D: SH degree of the next render (-1 = this render's)
     int64_t view_id = 0;                           // GsrForwardArgs::view_id
     int64_t extras = 0;                            // bit 0: clamped colour output, bit 1: visibility bytes
+    Tensor sh_origin;                              // GsrForwardArgs::sh_origin (detached, not an autograd input), or undefined
     double next_tanfovx = 0, next_tanfovy = 0;
 };
 
@@ -363,7 +378,7 @@ class RasterizeFn : public torch::autograd::Function<RasterizeFn> {
         Tensor none;
         auto out = op.call(m3, s, c, o, sc, r, cv, rs, v, p, cp, b, x, cfg.H, cfg.W, cfg.tanfovx, cfg.tanfovy, cfg.scale_modifier,
                            cfg.sh_degree, cfg.raw_params, cfg.prefiltered, cfg.debug, cfg.prepared.defined() ? cfg.prepared : x.new_empty({0}, x.options().dtype(at::kByte)),
-                           cfg.batch, cfg.view_id, cfg.extras);
+                           cfg.batch, cfg.view_id, cfg.extras, cfg.sh_origin.defined() ? c10::optional<Tensor>(cfg.sh_origin) : c10::nullopt);
         // hand-over buffer for the NEXT render, filled by this render's backward (stream-ordered): allocated here so that it
         // can be returned to the caller as an ordinary output
         Tensor prep_out = has(cfg.next_vm) ? at::empty({(int64_t)gsr_prepared_bytes((int32_t)m3.size(0))}, m3.options().dtype(at::kByte))
@@ -390,6 +405,7 @@ class RasterizeFn : public torch::autograd::Function<RasterizeFn> {
         ctx->saved_data["xf_rows"] = (has(xf) && xf.dim() == 2) ? xf.size(0) : (int64_t)0;
         ctx->saved_data["done"] = false;
         ctx->saved_data["prep_out"] = prep_out;
+        ctx->saved_data["sh_origin"] = cfg.sh_origin.defined() ? cfg.sh_origin : x.new_empty({0});
         ctx->saved_data["next_cam"] = std::vector<Tensor>{has(cfg.next_vm) ? f32c(cfg.next_vm) : x, has(cfg.next_vm) ? f32c(cfg.next_pm) : x,
                                                           has(cfg.next_vm) ? f32c(cfg.next_campos) : x,
                                                           has(cfg.next_xf) ? f32c(cfg.next_xf) : x.new_empty({0})};
@@ -427,6 +443,8 @@ class RasterizeFn : public torch::autograd::Function<RasterizeFn> {
         std::vector<Tensor> dens = ctx->saved_data["dens"].toTensorVector();
         const std::vector<int64_t> bfb = ctx->saved_data["batch"].toIntVector();
         const Tensor radii = ctx->saved_data["radii"].toTensor();
+        const Tensor sho_t = ctx->saved_data["sh_origin"].toTensor();
+        const c10::optional<Tensor> sho = has(sho_t) ? c10::optional<Tensor>(sho_t) : c10::nullopt;
         if (n_adam) {
             // a second backward through the same forward would apply the optimizer step twice
             TORCH_CHECK(!ctx->saved_data["done"].toBool(), "fused_adam: backward() ran twice on the same render (retain_graph); the in-kernel "
@@ -445,13 +463,13 @@ class RasterizeFn : public torch::autograd::Function<RasterizeFn> {
                              ctx->saved_data["b1"].toDouble(), ctx->saved_data["b2"].toDouble(), ctx->saved_data["eps"].toDouble(),
                              step_now, nc[0], nc[1], nc[2], ctx->saved_data["next_H"].toInt(),
                              ctx->saved_data["next_W"].toInt(), ctx->saved_data["next_tfx"].toDouble(), ctx->saved_data["next_tfy"].toDouble(),
-                             ctx->saved_data["prep_out"].toTensor(), nc[3], ctx->saved_data["next_D"].toInt(), dens, radii, bfb);
+                             ctx->saved_data["prep_out"].toTensor(), nc[3], ctx->saved_data["next_D"].toInt(), dens, radii, bfb, sho);
             commit_p[0] += 1;   // the update has been enqueued: the optimizer's step count advances (FusedAdam reconciles from this)
             out[1] = r[0]; out[9] = r[1]; out[10] = r[2]; out[11] = r[3]; d_xf = r[4];
         } else {
             static auto op = c10::Dispatcher::singleton().findSchemaOrThrow("gsr::rasterize_backward", "").typed<decltype(rasterize_backward)>();
             auto r = op.call(sv[0], sv[1], sv[2], sv[3], sv[4], sv[5], sv[6], sv[7], sv[8], sv[9], sv[10], sv[11], sv[12], sv[13], sv[14],
-                             sv[15], sv[16], orE(gc), orE(gd), orE(ga), H, W, tfx, tfy, smod, D, raw, need_vm, need_pm, need_cp, need_xf, dens, radii, bfb);
+                             sv[15], sv[16], orE(gc), orE(gd), orE(ga), H, W, tfx, tfy, smod, D, raw, need_vm, need_pm, need_cp, need_xf, dens, radii, bfb, sho);
             out[0] = r[0]; out[1] = r[1]; out[2] = r[2]; out[3] = r[3]; out[4] = r[4]; out[5] = r[5]; out[6] = r[6]; out[7] = r[7]; out[8] = r[8];
             out[9] = r[9]; out[10] = r[10]; out[11] = r[11]; d_xf = r[12];
         }
@@ -468,7 +486,8 @@ std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> rasterize(
     bool prefiltered, bool debug, bool cam_grad, at::TensorList adam_m, at::TensorList adam_v, at::ArrayRef<double> adam_lr, double beta1,
     double beta2, double eps, int64_t step, const Tensor& prepared, const Tensor& next_vm, const Tensor& next_pm, const Tensor& next_campos,
     int64_t next_H, int64_t next_W, double next_tanfovx, double next_tanfovy, const Tensor& next_xf, int64_t next_sh_degree,
-    const Tensor& adam_commit, at::TensorList densify_stats, at::IntArrayRef batch_first_block, int64_t view_id, int64_t extras)
+    const Tensor& adam_commit, at::TensorList densify_stats, at::IntArrayRef batch_first_block, int64_t view_id, int64_t extras,
+    const c10::optional<Tensor>& sh_origin)
 {
     Cfg cfg{H, W, sh_degree, step, tanfovx, tanfovy, scale_modifier, beta1, beta2, eps, raw_params, prefiltered, debug, cam_grad,
             std::vector<double>(adam_lr.begin(), adam_lr.end()), adam_m.vec(), adam_v.vec()};
@@ -477,6 +496,7 @@ std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> rasterize(
     cfg.batch.assign(batch_first_block.begin(), batch_first_block.end());
     cfg.view_id = view_id;
     cfg.extras = extras;
+    if (sh_origin.has_value() && sh_origin->defined()) cfg.sh_origin = sh_origin->detach();
     if (!adam_m.empty()) {
         TORCH_CHECK(has(adam_commit) && adam_commit.is_cpu() && adam_commit.scalar_type() == at::kLong, "fused_adam: adam_commit must be a CPU int64 tensor");
         cfg.adam_commit = adam_commit;
@@ -500,12 +520,14 @@ std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> rasterize_for
     bool prefiltered, bool debug, bool cam_grad, at::TensorList adam_m, at::TensorList adam_v, at::ArrayRef<double> adam_lr, double beta1,
     double beta2, double eps, int64_t step, const Tensor& prepared, const Tensor& next_vm, const Tensor& next_pm, const Tensor& next_campos,
     int64_t next_H, int64_t next_W, double next_tanfovx, double next_tanfovy, const Tensor& next_xf, int64_t next_sh_degree,
-    const Tensor& adam_commit, at::TensorList densify_stats, at::IntArrayRef batch_first_block, int64_t view_id, int64_t extras)
+    const Tensor& adam_commit, at::TensorList densify_stats, at::IntArrayRef batch_first_block, int64_t view_id, int64_t extras,
+    const c10::optional<Tensor>& sh_origin)
 {
     (void)means2D; (void)next_xf; (void)next_sh_degree; (void)adam_commit; (void)densify_stats; (void)cam_grad; (void)adam_m; (void)adam_v; (void)adam_lr; (void)beta1; (void)beta2; (void)eps; (void)step;
     (void)next_vm; (void)next_pm; (void)next_campos; (void)next_H; (void)next_W; (void)next_tanfovx; (void)next_tanfovy;
     auto out = rasterize_forward(means3D, sh, colors, opac, scales, rots, cov, rest, vm, pm, campos, bg, (has(xf) && xf.dim() == 2) ? xf.slice(0, 0, 3) : xf, H, W,
-                                 tanfovx, tanfovy, scale_modifier, sh_degree, raw_params, prefiltered, debug, prepared, batch_first_block, view_id, extras);
+                                 tanfovx, tanfovy, scale_modifier, sh_degree, raw_params, prefiltered, debug, prepared, batch_first_block, view_id, extras,
+                                 sh_origin);
     return {std::get<0>(out), std::get<1>(out), std::get<2>(out), std::get<3>(out), at::empty({0}, means3D.options().dtype(at::kByte)), std::get<8>(out),
             std::get<9>(out)};
 }
@@ -814,25 +836,28 @@ TORCH_LIBRARY(gsr, m)
     m.def("rasterize_forward(Tensor means3D, Tensor sh, Tensor colors_precomp, Tensor opacities, Tensor scales, Tensor rotations, "
           "Tensor cov3D_precomp, Tensor sh_rest, Tensor viewmatrix, Tensor projmatrix, Tensor campos, Tensor bg, Tensor points_transform, "
           "int image_height, int image_width, float tanfovx, float tanfovy, float scale_modifier, int sh_degree, bool raw_params, "
-          "bool prefiltered, bool debug, Tensor prepared, int[] batch_first_block, int view_id=0, int extras=0) -> (Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)");
+          "bool prefiltered, bool debug, Tensor prepared, int[] batch_first_block, int view_id=0, int extras=0, Tensor? sh_origin=None) -> (Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)");
     m.def("rasterize_backward(Tensor means3D, Tensor sh, Tensor colors_precomp, Tensor opacities, Tensor scales, Tensor rotations, "
           "Tensor cov3D_precomp, Tensor sh_rest, Tensor viewmatrix, Tensor projmatrix, Tensor campos, Tensor bg, Tensor points_transform, "
           "Tensor geom, Tensor image, Tensor binning, Tensor meta, Tensor grad_color, Tensor grad_depth, Tensor grad_alpha, "
           "int image_height, int image_width, float tanfovx, float tanfovy, float scale_modifier, int sh_degree, bool raw_params, "
-          "bool need_viewmatrix, bool need_projmatrix, bool need_campos, bool need_points_transform, Tensor(a!)[] densify_stats, Tensor radii, int[] batch_first_block) -> Tensor[]");
+          "bool need_viewmatrix, bool need_projmatrix, bool need_campos, bool need_points_transform, Tensor(a!)[] densify_stats, Tensor radii, int[] batch_first_block, "
+          "Tensor? sh_origin=None) -> Tensor[]");
     m.def("rasterize_backward_fused(Tensor(a!) means3D, Tensor(b!) sh, Tensor(c!) sh_rest, Tensor(d!) opacities, Tensor(e!) scales, "
           "Tensor(f!) rotations, Tensor viewmatrix, Tensor projmatrix, Tensor campos, Tensor bg, Tensor points_transform, Tensor geom, "
           "Tensor image, Tensor binning, Tensor meta, Tensor grad_color, Tensor grad_depth, Tensor grad_alpha, int image_height, "
           "int image_width, float tanfovx, float tanfovy, float scale_modifier, int sh_degree, bool need_viewmatrix, bool need_projmatrix, "
           "bool need_campos, bool need_points_transform, Tensor(g!)[] adam_m, Tensor(h!)[] adam_v, float[] adam_lr, float beta1, "
           "float beta2, float eps, int step, Tensor next_viewmatrix, Tensor next_projmatrix, Tensor next_campos, int next_height, "
-          "int next_width, float next_tanfovx, float next_tanfovy, Tensor(i!) prepared_out, Tensor next_points_transform, int next_sh_degree, Tensor(j!)[] densify_stats, Tensor radii, int[] batch_first_block) -> Tensor[]");
+          "int next_width, float next_tanfovx, float next_tanfovy, Tensor(i!) prepared_out, Tensor next_points_transform, int next_sh_degree, Tensor(j!)[] densify_stats, Tensor radii, int[] batch_first_block, "
+          "Tensor? sh_origin=None) -> Tensor[]");
     m.def("rasterize(Tensor means3D, Tensor means2D, Tensor sh, Tensor colors_precomp, Tensor opacities, Tensor scales, Tensor rotations, "
           "Tensor cov3D_precomp, Tensor sh_rest, Tensor viewmatrix, Tensor projmatrix, Tensor campos, Tensor bg, Tensor points_transform, "
           "int image_height, int image_width, float tanfovx, float tanfovy, float scale_modifier, int sh_degree, bool raw_params, "
           "bool prefiltered, bool debug, bool cam_grad, Tensor[] adam_m, Tensor[] adam_v, float[] adam_lr, float beta1, float beta2, "
           "float eps, int step, Tensor prepared, Tensor next_viewmatrix, Tensor next_projmatrix, Tensor next_campos, int next_height, "
-          "int next_width, float next_tanfovx, float next_tanfovy, Tensor next_points_transform, int next_sh_degree, Tensor adam_commit, Tensor[] densify_stats, int[] batch_first_block, int view_id=0, int extras=0) -> "
+          "int next_width, float next_tanfovx, float next_tanfovy, Tensor next_points_transform, int next_sh_degree, Tensor adam_commit, Tensor[] densify_stats, int[] batch_first_block, int view_id=0, int extras=0, "
+          "Tensor? sh_origin=None) -> "
           "(Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)");
     m.def("mark_visible(Tensor means3D, Tensor viewmatrix, Tensor projmatrix) -> Tensor");
     m.def("photometric_loss_forward(Tensor render, Tensor target, float lambda_dssim, bool clamp) -> (Tensor, Tensor)");

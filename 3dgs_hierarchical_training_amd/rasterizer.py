@@ -306,7 +306,7 @@ def _ecpu():
 
 def _rasterize_ext(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, rs, sh_rest, raw_params,
                    fused_adam, points_transform, prepared=None, prepare_next=None, next_points_transform=None, densify_stats=None,
-                   batch_first_block=None, fused_adam_deferred=False, view_id=0, extras=0):
+                   batch_first_block=None, fused_adam_deferred=False, view_id=0, extras=0, sh_origin=None):
     """torch.ops.gsr.rasterize: empty tensors stand for None; the camera tensors of the settings tuple are ordinary inputs
     (their gradients are produced when one of them requires grad)."""
     ops = E.load()
@@ -326,6 +326,12 @@ def _rasterize_ext(means3D, means2D, sh, colors_precomp, opacities, scales, rota
     if nb > 1 and (tuple(vm.shape) != (nb, 4, 4) or tuple(pm.shape) != (nb, 4, 4) or tuple(cp.shape) != (nb, 3)):
         raise RuntimeError("batch: raster_settings.viewmatrix / projmatrix must be [B,4,4] and campos [B,3]")
     xf = e if points_transform is None else points_transform.to(dev)
+    if sh_origin is not None:
+        if sh_origin.numel() != 3:
+            raise RuntimeError("sh_origin must hold three numbers (the origin of the SH view direction)")
+        if sh is None or nb > 1 or prepared is not None or prepare_next is not None:
+            raise RuntimeError("sh_origin needs SH coefficients and is not served with a batch, prepared or prepare_next")
+        sh_origin = sh_origin.detach().to(device=dev, dtype=torch.float32).reshape(3)
     m, v, lr, b1, b2, eps, step, commit = [], [], [], 0.0, 0.0, 0.0, 0, None
     if fused_adam is not None and not (torch.is_grad_enabled() and (means3D.requires_grad or opacities.requires_grad)):
         fused_adam = None       # a render that cannot reach a backward (torch.no_grad(), detached parameters): nothing to plan
@@ -365,7 +371,8 @@ def _rasterize_ext(means3D, means2D, sh, colors_precomp, opacities, scales, rota
             0.0 if nx is None else float(nx.tanfovx), 0.0 if nx is None else float(nx.tanfovy),
             e if (nx is None or next_points_transform is None) else next_points_transform.to(dev),
             -1 if nx is None else int(nx.sh_degree), _ecpu() if commit is None else commit,
-            [] if densify_stats is None else list(densify_stats), [] if nb <= 1 else [int(x) for x in batch_first_block], int(view_id), int(extras))
+            [] if densify_stats is None else list(densify_stats), [] if nb <= 1 else [int(x) for x in batch_first_block], int(view_id), int(extras),
+            sh_origin)
     if not rs.debug:
         out = ops.rasterize(*args)
         if extras:       # (color, radii, depth, alpha, clamped colour, visibility bytes)
@@ -396,7 +403,7 @@ def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales,
 def rasterize_gaussians_raw(means3D, means2D, features_dc, features_rest, opacity_logit, log_scales, rotations_raw,
                             raster_settings, fused_adam=None, points_transform=None, prepared=None, prepare_next=None,
                             next_points_transform=None, densify_stats=None, batch_first_block=None, fused_adam_deferred=False,
-                            view_id=0, extras=0):
+                            view_id=0, extras=0, sh_origin=None):
     """Extension ("next" row f-2): rasterize straight from HTGaussianModel's raw parameters (_xyz, _features_dc,
     _features_rest, _opacity, _scaling, _rotation; /root/reference/scene/gaussian_model_ht.py:74-82) with the
     activations of :49-65,128-133,176-188 fused into the HIP kernels; gradients are w.r.t. the raw tensors.
@@ -439,13 +446,21 @@ def rasterize_gaussians_raw(means3D, means2D, features_dc, features_rest, opacit
     extras (extension binding; not together with prepare_next): bit 0 adds the CLAMPED colour image -- `clamp(color, 0, 1)`, written by
     the blend kernel, differentiable like torch.clamp -- and bit 1 the visibility bytes `radii > 0` (uint8 [N], written by the
     preprocess) to the returned tuple: (color, radii, depth, alpha, clamped, visible) -- what the reference's render wrapper derives
-    with a torch launch each (gaussian_model_ht.py:883, :905)."""
+    with a torch launch each (gaussian_model_ht.py:883, :905).
+
+    sh_origin = three numbers o (detached): the SH colour is evaluated in the direction normalize(means3D - o) of the UNtransformed
+    means instead of normalize(posed mean - campos) -- the reference's `convert_SHs_python` render with `view_dependent`, whose origin
+    is the camera centre in the model's own frame, `get_RT(uid).inverse()[:3, 3].detach()` (gaussian_model_ht.py:845-865).  The
+    colour then sends no gradient to the pose or the camera; its direction gradient reaches means3D directly (include/gsr.h
+    GsrForwardArgs::sh_origin).  Not with batch_first_block, prepared or prepare_next."""
     if not E.use_ctypes():
         return _rasterize_ext(means3D, means2D, features_dc, None, opacity_logit, log_scales, rotations_raw, None, raster_settings,
                               features_rest, True, fused_adam, points_transform, prepared, prepare_next, next_points_transform,
-                              densify_stats, batch_first_block, fused_adam_deferred, view_id, extras)
-    if prepared is not None or extras or prepare_next is not None or densify_stats is not None or batch_first_block is not None or fused_adam_deferred:
-        raise RuntimeError("prepared / prepare_next / densify_stats / batch_first_block / fused_adam_deferred are served by the PyTorch extension binding only")
+                              densify_stats, batch_first_block, fused_adam_deferred, view_id, extras, sh_origin)
+    if prepared is not None or extras or prepare_next is not None or densify_stats is not None or batch_first_block is not None or fused_adam_deferred \
+            or sh_origin is not None:
+        raise RuntimeError("prepared / prepare_next / densify_stats / batch_first_block / fused_adam_deferred / sh_origin are served by the "
+                           "PyTorch extension binding only")
     e = torch.Tensor([])
     return _RasterizeGaussians.apply(means3D, means2D, features_dc, e, opacity_logit, log_scales, rotations_raw, e,
                                      raster_settings, features_rest, True, *_cam_inputs(raster_settings), fused_adam, points_transform, view_id)

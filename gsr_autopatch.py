@@ -28,8 +28,11 @@ Importing this module BEFORE the trainer swaps both for the HIP kernels of this 
     optimizer pass is gone.  (`GSR_AUTOPATCH_DEFERRED=0`: gradients to .grad and a one-launch FusedAdam.step() instead;
     `GSR_AUTOPATCH_DEFERRED_MIN_N`: the same for models below that many Gaussians, default 0.)  The returned dict is the
     reference's (`image` clamped, `depth`, `alpha`, `viewspace_points` whose .grad the backward fills, `visibility_filter`,
-    `radii`).  `override_color`, `compute_cov3D_python`, `convert_SHs_python`, CPU tensors or an unexpected parameter layout
-    fall back to the ORIGINAL method.  `GSR_AUTOPATCH_RENDER=0` leaves the method alone; `GSR_AUTOPATCH_POSE=0` keeps pose
+    `radii`).  `convert_SHs_python=True` with `view_dependent` (the trainer's default) takes the same route: the SH colour is
+    evaluated in the kernels in the reference's direction, normalize(`_xyz` - `get_RT(uid).inverse()[:3, 3]`) of the UNposed means
+    (gaussian_model_ht.py:845-865, include/gsr.h GsrForwardArgs::sh_origin); `GSR_AUTOPATCH_PYTHON_SH=0` keeps it on the original
+    method.  `override_color`, `compute_cov3D_python`, `convert_SHs_python` without `view_dependent`, CPU tensors or an unexpected
+    parameter layout fall back to the ORIGINAL method.  `GSR_AUTOPATCH_RENDER=0` leaves the method alone; `GSR_AUTOPATCH_POSE=0` keeps pose
     renders (rotate_xyz / rotate_seq) on the original method.
   * the frame poses (round 6): a lietorch SE3 `LieGroupParameter` that `get_xyz` reads (`P[k]`, gaussian_model_ht.py:135-148,
     :346-386) reaches the rasterizer through ONE autograd node over its six tangent numbers (`torch.ops.gsr.pose_matrix`: the [3,4]
@@ -341,6 +344,26 @@ def _view_id(cam, g) -> int:
         return 0
 
 
+def _sh_origin(g, cam, dev):
+    """The origin of the SH view direction of the reference's `convert_SHs_python` render (gaussian_model_ht.py:845-865):
+    `get_RT(uid).inverse()[:3, 3].detach()` -- the camera centre in the model's own frame -- without a host synchronisation.  `get_RT`
+    (:150-165) takes the identity when `P` is None, `P[0]` under `rotate_xyz` and `P[uid]` otherwise (the camera's uid, not seq_idx).
+    A lietorch-shaped pose: -R^T t of the detached `pose_opt.pose_matrix` (one kernel, three numbers); any other pose object -- or
+    GSR_AUTOPATCH_POSE_FUSED=0 -- the reference's own statement."""
+    P = getattr(g, "P", None)
+    if P is None:
+        return torch.zeros(3, dtype=torch.float32, device=dev)
+    uid = getattr(cam, "uid", None)
+    p = P[0] if getattr(g, "rotate_xyz", False) else (P[uid] if isinstance(uid, int) else None)
+    if p is not None and os.environ.get("GSR_AUTOPATCH_POSE_FUSED", "1") != "0":
+        PO = importlib.import_module("3dgs_hierarchical_training_amd.pose_opt")
+        if PO.is_lie_pose(p) and (p.is_cuda or not _REQUIRE_CUDA):
+            with torch.no_grad():
+                M = PO.pose_matrix(p, _ops())
+                return -(M[:, :3].t() @ M[:, 3])
+    return g.get_RT(uid).inverse()[:3, 3].detach()
+
+
 def _raw_tensors(g):
     """The six raw parameter tensors when they have the layout the fused path takes, else None."""
     ts = [getattr(g, k, None) for k in RAW_NAMES]
@@ -367,7 +390,12 @@ def render_fused(self, viewpoint_camera, scaling_modifier=1.0, invert_bg_color=F
     orig = next((f for c, a, f in _patched_render_classes if a == "render" and isinstance(self, c)), None)
     g = getattr(self, "gaussians", None)
     ts = None
-    if override_color is None and not compute_cov3D_python and not convert_SHs_python and g is not None:
+    # convert_SHs_python: served when the colour is the view-dependent SH evaluation (`view_dependent`, arguments/__init__.py:83);
+    # the raw-DC colour of view_dependent=False stays on the original method
+    # (the origin travels through the PyTorch extension binding only: GSR_BINDING=ctypes keeps these renders on the original method)
+    python_sh = bool(convert_SHs_python) and getattr(self, "view_dependent", False) is True and \
+        os.environ.get("GSR_AUTOPATCH_PYTHON_SH", "1") != "0" and _ext_binding()
+    if override_color is None and not compute_cov3D_python and (python_sh or not convert_SHs_python) and g is not None:
         ts = _raw_tensors(g)
     posed = ts is not None and (getattr(g, "rotate_xyz", False) or getattr(g, "rotate_xyz_inverse", False) or getattr(g, "rotate_seq", False))
     if posed and os.environ.get("GSR_AUTOPATCH_POSE", "1") == "0":
@@ -403,6 +431,7 @@ def render_fused(self, viewpoint_camera, scaling_modifier=1.0, invert_bg_color=F
         projmatrix=viewpoint_camera.full_proj_transform, sh_degree=g.active_sh_degree, campos=viewpoint_camera.camera_center,
         prefiltered=False, debug=False)
     M = _pose_matrix(g) if posed else None
+    sh_origin = _sh_origin(g, viewpoint_camera, dev) if python_sh else None
     # DEFERRED optimizer step: when the model's optimizer is the FusedAdam this module handed out, the backward kernel also computes
     # the Adam update -- into shadow buffers, the model untouched -- and the trainer's `optimizer.step()` adopts it by swapping
     # storages.  Everything the trainer may do in between keeps its meaning (surgery sees the un-updated state and drops the
@@ -420,12 +449,13 @@ def render_fused(self, viewpoint_camera, scaling_modifier=1.0, invert_bg_color=F
         # no torch launch for `clamp(0, 1)` / `radii > 0`
         image_raw, radii, depth, alpha, image, vis8 = R.rasterize_gaussians_raw(
             xyz, screenspace_points, f_dc, f_rest, opacity, scaling, rotation, settings, points_transform=M, fused_adam=opt if deferred else None,
-            fused_adam_deferred=deferred, view_id=_view_id(viewpoint_camera, g), extras=3)
+            fused_adam_deferred=deferred, view_id=_view_id(viewpoint_camera, g), extras=3, sh_origin=sh_origin)
         visible = vis8.view(torch.bool) if vis8.numel() == radii.numel() else radii > 0
     else:
         image_raw, radii, depth, alpha = R.rasterize_gaussians_raw(xyz, screenspace_points, f_dc, f_rest, opacity, scaling, rotation,
                                                                    settings, points_transform=M, fused_adam=opt if deferred else None,
-                                                                   fused_adam_deferred=deferred, view_id=_view_id(viewpoint_camera, g))
+                                                                   fused_adam_deferred=deferred, view_id=_view_id(viewpoint_camera, g),
+                                                                   sh_origin=sh_origin)
         image = image_raw.clamp(0, 1)
         visible = radii > 0
     image._gsr_raw = (image_raw, image._version)       # lets the patched Loss.forward fuse this clamp into the loss kernels

@@ -117,6 +117,13 @@ typedef struct GsrForwardArgs {
      *   visible [N] bytes: radii > 0, by the preprocess -- NOT written by a forward that takes a `prepared` buffer (no preprocess runs). */
     float* out_color_clamped;
     uint8_t* visible;
+    /* ---- version 111: origin of the SH view direction (3 floats, device).  NULL = the module's direction, normalize(posed mean - campos).
+     * Set: the direction is normalize(means3D - sh_origin) with the UNtransformed mean (points_transform moves the geometry, not the
+     * direction) -- the reference's `convert_SHs_python` render with `view_dependent` (/root/reference/scene/gaussian_model_ht.py:845-865),
+     * whose origin is the camera centre in the model's own frame, `get_RT(uid).inverse()[:3, 3]`, detached.  Needs shs; refused
+     * (GSR_ERR_ARG) with a batch of B > 1 or a `prepared` buffer.  At sh_degree 0 the colour does not depend on the direction: the
+     * result is bit-identical to NULL. */
+    const float* sh_origin;
 } GsrForwardArgs;
 
 typedef struct GsrForwardOut {
@@ -239,6 +246,10 @@ typedef struct GsrBackwardArgs {
     void* prepared_out;
     const struct GsrDensifyStats* densify_stats; /* NULL = none */
     const struct GsrBatch* batch;                 /* the forward's batch (NULL = one model) */
+    /* version 111: the forward's sh_origin (see GsrForwardArgs).  The colour's share of the mean gradient is then w.r.t. the
+     * untransformed mean: it is added to d_means3D after the R^T chain of points_transform and reaches none of d_points_transform,
+     * d_campos, d_viewmatrix.  Needs shs; refused (GSR_ERR_ARG) with a batch of B > 1 or next_view. */
+    const float* sh_origin;
 } GsrBackwardArgs;
 
 size_t gsr_geom_bytes(int32_t N);
@@ -266,7 +277,8 @@ int gsr_mark_visible(int32_t N, const float* means3D, const float* viewmatrix, c
 const char* gsr_last_error(void);
 /* 100 * major + minor.  110 (round 6): GsrForwardArgs ends with view_id, out_color_clamped, visible (appended in round 5 under
  * version 100: a caller compiled against a shorter struct must be rebuilt -- check gsr_version() >= 110 AND
- * gsr_struct_bytes(0) == sizeof(GsrForwardArgs), gsr_struct_bytes(1) == sizeof(GsrBackwardArgs) at start-up). */
+ * gsr_struct_bytes(0) == sizeof(GsrForwardArgs), gsr_struct_bytes(1) == sizeof(GsrBackwardArgs) at start-up).
+ * 111: GsrForwardArgs and GsrBackwardArgs end with sh_origin. */
 int gsr_version(void);
 size_t gsr_struct_bytes(int32_t which); /* 0 GsrForwardArgs, 1 GsrBackwardArgs, 2 GsrForwardOut; anything else 0 */
 

@@ -12,7 +12,9 @@ densification.  Inputs are resident in HBM before the timed region.  N>1 = one i
 per GPU ("one segment per GPU"): weak scaling, no data-path collective; value = images of all
 ranks / max-over-ranks time.
 
-Rank 0 prints ONE JSON line.  Besides the contract's keys:
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the steps, writes --dump-outputs and prints the contract's keys
+with the counters of the timed steps; everything below takes work of its own after them and comes with `--full`:
+  `stage_ms`       per-stage device times from a few untimed profiled steps after the timed ones (`fwd_bwd_ms` sums them).
   `roofline`       the per-tile forward blend kernel (the kernel BASELINE.json's north_star names): achieved =
                    algorithmic bytes (44 R_eff + 28 P + 8 T) / average launch duration measured with HIP
                    events on the launch stream inside the timed region; `peak` = 8 TB/s (vendor), `peak_measured` = the
@@ -100,8 +102,11 @@ def parse():
     ap.add_argument("--height", type=int, default=545)
     ap.add_argument("--sh-degree", type=int, default=3)
     ap.add_argument("--clustered", action="store_true", help="load-imbalance variant of the scene (synthetic.make_scene)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip dropin / other_workloads / merge / copy ceiling")
+    ap.add_argument("--full", action="store_true", help="after the headline, also measure what the line reports beside it: the per-stage "
+                    "profile and roofline, the process-group probe and merge level, the drop-in / other-workload / copy-ceiling / host-cost "
+                    "legs and the CPU baseline (a plain run sets up, warms up, times the steps, dumps and prints the headline only)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip dropin / other_workloads / merge / copy ceiling")
     ap.add_argument("--views", type=int, default=8, help="posed views the timed loop rotates through (1 = the same view every step)")
     ap.add_argument("--no-densify-stats", action="store_true", help="leave the reference's per-iteration densification statistics "
                     "(max_radii2D / xyz_gradient_accum / denom, ht3dgs_trainer.py:141-147) out of the step")
@@ -1031,6 +1036,62 @@ def main():
     if args.dump_outputs and rank == 0:      # before any further step or render changes the model
         dumped = dump_outputs(args.dump_outputs, last_pkg[0], params, den)
     last_pkg[0] = None
+    per_rank_ms = None
+    if dist is not None:
+        # MAX over ranks, as the contract asks -- taken from ONE all_gather of the ranks' own times, so that the line also shows every
+        # rank's ms per step and the slowest / fastest ratio (VERDICT r5 item 9: the first real 8-GPU run shows stragglers by itself)
+        tdev = torch.device("cpu") if dist.get_backend() == "gloo" else dev
+        t = torch.tensor([elapsed], device=tdev, dtype=torch.float64)
+        allt = [torch.empty(1, device=tdev, dtype=torch.float64) for _ in range(world)]
+        dist.all_gather(allt, t)
+        per_rank = [float(x.item()) for x in allt]
+        per_rank_ms = [1000.0 * x / args.steps for x in per_rank]
+        elapsed = max(per_rank)
+    ms_per_step = 1000.0 * elapsed / args.steps
+
+    # host-side enqueue intervals of the timed steps (a stall of the launching thread shows up as max >> median)
+    gaps = sorted(1e3 * (b - a) for a, b in zip(stamps[:-1], stamps[1:]))
+    step_host = {"median": gaps[len(gaps) // 2], "p90": gaps[min(len(gaps) - 1, (9 * len(gaps)) // 10)], "max": gaps[-1]} if gaps else {}
+    res = {
+        "metric": METRIC,
+        "value": world * args.steps / elapsed, "unit": "images/s", "n_gpus": world, "steps": args.steps,
+        "warmup": args.warmup, "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+        "config": {"workload": f"syn-{N} Gaussians{' (clustered)' if args.clustered else ''}, {W}x{H}, SH degree {deg}, pinhole camera "
+                               f"(FoVx {syn.FOVX_FRANCIS}); the timed loop rotates through {len(views)} posed views of the cloud (view 0 = the identity "
+                               "pose of the BASELINE recipe, the others rigid motions of it by <= 0.05 rad / ~0.05 units), each with its own "
+                               "U[0,1] target; one view per step per GPU",
+                   "views": len(views), "densification_statistics_in_step": den is not None,
+                   "gaussians": N, "width": W, "height": H, "sh_degree": deg, "visible": n_visible,
+                   "parallelism": f"{world} independent segment replica(s), no data-path collective",
+                   "train_step": "activations + rasterize fwd + 0.8*L1+0.2*(1-SSIM) + backward + Adam(eps=1e-15) on all 59 floats "
+                                 "per Gaussian (update applied inside the per-Gaussian backward kernel" +
+                                 ("" if args.no_prepare_next else ", which also runs the NEXT step's preprocess on the updated parameters: "
+                                  "one preprocess per step either way, k_preprocess is just not a separate launch") +
+                                 "); the unmodified reference trainer reaches the `dropin` path instead"},
+        "step_host_ms": step_host,
+        "spec_overflows": c1["spec_overflows"] - c0["spec_overflows"],
+        # the list cut (include/gsr.h "list_cut") over the timed steps: renders that ran it, renders whose lists had to be repaired on the
+        # device (a tile needed more than it kept: the counter of re-runs), tiles repaired, and per render the chunks of the depth
+        # order behind the frame's cut (of `chunks`) and the deep tiles served one by one
+        "list_cut": {"renders": lc1[0] - lc0[0], "renders_repaired": lc1[1] - lc0[1], "tiles_repaired": lc1[2] - lc0[2],
+                     "chunks_behind_cut_per_render": (lc1[3] - lc0[3]) / max(1, lc1[0] - lc0[0]),
+                     "deep_tiles_per_render": (lc1[4] - lc0[4]) / max(1, lc1[0] - lc0[0])},
+        "speculative_forwards": c1["spec_forwards"] - c0["spec_forwards"], "exact_forwards": c1["exact_forwards"] - c0["exact_forwards"],
+    }
+    if per_rank_ms is not None:
+        res["per_rank_ms_per_step"] = per_rank_ms
+        res["rank_time_max_over_min"] = max(per_rank_ms) / min(per_rank_ms)
+    if dumped is not None:
+        res["dump_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(res), flush=True)
+        if dist is not None:
+            dist.destroy_process_group()
+        return
+
+    # --full: everything below runs after the headline is measured and never changes it
     # R_eff of every view (the roofline's algorithmic bytes are the mean over the views the timed launches rendered)
     r_eff_views, r_views = [], []
     with torch.no_grad():
@@ -1045,17 +1106,6 @@ def main():
     lib.gsr_set_option(b"profile", 0)
     prof = read_profile(lib, STAGES)
     prof["blend_fwd"] = prof_blend   # the figure the roofline uses: measured inside the timed region
-    per_rank_ms = None
-    if dist is not None:
-        # MAX over ranks, as the contract asks -- taken from ONE all_gather of the ranks' own times, so that the line also shows every
-        # rank's ms per step and the slowest / fastest ratio (VERDICT r5 item 9: the first real 8-GPU run shows stragglers by itself)
-        tdev = torch.device("cpu") if dist.get_backend() == "gloo" else dev
-        t = torch.tensor([elapsed], device=tdev, dtype=torch.float64)
-        allt = [torch.empty(1, device=tdev, dtype=torch.float64) for _ in range(world)]
-        dist.all_gather(allt, t)
-        per_rank = [float(x.item()) for x in allt]
-        per_rank_ms = [1000.0 * x / args.steps for x in per_rank]
-        elapsed = max(per_rank)
     rccl = None     # filled under the watchdog below, after the throughput result is safe
 
     # host-side work of the library per forward + backward in the timed steps (counters of gsr_get_counter, read after them)
@@ -1120,10 +1170,6 @@ def main():
         return
     P = W * H
     T = ((W + 15) // 16) * ((H + 15) // 16)
-    ms_per_step = 1000.0 * elapsed / args.steps
-    # host-side enqueue intervals of the timed steps (a stall of the launching thread shows up as max >> median)
-    gaps = sorted(1e3 * (b - a) for a, b in zip(stamps[:-1], stamps[1:]))
-    step_host = {"median": gaps[len(gaps) // 2], "p90": gaps[min(len(gaps) - 1, (9 * len(gaps)) // 10)], "max": gaps[-1]} if gaps else {}
     stage_ms = {k: (v[0] / v[1] if v[1] else None) for k, v in prof.items()}
     fwd_stages = ["preprocess_fwd", "sort_depth", "scan", "emit", "sort_tile", "ranges", "blend_fwd"]
     bwd_stages = ["blend_bwd", "preprocess_bwd"]
@@ -1231,40 +1277,9 @@ def main():
                 "valu": valu_fwd, "binding_roof": binds,
                 "algorithmic_bytes_per_launch": alg_bytes, "avg_launch_ms": blend_ms,
                 "launches_timed": prof["blend_fwd"][1], "R": R, "R_eff": R_eff, "R_eff_per_view": r_eff_views, "P": P, "T": T}
-    res = {
-        "metric": METRIC,
-        "value": world * args.steps / elapsed, "unit": "images/s", "n_gpus": world, "steps": args.steps,
-        "warmup": args.warmup, "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "weak",
-        "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-        "config": {"workload": f"syn-{N} Gaussians{' (clustered)' if args.clustered else ''}, {W}x{H}, SH degree {deg}, pinhole camera "
-                               f"(FoVx {syn.FOVX_FRANCIS}); the timed loop rotates through {len(views)} posed views of the cloud (view 0 = the identity "
-                               "pose of the BASELINE recipe, the others rigid motions of it by <= 0.05 rad / ~0.05 units), each with its own "
-                               "U[0,1] target; one view per step per GPU",
-                   "views": len(views), "densification_statistics_in_step": den is not None,
-                   "gaussians": N, "width": W, "height": H, "sh_degree": deg, "visible": n_visible,
-                   "num_rendered_R": R, "parallelism": f"{world} independent segment replica(s), no data-path collective",
-                   "train_step": "activations + rasterize fwd + 0.8*L1+0.2*(1-SSIM) + backward + Adam(eps=1e-15) on all 59 floats "
-                                 "per Gaussian (update applied inside the per-Gaussian backward kernel" +
-                                 ("" if args.no_prepare_next else ", which also runs the NEXT step's preprocess on the updated parameters: "
-                                  "one preprocess per step either way, k_preprocess is just not a separate launch") +
-                                 "); the unmodified reference trainer reaches the `dropin` path instead"},
-        "fwd_bwd_ms": fwd_ms + bwd_ms, "rasterizer_fwd_ms": fwd_ms, "rasterizer_bwd_ms": bwd_ms,
-        "stage_ms": stage_ms, "step_host_ms": step_host, "roofline": roofline, "roofline_other_kernels": others,
-        "spec_overflows": c1["spec_overflows"] - c0["spec_overflows"],
-        # the list cut (include/gsr.h "list_cut") over the timed steps: renders that ran it, renders whose lists had to be repaired on the
-        # device (a tile needed more than it kept: the counter of re-runs), tiles repaired, and per render the chunks of the depth
-        # order behind the frame's cut (of `chunks`) and the deep tiles served one by one
-        "list_cut": {"renders": lc1[0] - lc0[0], "renders_repaired": lc1[1] - lc0[1], "tiles_repaired": lc1[2] - lc0[2],
-                     "chunks_behind_cut_per_render": (lc1[3] - lc0[3]) / max(1, lc1[0] - lc0[0]),
-                     "deep_tiles_per_render": (lc1[4] - lc0[4]) / max(1, lc1[0] - lc0[0])},
-        "speculative_forwards": c1["spec_forwards"] - c0["spec_forwards"], "exact_forwards": c1["exact_forwards"] - c0["exact_forwards"],
-        "rccl": rccl,
-    }
-    if per_rank_ms is not None:
-        res["per_rank_ms_per_step"] = per_rank_ms
-        res["rank_time_max_over_min"] = max(per_rank_ms) / min(per_rank_ms)
-    if dumped is not None:
-        res["dump_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
+    res["config"]["num_rendered_R"] = R
+    res.update({"fwd_bwd_ms": fwd_ms + bwd_ms, "rasterizer_fwd_ms": fwd_ms, "rasterizer_bwd_ms": bwd_ms,
+                "stage_ms": stage_ms, "roofline": roofline, "roofline_other_kernels": others, "rccl": rccl})
     state["res"] = res
     if dog is not None:
         dog.start()

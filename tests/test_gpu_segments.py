@@ -194,7 +194,7 @@ def test_bench_line_at_two_ranks_on_one_gpu():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     # round 5: the BARE command -- bench.py starts torch.distributed.run itself when --gpus > 1 and no launcher is around it
     # (tests/test_launch_cpu.py covers the launcher's refusals; the explicit torch.distributed.run form is what the 4-process walk uses)
-    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "2", "--gaussians", "200000"]
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "2", "--gaussians", "200000", "--full"]
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env.update(HSA_ENABLE_IPC_MODE_LEGACY="0", GSR_BENCH_BACKEND="gloo", GSR_BENCH_ONE_DEVICE="1", PYTORCH_NVML_BASED_CUDA_CHECK="1")  # (see above)
     out = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=900)
@@ -257,7 +257,7 @@ def test_rccl_process_group_at_world_one_through_bench():
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT=str(_free_port()), RANK="0", WORLD_SIZE="1", LOCAL_RANK="0",
                HSA_ENABLE_IPC_MODE_LEGACY="0", GSR_BENCH_FORCE_DIST="1")
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "2", "--warmup", "1", "--gaussians", "100000",
-                          "--no-extras"], cwd=root, env=env, capture_output=True, text=True, timeout=900)
+                          "--full", "--no-extras"], cwd=root, env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, lines
@@ -281,11 +281,42 @@ def test_merge_level_travels_through_rccl_point_to_point_on_one_gpu():
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT=str(_free_port()), RANK="0", WORLD_SIZE="1", LOCAL_RANK="0",
                HSA_ENABLE_IPC_MODE_LEGACY="0", GSR_BENCH_FORCE_DIST="1", GSR_BENCH_MERGE="1")
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "2", "--warmup", "1", "--gaussians", "100000",
-                          "--no-extras", "--no-cpu-baseline"], cwd=root, env=env, capture_output=True, text=True, timeout=900)
+                          "--full", "--no-extras", "--no-cpu-baseline"], cwd=root, env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-3000:]
     d = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][0])
     m = d["merge"]
     assert "RCCL" in m["transport"] and m["merge_bytes"] > 100000 * 236 and m["gaussians_merged"] == 100000 and m["merge_ms"] > 0, m
+
+
+def test_plain_bench_run_is_the_headline_of_a_full_run(tmp_path):
+    """A plain `bench.py` run stops at the headline: the line has the contract's keys and none of what `--full` measures after the
+    timed steps.  Both runs train the same model over the same steps, so --dump-outputs writes the same arrays bit for bit."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
+    lines = {}
+    for mode in ("plain", "full"):
+        cmd = [sys.executable, os.path.join(root, "bench.py"), "--steps", "3", "--warmup", "2", "--gaussians", "100000",
+               "--dump-outputs", str(tmp_path / mode)] + (["--full", "--no-extras", "--no-cpu-baseline"] if mode == "full" else [])
+        out = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=600)
+        assert out.returncode == 0, out.stderr[-3000:]
+        js = [l for l in out.stdout.splitlines() if l.startswith("{")]
+        assert len(js) == 1, js
+        lines[mode] = json.loads(js[0])
+    p, f = lines["plain"], lines["full"]
+    for k in ("metric", "unit", "higher_is_better", "dtype", "n_gpus", "steps", "warmup"):
+        assert p[k] == f[k], k
+    assert p["value"] > 0 and abs(p["value"] - 1000.0 / p["ms_per_step"]) < 1e-6 * p["value"]
+    for k in ("stage_ms", "fwd_bwd_ms", "roofline", "rccl", "merge", "cpu_baseline", "dropin", "other_workloads", "host_us"):
+        assert k not in p, k
+    assert "stage_ms" in f and "roofline" in f and "rccl" in f
+    assert p["dump_outputs"]["arrays"] == f["dump_outputs"]["arrays"]
+    for name in p["dump_outputs"]["arrays"]:
+        a, b = np.load(tmp_path / "plain" / (name + ".npy")), np.load(tmp_path / "full" / (name + ".npy"))
+        assert a.dtype == b.dtype and np.array_equal(a, b), name
 
 
 def test_child_message_over_rccl_as_a_self_pair():

@@ -7,7 +7,7 @@ cp $D/libgsr_hip.so /tmp/cur.so
 for r in $(seq 1 ${2:-2}); do
   for w in $1; do
     cp gpurun_libs/lib_$w.so $D/libgsr_hip.so
-    timeout 600 python bench.py --steps ${STEPS:-30} --warmup ${WARM:-5} --no-cpu-baseline --no-extras $3 2>/dev/null | python -c "
+    timeout 600 python bench.py --full --steps ${STEPS:-30} --warmup ${WARM:-5} --no-cpu-baseline --no-extras $3 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])
 print('$w', round(d['value'], 1), round(d['ms_per_step'], 4), {k: (round(v * 1000) if v is not None else None) for k, v in d.get('stage_ms', {}).items()})"

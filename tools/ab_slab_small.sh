@@ -3,7 +3,7 @@
 #   gpurun -- 'bash tools/ab_slab_small.sh'
 cd $GRAFT_REPO_ROOT
 run() {
-  env "$@" timeout 300 python bench.py --no-extras --no-cpu-baseline --steps 60 2>/dev/null | python -c "
+  env "$@" timeout 300 python bench.py --full --no-extras --no-cpu-baseline --steps 60 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); s=d['stage_ms']
 print('$*', 'img/s %.0f' % d['value'], 'ms %.4f' % d['ms_per_step'], {k: round(1e3*v,1) for k,v in s.items() if v})"

@@ -3,7 +3,7 @@
 # depth sort + direct binning, at the headline and at stage A's sizes.      gpurun -- 'bash tools/ab_tile_sort.sh'
 cd $GRAFT_REPO_ROOT
 run() {
-  GSR_OPTS=$1 timeout 300 python bench.py --no-extras --no-cpu-baseline --steps 60 "${@:2}" 2>/dev/null | python -c "
+  GSR_OPTS=$1 timeout 300 python bench.py --full --no-extras --no-cpu-baseline --steps 60 "${@:2}" 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); s=d['stage_ms']
 print('$*', 'img/s %.0f' % d['value'], 'ms %.4f' % d['ms_per_step'], {k: round(1e3*v,1) for k,v in s.items() if v})"

@@ -2,7 +2,7 @@
 # tile-sort route behind the EMIT path (frames above 4 096 tiles, batched renders): on / off, same box
 cd $GRAFT_REPO_ROOT
 run() {
-  GSR_OPTS=$1 timeout 300 python bench.py --no-extras --no-cpu-baseline --steps 60 "${@:2}" 2>/dev/null | python -c "
+  GSR_OPTS=$1 timeout 300 python bench.py --full --no-extras --no-cpu-baseline --steps 60 "${@:2}" 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); s=d['stage_ms']
 print('$*', 'ms %.4f' % d['ms_per_step'], {k: round(1e3*v,1) for k,v in s.items() if v})"

@@ -63,7 +63,7 @@ static int g_prep_hist_max_n = 262144;
 static int g_small_sort9 = 1;   // smallest N for which a forward with its own preprocess sorts depths in three 9-bit passes (0 = only above prep_hist_max_n).
                                 // Measured (same-box A/B, tools/ab_130k.sh): depth sort 53 -> 45 us at 130 k, 44 -> 37 us at 20 k
 static inline bool prep_counts_digits(int N) { return N <= g_prep_hist_max_n; }
-static int g_poll_iters = 400000;   // bound of gsr_forward's busy-wait for R in units of ~50 ns (20 ms); 0 = event record + hipEventSynchronize instead
+static int g_poll_iters = 400000;   // bound of gsr_forward's busy-wait for R in units of ~50 ns (20 ms); 0 = no polling: hipStreamSynchronize at once
 static int g_emit_hist = 1;   // 1: k_emit counts the tile sort's digits (no histogram launch); 0: k_radix_ghist
 static int g_sort_algo = 2;   // 2: onesweep for both sorts; 1: onesweep depth sort + hist/scan/scatter tile sort; 0: hist/scan/scatter
 
@@ -1102,7 +1102,6 @@ constexpr int kDbMaxTiles = 4096;
 constexpr int kDbCountWaves = 4;      // chunks per workgroup of k_chunk_counts (kEmitThreads / 64: balance_build shares the launch)
 struct DirectBin {
     int N, T, Tp /* T rounded up to 64 */, S, NC, G, Cg;
-    int NS, Ts, Tsp, slab_rows;   // round 5: the tile grid cut into NS slabs of slab_rows tile rows (Ts tiles, Tsp = Ts rounded up to 64); 1 slab = the whole frame
     uint16_t* M;        // [NC][Tp]  per-chunk tile counts -> exclusive prefixes inside the chunk's group
     uint32_t* GT;       // [G][Tp]   group totals -> absolute start of the group inside the tile's segment
     uint32_t* tbase;    // [T + 1]   tile bases (saturated at 2^32 - 1)
@@ -1131,8 +1130,8 @@ struct DirectBin {
 //     those of the full binning, bit for bit, by construction -- the instances a pixel blends are the same instances in the same
 //     order (tests/test_gpu_listcut.py).
 // What changes is what lies in the list buffer BEHIND a tile's valid prefix (stale words nobody reads) and ranges[t].y.
-// Off ("list_cut" 0, a frame seen for the first time, another model under the same frame, the tile-sort / sort / slabbed / batched
-// routes): every tile's cut is the last chunk and the code below is the round-5 code.
+// Off ("list_cut" 0, a frame seen for the first time, another model under the same frame, the tile-sort / sort / batched routes):
+// every tile's cut is the last chunk and the code below is the round-5 code.
 // ------------------------------------------------------------------------------------------------
 constexpr uint32_t kCutOpenKey = 0xffffffffu;   // a tile that reached the end of its FULL list with a live pixel: never cut
 struct ListCut {            // kernel-argument bundle; key == nullptr: off
@@ -1150,7 +1149,6 @@ struct ListCut {            // kernel-argument bundle; key == nullptr: off
     const uint32_t* tbase;  // [T + 1] the tile bases of the FULL binning (DirectBin::tbase)
     float margin;           // relative slack on the remembered depth
     int dmax;               // tiles that may keep more than the frame's cut
-    int enable;             // 0: tables are written for "everything kept" (the caller asked for full lists on a route that can cut)
 };
 
 // all 64 lanes walk the candidate tiles of ONE large rect (more than 32 tiles: no mask in its TileRec), 64 at a time, in the
@@ -1358,7 +1356,7 @@ __global__ __launch_bounds__(256) void k_chunk_scan2(DirectBin db, unsigned long
         // chunk[t] and a histogram over the chunks; the frame's cut C* is read off that histogram by the scatter's waves (cut_frame)
         if (t < db.T) {
             const uint32_t e = cut.cur[0] < (uint32_t)kVcEntries ? cut.cur[0] : 0u;
-            const bool use = cut.enable && cut.cur[9] != 0u && cut.owner_n[e] == (uint32_t)db.N;
+            const bool use = cut.cur[9] != 0u && cut.owner_n[e] == (uint32_t)db.N;
             uint32_t ck = (uint32_t)(db.NC - 1);
             const uint32_t k = use ? cut.key[(size_t)e * db.T + t] : kCutOpenKey;
             if (k != kCutOpenKey && k != 0u) {
@@ -1536,27 +1534,22 @@ __device__ unsigned long long g_db_dbg[16];   // s_memtime ticks per part, summe
 #else
 #define DB_T(k) do { } while (0)
 #endif
-// SLAB (round 5, frames above kDbMaxTiles tiles): the tile grid is cut into db.NS slabs of whole tile rows and a chunk is walked by NS
-// waves, each with the tables of ITS slab in LDS and blind to every other tile: a small rect's mask is cut down to the slab's rows when
-// the record is loaded (whole tile rows: a contiguous bit range), a large rect is always walked outside the pair buffer (its count
-// inside a slab is not known without the walk) with its tiles tested against the slab.  Every tile belongs to one slab and the
-// chunks of a slab are the chunks of the frame, so the list is the same list.
 // PAIRS (the tile-sort route, round 5): the chunks cut the Gaussians in index order (sorted_gid == nullptr, sorted_rec = the records where
 // the preprocess left them) and what is placed is the PAIR (depth key, Gaussian) -- eight bytes per store instead of four -- into
 // `pairs`; k_tile_sort orders every tile's pairs by key and writes the list.
 // CUT (round 6, see ListCut): 1 = the cut pass -- the chunks up to C* are scattered as ever, a wave of a chunk behind C* serves the few deep
 // tiles whose own cut lies at or behind its chunk (cut_chunk_tiles), and the ranges end at the tiles' valid prefixes; 2 = the repair
 // pass: nothing unless a blend wave flagged a tile, then the flagged tiles' pairs in the chunks behind their cuts.
-template <bool SLAB, bool PAIRS = false, int CUT = 0>
+template <bool PAIRS = false, int CUT = 0>
 __global__ __launch_bounds__(64) void k_chunk_scatter(DirectBin db, int W, int H, int tiles_x, int tiles_y,
                                                       const uint32_t* __restrict__ sorted_gid, const TileRec* __restrict__ sorted_rec,
                                                       const Splat* __restrict__ splat, uint32_t* __restrict__ list, uint2* __restrict__ ranges,
                                                       uint32_t cap, const uint32_t* __restrict__ dkey = nullptr, uint2* __restrict__ pairs = nullptr,
                                                       ListCut cut = ListCut{})
 {
-    static_assert(!CUT || (!SLAB && !PAIRS), "the list cut serves the plain direct binning");
+    static_assert(!CUT || !PAIRS, "the list cut serves the plain direct binning");
     extern __shared__ unsigned long long s_dyn[];
-    const int LT = SLAB ? db.Tsp : db.Tp;                                      // tiles this wave keeps tables for
+    const int LT = db.Tp;                                                      // tiles this wave keeps tables for
     unsigned long long* const s_mask = s_dyn;                                  // [LT]
     uint32_t* const s_cnt = reinterpret_cast<uint32_t*>(s_dyn + LT);          // [LT]
     uint32_t* const s_pair = s_cnt + LT;                                       // [kDbPairs]
@@ -1592,9 +1585,9 @@ __global__ __launch_bounds__(64) void k_chunk_scatter(DirectBin db, int W, int H
             } else { cut.stats[1] += 1u; cut.stats[2] += cut.ctl[2]; }
         }
     }
-    // XCD x = b & 7 owns the chunks [x per, (x + 1) per); a chunk's NS slab waves sit next to each other (they read the same records)
-    const int per = (db.NC + 7) >> 3, kk = b >> 3, c = (b & 7) * per + (SLAB ? kk / db.NS : kk), slab = SLAB ? kk % db.NS : 0;
-    if ((SLAB ? kk / db.NS : kk) >= per || c >= db.NC) return;
+    // XCD x = b & 7 owns the chunks [x per, (x + 1) per)
+    const int per = (db.NC + 7) >> 3, kk = b >> 3, c = (b & 7) * per + kk;
+    if (kk >= per || c >= db.NC) return;
     if (CUT && (uint32_t)c > cstar) {             // behind the frame's cut: only a few tiles want this chunk's pairs
         if (CUT == 1 && ndeep == 0u) return;                               // (no deep tile at all)
         uint32_t* const s_tile = s_pair;                                   // (the pair buffer is not in use on this path)
@@ -1606,9 +1599,6 @@ __global__ __launch_bounds__(64) void k_chunk_scatter(DirectBin db, int W, int H
         return;
     }
     if (CUT == 2) return;                         // (the chunks up to C* were written for every tile)
-    const uint32_t t0 = SLAB ? (uint32_t)(slab * db.Ts) : 0u;                                   // first tile of the slab
-    const uint32_t tn = SLAB ? (uint32_t)min(db.Ts, db.T - slab * db.Ts) : (uint32_t)db.T;       // tiles in it
-    const int srow0 = slab * db.slab_rows, srow1 = srow0 + db.slab_rows;                         // its tile rows (SLAB)
 #ifdef GSR_DB_TIMING
     unsigned long long dbt[8] = {0, 0, 0, 0, 0, 0, 0, 0}, dbt_last = __builtin_readcyclecounter();
 #endif
@@ -1622,12 +1612,11 @@ __global__ __launch_bounds__(64) void k_chunk_scatter(DirectBin db, int W, int H
             uint32_t tb[kRows], gb[kRows], mc[kRows];   // tile base, the group's start in the tile, the chunk's start in the group
 #pragma unroll
             for (int q = 0; q < kRows; q++) {
-                const int i = i0 + 64 * q + lane;       // tile inside the slab; t0 + i in the frame
-                const bool v = i < LT && (uint32_t)i < tn + (SLAB ? 0u : (uint32_t)(db.Tp - db.T));
-                const int g = (int)t0 + i;
-                tb[q] = v && g < db.T ? db.tbase[g] : 0u;
-                gb[q] = v ? gt[g] : 0u;
-                mc[q] = v ? (uint32_t)mr[g] : 0u;
+                const int i = i0 + 64 * q + lane;
+                const bool v = i < LT && (uint32_t)i < (uint32_t)LT;   // (signed and unsigned: the loop compiles as it was measured)
+                tb[q] = v && i < db.T ? db.tbase[i] : 0u;
+                gb[q] = v ? gt[i] : 0u;
+                mc[q] = v ? (uint32_t)mr[i] : 0u;
             }
 #pragma unroll
             for (int q = 0; q < kRows; q++) {
@@ -1655,15 +1644,9 @@ __global__ __launch_bounds__(64) void k_chunk_scatter(DirectBin db, int W, int H
         gB = load_gid(j + 128);
         rB = load_rec(j + 128);
         kB = load_key(j + 128);
-        if (SLAB && !(r.rect & kTileRecBig)) {   // the rect's rows inside the slab are a contiguous run of mask bits
-            const int ww = (int)((r.rect >> 24) & 63u), ry0 = (int)((r.rect >> 12) & 0xfffu);
-            const int lo = min(32, max(0, (srow0 - ry0) * ww)), hi = min(32, max(0, (srow1 - ry0) * ww));
-            const uint32_t below_hi = hi >= 32 ? 0xffffffffu : ((1u << hi) - 1u), below_lo = lo >= 32 ? 0xffffffffu : ((1u << lo) - 1u);
-            r.mask &= below_hi & ~below_lo;
-        }
         // A large rect (no mask in its record) is walked by all 64 lanes, once, and its accepted tiles go into the pair buffer like
         // everyone's; one of more tiles than the buffer holds ("huge") is walked three times instead, outside the buffer.
-        const bool big = (r.rect & kTileRecBig) != 0u && r.mask != 0u, huge = big && (SLAB || r.mask > (uint32_t)kDbPairs);
+        const bool big = (r.rect & kTileRecBig) != 0u && r.mask != 0u, huge = big && r.mask > (uint32_t)kDbPairs;
         const unsigned long long bigs = __ballot(big && !huge), huges = __ballot(huge);
         const uint32_t cnt = huge ? 0u : tilerec_count(r);
         const uint32_t incl = wave_inclusive_sum(cnt);
@@ -1677,8 +1660,7 @@ __global__ __launch_bounds__(64) void k_chunk_scatter(DirectBin db, int W, int H
             const bool mine = lane >= lo && lane < hi;
             if (!big && (with_or || mine)) {
                 uint32_t* o = s_pair + (incl - cnt - before);
-                small_rect_tiles(r, tiles_x, [&](uint32_t tg) {
-                    const uint32_t t = tg - t0;          // (index inside the slab; the mask was cut down to it)
+                small_rect_tiles(r, tiles_x, [&](uint32_t t) {
                     if (with_or) atomicOr(&s_mask[t], me);
                     if (mine) *o++ = (t << 6) | (uint32_t)lane;
                 });
@@ -1690,8 +1672,7 @@ __global__ __launch_bounds__(64) void k_chunk_scatter(DirectBin db, int W, int H
                 const uint32_t gg = (uint32_t)__builtin_amdgcn_readlane((int)g, bl), rect = (uint32_t)__builtin_amdgcn_readlane((int)r.rect, bl);
                 uint32_t o = (uint32_t)__builtin_amdgcn_readlane((int)(incl - cnt), bl) - before;
                 const Splat s = splat[gg];
-                big_rect_tiles(s, rect, W, H, tiles_x, tiles_y, lane, [&](bool ok, uint32_t tg) {
-                    const uint32_t t = tg - t0;          // (this branch only runs without slabs: t0 = 0)
+                big_rect_tiles(s, rect, W, H, tiles_x, tiles_y, lane, [&](bool ok, uint32_t t) {
                     const unsigned long long acc = __ballot(ok);
                     if (ok) {
                         if (with_or) atomicOr(&s_mask[t], 1ull << bl);
@@ -1711,7 +1692,7 @@ __global__ __launch_bounds__(64) void k_chunk_scatter(DirectBin db, int W, int H
             const int bl = (int)__builtin_ctzll(bm);
             const uint32_t gg = (uint32_t)__builtin_amdgcn_readlane((int)g, bl), rect = (uint32_t)__builtin_amdgcn_readlane((int)r.rect, bl);
             const Splat s = splat[gg];
-            big_rect_tiles(s, rect, W, H, tiles_x, tiles_y, lane, [&](bool ok, uint32_t tg) { const uint32_t t = tg - t0; if (ok && t < tn) atomicOr(&s_mask[t], 1ull << bl); });
+            big_rect_tiles(s, rect, W, H, tiles_x, tiles_y, lane, [&](bool ok, uint32_t t) { if (ok && t < (uint32_t)db.T) atomicOr(&s_mask[t], 1ull << bl); });
         }
         // the loads of the step after next have had a step and this owner loop to arrive; taken HERE, in front of this step's
         // scattered stores (a wait for a load is a wait for every store issued before it: vmcnt counts both)
@@ -1769,9 +1750,8 @@ __global__ __launch_bounds__(64) void k_chunk_scatter(DirectBin db, int W, int H
             const int bl = (int)__builtin_ctzll(bm);
             const uint32_t gg = (uint32_t)__builtin_amdgcn_readlane((int)g, bl), rect = (uint32_t)__builtin_amdgcn_readlane((int)r.rect, bl);
             const Splat s = splat[gg];
-            big_rect_tiles(s, rect, W, H, tiles_x, tiles_y, lane, [&](bool ok, uint32_t tg) {
-                const uint32_t t = tg - t0;
-                if (ok && t < tn) {
+            big_rect_tiles(s, rect, W, H, tiles_x, tiles_y, lane, [&](bool ok, uint32_t t) {
+                if (ok && t < (uint32_t)db.T) {
                     const uint32_t pos = s_cnt[t] + (uint32_t)__popcll(s_mask[t] & ((1ull << bl) - 1ull));
                     if (pos < cap) {
                         if (PAIRS) pairs[pos] = make_uint2((uint32_t)__builtin_amdgcn_readlane((int)kd, bl), gg);
@@ -1802,19 +1782,19 @@ __global__ __launch_bounds__(64) void k_chunk_scatter(DirectBin db, int W, int H
                 else batch(std::integral_constant<int, 8>{});
             }
         } else {
-            if (!big) small_rect_tiles(r, tiles_x, [&](uint32_t tg) { const uint32_t t = tg - t0; atomicAdd(&s_cnt[t], 1u); s_mask[t] = 0ull; });
+            if (!big) small_rect_tiles(r, tiles_x, [&](uint32_t t) { atomicAdd(&s_cnt[t], 1u); s_mask[t] = 0ull; });
             for (unsigned long long bm = bigs; bm != 0ull; bm &= bm - 1ull) {
                 const int bl = (int)__builtin_ctzll(bm);
                 const uint32_t gg = (uint32_t)__builtin_amdgcn_readlane((int)g, bl), rect = (uint32_t)__builtin_amdgcn_readlane((int)r.rect, bl);
                 const Splat s = splat[gg];
-                big_rect_tiles(s, rect, W, H, tiles_x, tiles_y, lane, [&](bool ok, uint32_t tg) { const uint32_t t = tg - t0; if (ok && t < tn) { atomicAdd(&s_cnt[t], 1u); s_mask[t] = 0ull; } });
+                big_rect_tiles(s, rect, W, H, tiles_x, tiles_y, lane, [&](bool ok, uint32_t t) { if (ok && t < (uint32_t)db.T) { atomicAdd(&s_cnt[t], 1u); s_mask[t] = 0ull; } });
             }
         }
         for (unsigned long long bm = huges; bm != 0ull; bm &= bm - 1ull) {
             const int bl = (int)__builtin_ctzll(bm);
             const uint32_t gg = (uint32_t)__builtin_amdgcn_readlane((int)g, bl), rect = (uint32_t)__builtin_amdgcn_readlane((int)r.rect, bl);
             const Splat s = splat[gg];
-            big_rect_tiles(s, rect, W, H, tiles_x, tiles_y, lane, [&](bool ok, uint32_t tg) { const uint32_t t = tg - t0; if (ok && t < tn) { atomicAdd(&s_cnt[t], 1u); s_mask[t] = 0ull; } });
+            big_rect_tiles(s, rect, W, H, tiles_x, tiles_y, lane, [&](bool ok, uint32_t t) { if (ok && t < (uint32_t)db.T) { atomicAdd(&s_cnt[t], 1u); s_mask[t] = 0ull; } });
         }
         lds_order();
         DB_T(5);
@@ -1830,7 +1810,7 @@ __global__ __launch_bounds__(64) void k_chunk_scatter(DirectBin db, int W, int H
 
 // ------------------------------------------------------------------------------------------------
 // Tile-sort route (round 5): NO global depth sort.  The direct binning runs over the Gaussians in index order (k_chunk_counts /
-// k_chunk_scatter<.., PAIRS>), every tile's (depth key, Gaussian) pairs land in its segment in index order, and ONE workgroup per tile
+// k_chunk_scatter<PAIRS>), every tile's (depth key, Gaussian) pairs land in its segment in index order, and ONE workgroup per tile
 // sorts its segment by key -- stable, so equal keys stay in index order: exactly the order the stable global sort of (key, index) gave
 // the tile, the list is the other routes' list bit for bit.  What it replaces at 1 M Gaussians: a histogram launch and three
 // look-back passes over 1 M keys (71 us, latency-bound: a chain over 245 tiles per pass) and the 8-byte gather of the tile records
@@ -4123,15 +4103,14 @@ static BinScratch bin_scratch_layout(int64_t R, int key_bytes = 4)
 // alternates models of very different size on one process -- teacher and student (ht3dgs_trainer.py:877-883), the
 // single-image models of stage A next to a leaf -- and one process-wide hint would thrash between over-allocation and
 // the overflow re-run.  Buckets are half octaves of N, so a model that densifies keeps its entry.
-// The pinned read-back slot and its event belong to ONE device (an event recorded on another device's stream is an
-// invalid-handle error), and a slot is held by one call at a time: callers on several threads / devices do not serialise
-// on each other while they enqueue or wait.
+// The pinned read-back slot belongs to ONE device (its device pointer is that device's mapping), and a slot is held by one
+// call at a time: callers on several threads / devices do not serialise on each other while they enqueue or wait.
 // the per-view cost cache of the balanced forward blend: one per (device, frame geometry), a handful at most
 struct ViewCostCache { int dev, W, H, map, items; uint8_t* mem; size_t bytes; };
 static std::vector<ViewCostCache> g_view_costs;   // guarded by g_state_mutex
 static std::map<std::tuple<int, int, int, int>, bool> g_full_depth_sort;   // callers whose depths left the 27-bit window once: four 8-bit passes from then on
 
-struct PinSlot { unsigned long long* host = nullptr; unsigned long long* dev = nullptr; hipEvent_t ev = nullptr; bool busy = false;
+struct PinSlot { unsigned long long* host = nullptr; unsigned long long* dev = nullptr; bool busy = false;
                  unsigned long long seq = 0;      // seq: number of the slot's last use; the scan kernel echoes it behind the count
                  // early R: what the host took from the rider, to be held against the scan's own report (words 4..6 of the slot) the next
                  // time the slot is taken or gsr_backward is entered (late_check)
@@ -4155,7 +4134,6 @@ static int g_tile_sort_max_avg = 700;   // measured (tools/ab_tile_sort*.sh, 980
                                         // 1 M (2 070 per tile) +6 %: the per-tile sorts move R pairs where the depth sort moves N keys
 static int g_direct_bin = 1;      // tile lists by direct placement (k_chunk_counts / k_chunk_scatter) instead of emit + tile sort + ranges; 0 = the sort route
 static int g_view_pose_tol_e6 = 2000;   // balanced placement without a view id: a render belongs to the cached view whose pose is within this (x 1e-6) in every matrix entry
-static int g_db_slab_tiles = 0;   // frames above kDbMaxTiles tiles: tiles per slab of the slabbed scatter (0 = such frames keep the sort route)
 static int g_list_cut = 1;        // round 6: tile lists written only up to where the tiles stopped at the frame's previous render (ListCut); 0 = full lists,
                                   // 1 = for models of at least g_list_cut_min_n Gaussians (where it was measured to pay), 2 = wherever the route allows
 static int g_list_cut_min_n = 2000000;
@@ -4185,8 +4163,7 @@ static PinSlot* acquire_pin_slot(int dev)
         if (!s->busy) { s->busy = true; return s; }
     PinSlot* s = new PinSlot();
     if (hipHostMalloc((void**)&s->host, 64, hipHostMallocMapped) != hipSuccess ||
-        hipHostGetDevicePointer((void**)&s->dev, s->host, 0) != hipSuccess ||
-        hipEventCreateWithFlags(&s->ev, hipEventDisableTiming) != hipSuccess) { delete s; return nullptr; }
+        hipHostGetDevicePointer((void**)&s->dev, s->host, 0) != hipSuccess) { delete s; return nullptr; }
     s->host[0] = 0; s->host[1] = 0;
     for (int q = 4; q < 8; q++) s->host[q] = 0;
     s->busy = true;
@@ -4386,7 +4363,6 @@ int gsr_set_option(const char* name, int value)
     if (!strcmp(name, "debug_late_bias")) { g_debug_late_bias = value; return GSR_OK; }   // tests: added ONCE to the early count a forward remembers for its late check
     if (!strcmp(name, "tile_sort")) { if (value < 0 || value > 2) return GSR_ERR_ARG; g_tile_sort = value; return GSR_OK; }
     if (!strcmp(name, "tile_sort_max_avg")) { if (value < 0) return GSR_ERR_ARG; g_tile_sort_max_avg = value; return GSR_OK; }
-    if (!strcmp(name, "direct_slab_tiles")) { if (value < 0) return GSR_ERR_ARG; g_db_slab_tiles = value; return GSR_OK; }
     if (!strcmp(name, "view_pose_tol_e6")) { if (value < 0) return GSR_ERR_ARG; g_view_pose_tol_e6 = value; return GSR_OK; }
     if (!strcmp(name, "depth_sort9")) { g_depth_sort9 = value ? 1 : 0; return GSR_OK; }
     if (!strcmp(name, "direct_binning")) { g_direct_bin = value ? 1 : 0; return GSR_OK; }
@@ -4420,17 +4396,9 @@ int gsr_set_option(const char* name, int value)
 
 // geometry + scratch of the direct binning for N Gaussians on T tiles; false: this frame keeps the sort route
 struct DirectBinScratch { size_t M, GT, tbase, bsum, cut_chunk, cut_tend, cut_flag, cut_ctl, cut_bkey, cut_hist, bytes; };
-static bool direct_bin_geometry(int N, int T, DirectBin& db, DirectBinScratch& ds, int tiles_x = 0, int tile_rows = 0)
+static bool direct_bin_geometry(int N, int T, DirectBin& db, DirectBinScratch& ds)
 {
-    if (N < 1 || T < 1) return false;
-    db.NS = 1; db.Ts = 0; db.Tsp = 0; db.slab_rows = 0;
-    static const bool force_slabs = getenv("GSR_DB_FORCE_SLABS") != nullptr;   // (experiments: the slabbed scatter on a frame that fits one wave's tables)
-    if (T > kDbMaxTiles || (force_slabs && g_db_slab_tiles > 0 && tiles_x > 0 && tile_rows > 0 && tiles_x * tile_rows == T)) {   // slabs of whole tile rows
-        if (g_db_slab_tiles <= 0 || tiles_x <= 0 || tile_rows <= 0 || tiles_x * tile_rows != T || tiles_x > kDbMaxTiles || T > 32768) return false;
-        const int rows = std::max(1, std::min(g_db_slab_tiles, kDbMaxTiles) / tiles_x);
-        db.slab_rows = rows; db.Ts = rows * tiles_x; db.Tsp = (db.Ts + 63) & ~63; db.NS = (tile_rows + rows - 1) / rows;
-        if (db.NS > 16) return false;
-    }
+    if (N < 1 || T < 1 || T > kDbMaxTiles) return false;
     static std::atomic<int> cus_cached{0};   // (compute units of the first device asked about: all devices of a node are alike)
     int cus = cus_cached.load(std::memory_order_relaxed);
     if (!cus) {
@@ -4439,13 +4407,10 @@ static bool direct_bin_geometry(int N, int T, DirectBin& db, DirectBinScratch& d
         cus_cached.store(cus, std::memory_order_relaxed);
     }
     db.N = N; db.T = T; db.Tp = (T + 63) & ~63;
-    const int lds = 12 * (db.NS > 1 ? db.Tsp : db.Tp) + 4 * kDbPairs;
-    const char* env = getenv("GSR_DB_WAVES_PER_CU");   // (experiments)
-    int per_cu = std::min(16, (160 * 1024) / lds);
-    if (env && atoi(env) > 0) per_cu = atoi(env);
-    const long long resident = std::max<long long>(1, (long long)cus * per_cu / db.NS);   // chunks such that chunks x slabs fill the chip
-    const char* env_s = getenv("GSR_DB_MIN_CHUNK");
-    const int min_s = env_s && atoi(env_s) > 0 ? atoi(env_s) : 128;   // (measured at 20 k - 130 k Gaussians: 128 beats 64, 256 and 512)
+    const int lds = 12 * db.Tp + 4 * kDbPairs;
+    const int per_cu = std::min(16, (160 * 1024) / lds);
+    const long long resident = std::max<long long>(1, (long long)cus * per_cu);   // chunks that fill the chip
+    const int min_s = 128;   // (measured at 20 k - 130 k Gaussians: 128 beats 64, 256 and 512)
     long long S = ((long long)N + resident - 1) / resident;
     S = std::max<long long>(min_s, (S + 63) & ~63ll);
     if (S > 65472) return false;
@@ -4489,8 +4454,6 @@ int gsr_forward(const GsrForwardArgs* a, GsrForwardOut* out, void* stream_)
     // the process-wide options as they are NOW: one forward uses one consistent set and hands it to its backward
     const int opt_ppt = g_blend_ppt ? g_blend_ppt : 7, opt_map = g_tile_map, opt_ckpt = g_ckpt_first;
     const int tiles_x = (W + kTile - 1) / kTile, tiles_y = (H + kTile - 1) / kTile, T = tiles_x * tiles_y * NB;
-    if (NB > 1 && opt_ppt < 6) return fail(GSR_ERR_ARG, "batch: served by the default forward blend kernel only%s");
-    if (a->out_color_clamped && opt_ppt < 6) return fail(GSR_ERR_ARG, "out_color_clamped: served by the default forward blend kernel only%s");
     if (a->sh_origin && (!a->shs || NB > 1 || a->prepared))
         return fail(GSR_ERR_ARG, "sh_origin needs shs and is not served with a batch of B > 1 or a prepared buffer%s");
     out->num_rendered = 0; out->binning = nullptr; out->binning_bytes = 0; out->binning_capacity = 0;
@@ -4518,9 +4481,9 @@ int gsr_forward(const GsrForwardArgs* a, GsrForwardOut* out, void* stream_)
     // direct binning (k_chunk_counts ... k_chunk_scatter) where the frame's tile tables fit a wave's LDS; else emit + tile sort
     DirectBin db = {};
     DirectBinScratch dbs = {};
-    const bool direct = g_direct_bin && g_sort_algo == 2 && !wide_keys && direct_bin_geometry(N, T, db, dbs, NB == 1 ? tiles_x : 0, tiles_y);
+    const bool direct = g_direct_bin && g_sort_algo == 2 && !wide_keys && direct_bin_geometry(N, T, db, dbs);
     // tile-sort route (round 5): the binning runs over the Gaussians in index order and k_tile_sort orders every tile's pairs by depth:
-    // single renders whose tile tables fit one wave (no slabs), onesweep configuration
+    // single renders whose tile tables fit one wave, onesweep configuration
     bool tsort = false;   // (decided below, once the caller's capacity hint is known)
     uint2* ranges = nullptr;
     uint32_t* list = nullptr;
@@ -4600,11 +4563,11 @@ int gsr_forward(const GsrForwardArgs* a, GsrForwardOut* out, void* stream_)
     auto launch_binning = [&](uint64_t capacity, const unsigned long long* n_dev, bool prezeroed) -> int {
         if (direct) {
             if (capacity == 0) { GSR_HIP(hipMemsetAsync(ranges, 0, (size_t)T * sizeof(uint2), st)); return GSR_OK; }
-            const int per = (db.NC + 7) / 8, grid = std::max(8 * per * db.NS, (T + 63) / 64);
+            const int per = (db.NC + 7) / 8, grid = std::max(8 * per, (T + 63) / 64);
             if (tsort) {
                 {
                     ProfScope ps(P_EMIT, st);
-                    hipLaunchKernelGGL((k_chunk_scatter<false, true>), dim3(grid), dim3(64), (size_t)12 * db.Tp + 4 * kDbPairs, st, db, W, H, tiles_x, tiles_y,
+                    hipLaunchKernelGGL((k_chunk_scatter<true>), dim3(grid), dim3(64), (size_t)12 * db.Tp + 4 * kDbPairs, st, db, W, H, tiles_x, tiles_y,
                                        (const uint32_t*)nullptr, ts_rec, splat, list, ranges, (uint32_t)std::min<uint64_t>(capacity, 0xffffffffull), ts_dkey, pairs);
                 }
                 ProfScope ps2(P_SORT_TILE, st);
@@ -4613,12 +4576,9 @@ int gsr_forward(const GsrForwardArgs* a, GsrForwardOut* out, void* stream_)
                 return GSR_OK;
             }
             ProfScope ps(P_EMIT, st);
-            if (db.NS > 1)
-                hipLaunchKernelGGL(k_chunk_scatter<true>, dim3(grid), dim3(64), (size_t)12 * db.Tsp + 4 * kDbPairs, st, db, W, H, tiles_x, tiles_y, sorted_gid,
-                                   reinterpret_cast<const TileRec*>(fs + L.srec), splat, list, ranges, (uint32_t)std::min<uint64_t>(capacity, 0xffffffffull));
-            else if (lc.key) {
+            if (lc.key) {
                 lc_capacity = capacity;
-                hipLaunchKernelGGL((k_chunk_scatter<false, false, 1>), dim3(grid), dim3(64), (size_t)12 * db.Tp + 4 * kDbPairs, st, db, W, H,
+                hipLaunchKernelGGL((k_chunk_scatter<false, 1>), dim3(grid), dim3(64), (size_t)12 * db.Tp + 4 * kDbPairs, st, db, W, H,
                                    tiles_x, tiles_y, sorted_gid, reinterpret_cast<const TileRec*>(fs + L.srec), splat, list, ranges,
                                    (uint32_t)std::min<uint64_t>(capacity, 0xffffffffull), (const uint32_t*)nullptr, (uint2*)nullptr, lc);
             } else
@@ -4629,7 +4589,7 @@ int gsr_forward(const GsrForwardArgs* a, GsrForwardOut* out, void* stream_)
         return wide_keys ? launch_binning_t(uint32_t{}, capacity, n_dev, prezeroed) : launch_binning_t(uint16_t{}, capacity, n_dev, prezeroed);
     };
     auto launch_blend = [&](bool prezeroed) -> int {
-        const int ppt = opt_ppt;   // default 7: one wave per 8x8 sub-tile, sign-encoded done + sub-tile reach bits (6: without the bits, 5: lane mask)
+        const int ppt = opt_ppt;   // default 7: one wave per 8x8 sub-tile, sign-encoded done + sub-tile reach bits (6: without the bits)
         if (!prezeroed) GSR_HIP(hipMemsetAsync(staged, 0, (size_t)T * 16, st));
         float* ckpt = reinterpret_cast<float*>(bin + B.ckpt);
         if (ppt == 7 && g_profile && (g_profile != 3 || g_profile_tick.fetch_add(1u) % 3u == 0u)) {
@@ -4649,17 +4609,16 @@ int gsr_forward(const GsrForwardArgs* a, GsrForwardOut* out, void* stream_)
                 hipLaunchKernelGGL(k_blend_fwd_w6<true>, dim3(8 * 4 * slots_per_xcd(opt_map, T, tiles_x)), dim3(64), 0, st, W, H, tiles_x, T, ranges, list, splat, a->bg,
                                    a->out_color, a->out_depth, a->out_alpha, img, staged, opt_map, ckpt, opt_ckpt, tiles_y, bb, a->out_color_clamped,
                                    lc, lc.key ? 1 : 0);
-            else if (ppt == 6)
+            else
                 hipLaunchKernelGGL(k_blend_fwd_w6<false>, dim3(8 * 4 * slots_per_xcd(opt_map, T, tiles_x)), dim3(64), 0, st, W, H, tiles_x, T, ranges, list, splat, a->bg,
                                    a->out_color, a->out_depth, a->out_alpha, img, staged, opt_map, ckpt, opt_ckpt, tiles_y, BlendBalance{}, a->out_color_clamped);
-            else return fail(GSR_ERR_ARG, "unknown forward blend variant%s");
         }
         if (ppt == 7 && lc.key && lc_capacity > 0) {
             // the repair pass of the list cut: the same scatter over the chunks behind the flagged tiles' cuts and the same blend over
             // the flagged tiles' full lists -- every workgroup of both launches reads one word and leaves unless a wave flagged a tile
             ProfScope ps(P_CUT_REPAIR, st);
-            const int per = (db.NC + 7) / 8, grid = std::max(8 * per * db.NS, (T + 63) / 64);
-            hipLaunchKernelGGL((k_chunk_scatter<false, false, 2>), dim3(grid), dim3(64), (size_t)12 * db.Tp + 4 * kDbPairs, st, db, W, H,
+            const int per = (db.NC + 7) / 8, grid = std::max(8 * per, (T + 63) / 64);
+            hipLaunchKernelGGL((k_chunk_scatter<false, 2>), dim3(grid), dim3(64), (size_t)12 * db.Tp + 4 * kDbPairs, st, db, W, H,
                                tiles_x, tiles_y, sorted_gid, reinterpret_cast<const TileRec*>(fs + L.srec), splat, list, ranges,
                                (uint32_t)std::min<uint64_t>(lc_capacity, 0xffffffffull), (const uint32_t*)nullptr, (uint2*)nullptr, lc);
             hipLaunchKernelGGL(k_blend_fwd_w6<true>, dim3(8 * 4 * slots_per_xcd(opt_map, T, tiles_x)), dim3(64), 0, st, W, H, tiles_x, T, ranges, list, splat, a->bg,
@@ -4714,7 +4673,7 @@ int gsr_forward(const GsrForwardArgs* a, GsrForwardOut* out, void* stream_)
         // (on the emit path the keys are gathered per pair and the lists of a large model spread widely: measured at 1920x1080, 300 k
         //  Gaussians -1.7 % of the step, 1 M +1 ... +12 %; eight stage-A models in one launch chain -2.5 %: small models only)
         const bool auto_ok = ts_mode == 1 && avg <= (uint64_t)g_tile_sort_max_avg && (direct || N / std::max(1, NB) <= g_tile_sort_emit_max_n);
-        tsort = (ts_mode == 2 || auto_ok) && g_sort_algo == 2 && (direct ? (NB == 1 && db.NS == 1) : true);
+        tsort = (ts_mode == 2 || auto_ok) && g_sort_algo == 2 && (direct ? NB == 1 : true);
     }
 
     fs = static_cast<uint8_t*>(a->alloc(align256(L.bytes) + (direct ? dbs.bytes : 0), GSR_ALLOC_SCRATCH, a->alloc_user));   // (+ the chunk tables of the direct binning)
@@ -4902,7 +4861,7 @@ int gsr_forward(const GsrForwardArgs* a, GsrForwardOut* out, void* stream_)
                     bb.tol = 1e-6f * (float)g_view_pose_tol_e6;
                     bb.items = items; bb.nslots4 = nslots4; bb.W = W; bb.H = H;
                     // the list cut: the plain direct binning behind a global depth sort, one model, the default blend
-                    if (direct && !tsort && db.NS == 1 && db.NC <= 16000 && T == db.T && (g_list_cut == 2 || (g_list_cut == 1 && N >= g_list_cut_min_n))) {
+                    if (direct && !tsort && db.NC <= 16000 && T == db.T && (g_list_cut == 2 || (g_list_cut == 1 && N >= g_list_cut_min_n))) {
                         uint8_t* dm = fs + align256(L.bytes);
                         lc.key = reinterpret_cast<uint32_t*>(mem + vc_cut);
                         lc.owner_n = reinterpret_cast<uint32_t*>(mem + vc_own);
@@ -4918,7 +4877,6 @@ int gsr_forward(const GsrForwardArgs* a, GsrForwardOut* out, void* stream_)
                         lc.tbase = reinterpret_cast<uint32_t*>(dm + dbs.tbase);
                         lc.margin = 1e-3f * (float)g_list_cut_margin_e3;
                         lc.dmax = std::max(0, g_list_cut_deep);
-                        lc.enable = 1;
                     }
                 }
             }
@@ -4940,9 +4898,7 @@ int gsr_forward(const GsrForwardArgs* a, GsrForwardOut* out, void* stream_)
         // the scan any more (round 4): an event record is a barrier packet with a completion signal, and the queue idled ~6 us at it
         // on EVERY forward (tools/api_timeline.sh) for the sake of a fallback.  The poll is bounded by wall time ("poll_iters" x ~50 ns,
         // default 20 ms: a device that far behind, or one that has faulted, is waited for with hipStreamSynchronize, which reports it).
-        // "poll_iters" 0 keeps the old protocol: event record + hipEventSynchronize, no busy waiting.
-        const bool use_event = g_poll_iters <= 0;
-        if (use_event) GSR_HIP(hipEventRecord(pin.s->ev, st));
+        // "poll_iters" 0: no polling, hipStreamSynchronize at once.
         rc = launch_binning(cap, total, true);
         if (rc) return rc;
         rc = launch_blend(true);
@@ -4952,17 +4908,14 @@ int gsr_forward(const GsrForwardArgs* a, GsrForwardOut* out, void* stream_)
             volatile unsigned long long* hp = pin.s->host;
             const unsigned long long want = pin.s->seq;
             bool seen = false;
-            if (!use_event) {
+            if (g_poll_iters > 0) {
                 const auto limit = w0 + std::chrono::nanoseconds((long long)g_poll_iters * 50);
                 while (!(seen = (hp[1] == want))) {
                     for (int it = 0; it < 64 && !(seen = (hp[1] == want)); it++) cpu_relax();
                     if (seen || std::chrono::steady_clock::now() > limit) break;
                 }
             }
-            if (!seen) {
-                if (use_event) GSR_HIP(hipEventSynchronize(pin.s->ev));
-                else GSR_HIP(hipStreamSynchronize(st));
-            }
+            if (!seen) GSR_HIP(hipStreamSynchronize(st));
             std::atomic_thread_fence(std::memory_order_acquire);
             g_fwd_wait_ns += std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - w0).count();
         }
@@ -5051,8 +5004,6 @@ static int blend_bwd_resident(int has_da, int ppt = 2)
     else e = has_da ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_blend_bwd2<true>, 128, 0)
                     : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_blend_bwd2<false>, 128, 0);
     if (e != hipSuccess || per_cu < 1) per_cu = v ? 6 : 12;
-    const char* env = getenv("GSR_BWD_WG_PER_CU");   // (experiments)
-    if (env && atoi(env) > 0) per_cu = atoi(env);
     return cached[v][has_da] = per_cu * cus;
 }
 
@@ -5122,7 +5073,7 @@ int gsr_backward(const GsrBackwardArgs* a, void* stream_)
     // (the fixed-order debug mode runs the two-pixel kernel whatever the option says: its two waves add their partials into the tile's LDS
     //  row commutatively, the four waves of k_blend_bwd1 do not -- a + b + c + d depends on the order the LDS atomics land in)
     const int bwd_ppt = g_deterministic ? 2 : (g_bwd_ppt ? g_bwd_ppt : 2);
-    const bool blend_items = a->num_rendered > 0 && (bwd_ppt == 2 || bwd_ppt == 1);
+    const bool blend_items = a->num_rendered > 0;
     // ONE launch clears the per-Gaussian accumulators and (workgroup 0) builds the backward blend's work items from the forward's
     // staged depths -- where the 48 N-byte memset stood
     BwdItemHdr* item_hdr = nullptr;
@@ -5153,49 +5104,45 @@ int gsr_backward(const GsrBackwardArgs* a, void* stream_)
     }
     if (a->num_rendered > 0) {
         const int ppt = bwd_ppt;
-        if (NB > 1 && ppt != 2 && ppt != 1) return fail(GSR_ERR_ARG, "batch: served by the persistent backward blend kernels only%s");
         const float* img = static_cast<const float*>(a->image);
         ProfScope ps(P_BLEND_BWD, st);
-        if (ppt == 2 || ppt == 1) {
-            // (checkpoints are written by k_blend_fwd_w only)
-            const float* ckpt = reinterpret_cast<const float*>(bin + B.ckpt);
-            // deterministic debug mode: R-sized slots + a sort of the instance positions by Gaussian id (stream-ordered
-            // allocations of the library's own: gsr_backward has no allocator callback and this is not a hot path)
-            float* det_part = nullptr;
-            uint8_t* det_mem = nullptr;
-            const uint32_t Rn = (uint32_t)a->num_rendered;
-            size_t o_part = 0, o_k0 = 0, o_k1 = 0, o_v0 = 0, o_v1 = 0, o_sort = 0, det_bytes = 0;
-            if (g_deterministic) {
-                size_t o = 0;
-                o_part = o; o += align256((size_t)Rn * kDetStride * 4);
-                o_k0 = o; o += align256((size_t)Rn * 4); o_k1 = o; o += align256((size_t)Rn * 4);
-                o_v0 = o; o += align256((size_t)Rn * 4); o_v1 = o; o += align256((size_t)Rn * 4);
-                o_sort = o; o += radix_scratch_bytes(Rn);
-                det_bytes = o;
-                GSR_HIP(hipMallocAsync((void**)&det_mem, det_bytes, st));
-                det_part = reinterpret_cast<float*>(det_mem + o_part);
-                GSR_HIP(hipMemsetAsync(det_part, 0, (size_t)Rn * kDetStride * 4, st));
-            }
-            BlendBwdArgs ba = {W, H, tiles_x, tiles_y, T, f_map, f_ckpt, 0, ranges, list, splat, a->bg, img, a->grad_color, a->grad_depth,
-                               a->grad_alpha, gg, ckpt, det_part, item_hdr, items};
-            if (ppt == 1) {
-                if (a->grad_depth || a->grad_alpha) hipLaunchKernelGGL(k_blend_bwd1<true>, dim3(bwd_grid), dim3(256), 0, st, ba);
-                else hipLaunchKernelGGL(k_blend_bwd1<false>, dim3(bwd_grid), dim3(256), 0, st, ba);
-            } else if (a->grad_depth || a->grad_alpha) hipLaunchKernelGGL(k_blend_bwd2<true>, dim3(bwd_grid), dim3(128), 0, st, ba);
-            else hipLaunchKernelGGL(k_blend_bwd2<false>, dim3(bwd_grid), dim3(128), 0, st, ba);
-            if (g_deterministic) {
-                uint32_t* k0 = reinterpret_cast<uint32_t*>(det_mem + o_k0); uint32_t* k1 = reinterpret_cast<uint32_t*>(det_mem + o_k1);
-                uint32_t* v0 = reinterpret_cast<uint32_t*>(det_mem + o_v0); uint32_t* v1 = reinterpret_cast<uint32_t*>(det_mem + o_v1);
-                hipLaunchKernelGGL(k_det_iota, dim3((Rn + 255) / 256), dim3(256), 0, st, Rn, v0, list, k0, (uint32_t)N);
-                int nbits = 1;
-                while ((1ll << nbits) < (long long)N) nbits++;
-                int in_alt = 0;
-                GSR_HIP(radix_sort_pairs<uint32_t>(k0, v0, k1, v1, Rn, 0, ((nbits + 7) / 8) * 8, det_mem + o_sort, &in_alt, st));
-                hipLaunchKernelGGL(k_det_reduce, dim3((Rn + 255) / 256), dim3(256), 0, st, Rn, in_alt ? k1 : k0, in_alt ? v1 : v0, det_part, gg);
-                GSR_HIP(hipFreeAsync(det_mem, st));
-            }
+        // (checkpoints are written by k_blend_fwd_w only)
+        const float* ckpt = reinterpret_cast<const float*>(bin + B.ckpt);
+        // deterministic debug mode: R-sized slots + a sort of the instance positions by Gaussian id (stream-ordered
+        // allocations of the library's own: gsr_backward has no allocator callback and this is not a hot path)
+        float* det_part = nullptr;
+        uint8_t* det_mem = nullptr;
+        const uint32_t Rn = (uint32_t)a->num_rendered;
+        size_t o_part = 0, o_k0 = 0, o_k1 = 0, o_v0 = 0, o_v1 = 0, o_sort = 0, det_bytes = 0;
+        if (g_deterministic) {
+            size_t o = 0;
+            o_part = o; o += align256((size_t)Rn * kDetStride * 4);
+            o_k0 = o; o += align256((size_t)Rn * 4); o_k1 = o; o += align256((size_t)Rn * 4);
+            o_v0 = o; o += align256((size_t)Rn * 4); o_v1 = o; o += align256((size_t)Rn * 4);
+            o_sort = o; o += radix_scratch_bytes(Rn);
+            det_bytes = o;
+            GSR_HIP(hipMallocAsync((void**)&det_mem, det_bytes, st));
+            det_part = reinterpret_cast<float*>(det_mem + o_part);
+            GSR_HIP(hipMemsetAsync(det_part, 0, (size_t)Rn * kDetStride * 4, st));
         }
-        else return fail(GSR_ERR_ARG, "unknown backward blend variant%s");
+        BlendBwdArgs ba = {W, H, tiles_x, tiles_y, T, f_map, f_ckpt, 0, ranges, list, splat, a->bg, img, a->grad_color, a->grad_depth,
+                           a->grad_alpha, gg, ckpt, det_part, item_hdr, items};
+        if (ppt == 1) {
+            if (a->grad_depth || a->grad_alpha) hipLaunchKernelGGL(k_blend_bwd1<true>, dim3(bwd_grid), dim3(256), 0, st, ba);
+            else hipLaunchKernelGGL(k_blend_bwd1<false>, dim3(bwd_grid), dim3(256), 0, st, ba);
+        } else if (a->grad_depth || a->grad_alpha) hipLaunchKernelGGL(k_blend_bwd2<true>, dim3(bwd_grid), dim3(128), 0, st, ba);
+        else hipLaunchKernelGGL(k_blend_bwd2<false>, dim3(bwd_grid), dim3(128), 0, st, ba);
+        if (g_deterministic) {
+            uint32_t* k0 = reinterpret_cast<uint32_t*>(det_mem + o_k0); uint32_t* k1 = reinterpret_cast<uint32_t*>(det_mem + o_k1);
+            uint32_t* v0 = reinterpret_cast<uint32_t*>(det_mem + o_v0); uint32_t* v1 = reinterpret_cast<uint32_t*>(det_mem + o_v1);
+            hipLaunchKernelGGL(k_det_iota, dim3((Rn + 255) / 256), dim3(256), 0, st, Rn, v0, list, k0, (uint32_t)N);
+            int nbits = 1;
+            while ((1ll << nbits) < (long long)N) nbits++;
+            int in_alt = 0;
+            GSR_HIP(radix_sort_pairs<uint32_t>(k0, v0, k1, v1, Rn, 0, ((nbits + 7) / 8) * 8, det_mem + o_sort, &in_alt, st));
+            hipLaunchKernelGGL(k_det_reduce, dim3((Rn + 255) / 256), dim3(256), 0, st, Rn, in_alt ? k1 : k0, in_alt ? v1 : v0, det_part, gg);
+            GSR_HIP(hipFreeAsync(det_mem, st));
+        }
     }
     CamParams cp = {a->viewmatrix, a->projmatrix, a->campos, a->tanfovx, a->tanfovy, a->scale_modifier, W, H, a->D, a->M, a->points_transform, bt};
     const int grid = (N + kPreThreads - 1) / kPreThreads;

@@ -313,9 +313,6 @@ size_t gsr_struct_bytes(int32_t which); /* 0 GsrForwardArgs, 1 GsrBackwardArgs, 
  *                          render of the same frame (device-side cache of 128 frames per frame size, least recently used out; a
  *                          frame is recognised by GsrForwardArgs::view_id or, without one, by its pose; single renders through
  *                          the default kernel); 0 = dispatch order = tile order.  Same image either way
- *   "direct_slab_tiles"    (default 0 = off) frames above 4 096 tiles on the direct route: the tile grid is cut into slabs of whole tile
- *                          rows of at most this many tiles and a chunk is walked by one wave per slab.  Same list bit for bit; measured
- *                          no faster than the sort route such frames take by default
  *   "small_sort9"          (default 1) smallest model for which a forward that runs its own preprocess sorts its depth keys in three
  *                          9-bit passes over the 27-bit window instead of four 8-bit ones (it launches a digit histogram either way);
  *                          0 = only models above 262 144 Gaussians.  Same order either way (a depth beyond the window is detected
@@ -374,8 +371,7 @@ size_t gsr_struct_bytes(int32_t which); /* 0 GsrForwardArgs, 1 GsrBackwardArgs, 
  *                          and the forward that consumes it: do not change it between the two
  *   "poll_iters"           bound of gsr_forward's busy-wait on the pinned instance-count word, in units of ~50 ns (default
  *                          400 000 = 20 ms; past it the call waits with hipStreamSynchronize, which also reports a faulted
- *                          device); 0 = no busy waiting: an event is recorded behind the scan kernel and waited on (up to
- *                          round 3 that event was recorded on every forward: ~6 us of idle queue each) */
+ *                          device); 0 = no polling: hipStreamSynchronize at once */
 int gsr_set_option(const char* name, int value);
 /* Monotonic counters: "spec_forwards" (forwards launched against a capacity), "spec_overflows" (of those, how many had to
  * re-run the binning because R exceeded the capacity), "exact_forwards" (read-then-launch forwards), "spec_callers"

@@ -159,6 +159,23 @@ def _register_fakes():
     def _(render, target, workspace, grad_loss, lambda_dssim, clamp):
         return torch.empty_like(render, dtype=torch.float32)
 
+    @torch.library.register_fake("gsr::depth_loss_forward")
+    def _(depth, depth_gt, kind, clamp_lo, clamp_hi):
+        H, W = depth.shape[-2:]
+        return depth.new_empty((6,), dtype=torch.float32), depth.new_empty((lib.gsr_depth_loss_workspace_bytes(int(H), int(W)),), dtype=torch.uint8)
+
+    @torch.library.register_fake("gsr::depth_loss_backward")
+    def _(depth, depth_gt, workspace, grad_loss, kind, clamp_lo, clamp_hi, lambda_depth):
+        return torch.empty_like(depth, dtype=torch.float32)
+
+    @torch.library.register_fake("gsr::depth_loss")
+    def _(depth, depth_gt, kind, clamp_lo, clamp_hi):
+        return depth.new_empty((), dtype=torch.float32)
+
+    @torch.library.register_fake("gsr::training_loss_terms")
+    def _(render, target, depth, depth_gt, lambda_dssim, lambda_depth, kind, clamp, clamp_lo, clamp_hi):
+        return render.new_empty((), dtype=torch.float32), render.new_empty((6,), dtype=torch.float32)
+
     @torch.library.register_fake("gsr::knn_mean_dist2")
     def _(points):
         return points.new_empty((points.shape[0],), dtype=torch.float32)

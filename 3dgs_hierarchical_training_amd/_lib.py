@@ -79,7 +79,9 @@ EXPORTS = [
     "gsr_prepare_supported", "gsr_prepared_radii_offset", "gsr_stream_copy", "gsr_image_bytes_batched",
     "gsr_masked_max", "gsr_densify_stats_add", "gsr_psnr_scratch_bytes", "gsr_psnr",
     "gsr_loss_workspace_bytes_batched", "gsr_loss_forward_batched", "gsr_loss_backward_batched", "gsr_loss_forward_terms", "gsr_pose_grad", "gsr_struct_bytes", "gsr_debug_list_cut_stats",
+    "gsr_depth_loss_workspace_bytes", "gsr_depth_loss_forward", "gsr_depth_loss_backward", "gsr_depth_loss_forward_terms",
 ]
+GSR_DEPTH_LOSS_L1, GSR_DEPTH_LOSS_INVARIANT = 0, 1
 
 _lib = None
 
@@ -115,6 +117,16 @@ def load():
     lib.gsr_loss_backward.restype = C.c_int
     lib.gsr_loss_backward.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32,
                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.gsr_depth_loss_workspace_bytes.restype = C.c_size_t
+    lib.gsr_depth_loss_workspace_bytes.argtypes = [C.c_int32, C.c_int32]
+    # (depth, depth_gt, H, W, kind, clamp_lo, clamp_hi, lambda_depth, workspace, ...)
+    _depth = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_float, C.c_void_p]
+    lib.gsr_depth_loss_forward.restype = C.c_int
+    lib.gsr_depth_loss_forward.argtypes = _depth + [C.c_void_p, C.c_void_p]                         # out6, stream
+    lib.gsr_depth_loss_backward.restype = C.c_int
+    lib.gsr_depth_loss_backward.argtypes = _depth + [C.c_void_p, C.c_void_p, C.c_void_p]            # grad_loss, d_depth, stream
+    lib.gsr_depth_loss_forward_terms.restype = C.c_int
+    lib.gsr_depth_loss_forward_terms.argtypes = _depth + [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]   # out6, terms6, loss_copy, stream
     lib.gsr_knn_scratch_bytes.restype = C.c_size_t
     lib.gsr_knn_scratch_bytes.argtypes = [C.c_int32]
     lib.gsr_knn_mean_dist2.restype = C.c_int

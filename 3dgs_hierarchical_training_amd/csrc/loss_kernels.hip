@@ -11,6 +11,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <algorithm>
+
 #include "../../include/gsr.h"
 
 namespace gsr {
@@ -331,6 +333,202 @@ __global__ __launch_bounds__(256) void k_loss_bwd(const float* __restrict__ raw,
     }
 }
 
+// ---- depth term of Loss.forward (/root/reference/trainer/losses.py:86-95, :114-119; the MiDaS scale-and-shift-invariant loss
+// :259-393 constructed with alpha = 0.5, scales = 1, :41) ----------------------------------------------------------------------
+// p = the rasterizer's depth plane, g = depth_gt, pc = min(max(p, lo), hi) (the two masked assignments of :116-117, fused).
+//   'l1' (kind 0):        sum |pc - g| / (H W)
+//   'invariant' (kind 1): m = g > 0.02; (s, t) = the masked least-squares fit of s pc + t to g; d = m (s pc + t - g);
+//                         data = sum d^2 / (2 M), reg = sum over adjacent pairs m_a m_b |d_b - d_a| / M, loss = data + 0.5 reg
+// The chain is launch-bound (five passes over one or two planes of a few MB), so it is four short launches forward and one
+// backward.  Every sum is float64 with a fixed grid and fixed-order partials -- no atomics, the same bits on every run; det = a00 a11 -
+// a01^2 is a difference of products of sums and cancels in binary32.  The residual d is evaluated by ONE function (depth_resid) in
+// the forward and the backward, so the sign of a pair's |.| is decided identically in both.
+constexpr int kDS1 = 256;          // workgroups of k_depth_sums at most (one partial row per thread of the consumers)
+constexpr int kDS2 = 1024;         // workgroups of k_depth_terms at most
+constexpr int kDV = 5;             // values per partial row
+constexpr float kDepthValid = 0.02f;   // mask = depth_gt > 0.02 (losses.py:92; a constant of the reference, not the clamp bound)
+// workspace: coefficients | partial rows of k_depth_sums | partial rows of k_depth_terms
+enum { kDcS = 0, kDcT, kDcInvM, kDcU0, kDcU1, kDcLs, kDcLt, kDcLoss, kDcSums /* 5 */, kDcDet = kDcSums + kDV, kDcLambda, kDcN = 16 };
+struct DepthWs { double coef[kDcN]; double p1[kDS1 * kDV]; double p2[kDS2 * kDV]; };
+
+__device__ __forceinline__ float depth_clamp(float v, float lo, float hi) { return fminf(fmaxf(v, lo), hi); }
+__device__ __forceinline__ double depth_resid(double s, double t, float pr, float gr, float lo, float hi)
+{
+    return __builtin_fma(s, (double)depth_clamp(pr, lo, hi), t) - (double)gr;
+}
+__device__ __forceinline__ double depth_sgn(double v) { return v > 0.0 ? 1.0 : (v < 0.0 ? -1.0 : 0.0); }
+
+// sum of the workgroup's kDV lane values -> dst[0..kDV) (thread 0 writes; wave shuffles, then the four waves in index order)
+__device__ __forceinline__ void depth_block_sum(double (&v)[kDV], double* s_red, double* __restrict__ dst)
+{
+    const int tid = threadIdx.x;
+#pragma unroll
+    for (int k = 0; k < kDV; k++)
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) v[k] += __shfl_xor(v[k], off, 64);
+    if ((tid & 63) == 0)
+#pragma unroll
+        for (int k = 0; k < kDV; k++) s_red[(tid >> 6) * kDV + k] = v[k];
+    __syncthreads();
+    if (tid == 0)
+#pragma unroll
+        for (int k = 0; k < kDV; k++) dst[k] = ((s_red[k] + s_red[kDV + k]) + s_red[2 * kDV + k]) + s_red[3 * kDV + k];
+}
+
+// column sums of n <= NT partial rows, the same tree in every workgroup that calls it (every thread of the workgroup calls)
+template <int NT>
+__device__ __forceinline__ void depth_rows_sum(const double* __restrict__ rows, int n, double* s_buf, double (&out)[kDV])
+{
+    const int r = threadIdx.x;
+#pragma unroll
+    for (int k = 0; k < kDV; k++) s_buf[k * NT + r] = r < n ? rows[r * kDV + k] : 0.0;
+    __syncthreads();
+    for (int off = NT / 2; off > 0; off >>= 1) {
+        if (r < off)
+#pragma unroll
+            for (int k = 0; k < kDV; k++) s_buf[k * NT + r] += s_buf[k * NT + r + off];
+        __syncthreads();
+    }
+#pragma unroll
+    for (int k = 0; k < kDV; k++) out[k] = s_buf[k * NT];
+    __syncthreads();
+}
+
+// pass 1: the five sums of the normal equations (kind 1) or sum |pc - g| (kind 0); grid <= kDS1, one partial row per workgroup
+__global__ __launch_bounds__(256) void k_depth_sums(const float* __restrict__ p, const float* __restrict__ g, size_t P, int vec, int kind,
+                                                    float lo, float hi, double* __restrict__ part)
+{
+    __shared__ double s_red[4 * kDV];
+    double v[kDV] = {0.0, 0.0, 0.0, 0.0, 0.0};
+    auto acc = [&](float pr, float gr) {
+        const double pc = (double)depth_clamp(pr, lo, hi), gd = (double)gr;
+        if (kind == 0) v[0] += fabs(pc - gd);
+        else if (gr > kDepthValid) { v[0] += pc * pc; v[1] += pc; v[2] += 1.0; v[3] += pc * gd; v[4] += gd; }
+    };
+    const size_t stride = (size_t)gridDim.x * 256, first = (size_t)blockIdx.x * 256 + threadIdx.x;
+    const size_t n4 = vec ? P / 4 : 0;
+    for (size_t i = first; i < n4; i += stride) {   // 16-byte loads
+        const float4 a = reinterpret_cast<const float4*>(p)[i], b = reinterpret_cast<const float4*>(g)[i];
+        acc(a.x, b.x); acc(a.y, b.y); acc(a.z, b.z); acc(a.w, b.w);
+    }
+    for (size_t i = n4 * 4 + first; i < P; i += stride) acc(p[i], g[i]);
+    depth_block_sum(v, s_red, part + (size_t)blockIdx.x * kDV);
+}
+
+// pass 2 (kind 1): every workgroup reduces the partial rows in the same order and solves the 2x2 in float64 -- the same (s, t)
+// everywhere -- then walks its pixels with the neighbour to the right and the one below.  Partial row: sum d^2, sum |d_b - d_a|,
+// sum sgn(d_b - d_a) (pc_b - pc_a) (= M d reg / ds), sum d pc, sum d (= M d data / ds, dt; zero up to rounding at the fit).
+__global__ __launch_bounds__(256) void k_depth_terms(const float* __restrict__ p, const float* __restrict__ g, int H, int W, float lo,
+                                                     float hi, const double* __restrict__ part1, int n1, double* __restrict__ coef,
+                                                     double* __restrict__ part2)
+{
+    __shared__ double s_buf[kDV * 256];
+    __shared__ double s_red[4 * kDV];
+    double S[kDV];
+    depth_rows_sum<256>(part1, n1, s_buf, S);
+    const double det = S[0] * S[2] - S[1] * S[1];
+    double s = 0.0, t = 0.0;
+    if (det != 0.0) { s = (S[2] * S[3] - S[1] * S[4]) / det; t = (-S[1] * S[3] + S[0] * S[4]) / det; }   // losses.py:273-279
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        coef[kDcS] = s; coef[kDcT] = t; coef[kDcDet] = det;
+#pragma unroll
+        for (int k = 0; k < kDV; k++) coef[kDcSums + k] = S[k];
+    }
+    double v[kDV] = {0.0, 0.0, 0.0, 0.0, 0.0};
+    const size_t P = (size_t)H * W, stride = (size_t)gridDim.x * 256;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < P; i += stride) {
+        const float gi = g[i];
+        if (!(gi > kDepthValid)) continue;
+        const int y = (int)(i / (size_t)W), x = (int)(i - (size_t)y * W);
+        const float pi = p[i];
+        const double pc = (double)depth_clamp(pi, lo, hi), d = depth_resid(s, t, pi, gi, lo, hi);
+        v[0] += d * d; v[3] += d * pc; v[4] += d;
+        if (x + 1 < W) {
+            const float gj = g[i + 1];
+            if (gj > kDepthValid) {
+                const float pj = p[i + 1];
+                const double diff = depth_resid(s, t, pj, gj, lo, hi) - d;
+                v[1] += fabs(diff); v[2] += depth_sgn(diff) * ((double)depth_clamp(pj, lo, hi) - pc);
+            }
+        }
+        if (y + 1 < H) {
+            const float gj = g[i + W];
+            if (gj > kDepthValid) {
+                const float pj = p[i + W];
+                const double diff = depth_resid(s, t, pj, gj, lo, hi) - d;
+                v[1] += fabs(diff); v[2] += depth_sgn(diff) * ((double)depth_clamp(pj, lo, hi) - pc);
+            }
+        }
+    }
+    depth_block_sum(v, s_red, part2 + (size_t)blockIdx.x * kDV);
+}
+
+// single workgroup: out6 = {loss_depth, s, t, M, data, reg} and the backward's coefficients.  With dL/ds = Ls, dL/dt = Lt and the
+// normal matrix A = [[a00, a01], [a01, a11]]: u = A^-1 (Ls, Lt), and pixel i adds -u0 (d_i + s pc_i) - u1 s (the closed form of
+// ds/dpc_i, dt/dpc_i contracted with (Ls, Lt)).  terms6 (may be NULL): the six-float vector of gsr_loss_forward_terms -- the weighted
+// depth term is added to its total and slot 5 receives the unweighted term; loss_dup: a second place for the total.
+__global__ __launch_bounds__(1024) void k_depth_finish(const double* __restrict__ part1, int n1, const double* __restrict__ part2, int n2,
+                                                       int kind, double npix, double lambda, double* __restrict__ coef,
+                                                       float* __restrict__ out6, float* __restrict__ terms6, float* __restrict__ loss_dup)
+{
+    __shared__ double s_buf[kDV * 1024];
+    double T[kDV];
+    depth_rows_sum<1024>(kind == 0 ? part1 : part2, kind == 0 ? n1 : n2, s_buf, T);
+    if (threadIdx.x != 0) return;
+    double loss = 0.0, s = 0.0, t = 0.0, M = npix, data = 0.0, reg = 0.0, invM = 0.0, u0 = 0.0, u1 = 0.0, Ls = 0.0, Lt = 0.0;
+    if (kind == 0) loss = T[0] / npix;
+    else {
+        s = coef[kDcS]; t = coef[kDcT]; M = coef[kDcSums + 2];
+        if (M > 0.0) {   // reduction_batch_based (:284-293): both terms are 0 when no pixel is valid
+            invM = 1.0 / M;
+            data = T[0] / (2.0 * M); reg = T[1] / M; loss = data + 0.5 * reg;
+            const double det = coef[kDcDet], a00 = coef[kDcSums], a01 = coef[kDcSums + 1];
+            if (det != 0.0) {   // (s = t = 0 are constants otherwise: no gradient through the fit, :270-279)
+                Ls = (T[3] + 0.5 * T[2]) * invM; Lt = T[4] * invM;
+                u0 = (M * Ls - a01 * Lt) / det; u1 = (-a01 * Ls + a00 * Lt) / det;
+            }
+        }
+    }
+    coef[kDcS] = s; coef[kDcT] = t; coef[kDcInvM] = kind == 0 ? 1.0 / npix : invM; coef[kDcU0] = u0; coef[kDcU1] = u1;
+    coef[kDcLs] = Ls; coef[kDcLt] = Lt; coef[kDcLoss] = loss; coef[kDcLambda] = lambda;
+    out6[0] = (float)loss; out6[1] = (float)s; out6[2] = (float)t; out6[3] = (float)M; out6[4] = (float)data; out6[5] = (float)reg;
+    if (terms6) {
+        terms6[0] = (float)((double)terms6[0] + lambda * loss);
+        terms6[5] = (float)loss;
+        if (loss_dup) *loss_dup = terms6[0];
+    }
+}
+
+// d_p[i] = upstream * lambda * pass(p_i) * dL/dpc_i, one store per pixel.  pass: a pixel strictly outside [lo, hi] gets zero, one on a
+// bound passes (the masked assignments of :116-117).  invariant: m_i [ s/M (d_i + 0.5 stencil_i) - u0 (d_i + s pc_i) - u1 s ], stencil
+// = the signs of the pixel's four incident pairs.
+__global__ __launch_bounds__(256) void k_depth_bwd(const float* __restrict__ p, const float* __restrict__ g, int H, int W, int kind, float lo,
+                                                   float hi, double lambda, const double* __restrict__ coef, const float* __restrict__ gscale,
+                                                   float* __restrict__ d_p)
+{
+    const double up = (gscale ? (double)gscale[0] : 1.0) * lambda;
+    const double s = coef[kDcS], t = coef[kDcT], invM = coef[kDcInvM], u0 = coef[kDcU0], u1 = coef[kDcU1];
+    const size_t P = (size_t)H * W, stride = (size_t)gridDim.x * 256;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < P; i += stride) {
+        const float pi = p[i], gi = g[i];
+        float out = 0.f;
+        if (pi >= lo && pi <= hi) {
+            if (kind == 0) out = (float)(up * invM * depth_sgn((double)pi - (double)gi));
+            else if (gi > kDepthValid) {
+                const int y = (int)(i / (size_t)W), x = (int)(i - (size_t)y * W);
+                const double d = depth_resid(s, t, pi, gi, lo, hi);
+                double st = 0.0;
+                if (x > 0 && g[i - 1] > kDepthValid) st += depth_sgn(d - depth_resid(s, t, p[i - 1], g[i - 1], lo, hi));
+                if (x + 1 < W && g[i + 1] > kDepthValid) st -= depth_sgn(depth_resid(s, t, p[i + 1], g[i + 1], lo, hi) - d);
+                if (y > 0 && g[i - W] > kDepthValid) st += depth_sgn(d - depth_resid(s, t, p[i - W], g[i - W], lo, hi));
+                if (y + 1 < H && g[i + W] > kDepthValid) st -= depth_sgn(depth_resid(s, t, p[i + W], g[i + W], lo, hi) - d);
+                out = (float)(up * (s * invM * (d + 0.5 * st) - u0 * (d + s * (double)pi) - u1 * s));
+            }
+        }
+        d_p[i] = out;
+    }
+}
+
 }  // namespace gsr
 
 using namespace gsr;
@@ -393,6 +591,57 @@ int gsr_loss_backward(const float* render, const float* target, int32_t C, int32
                       int32_t clamp01_render, const void* workspace, const float* grad_loss, float* d_render, void* stream)
 {
     return gsr_loss_backward_batched(render, target, 1, C, H, W, lambda_dssim, clamp01_render, workspace, grad_loss, d_render, stream);
+}
+
+size_t gsr_depth_loss_workspace_bytes(int32_t H, int32_t W)
+{
+    (void)H; (void)W;   // coefficients + the two fixed grids' partial rows: the same size for every plane
+    return (sizeof(DepthWs) + 255) & ~(size_t)255;
+}
+
+static int depth_loss_forward_impl(const float* depth, const float* depth_gt, int32_t H, int32_t W, int32_t kind, float clamp_lo, float clamp_hi,
+                                   float lambda_depth, void* workspace, float* out6, float* terms6, float* loss_copy, void* stream)
+{
+    if (!depth || !depth_gt || !workspace || !out6 || H <= 0 || W <= 0 || (kind != GSR_DEPTH_LOSS_L1 && kind != GSR_DEPTH_LOSS_INVARIANT) ||
+        !(clamp_lo <= clamp_hi) || ((uintptr_t)workspace & 7) != 0)
+        return GSR_ERR_ARG;
+    DepthWs* ws = static_cast<DepthWs*>(workspace);
+    const size_t P = (size_t)H * W;
+    const int vec = ((((uintptr_t)depth | (uintptr_t)depth_gt) & 15) == 0) ? 1 : 0;
+    const int n1 = (int)std::min<size_t>(kDS1, (P + 1023) / 1024), n2 = (int)std::min<size_t>(kDS2, (P + 255) / 256);
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(k_depth_sums, dim3(n1), dim3(256), 0, st, depth, depth_gt, P, vec, (int)kind, clamp_lo, clamp_hi, ws->p1);
+    if (kind == GSR_DEPTH_LOSS_INVARIANT)
+        hipLaunchKernelGGL(k_depth_terms, dim3(n2), dim3(256), 0, st, depth, depth_gt, (int)H, (int)W, clamp_lo, clamp_hi, ws->p1, n1, ws->coef, ws->p2);
+    hipLaunchKernelGGL(k_depth_finish, dim3(1), dim3(1024), 0, st, ws->p1, n1, ws->p2, n2, (int)kind, (double)P, (double)lambda_depth, ws->coef,
+                       out6, terms6, loss_copy);
+    return hipGetLastError() == hipSuccess ? GSR_OK : GSR_ERR_HIP;
+}
+
+int gsr_depth_loss_forward(const float* depth, const float* depth_gt, int32_t H, int32_t W, int32_t kind, float clamp_lo, float clamp_hi,
+                           float lambda_depth, void* workspace, float* out6, void* stream)
+{
+    return depth_loss_forward_impl(depth, depth_gt, H, W, kind, clamp_lo, clamp_hi, lambda_depth, workspace, out6, nullptr, nullptr, stream);
+}
+
+int gsr_depth_loss_forward_terms(const float* depth, const float* depth_gt, int32_t H, int32_t W, int32_t kind, float clamp_lo, float clamp_hi,
+                                 float lambda_depth, void* workspace, float* out6, float* terms6, float* loss_copy, void* stream)
+{
+    if (!terms6) return GSR_ERR_ARG;
+    return depth_loss_forward_impl(depth, depth_gt, H, W, kind, clamp_lo, clamp_hi, lambda_depth, workspace, out6, terms6, loss_copy, stream);
+}
+
+int gsr_depth_loss_backward(const float* depth, const float* depth_gt, int32_t H, int32_t W, int32_t kind, float clamp_lo, float clamp_hi,
+                            float lambda_depth, const void* workspace, const float* grad_loss, float* d_depth, void* stream)
+{
+    if (!depth || !depth_gt || !workspace || !d_depth || H <= 0 || W <= 0 || (kind != GSR_DEPTH_LOSS_L1 && kind != GSR_DEPTH_LOSS_INVARIANT))
+        return GSR_ERR_ARG;
+    const DepthWs* ws = static_cast<const DepthWs*>(workspace);
+    const size_t P = (size_t)H * W;
+    const int nb = (int)std::min<size_t>(2048, (P + 255) / 256);
+    hipLaunchKernelGGL(k_depth_bwd, dim3(nb), dim3(256), 0, (hipStream_t)stream, depth, depth_gt, (int)H, (int)W, (int)kind, clamp_lo, clamp_hi,
+                       (double)lambda_depth, ws->coef, grad_loss, d_depth);
+    return hipGetLastError() == hipSuccess ? GSR_OK : GSR_ERR_HIP;
 }
 
 }  // extern "C"

@@ -12,6 +12,7 @@
 //   gsr::rasterize_backward_fused  -> gsr_backward with the in-kernel Adam step (parameters / moments updated in place)
 //   gsr::mark_visible         -> gsr_mark_visible
 //   gsr::photometric_loss_forward / _backward -> gsr_loss_forward / gsr_loss_backward
+//   gsr::depth_loss_forward / _backward, gsr::training_loss_terms -> gsr_depth_loss_forward / _backward / _forward_terms
 //   gsr::adam_step            -> gsr_adam_step
 //   gsr::pose_step            -> gsr_pose_step (stage A: tangent-space Adam + exponential map between two renders)
 //   gsr::knn_mean_dist2       -> gsr_knn_mean_dist2
@@ -680,6 +681,130 @@ Tensor photometric_loss_no_grad(const Tensor& render, const Tensor& target, doub
     return std::get<0>(photometric_loss_forward(render, target.device() == render.device() ? target : target.to(render.device()), lambda_dssim, clamp)).select(0, 0);
 }
 
+// ---- the depth term of the loss (gsr_depth_loss_*): depth / depth_gt are [H,W] or [1,H,W] planes; kind 0 = 'l1', 1 = 'invariant'
+static void depth_dims(const Tensor& d, const Tensor& g, int32_t& H, int32_t& W)
+{
+    TORCH_CHECK((d.dim() == 2 || (d.dim() == 3 && d.size(0) == 1)) && d.numel() > 0 && g.numel() == d.numel() &&
+                g.size(-1) == d.size(-1) && g.size(-2) == d.size(-2), "fused_depth_loss: [H,W] or [1,H,W] depth and depth_gt of one size");
+    H = (int32_t)d.size(-2); W = (int32_t)d.size(-1);
+}
+inline Tensor on_device_of(const Tensor& t, const Tensor& like) { return t.device() == like.device() ? t : t.to(like.device()); }
+
+std::tuple<Tensor, Tensor> depth_loss_forward(const Tensor& depth_, const Tensor& gt_, int64_t kind, double clamp_lo, double clamp_hi)
+{
+    TORCH_CHECK(depth_.is_cuda(), "fused_depth_loss: tensors must be on a ROCm/HIP device (no CPU fallback)");
+    const c10::hip::HIPGuardMasqueradingAsCUDA guard(depth_.device());
+    const Tensor depth = f32c(depth_), gt = f32c(on_device_of(gt_, depth_));
+    int32_t H, W;
+    depth_dims(depth, gt, H, W);
+    Tensor ws = at::empty({(int64_t)gsr_depth_loss_workspace_bytes(H, W)}, depth.options().dtype(at::kByte));
+    Tensor out = at::empty({6}, depth.options());
+    check(gsr_depth_loss_forward(fp(depth), fp(gt), H, W, (int32_t)kind, (float)clamp_lo, (float)clamp_hi, 1.0f, ws.data_ptr(), out.data_ptr<float>(),
+                                 c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream()), "gsr_depth_loss_forward");
+    return {out, ws};
+}
+
+Tensor depth_loss_backward(const Tensor& depth_, const Tensor& gt_, const Tensor& ws, const Tensor& grad_loss_, int64_t kind, double clamp_lo,
+                           double clamp_hi, double lambda_depth)
+{
+    const c10::hip::HIPGuardMasqueradingAsCUDA guard(depth_.device());
+    const Tensor depth = f32c(depth_), gt = f32c(on_device_of(gt_, depth_)), g = f32c(grad_loss_);
+    int32_t H, W;
+    depth_dims(depth, gt, H, W);
+    Tensor d = at::empty_like(depth);
+    check(gsr_depth_loss_backward(fp(depth), fp(gt), H, W, (int32_t)kind, (float)clamp_lo, (float)clamp_hi, (float)lambda_depth, ws.data_ptr(), fp(g),
+                                  d.data_ptr<float>(), c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream()), "gsr_depth_loss_backward");
+    return d;
+}
+
+class DepthLossFn : public torch::autograd::Function<DepthLossFn> {
+   public:
+    static Tensor forward(torch::autograd::AutogradContext* ctx, const Tensor& depth, const Tensor& gt, int64_t kind, double lo, double hi)
+    {
+        static auto op = c10::Dispatcher::singleton().findSchemaOrThrow("gsr::depth_loss_forward", "").typed<decltype(depth_loss_forward)>();
+        const Tensor d = f32c(depth), t = f32c(on_device_of(gt, depth));
+        auto out = op.call(d, t, kind, lo, hi);
+        ctx->save_for_backward({d, t, std::get<1>(out)});
+        ctx->saved_data["kind"] = kind; ctx->saved_data["lo"] = lo; ctx->saved_data["hi"] = hi;
+        return std::get<0>(out).select(0, 0);
+    }
+    static torch::autograd::variable_list backward(torch::autograd::AutogradContext* ctx, torch::autograd::variable_list g)
+    {
+        static auto op = c10::Dispatcher::singleton().findSchemaOrThrow("gsr::depth_loss_backward", "").typed<decltype(depth_loss_backward)>();
+        auto sv = ctx->get_saved_variables();
+        Tensor d = op.call(sv[0], sv[1], sv[2], g[0], ctx->saved_data["kind"].toInt(), ctx->saved_data["lo"].toDouble(), ctx->saved_data["hi"].toDouble(), 1.0);
+        return {d, Tensor(), Tensor(), Tensor(), Tensor()};
+    }
+};
+Tensor depth_loss(const Tensor& depth, const Tensor& gt, int64_t kind, double lo, double hi) { return DepthLossFn::apply(depth, gt, kind, lo, hi); }
+Tensor depth_loss_no_grad(const Tensor& depth, const Tensor& gt, int64_t kind, double lo, double hi)
+{
+    return std::get<0>(depth_loss_forward(depth, gt, kind, lo, hi)).select(0, 0);
+}
+
+// The whole of Loss.forward (/root/reference/trainer/losses.py:98-136) with a depth term: (loss, terms), terms = {total loss, mean SSIM,
+// mean L1, loss_rgb, loss_dssim, loss_depth (unweighted)} -- the photometric forward, then the depth chain whose finishing kernel completes
+// the vector.  ONE autograd node hands back d_render and d_depth.
+static std::tuple<Tensor, Tensor, Tensor, Tensor> training_loss_forward(const Tensor& r, const Tensor& t, const Tensor& dp, const Tensor& dg,
+                                                                        double lambda_dssim, double lambda_depth, int64_t kind, bool clamp,
+                                                                        double lo, double hi)
+{
+    TORCH_CHECK(r.dim() == 3, "fused_training_loss_report: a single [C,H,W] render (the batched form has no depth term)");
+    auto out = photometric_loss_forward_terms(r, t, lambda_dssim, clamp);
+    const c10::hip::HIPGuardMasqueradingAsCUDA guard(r.device());
+    int32_t H, W;
+    depth_dims(dp, dg, H, W);
+    Tensor terms = std::get<0>(out), loss = std::get<2>(out);
+    Tensor dws = at::empty({(int64_t)gsr_depth_loss_workspace_bytes(H, W)}, r.options().dtype(at::kByte)), dout = at::empty({6}, r.options());
+    check(gsr_depth_loss_forward_terms(fp(dp), fp(dg), H, W, (int32_t)kind, (float)lo, (float)hi, (float)lambda_depth, dws.data_ptr(),
+                                       dout.data_ptr<float>(), terms.data_ptr<float>(), loss.data_ptr<float>(),
+                                       c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream()), "gsr_depth_loss_forward_terms");
+    return {loss, terms, std::get<1>(out), dws};
+}
+class TrainingLossFn : public torch::autograd::Function<TrainingLossFn> {
+   public:
+    static torch::autograd::variable_list forward(torch::autograd::AutogradContext* ctx, const Tensor& render, const Tensor& target, const Tensor& depth,
+                                                  const Tensor& depth_gt, double lambda_dssim, double lambda_depth, int64_t kind, bool clamp, double lo,
+                                                  double hi)
+    {
+        const Tensor r = f32c(render), t = f32c(on_device_of(target, render)), dp = f32c(depth), dg = f32c(on_device_of(depth_gt, render));
+        auto out = training_loss_forward(r, t, dp, dg, lambda_dssim, lambda_depth, kind, clamp, lo, hi);
+        ctx->save_for_backward({r, t, std::get<2>(out), dp, dg, std::get<3>(out)});
+        ctx->saved_data["lam"] = lambda_dssim; ctx->saved_data["clamp"] = clamp; ctx->saved_data["lamd"] = lambda_depth;
+        ctx->saved_data["kind"] = kind; ctx->saved_data["lo"] = lo; ctx->saved_data["hi"] = hi;
+        Tensor loss = std::get<0>(out), terms = std::get<1>(out);
+        ctx->mark_non_differentiable({terms});
+        ctx->set_materialize_grads(false);
+        return {loss, terms};
+    }
+    static torch::autograd::variable_list backward(torch::autograd::AutogradContext* ctx, torch::autograd::variable_list g)
+    {
+        torch::autograd::variable_list out(10);
+        if (!g[0].defined()) return out;
+        static auto op = c10::Dispatcher::singleton().findSchemaOrThrow("gsr::photometric_loss_backward", "").typed<decltype(photometric_loss_backward)>();
+        static auto opd = c10::Dispatcher::singleton().findSchemaOrThrow("gsr::depth_loss_backward", "").typed<decltype(depth_loss_backward)>();
+        auto sv = ctx->get_saved_variables();
+        if (ctx->needs_input_grad(0)) out[0] = op.call(sv[0], sv[1], sv[2], g[0], ctx->saved_data["lam"].toDouble(), ctx->saved_data["clamp"].toBool());
+        if (ctx->needs_input_grad(2))
+            out[2] = opd.call(sv[3], sv[4], sv[5], g[0], ctx->saved_data["kind"].toInt(), ctx->saved_data["lo"].toDouble(), ctx->saved_data["hi"].toDouble(),
+                              ctx->saved_data["lamd"].toDouble());
+        return out;
+    }
+};
+std::tuple<Tensor, Tensor> training_loss_terms(const Tensor& render, const Tensor& target, const Tensor& depth, const Tensor& depth_gt, double lambda_dssim,
+                                               double lambda_depth, int64_t kind, bool clamp, double lo, double hi)
+{
+    auto r = TrainingLossFn::apply(render, target, depth, depth_gt, lambda_dssim, lambda_depth, kind, clamp, lo, hi);
+    return {r[0], r[1]};
+}
+std::tuple<Tensor, Tensor> training_loss_terms_no_grad(const Tensor& render, const Tensor& target, const Tensor& depth, const Tensor& depth_gt,
+                                                       double lambda_dssim, double lambda_depth, int64_t kind, bool clamp, double lo, double hi)
+{
+    auto out = training_loss_forward(f32c(render), f32c(on_device_of(target, render)), f32c(depth), f32c(on_device_of(depth_gt, render)), lambda_dssim,
+                                     lambda_depth, kind, clamp, lo, hi);
+    return {std::get<0>(out), std::get<1>(out)};
+}
+
 // Pose step of stage A: delta / exp_avg / exp_avg_sq ([6] float32) updated in place from dL/dM, the new M = Exp(delta) * base written
 // into `xf` ([3,4] or [4,4] float32, rows 0..2) -- the tensor the next render reads as points_transform.  step = 0: only evaluates M.
 void pose_step(Tensor delta, Tensor exp_avg, Tensor exp_avg_sq, const Tensor& d_xf, const Tensor& base, Tensor xf, double lr,
@@ -864,6 +989,12 @@ TORCH_LIBRARY(gsr, m)
     m.def("photometric_loss_backward(Tensor render, Tensor target, Tensor workspace, Tensor grad_loss, float lambda_dssim, bool clamp) -> Tensor");
     m.def("photometric_loss(Tensor render, Tensor target, float lambda_dssim, bool clamp) -> Tensor");
     m.def("photometric_loss_terms(Tensor render, Tensor target, float lambda_dssim, bool clamp) -> (Tensor, Tensor)");
+    m.def("depth_loss_forward(Tensor depth, Tensor depth_gt, int kind, float clamp_lo, float clamp_hi) -> (Tensor, Tensor)");
+    m.def("depth_loss_backward(Tensor depth, Tensor depth_gt, Tensor workspace, Tensor grad_loss, int kind, float clamp_lo, float clamp_hi, "
+          "float lambda_depth) -> Tensor");
+    m.def("depth_loss(Tensor depth, Tensor depth_gt, int kind, float clamp_lo, float clamp_hi) -> Tensor");
+    m.def("training_loss_terms(Tensor render, Tensor target, Tensor depth, Tensor depth_gt, float lambda_dssim, float lambda_depth, int kind, "
+          "bool clamp, float clamp_lo, float clamp_hi) -> (Tensor, Tensor)");
     m.def("adam_step(Tensor(a!)[] params, Tensor[] grads, Tensor(b!)[] exp_avg, Tensor(c!)[] exp_avg_sq, float[] lr, float beta1, "
           "float beta2, float eps, int step) -> ()");
     m.def("pose_step(Tensor(a!) delta, Tensor(b!) exp_avg, Tensor(c!) exp_avg_sq, Tensor d_xf, Tensor base, Tensor(d!) xf, float lr, "
@@ -902,6 +1033,10 @@ TORCH_LIBRARY_IMPL(gsr, CUDA, m)   // the dispatch key of HIP tensors on a ROCm 
     m.impl("rasterize", &rasterize_forward_only);
     m.impl("photometric_loss", &photometric_loss_no_grad);
     m.impl("photometric_loss_terms", &photometric_loss_terms_no_grad);
+    m.impl("depth_loss_forward", &depth_loss_forward);
+    m.impl("depth_loss_backward", &depth_loss_backward);
+    m.impl("depth_loss", &depth_loss_no_grad);
+    m.impl("training_loss_terms", &training_loss_terms_no_grad);
 }
 
 TORCH_LIBRARY_IMPL(gsr, Autograd, m)
@@ -909,5 +1044,7 @@ TORCH_LIBRARY_IMPL(gsr, Autograd, m)
     m.impl("rasterize", &rasterize);
     m.impl("photometric_loss", &photometric_loss);
     m.impl("photometric_loss_terms", &photometric_loss_terms);
+    m.impl("depth_loss", &depth_loss);
+    m.impl("training_loss_terms", &training_loss_terms);
     m.impl("pose_matrix", &pose_matrix);
 }

@@ -1,4 +1,4 @@
-"""Fused photometric loss (1-l)*L1 + l*(1-SSIM) of the train step, HIP kernels behind the C ABI.
+"""Fused photometric loss (1-l)*L1 + l*(1-SSIM) of the train step and its depth term, HIP kernels behind the C ABI.
 
 Host-side mirror of what the reference computes with torch ops: `Loss.forward`
 (/root/reference/trainer/losses.py:98-136) with the 11x11 Gaussian-window SSIM (:147-209), applied to the
@@ -80,3 +80,71 @@ def fused_photometric_loss_report(render: torch.Tensor, target: torch.Tensor, la
     if render.device.type != "cuda":
         raise RuntimeError("fused_photometric_loss: tensors must be on a ROCm/HIP device (no CPU fallback)")
     return E.load().photometric_loss_terms(render, target, float(lambda_dssim), bool(clamp))
+
+
+# ---- the depth term of Loss.forward (/root/reference/trainer/losses.py:86-95, :114-119) -----------------------------------------------
+DEPTH_LOSS_KINDS = {"l1": 0, "invariant": 1}       # GSR_DEPTH_LOSS_L1 / GSR_DEPTH_LOSS_INVARIANT of include/gsr.h
+DEPTH_CLAMP = (0.02, 20.0)                         # the bounds of the reference's two masked assignments (losses.py:116-117)
+
+
+def _depth_kind(kind) -> int:
+    if kind not in DEPTH_LOSS_KINDS:
+        raise ValueError(f"depth loss type {kind!r}: 'l1' or 'invariant' (the reference's depth_loss_type)")
+    return DEPTH_LOSS_KINDS[kind]
+
+
+def _check_depth(depth, depth_gt):
+    if depth.device.type != "cuda":
+        raise RuntimeError("fused_depth_loss: tensors must be on a ROCm/HIP device (no CPU fallback)")
+    if not (depth.dim() == 2 or (depth.dim() == 3 and depth.shape[0] == 1)) or tuple(depth_gt.shape[-2:]) != tuple(depth.shape[-2:]) \
+            or depth_gt.numel() != depth.numel():
+        raise RuntimeError("fused_depth_loss: depth and depth_gt must be [H,W] or [1,H,W] planes of one size")
+
+
+class _FusedDepthLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, depth, depth_gt, kind, lo, hi):
+        ops = E.load()
+        depth = depth.float().contiguous()
+        depth_gt = depth_gt.to(depth.device).float().contiguous()
+        out, ws = ops.depth_loss_forward(depth, depth_gt, kind, lo, hi)
+        ctx.save_for_backward(depth, depth_gt, ws)
+        ctx.cfg = (kind, lo, hi)
+        return out[0]
+
+    @staticmethod
+    def backward(ctx, grad_loss):
+        depth, depth_gt, ws = ctx.saved_tensors
+        kind, lo, hi = ctx.cfg
+        return E.load().depth_loss_backward(depth, depth_gt, ws, grad_loss.contiguous(), kind, lo, hi, 1.0), None, None, None, None
+
+
+def fused_depth_loss(depth: torch.Tensor, depth_gt: torch.Tensor, kind: str = "invariant", clamp=DEPTH_CLAMP) -> torch.Tensor:
+    """`get_depth_loss(depth_pred, depth_gt)` of the reference after its clamp statements (losses.py:116-119, :86-95), unweighted:
+    depth = the rasterizer's depth plane [H,W] or [1,H,W] (clamped to `clamp` inside; strictly clamped pixels get zero gradient),
+    kind = the reference's depth_loss_type: 'l1', or 'invariant' = the scale-and-shift-invariant loss (alpha 0.5, one scale, mask
+    depth_gt > 0.02) whose gradient flows through the fitted scale and shift.  Four short launches forward, one backward, float64
+    fixed-order sums: bit-identical from run to run, no host synchronisation.  Autograd node in the extension (DepthLossFn); the
+    Python autograd.Function above states the same thing and serves the plain-FFI binding route."""
+    _check_depth(depth, depth_gt)
+    k, lo, hi = _depth_kind(kind), float(clamp[0]), float(clamp[1])
+    if E.use_ctypes():
+        return _FusedDepthLoss.apply(depth, depth_gt, k, lo, hi)
+    return E.load().depth_loss(depth, depth_gt, k, lo, hi)
+
+
+def fused_training_loss_report(render: torch.Tensor, target: torch.Tensor, depth: torch.Tensor = None, depth_gt: torch.Tensor = None,
+                               lambda_dssim: float = 0.2, lambda_depth: float = 0.0, kind: str = "invariant", clamp: bool = True,
+                               depth_clamp=DEPTH_CLAMP):
+    """(loss, terms): the whole of `Loss.forward` (losses.py:98-136) -- loss = photometric + lambda_depth * depth term, and the
+    six-float vector {total loss, mean SSIM, mean L1, loss_rgb, loss_dssim, loss_depth (unweighted)}, i.e. every entry of the dict the
+    reference returns -- from one dispatcher call; ONE autograd node hands back d_render and d_depth.  `clamp` is the render's
+    clamp(0, 1) as in fused_photometric_loss; the depth plane is clamped to `depth_clamp` inside.  Without a depth_gt, or with
+    lambda_depth = 0, this is fused_photometric_loss_report: the same launches, the same bits.  Extension binding only."""
+    if depth_gt is None or depth is None or float(lambda_depth) == 0.0:
+        return fused_photometric_loss_report(render, target, lambda_dssim, clamp)
+    if render.device.type != "cuda":
+        raise RuntimeError("fused_photometric_loss: tensors must be on a ROCm/HIP device (no CPU fallback)")
+    _check_depth(depth, depth_gt)
+    return E.load().training_loss_terms(render, target, depth, depth_gt, float(lambda_dssim), float(lambda_depth), _depth_kind(kind),
+                                        bool(clamp), float(depth_clamp[0]), float(depth_clamp[1]))

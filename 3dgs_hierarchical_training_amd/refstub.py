@@ -166,3 +166,63 @@ class StubRender:
         image, radii, depth, alpha = out
         return {"image": image.clamp(0, 1), "depth": depth, "alpha": alpha, "viewspace_points": screenspace_points,
                 "visibility_filter": radii > 0, "radii": radii}
+
+
+class StubLoss:
+    """`trainer.losses.Loss` as far as `gsr_autopatch.loss_forward` and the trainer read it: `.cfg` (lambda_dssim, lambda_depth),
+    `.depth_loss_type`, `get_depth_loss` and `forward` (losses.py:86-136), restated with the reference's sequence of torch statements --
+    its three host synchronisations included (`det.nonzero()` in the 2x2 solve, `if divisor == 0` in both reductions) -- i.e. the
+    unpatched route against which the fused depth term is compared and timed."""
+
+    def __init__(self, depth_loss_type="invariant", lambda_dssim=0.2, lambda_depth=0.0):
+        import types
+        self.depth_loss_type = depth_loss_type
+        self.cfg = types.SimpleNamespace(lambda_dssim=lambda_dssim, lambda_depth=lambda_depth, depth_loss_type=depth_loss_type)
+
+    @staticmethod
+    def _batch_mean(total, divisor):                                   # reduction_batch_based
+        divisor = torch.sum(divisor)
+        if divisor == 0:
+            return 0
+        return torch.sum(total) / divisor
+
+    def _scale_shift_invariant(self, pred, target, mask, alpha=0.5):   # [1,H,W] each
+        a00, a01, a11 = torch.sum(mask * pred * pred, (1, 2)), torch.sum(mask * pred, (1, 2)), torch.sum(mask, (1, 2))
+        b0, b1 = torch.sum(mask * pred * target, (1, 2)), torch.sum(mask * target, (1, 2))
+        scale, shift = torch.zeros_like(b0), torch.zeros_like(b1)
+        det = a00 * a11 - a01 * a01
+        ok = det.nonzero()
+        scale[ok] = (a11[ok] * b0[ok] - a01[ok] * b1[ok]) / det[ok]
+        shift[ok] = (-a01[ok] * b0[ok] + a00[ok] * b1[ok]) / det[ok]
+        fit = scale.view(-1, 1, 1) * pred + shift.view(-1, 1, 1)
+        M = torch.sum(mask, (1, 2))
+        res = fit - target
+        total = self._batch_mean(torch.sum(mask * res * res, (1, 2)), 2 * M)
+        diff = mask * res
+        gx = mask[:, :, 1:] * mask[:, :, :-1] * torch.abs(diff[:, :, 1:] - diff[:, :, :-1])
+        gy = mask[:, 1:, :] * mask[:, :-1, :] * torch.abs(diff[:, 1:, :] - diff[:, :-1, :])
+        return total + alpha * self._batch_mean(torch.sum(gx, (1, 2)) + torch.sum(gy, (1, 2)), M)
+
+    def get_depth_loss(self, depth_pred, depth_gt):                    # [H,W] each
+        if self.depth_loss_type == "l1":
+            return torch.abs(depth_pred - depth_gt).sum() / float(depth_pred.shape[0] * depth_pred.shape[1])
+        mask = (depth_gt > 0.02).float()
+        return self._scale_shift_invariant(depth_pred[None], depth_gt[None], mask[None])
+
+    def forward(self, rgb_pred, rgb_gt, depth_pred=None, depth_gt=None, rgb_loss_type='l1', **kwargs):
+        from .train_step import ssim
+        lambda_dssim, lambda_depth = self.cfg.lambda_dssim, self.cfg.lambda_depth
+        rgb_gt = rgb_gt.to(rgb_pred.device)
+        rgb_full_loss = (1 - lambda_dssim) * torch.abs(rgb_pred - rgb_gt).mean()
+        dssim_loss = 1 - ssim(rgb_pred, rgb_gt)
+        if lambda_depth != 0.0 and depth_pred is not None and depth_gt is not None:
+            depth_gt = depth_gt.to(rgb_pred.device)
+            depth_pred[depth_pred < 0.02] = 0.02
+            depth_pred[depth_pred > 20.0] = 20.0
+            depth_loss = self.get_depth_loss(depth_pred.squeeze(), depth_gt.squeeze())
+        else:
+            depth_loss = torch.zeros((), device=rgb_pred.device)
+        loss = rgb_full_loss + lambda_dssim * dssim_loss + lambda_depth * depth_loss
+        return {'loss': loss, 'loss_rgb': rgb_full_loss, 'loss_dssim': dssim_loss, 'loss_depth': depth_loss}
+
+    __call__ = forward

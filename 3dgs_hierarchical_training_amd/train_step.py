@@ -16,7 +16,7 @@ import torch
 import torch.nn.functional as F
 
 from ._ext import use_ctypes as E_use_ctypes
-from .loss import fused_photometric_loss
+from .loss import DEPTH_CLAMP, fused_depth_loss, fused_photometric_loss, fused_training_loss_report
 from .optim import FusedAdam
 from .rasterizer import GaussianRasterizationSettings, GaussianRasterizer, rasterize_gaussians_raw
 
@@ -59,6 +59,43 @@ def ssim(img1: torch.Tensor, img2: torch.Tensor, window_size: int = 11) -> torch
 def photometric_loss(pred: torch.Tensor, gt: torch.Tensor, lambda_dssim: float = 0.2) -> torch.Tensor:
     l1 = torch.abs(pred - gt).mean()
     return (1.0 - lambda_dssim) * l1 + lambda_dssim * (1.0 - ssim(pred, gt))
+
+
+def depth_loss(depth: torch.Tensor, depth_gt: torch.Tensor, kind: str = "invariant", clamp=DEPTH_CLAMP, return_fit: bool = False):
+    """The depth term of the reference's `Loss.forward` in torch ops: the clamp of losses.py:116-117, then `get_depth_loss` (:86-95) --
+    'l1' = sum |pc - g| / (H W); 'invariant' = the scale-and-shift-invariant loss of :259-393 as constructed at :41 (alpha 0.5, one
+    scale, batch-based reduction) with the mask depth_gt > 0.02.  Same statements in the same order as the reference, in the dtype of
+    `depth` (float64-capable), differentiable through the fitted scale and shift -- but the three data-dependent branches (`det.nonzero()`,
+    `if divisor == 0` twice) are `torch.where`, so nothing waits for the device.  The twin of `photometric_loss`: it serves
+    fused_loss=False and is what the fused kernels (loss.fused_depth_loss) are tested against.
+    depth, depth_gt: [H,W] or [1,H,W].  return_fit=True: (loss, scale, shift, number of valid pixels)."""
+    p = depth.reshape(depth.shape[-2:])
+    g = depth_gt.reshape(depth_gt.shape[-2:]).to(device=p.device, dtype=p.dtype)
+    pc = p.clamp(float(clamp[0]), float(clamp[1]))        # (gradient: zero strictly outside the bounds, passed on them -- as the masked assignments)
+    if kind == "l1":
+        loss = torch.abs(pc - g).sum() / float(pc.numel())
+        return (loss, None, None, float(pc.numel())) if return_fit else loss
+    if kind != "invariant":
+        raise ValueError(f"depth loss type {kind!r}: 'l1' or 'invariant'")
+    m = (g > 0.02).to(p.dtype)
+    a00, a01, a11 = torch.sum(m * pc * pc), torch.sum(m * pc), torch.sum(m)
+    b0, b1 = torch.sum(m * pc * g), torch.sum(m * g)
+    det = a00 * a11 - a01 * a01
+    ok = det != 0
+    safe = torch.where(ok, det, torch.ones_like(det))
+    zero = torch.zeros_like(det)
+    s = torch.where(ok, (a11 * b0 - a01 * b1) / safe, zero)
+    t = torch.where(ok, (-a01 * b0 + a00 * b1) / safe, zero)
+    res = s * pc + t - g
+    any_valid = a11 > 0
+    div = torch.where(any_valid, a11, torch.ones_like(a11))
+    data = torch.where(any_valid, torch.sum(m * res * res) / (2 * div), zero)
+    d = m * res
+    gx = m[:, 1:] * m[:, :-1] * torch.abs(d[:, 1:] - d[:, :-1])
+    gy = m[1:, :] * m[:-1, :] * torch.abs(d[1:, :] - d[:-1, :])
+    reg = torch.where(any_valid, (torch.sum(gx) + torch.sum(gy)) / div, zero)
+    loss = data + 0.5 * reg
+    return (loss, s, t, a11) if return_fit else loss
 
 
 class GaussianParams:
@@ -406,7 +443,8 @@ def _same_transform(tag, xf) -> bool:
 def train_step(params: GaussianParams, settings: GaussianRasterizationSettings, gt: torch.Tensor,
                lambda_dssim: float = 0.2, fused_loss: bool = True, fused_activations: bool = True,
                fused_optimizer: bool = True, densifier=None, iteration: int = 0, next_settings=None,
-               pose: "PoseState" = None, next_pose: "PoseState" = None, next_sh_degree: int = None, view_id: int = 0) -> Dict:
+               pose: "PoseState" = None, next_pose: "PoseState" = None, next_sh_degree: int = None, view_id: int = 0,
+               depth_gt: torch.Tensor = None, lambda_depth: float = 0.0, depth_loss_type: str = "invariant") -> Dict:
     """render -> loss -> backward -> Adam step (ht3dgs_trainer.py:102-166 without densification).
     fused_loss=True evaluates clamp + L1 + SSIM in the HIP loss kernels; False uses the torch restatement.
     fused_activations=True runs exp / sigmoid / normalize / cat inside the rasterizer kernels.
@@ -421,7 +459,12 @@ def train_step(params: GaussianParams, settings: GaussianRasterizationSettings, 
     when global_iteration % 1000 == 0) -- the hand-over then already carries the colours of the higher degree.
     densifier (densify.Densifier) + iteration: the adaptive density control of ht3dgs_trainer.py:137-155 runs between
     backward() and optimizer.step(), as in the reference; on the iterations where it replaces parameter tensors the step is not
-    fused into the backward, so that the update the reference drops there is dropped here too (densify.py)."""
+    fused into the backward, so that the update the reference drops there is dropped here too (densify.py).
+    depth_gt ([H,W] or [1,H,W]) with a non-zero lambda_depth: the loss is photometric + lambda_depth * depth term (`Loss.forward`,
+    losses.py:114-124; depth_loss_type 'l1' or 'invariant') on the render's depth plane, and the render's backward receives grad_depth
+    -- on every route above (the blend's depth / alpha instantiation, then the depth terms of the per-Gaussian backward).  Without it
+    nothing changes: the same launches, the same bits."""
+    with_depth = depth_gt is not None and float(lambda_depth) != 0.0
     fused_adam = params.optimizer if (fused_optimizer and fused_activations and isinstance(params.optimizer, FusedAdam)) else None
     # an iteration whose `after_backward` replaces parameter tensors (densify / prune, opacity reset) runs UNFUSED: the reference's
     # surgery sits between backward() and optimizer.step() and drops that iteration's update of the tensors it replaces
@@ -452,10 +495,20 @@ def train_step(params: GaussianParams, settings: GaussianRasterizationSettings, 
     pkg = render(params, settings, clamp=not fused_loss, fused_activations=fused_activations, fused_adam=fused_adam,
                  next_settings=nxt, points_transform=xf, densify_stats=dstats, view_id=view_id,
                  next_points_transform=next_pose.M if (xf is not None and next_pose is not None and nxt is not None) else None)
-    if fused_loss:          # (a batch hands [B,3,H,W] stacks: the fused loss is then the SUM of the models' losses, every image
-        loss = fused_photometric_loss(pkg["raw_image"], gt, lambda_dssim, clamp=True)     # normalised on its own -- each model gets
-    else:                   # exactly its own loss's gradient, bit-identical with training it alone)
+    if with_depth and pkg["depth"].dim() != 3:
+        raise RuntimeError("train_step: the depth term is not served for a batch of models")
+    # (a batch hands [B,3,H,W] stacks: the fused loss is then the SUM of the models' losses, every image normalised on its own -- each
+    #  model gets exactly its own loss's gradient, bit-identical with training it alone)
+    if fused_loss and with_depth and not E_use_ctypes():      # one dispatcher call, one autograd node for d_render and d_depth
+        loss = fused_training_loss_report(pkg["raw_image"], gt, pkg["depth"], depth_gt, lambda_dssim, lambda_depth, depth_loss_type, clamp=True)[0]
+    elif fused_loss:
+        loss = fused_photometric_loss(pkg["raw_image"], gt, lambda_dssim, clamp=True)
+        if with_depth:      # (the plain-FFI binding: the two ops side by side)
+            loss = loss + float(lambda_depth) * fused_depth_loss(pkg["depth"], depth_gt, depth_loss_type)
+    else:
         loss = photometric_loss(pkg["image"], gt, lambda_dssim)
+        if with_depth:
+            loss = loss + float(lambda_depth) * depth_loss(pkg["depth"], depth_gt, depth_loss_type)
     # same as loss.backward(); the upstream "1" is kept on the device instead of being filled by a launch every step
     one = getattr(params, "_grad_one", None)
     if one is None or one.device != loss.device:

@@ -172,6 +172,16 @@ def loss_forward(self, rgb_pred, rgb_gt, depth_pred=None, depth_gt=None, rgb_los
     raw = getattr(rgb_pred, "_gsr_raw", None)      # the patched render's un-clamped colour output (render_fused below), valid while
     fused_clamp = raw is not None and raw[1] == rgb_pred._version and raw[0].shape == rgb_pred.shape     # nobody wrote into the clamped image
     src = raw[0] if fused_clamp else rgb_pred
+    want_depth = lambda_depth != 0.0 and depth_pred is not None and depth_gt is not None
+    if want_depth and _fused_depth_route(self, rgb_pred, depth_pred, depth_gt):
+        # the depth term on the kernels as well (include/gsr.h gsr_depth_loss_*): the reference's two masked assignments are ONE in-place
+        # clamp of the caller's plane -- it holds the clamped values afterwards and strictly clamped pixels get zero gradient, as at
+        # losses.py:116-117 -- then one dispatcher call writes the whole dict; no host synchronisation (the reference's statements have
+        # three: `det.nonzero()` and `if divisor == 0` twice)
+        depth_pred.clamp_(0.02, 20.0)
+        loss, terms = loss_mod.fused_training_loss_report(src, rgb_gt, depth_pred, depth_gt.to(rgb_pred.device), lambda_dssim, lambda_depth,
+                                                          self.depth_loss_type, clamp=fused_clamp)
+        return {'loss': loss, 'loss_rgb': terms[3], 'loss_dssim': terms[4], 'loss_depth': terms[5]}
     if _ext_binding() and os.environ.get("GSR_AUTOPATCH_LOSS_REPORT", "1") != "0":
         # one dispatcher call: the finishing kernel wrote every entry of the returned dict (loss_rgb, loss_dssim, a zero loss_depth);
         # the entries are views of its six-float result -- no torch kernel per term, no zero fills in the backward
@@ -182,7 +192,7 @@ def loss_forward(self, rgb_pred, rgb_gt, depth_pred=None, depth_gt=None, rgb_los
         rgb_full_loss = (1.0 - lambda_dssim) * l1_v
         dssim_loss = 1.0 - ssim_v
         zero_depth = None
-    if lambda_depth != 0.0 and depth_pred is not None and depth_gt is not None:
+    if want_depth:      # GSR_AUTOPATCH_DEPTH_LOSS=0, another depth_loss_type, shape or device: the reference's own statements
         depth_gt = depth_gt.to(rgb_pred.device)
         depth_pred[depth_pred < 0.02] = 0.02
         depth_pred[depth_pred > 20.0] = 20.0
@@ -191,6 +201,21 @@ def loss_forward(self, rgb_pred, rgb_gt, depth_pred=None, depth_gt=None, rgb_los
     else:
         depth_loss = zero_depth if zero_depth is not None else torch.zeros((), device=rgb_pred.device)
     return {'loss': loss, 'loss_rgb': rgb_full_loss, 'loss_dssim': dssim_loss, 'loss_depth': depth_loss}
+
+
+def _fused_depth_route(self, rgb_pred, depth_pred, depth_gt) -> bool:
+    """The fused depth term serves the trainer's own call: depth_loss_type 'l1' or 'invariant', depth_pred the [1,H,W] float32 device
+    plane of the render and a depth_gt of the same size.  GSR_AUTOPATCH_DEPTH_LOSS=0 keeps the reference's torch statements."""
+    if os.environ.get("GSR_AUTOPATCH_DEPTH_LOSS", "1") == "0" or os.environ.get("GSR_AUTOPATCH_LOSS_REPORT", "1") == "0" or not _ext_binding():
+        return False
+    if getattr(self, "depth_loss_type", None) not in ("l1", "invariant"):
+        return False
+    if not (torch.is_tensor(depth_pred) and torch.is_tensor(depth_gt)):
+        return False
+    return (depth_pred.is_cuda and depth_pred.device == rgb_pred.device and depth_pred.dtype == torch.float32 and depth_pred.dim() == 3
+            and depth_pred.shape[0] == 1 and tuple(depth_pred.shape[1:]) == tuple(rgb_pred.shape[1:]) and depth_pred.is_contiguous()
+            and depth_gt.numel() == depth_pred.numel() and tuple(depth_gt.shape[-2:]) == tuple(depth_pred.shape[1:])
+            and depth_gt.dim() in (2, 3) and depth_gt.dtype.is_floating_point)
 
 
 def _ext_binding() -> bool:

@@ -278,7 +278,8 @@ const char* gsr_last_error(void);
 /* 100 * major + minor.  110 (round 6): GsrForwardArgs ends with view_id, out_color_clamped, visible (appended in round 5 under
  * version 100: a caller compiled against a shorter struct must be rebuilt -- check gsr_version() >= 110 AND
  * gsr_struct_bytes(0) == sizeof(GsrForwardArgs), gsr_struct_bytes(1) == sizeof(GsrBackwardArgs) at start-up).
- * 111: GsrForwardArgs and GsrBackwardArgs end with sh_origin. */
+ * 111: GsrForwardArgs and GsrBackwardArgs end with sh_origin.
+ * 112: the depth term of the loss (gsr_depth_loss_*); no struct changed. */
 int gsr_version(void);
 size_t gsr_struct_bytes(int32_t which); /* 0 GsrForwardArgs, 1 GsrBackwardArgs, 2 GsrForwardOut; anything else 0 */
 
@@ -429,6 +430,33 @@ int gsr_loss_backward_batched(const float* render, const float* target, int32_t 
  * (the binding's differentiable scalar lives in storage of its own). */
 int gsr_loss_forward_terms(const float* render, const float* target, int32_t images, int32_t C, int32_t H, int32_t W, float lambda_dssim,
                            int32_t clamp01_render, void* workspace, float* out6, float* loss_copy, void* stream);
+
+/* ---- "next" row f-3, depth term (version 112): `lambda_depth * get_depth_loss(depth_pred, depth_gt)` of Loss.forward ---------
+ * Replaces the torch statements of /root/reference/trainer/losses.py:114-119 (the two masked clamp assignments and the call) and
+ * :86-95 (get_depth_loss): kind GSR_DEPTH_LOSS_L1 = sum |pc - g| / (H W) (:88-89); GSR_DEPTH_LOSS_INVARIANT = the MiDaS
+ * scale-and-shift-invariant loss as constructed at :41 (alpha = 0.5, scales = 1, batch-based reduction; :259-393) with the mask
+ * depth_gt > 0.02 (:92).  pc = min(max(depth, clamp_lo), clamp_hi) is fused (the reference clamps to [0.02, 20]); a pixel strictly
+ * outside the bounds gets zero gradient, one on a bound passes it.  The gradient flows through the fitted scale and shift, as under
+ * autograd in the reference.  depth, depth_gt: [H,W] float32 planes on the device.
+ * All sums are float64 over fixed grids in a fixed order (no atomics): the same input gives the same bits on every run.  No host
+ * synchronisation (the reference has three: `det.nonzero()` :274 and `if divisor == 0` :290 twice).
+ * out6 = {loss_depth (unweighted, as Loss.forward reports it, :133), scale s, shift t, M = number of valid pixels (H W for l1), data term,
+ * regulariser (before its 0.5)}.  lambda_depth is recorded in the workspace next to the coefficients; the weighted term is
+ * lambda_depth * out6[0].  workspace (gsr_depth_loss_workspace_bytes, 8-byte aligned) is kept for the backward.
+ * gsr_depth_loss_backward: d_depth[H,W] = grad_loss * lambda_depth * d loss_depth / d depth, one store per pixel; grad_loss = device
+ * pointer to the upstream scalar gradient, or NULL for 1. */
+#define GSR_DEPTH_LOSS_L1 0
+#define GSR_DEPTH_LOSS_INVARIANT 1
+size_t gsr_depth_loss_workspace_bytes(int32_t H, int32_t W);
+int gsr_depth_loss_forward(const float* depth, const float* depth_gt, int32_t H, int32_t W, int32_t kind, float clamp_lo, float clamp_hi,
+                           float lambda_depth, void* workspace, float* out6, void* stream);
+int gsr_depth_loss_backward(const float* depth, const float* depth_gt, int32_t H, int32_t W, int32_t kind, float clamp_lo, float clamp_hi,
+                            float lambda_depth, const void* workspace, const float* grad_loss, float* d_depth, void* stream);
+/* gsr_depth_loss_forward behind gsr_loss_forward_terms on the same stream: the finishing kernel completes that call's six-float vector
+ * into the whole dict of Loss.forward (:123-136) -- terms6[0] += lambda_depth * loss_depth, terms6[5] = loss_depth -- and writes the
+ * new total to loss_copy (may be NULL) as well. */
+int gsr_depth_loss_forward_terms(const float* depth, const float* depth_gt, int32_t H, int32_t W, int32_t kind, float clamp_lo, float clamp_hi,
+                                 float lambda_depth, void* workspace, float* out6, float* terms6, float* loss_copy, void* stream);
 
 /* ---- "next" row f-2: multi-tensor Adam step in one launch ------------------------------------------------
  * Same update rule as torch.optim.Adam(l, lr=0.0, eps=1e-15) of /root/reference/scene/gaussian_model_ht.py:275-289

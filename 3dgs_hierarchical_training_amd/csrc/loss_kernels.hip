@@ -33,7 +33,9 @@ __device__ __constant__ float kGauss[11] = {0.0010283801f, 0.0075987581f, 0.0360
                                             0.2660117249f, 0.2130055377f, 0.1093606895f, 0.0360007721f, 0.0075987581f,
                                             0.0010283801f};
 
-__device__ __forceinline__ float clamp01(float v) { return fminf(fmaxf(v, 0.f), 1.f); }
+// clamp(v, 0, 1) as torch's: a NaN stays a NaN (fminf / fmaxf would return the other operand, and a diverged render would report
+// a finite loss); +-Inf go to the bounds
+__device__ __forceinline__ float clamp01(float v) { return v < 0.f ? 0.f : (v > 1.f ? 1.f : v); }
 
 // Two moments per register pair: (x, y) and (x^2, y^2) ride through the separable window as float2, so a tap is one
 // v_pk_fma_f32 instead of two fmas (per-component fma: same rounding as scalar code).

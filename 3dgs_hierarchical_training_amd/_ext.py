@@ -53,6 +53,23 @@ def _register_fakes():
                 b(lib.gsr_image_bytes_batched(int(W), int(H), B)), b(nbin), torch.empty((3,), dtype=torch.int64),
                 f(*lead, 3, H, W) if (extras & 1) else f(0), b(N if ((extras & 2) and prepared.numel() == 0) else 0))
 
+    @torch.library.register_fake("gsr::importance_accumulate")
+    def _(acc, means3D, sh, colors_precomp, opacities, scales, rotations, cov3D_precomp, sh_rest, viewmatrix, projmatrix, campos, bg,
+          points_transform, image_height, image_width, tanfovx, tanfovy, scale_modifier, sh_degree, raw_params, batch_first_block,
+          view_id=0, sh_origin=None):
+        # acc is mutated in place (the schema's (a!)); the forward's {color, radii, depth, alpha, geom, image, binning, meta} come back
+        N, H, W = means3D.shape[0], image_height, image_width
+        f = lambda *s: means3D.new_empty(s, dtype=torch.float32)
+        b = lambda n: means3D.new_empty((n,), dtype=torch.uint8)
+        nbin = torch.library.get_ctx().new_dynamic_size()
+        return [f(3, H, W), means3D.new_empty((N,), dtype=torch.int32), f(1, H, W), f(1, H, W), b(lib.gsr_geom_bytes(int(N))),
+                b(lib.gsr_image_bytes_batched(int(W), int(H), 1)), b(nbin), torch.empty((3,), dtype=torch.int64)]
+
+    @torch.library.register_fake("gsr::importance_pass")
+    def _(acc, means3D, sh, sh_rest, campos, points_transform, color, geom, image, binning, meta, image_height, image_width, sh_degree,
+          sh_origin=None):
+        return None
+
     @torch.library.register_fake("gsr::rasterize")
     def _(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3D_precomp, sh_rest, viewmatrix, projmatrix, campos,
           bg, points_transform, image_height, image_width, tanfovx, tanfovy, scale_modifier, sh_degree, raw_params, prefiltered, debug,

@@ -80,6 +80,7 @@ EXPORTS = [
     "gsr_masked_max", "gsr_densify_stats_add", "gsr_psnr_scratch_bytes", "gsr_psnr",
     "gsr_loss_workspace_bytes_batched", "gsr_loss_forward_batched", "gsr_loss_backward_batched", "gsr_loss_forward_terms", "gsr_pose_grad", "gsr_struct_bytes", "gsr_debug_list_cut_stats",
     "gsr_depth_loss_workspace_bytes", "gsr_depth_loss_forward", "gsr_depth_loss_backward", "gsr_depth_loss_forward_terms",
+    "gsr_importance_scratch_bytes", "gsr_importance_accumulate",
 ]
 GSR_DEPTH_LOSS_L1, GSR_DEPTH_LOSS_INVARIANT = 0, 1
 
@@ -98,7 +99,8 @@ def load():
     lib = C.CDLL(LIB_PATH)
     lib.gsr_prepare_supported.restype = C.c_int
     lib.gsr_prepare_supported.argtypes = [C.c_int32, C.c_int32, C.c_int32]
-    for fn in ["gsr_geom_bytes", "gsr_forward_scratch_bytes", "gsr_backward_scratch_bytes", "gsr_prepared_bytes", "gsr_prepared_radii_offset"]:
+    for fn in ["gsr_geom_bytes", "gsr_forward_scratch_bytes", "gsr_backward_scratch_bytes", "gsr_prepared_bytes", "gsr_prepared_radii_offset",
+               "gsr_importance_scratch_bytes"]:
         getattr(lib, fn).restype = C.c_size_t
         getattr(lib, fn).argtypes = [C.c_int32]
     lib.gsr_image_bytes.restype = C.c_size_t
@@ -147,6 +149,8 @@ def load():
     lib.gsr_forward.argtypes = [C.POINTER(GsrForwardArgs), C.POINTER(GsrForwardOut), C.c_void_p]
     lib.gsr_backward.restype = C.c_int
     lib.gsr_backward.argtypes = [C.POINTER(GsrBackwardArgs), C.c_void_p]
+    lib.gsr_importance_accumulate.restype = C.c_int
+    lib.gsr_importance_accumulate.argtypes = [C.POINTER(GsrForwardArgs), C.POINTER(GsrForwardOut), C.c_void_p, C.c_void_p, C.c_void_p]
     lib.gsr_mark_visible.restype = C.c_int
     lib.gsr_mark_visible.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.gsr_last_error.restype = C.c_char_p

@@ -89,9 +89,10 @@ static inline void cpu_relax()
 static inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 // Optional per-kernel timing with HIP events on the caller's stream (bench.py roofline leg).
-enum ProfId { P_PRE_FWD, P_SORT_DEPTH, P_SCAN, P_EMIT, P_SORT_TILE, P_RANGES, P_BLEND_FWD, P_BLEND_BWD, P_PRE_BWD, P_CUT_REPAIR, P_COUNT };
+enum ProfId { P_PRE_FWD, P_SORT_DEPTH, P_SCAN, P_EMIT, P_SORT_TILE, P_RANGES, P_BLEND_FWD, P_BLEND_BWD, P_PRE_BWD, P_CUT_REPAIR,
+              P_IMP_BLEND, P_IMP_FINISH, P_COUNT };
 static const char* kProfNames[P_COUNT] = {"preprocess_fwd", "sort_depth", "scan", "emit", "sort_tile", "ranges",
-                                          "blend_fwd", "blend_bwd", "preprocess_bwd", "cut_repair"};
+                                          "blend_fwd", "blend_bwd", "preprocess_bwd", "cut_repair", "importance_blend", "importance_finish"};
 static int g_profile = 0;
 static std::atomic<unsigned> g_profile_tick{0};   // mode 3: every third launch of the forward blend is timed
 struct ProfPair { hipEvent_t a, b; };
@@ -2115,7 +2116,50 @@ __device__ uint32_t g_k6_cnt[2 * 65536];   // per forward-blend wave: visits, ta
 #define GSR_FWD_BUFS 2      // staging buffers of a forward-blend wave (round 5, measured: 1 -- a lone wave's LDS operations execute in order, so the next
 #endif                      // batch may overwrite the one just visited; 2.5 instead of 5 kB per wave -- the same 96-97 us: LDS does not bound its residency)
 constexpr int kFwdBufs = GSR_FWD_BUFS;
-template <bool REACH>
+
+// ---- importance pass (gsr_importance_accumulate): what the IMP instantiation of blend_fwd_item needs on top of the forward's arguments.
+// The pass walks a finished forward's lists again, in forward order, with the forward's out_color in hand: per taken visit it needs
+// sum over the wave's 64 pixels of w gate_c (w = alpha T, the weight the forward blend forms; gate_c = [0 <= out_color_c <= 1]) for
+// c = 0..2, added to S[gaussian id][c].  Three values are reduced with the transposed tree of wave_reduce_transposed2 cut down to
+// three: the row_ror levels pair (v0, v1) and then (r01, r2), the quad_perm levels and the two row swaps finish one register --
+// 13 vector instructions instead of 24; lane 0 / 4 / 8 hold the totals of v0 / v1 / v2.
+struct ImpArgs {
+    const float* color;   // [3,H,W] the forward's out_color
+    float* S;             // [N][4] per-Gaussian sums of this view (component 3 unused: a row is one 16-byte segment)
+    float (*s_sum)[64];   // [3][64] LDS, this wave's: sums of the batch's 64 instances
+    uint32_t* s_id;       // [64] LDS: the batch's Gaussian ids
+};
+constexpr int kImpStride = 4;
+__device__ __forceinline__ float wave_swap_rows_sum(float t)
+{
+    {
+        const unsigned u = __float_as_uint(t);
+        const auto r = __builtin_amdgcn_permlane16_swap(u, u, false, false);   // rows (0,1) and (2,3) exchange
+        t = __uint_as_float(r[0]) + __uint_as_float(r[1]);
+    }
+    {
+        const unsigned u = __float_as_uint(t);
+        const auto r = __builtin_amdgcn_permlane32_swap(u, u, false, false);   // halves exchange
+        t = __uint_as_float(r[0]) + __uint_as_float(r[1]);
+    }
+    return t;
+}
+__device__ __forceinline__ float wave_reduce_one(float v)      // every lane: the wave's total
+{
+    return wave_swap_rows_sum(bfly_single<0x128>(bfly_single<0x124>(bfly_single<0x4E>(bfly_single<0xB1>(v)))));
+}
+__device__ __forceinline__ float wave_reduce_three(float v0, float v1, float v2, int lane)   // lanes 0 / 4 / 8: totals of v0 / v1 / v2
+{
+    const float r01 = bfly_pair<0x124>(v0, v1, (lane & 4) != 0);
+    const float r2 = bfly_single<0x124>(v2);
+    const float q = bfly_pair<0x128>(r01, r2, (lane & 8) != 0);
+    return wave_swap_rows_sum(bfly_single<0x4E>(bfly_single<0xB1>(q)));
+}
+
+// IMP = the importance pass over a finished forward (see ImpArgs): the same staging, the same visit arithmetic in the same order, so
+// the same contributions are taken (and a pixel takes nothing behind the forward's recorded `last`); no image state, checkpoint,
+// counter or output is written -- per taken visit the gated weights are summed over the wave into LDS, per batch they are added to S.
+template <bool REACH, bool IMP = false>
 __device__ __forceinline__ void blend_fwd_item(const int xcd, const int kslot, float4 (*s_ab)[64], float2 (*s_c)[64],
                                                int W, int H, int tiles_x, int T, const uint2* __restrict__ ranges,
                                                const uint32_t* __restrict__ list, const Splat* __restrict__ splat,
@@ -2123,7 +2167,8 @@ __device__ __forceinline__ void blend_fwd_item(const int xcd, const int kslot, f
                                                float* __restrict__ out_depth, float* __restrict__ out_alpha,
                                                float* __restrict__ img, uint32_t* __restrict__ staged4, int interleave,
                                                float* __restrict__ ckpt, int kCkptFirst, int tiles_y, uint16_t* __restrict__ cost_out,
-                                               float* __restrict__ out_clamped, const ListCut& cut, const int cut_pass)
+                                               float* __restrict__ out_clamped, const ListCut& cut, const int cut_pass,
+                                               const ImpArgs imp = ImpArgs{})
 {
     // cut_pass (see ListCut): 0 = full lists; 1 = the lists may be cut: a wave that runs out of a cut list with a live pixel flags its
     // tile, every other wave records the depth it needed; 2 = the repair pass: only flagged tiles, on their full lists
@@ -2149,12 +2194,33 @@ __device__ __forceinline__ void blend_fwd_item(const int xcd, const int kslot, f
     const float pxf = (float)((sub & 1) * 8 + (lane & 7)), pyf = (float)((sub >> 1) * 8 + (lane >> 3));
     const float tox = (float)(tx * kTile) - 0.5f * (float)W, toy = (float)(ty * kTile) - 0.5f * (float)H;
     const uint2 rg = ranges[tile];
-    const int n = (int)(rg.y - rg.x);
+    // (IMP: no further than this wave staged in the forward)
+    const int n = IMP ? min((int)(rg.y - rg.x), (int)staged4[tile * 4 + sub]) : (int)(rg.y - rg.x);
     const int nb = (n + NT - 1) / NT;
     const bool inside = px < W && py < H;
     float Tr = inside ? 1.f : -1.f;            // running transmittance; negative = this pixel is finished
     float C0 = 0.f, C1 = 0.f, C2 = 0.f, Dd = 0.f, Aa = 0.f;
     uint32_t last = 0;
+    float g0 = 0.f, g1 = 0.f, g2 = 0.f;        // IMP: this pixel's three gates (1 = open), the forward's `last`, one sum serves all three
+    uint32_t lastp = 0u, id_rec = 0u;
+    bool uni = false;
+    if constexpr (IMP) {
+        if (inside) {
+            const size_t Pl = (size_t)W * H, P = Pl * (size_t)(T / Tl), pl = (size_t)py * W + px, pid = (size_t)bimg * Pl + pl;
+            const float* oc = imp.color + (size_t)bimg * 3 * Pl + pl;
+            const float o0 = oc[0], o1 = oc[Pl], o2 = oc[2 * Pl];
+            g0 = (o0 >= 0.f && o0 <= 1.f) ? 1.f : 0.f;     // NaN closes the gate, as torch's clamp backward does
+            g1 = (o1 >= 0.f && o1 <= 1.f) ? 1.f : 0.f;
+            g2 = (o2 >= 0.f && o2 <= 1.f) ? 1.f : 0.f;
+            lastp = reinterpret_cast<const uint32_t*>(img)[P + pid];
+        }
+        const bool want = lastp > 0u && (g0 + g1 + g2) > 0.f;   // a pixel that took nothing, or whose gates are all closed, adds nothing
+        if (!__any(want)) return;
+        Tr = want ? 1.f : -1.f;
+        if (!want) g0 = g1 = g2 = 0.f;
+        uni = __all(g0 == g1 && g1 == g2);
+        imp.s_sum[0][lane] = 0.f; imp.s_sum[1][lane] = 0.f; imp.s_sum[2][lane] = 0.f;
+    }
     float4 ra = {0, 0, 0, 0}, rb = ra, rc = ra;
     constexpr float kL2E = 1.4426950408889634f;
     // REACH: the staging lane also runs the exact box test of the tile culling (gsr_math.h box_accept: the minimum of the conic
@@ -2178,7 +2244,8 @@ __device__ __forceinline__ void blend_fwd_item(const int xcd, const int kslot, f
     // (every lane loads, from a clamped position: a load under a lane condition ends in copies of its result at the join, and
     //  the copies wait for the load right there)
     if (n > 0) {
-        fetch(list[rg.x + min(lane, n - 1)]);
+        id_rec = list[rg.x + min(lane, n - 1)];
+        fetch(id_rec);
         id_nn = list[rg.x + min(NT + lane, n - 1)];
     }
     int batches = 0;
@@ -2202,7 +2269,9 @@ __device__ __forceinline__ void blend_fwd_item(const int xcd, const int kslot, f
             ra.x = pixel_rel(ra.x, pixel_lo_x(lo), tox); ra.y = pixel_rel(ra.y, pixel_lo_y(lo), toy);
         }
         ra.z *= -0.5f * kL2E; ra.w *= -kL2E; rb.x *= -0.5f * kL2E;
-        s_ab[buf][lane] = ra; s_ab[kFwdBufs + buf][lane] = rb; s_c[buf][lane] = make_float2(rc.x, rc.y);
+        s_ab[buf][lane] = ra; s_ab[kFwdBufs + buf][lane] = rb;
+        if constexpr (IMP) imp.s_id[lane] = id_rec;            // (the colour plane s_c is the forward's alone: the pass has none)
+        else s_c[buf][lane] = make_float2(rc.x, rc.y);
         const unsigned long long reach = REACH ? __ballot(reach_me && lane < cnt) : 0ull;
         visits += REACH ? (uint32_t)__popcll(reach) : (uint32_t)cnt;
         // the staging area belongs to this wave alone: LDS instructions of one wave execute in issue order, so the broadcast
@@ -2217,6 +2286,7 @@ __device__ __forceinline__ void blend_fwd_item(const int xcd, const int kslot, f
 #endif
         const int nxt = (b + 1) * NT + lane;
         fetch(id_nn);
+        if constexpr (IMP) id_rec = id_nn;
         id_nn = list[rg.x + min(nxt + NT, n - 1)];
         auto alpha_of = [&](int j, float& p2) {
             const float4 A = s_ab[buf][j];
@@ -2234,16 +2304,22 @@ __device__ __forceinline__ void blend_fwd_item(const int xcd, const int kslot, f
             // every lane runs the blend with alpha = 0 where its own test failed -- a live pixel then passes the stop test with
             // test_T = T and adds (+-)0 everywhere.  (The exec-masked form cost s_and_saveexec + s_or exec on every visit, taken or
             // not: this loop is bound by instructions issued per wave, scalar ones included.)
-            const bool hit = !(p2 > 0.f) && !(alpha < kAlphaMin);
+            const bool inl = !IMP || (uint32_t)(b * NT + j + 1) <= lastp;   // IMP: nothing behind the forward's last contribution
+            const bool hit = !(p2 > 0.f) && !(alpha < kAlphaMin) && inl;
 #ifdef GSR_K6_TIMING
             dbg_visits++;
 #endif
-            if ((__builtin_amdgcn_ballot_w64(!(p2 > 0.f)) & __builtin_amdgcn_ballot_w64(!(alpha < kAlphaMin))) == 0ull) return;
+            if constexpr (IMP) {
+                if ((__builtin_amdgcn_ballot_w64(!(p2 > 0.f)) & __builtin_amdgcn_ballot_w64(!(alpha < kAlphaMin)) & __builtin_amdgcn_ballot_w64(inl)) == 0ull) return;
+            } else {
+                if ((__builtin_amdgcn_ballot_w64(!(p2 > 0.f)) & __builtin_amdgcn_ballot_w64(!(alpha < kAlphaMin))) == 0ull) return;
+            }
 #ifdef GSR_K6_TIMING
             dbg_taken++;
 #endif
             const float4 B = s_ab[kFwdBufs + buf][j];
-            const float2 C = s_c[buf][j];
+            float2 C = {0.f, 0.f};
+            if constexpr (!IMP) C = s_c[buf][j];
             const float am = hit ? alpha : 0.f;
             const float test_T = Tr * (1.f - am);             // negative for a finished pixel: fails the stop test below
             const bool pass = !(test_T < kTStop);
@@ -2253,6 +2329,16 @@ __device__ __forceinline__ void blend_fwd_item(const int xcd, const int kslot, f
             Dd = fmaf(B.z, w, Dd); Aa = fmaf(Tr, asel, Aa);   // (k_blend_fwd_w's `A += alpha * T` is contracted to this fma)
             Tr = pass ? test_T : -fabsf(Tr);                  // first failure flips the sign: done, |T| kept
             last = (pass && hit) ? (uint32_t)(b * NT + j + 1) : last;
+            if constexpr (IMP) {
+                // the instance's sums over this wave's pixels, into the batch's LDS row (this wave's alone: plain LDS adds, in order)
+                if (uni) {
+                    const float t = wave_reduce_one(w * g0);
+                    if (lane == 0) atomicAdd(&imp.s_sum[0][j], t);
+                } else {
+                    const float t = wave_reduce_three(w * g0, w * g1, w * g2, lane);
+                    if (lane < 12 && !(lane & 3)) atomicAdd(&imp.s_sum[lane >> 2][j], t);
+                }
+            }
             // (round 4, measured again at eight waves per SIMD and 0.86 counted vector-pipe activity: the lanes that blend under EXEC
             //  -- `if (hit) { if (pass) {...} else T = -|T| }`, 26 instead of 31 vector instructions per taken visit, three more
             //  branches -- 105 us against 99-101)
@@ -2285,7 +2371,28 @@ __device__ __forceinline__ void blend_fwd_item(const int xcd, const int kslot, f
 #ifdef GSR_K6_TIMING
         dbg_loop += __builtin_readcyclecounter() - dbg_mark;
 #endif
+        if constexpr (IMP) {
+            // flush: four lanes per Gaussian, lane c adds channel c, so one atomic instruction touches sixteen 16-byte rows of S with
+            // three consecutive floats each instead of 64 rows with one (the backward blend's flush, cut down to three components)
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            const int c = lane & 3;
+#pragma unroll
+            for (int q = 0; q < 4; q++) {
+                const int jj = q * 16 + (lane >> 2);
+                if (c < 3 && jj < cnt) {
+                    const float v = imp.s_sum[uni ? 0 : c][jj];
+                    if (v != 0.f) atomicAdd(imp.S + (size_t)imp.s_id[jj] * kImpStride + c, v);
+                }
+            }
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            imp.s_sum[0][lane] = 0.f; imp.s_sum[1][lane] = 0.f; imp.s_sum[2][lane] = 0.f;   // (ordered in front of the next batch's adds: one wave's LDS operations execute in order)
+        }
     }
+    if constexpr (IMP) return;
     if (lane == 0) staged4[tile * 4 + sub] = (uint32_t)min(n, batches * NT);
     if (cost_out && lane == 0) cost_out[xcd + 8 * kslot] = (uint16_t)min(visits, 65535u);
     if (cut_pass) {
@@ -2370,6 +2477,47 @@ __global__ __launch_bounds__(64) void k_blend_fwd_w6(int W, int H, int tiles_x, 
     }
     blend_fwd_item<REACH>((int)(blockIdx.x & 7), kslot, s_ab, s_c, W, H, tiles_x, T, ranges, list, splat, bg, out_color, out_depth,
                           out_alpha, img, staged4, interleave, ckpt, kCkptFirst, tiles_y, cost_out, out_clamped, cut, cut_pass);
+}
+
+// Importance blend (gsr_importance_accumulate): the forward blend's walk a second time -- blend_fwd_item<true, true> -- in dispatch order
+// (no balanced placement: nothing records this launch's visits), one wave per 8x8 sub-tile.
+__global__ __launch_bounds__(64) void k_blend_importance(int W, int H, int tiles_x, int T, const uint2* __restrict__ ranges,
+                                                         const uint32_t* __restrict__ list, const Splat* __restrict__ splat,
+                                                         float* __restrict__ img, uint32_t* __restrict__ staged4, int interleave, int tiles_y,
+                                                         const float* __restrict__ color, float* __restrict__ S)
+{
+    __shared__ float4 s_ab[2 * kFwdBufs][64];
+    __shared__ float s_sum[3][64];
+    __shared__ uint32_t s_id[64];
+    blend_fwd_item<true, true>((int)(blockIdx.x & 7), (int)(blockIdx.x >> 3), s_ab, nullptr, W, H, tiles_x, T, ranges, list, splat, nullptr, nullptr, nullptr,
+                               nullptr, img, staged4, interleave, nullptr, 0, tiles_y, nullptr, nullptr, ListCut{}, 0, ImpArgs{color, S, s_sum, s_id});
+}
+
+// Finish of the importance pass: acc[n,k,c] += |basis_k(dir_n)| [colour_{n,c} > 0] S[n,c] for k < (D+1)^2 -- sixteen threads per
+// Gaussian, thread k the three channels of coefficient k (a Gaussian's 16 x 12 bytes are one contiguous run of the accumulator).
+// Rows whose three sums are zero are neither read nor written; coefficients k >= (D+1)^2 are left alone.  The direction is the one
+// the forward's preprocess used (splat_sh_color): normalize(posed mean - campos), or normalize(mean - sh_origin); "colour > 0" in the
+// splat record is the statement "this channel's SH colour was not clamped at 0".
+__global__ __launch_bounds__(256) void k_importance_finish(int N, int M, int D, const float* __restrict__ means, const float* __restrict__ xf,
+                                                           const float* __restrict__ campos, const float* __restrict__ sh_origin,
+                                                           const Splat* __restrict__ splat, const float* __restrict__ S, float* __restrict__ acc)
+{
+    const int n = (int)blockIdx.x * 16 + (int)(threadIdx.x >> 4), k = (int)(threadIdx.x & 15);
+    if (n >= N || k >= (D + 1) * (D + 1)) return;
+    const float4 s = reinterpret_cast<const float4*>(S)[n];
+    if (s.x == 0.f && s.y == 0.f && s.z == 0.f) return;
+    float mean[3] = {means[3 * (size_t)n], means[3 * (size_t)n + 1], means[3 * (size_t)n + 2]};
+    float o[3];
+    if (sh_origin) { o[0] = sh_origin[0]; o[1] = sh_origin[1]; o[2] = sh_origin[2]; }
+    else { apply_points_transform(xf, mean); o[0] = campos[0]; o[1] = campos[1]; o[2] = campos[2]; }
+    float basis[16];
+    sh_basis_dir(D, mean, o, basis);
+    const Splat sp = splat[n];
+    const float b = fabsf(basis[k]);
+    float* a = acc + ((size_t)n * M + k) * 3;
+    if (sp.r > 0.f) a[0] += b * s.x;
+    if (sp.g > 0.f) a[1] += b * s.y;
+    if (sp.b > 0.f) a[2] += b * s.z;
 }
 
 // (round 3, measured with tools/k6_wave_timing.py on the 1 M / 980x545 frame: the 8.6 k waves are all resident at once, eight to
@@ -4292,7 +4440,7 @@ size_t gsr_prepared_bytes(int32_t N) { return prep_layout(N).bytes; }
 size_t gsr_prepared_radii_offset(int32_t N) { return prep_layout(N).radii; }
 int gsr_prepare_supported(int32_t M, int32_t D, int32_t raw_params) { return (raw_params && M == 16 && D >= 0 && D <= 3) ? 1 : 0; }
 const char* gsr_last_error(void) { return g_err; }
-int gsr_version(void) { return 112; }
+int gsr_version(void) { return 113; }
 size_t gsr_struct_bytes(int32_t which)
 {
     return which == 0 ? sizeof(GsrForwardArgs) : which == 1 ? sizeof(GsrBackwardArgs) : which == 2 ? sizeof(GsrForwardOut) : 0;
@@ -5285,6 +5433,51 @@ int gsr_backward(const GsrBackwardArgs* a, void* stream_)
     if (want_cam)
         hipLaunchKernelGGL(k_cam_reduce, dim3(kCamVals, NB), dim3(256), 0, st, cam_partial, grid, a->d_viewmatrix, a->d_projmatrix, a->d_campos,
                            a->d_points_transform, bt);
+    GSR_HIP(hipGetLastError());
+    return GSR_OK;
+}
+
+// ---- merge-time colour importance of one view, from the forward alone (include/gsr.h) --------------------------------------------
+size_t gsr_importance_scratch_bytes(int32_t N) { return align256((size_t)(N > 0 ? N : 1) * kImpStride * sizeof(float)); }
+
+int gsr_importance_accumulate(const GsrForwardArgs* a, const GsrForwardOut* out, float* acc, void* scratch, void* stream_)
+{
+    hipStream_t st = (hipStream_t)stream_;
+    if (!a || !out) return fail(GSR_ERR_ARG, "null args%s");
+    int rc = check_common(a->N, a->M, a->D, a->W, a->H);
+    if (rc) return rc;
+    if (a->colors_precomp || !a->shs) return fail(GSR_ERR_ARG, "importance: the model must carry SH coefficients (colors_precomp has none)%s");
+    if (a->batch && a->batch->B > 1) return fail(GSR_ERR_ARG, "importance: not served with a batch of B > 1%s");
+    if (a->M < (a->D + 1) * (a->D + 1) || !a->campos) return fail(GSR_ERR_ARG, "shs needs campos and M >= (D+1)^2%s");
+    const int N = a->N, W = a->W, H = a->H;
+    if (N == 0) return GSR_OK;
+    if (!acc || !scratch || !a->geom || !a->image || !a->out_color || !a->means3D) return fail(GSR_ERR_ARG, "missing workspace / accumulator pointer%s");
+    if (out->num_rendered <= 0 || !out->binning) return GSR_OK;   // nothing was blended: every sum is zero, the accumulator keeps its bits
+    int f_map = g_tile_map;
+    if (out->forward_flags & 1) {
+        f_map = (int)((out->forward_flags >> 4) & 3);
+        if (f_map > 2) return fail(GSR_ERR_ARG, "forward_flags do not come from gsr_forward%s");
+    }
+    const int tiles_x = (W + kTile - 1) / kTile, tiles_y = (H + kTile - 1) / kTile, T = tiles_x * tiles_y;
+    const Splat* splat = static_cast<const Splat*>(a->geom);
+    const BinLayout B = bin_layout(out->binning_capacity > 0 ? out->binning_capacity : out->num_rendered, W, H, 1);
+    const uint8_t* bin = static_cast<const uint8_t*>(out->binning);
+    const uint2* ranges = reinterpret_cast<const uint2*>(bin + B.ranges);
+    const uint32_t* list = reinterpret_cast<const uint32_t*>(bin + B.list);
+    float* img = static_cast<float*>(a->image);
+    uint32_t* staged = reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(a->image) + image_staged_offset(W, H, 1));
+    float* S = static_cast<float*>(scratch);
+    GSR_HIP(hipMemsetAsync(S, 0, (size_t)N * kImpStride * sizeof(float), st));
+    {
+        ProfScope ps(P_IMP_BLEND, st);
+        hipLaunchKernelGGL(k_blend_importance, dim3(8 * 4 * slots_per_xcd(f_map, T, tiles_x)), dim3(64), 0, st, W, H, tiles_x, T, ranges, list, splat,
+                           img, staged, f_map, tiles_y, (const float*)a->out_color, S);
+    }
+    {
+        ProfScope ps(P_IMP_FINISH, st);
+        hipLaunchKernelGGL(k_importance_finish, dim3((N + 15) / 16), dim3(256), 0, st, N, a->M, a->D, a->means3D, a->points_transform, a->campos,
+                           a->sh_origin, splat, (const float*)S, acc);
+    }
     GSR_HIP(hipGetLastError());
     return GSR_OK;
 }

@@ -398,6 +398,30 @@ GSR_HD void splat_sh_color(const Camera& c, const float mean[3], const float* sh
     }
 }
 
+// The SH basis functions of degree <= deg in the direction normalize(mean - origin), formed as splat_sh_color forms it
+// (the factors that multiply sh[k] in sh_channel); entries beyond (deg + 1)^2 are zero.
+GSR_HD void sh_basis_dir(int deg, const float mean[3], const float origin[3], float basis[16])
+{
+    float dx = mean[0] - origin[0], dy = mean[1] - origin[1], dz = mean[2] - origin[2];
+    const float inv_n = 1.0f / sqrtf(dx * dx + dy * dy + dz * dz);
+    const float x = dx * inv_n, y = dy * inv_n, z = dz * inv_n;
+    for (int k = 0; k < 16; k++) basis[k] = 0.f;
+    basis[0] = SH_C0;
+    if (deg > 0) {
+        basis[1] = -SH_C1 * y; basis[2] = SH_C1 * z; basis[3] = -SH_C1 * x;
+        if (deg > 1) {
+            const float xx = x * x, yy = y * y, zz = z * z, xy = x * y, yz = y * z, xz = x * z;
+            basis[4] = SH_C2_0 * xy; basis[5] = SH_C2_1 * yz; basis[6] = SH_C2_2 * (2.f * zz - xx - yy);
+            basis[7] = SH_C2_3 * xz; basis[8] = SH_C2_4 * (xx - yy);
+            if (deg > 2) {
+                basis[9] = SH_C3_0 * y * (3.f * xx - yy); basis[10] = SH_C3_1 * xy * z; basis[11] = SH_C3_2 * y * (4.f * zz - xx - yy);
+                basis[12] = SH_C3_3 * z * (2.f * zz - 3.f * xx - 3.f * yy); basis[13] = SH_C3_4 * x * (4.f * zz - xx - yy);
+                basis[14] = SH_C3_5 * z * (xx - yy); basis[15] = SH_C3_6 * x * (xx - 3.f * yy);
+            }
+        }
+    }
+}
+
 // Forward projection of one Gaussian.  `sh` may be null when `color_pre` is given (and vice versa);
 // `cov_pre` null means build Sigma from scale/rot.  sh coefficient k of channel ch is at
 // sh[k*sh_kstride + ch*sh_cstride] (lets the caller hand either the global [M][3] row or an LDS copy).

@@ -11,6 +11,8 @@
 //   gsr::rasterize_backward   -> gsr_backward
 //   gsr::rasterize_backward_fused  -> gsr_backward with the in-kernel Adam step (parameters / moments updated in place)
 //   gsr::mark_visible         -> gsr_mark_visible
+//   gsr::importance_accumulate -> gsr_forward + gsr_importance_accumulate (merge-time colour importance, no backward)
+//   gsr::importance_pass      -> gsr_importance_accumulate over a rasterize_forward's outputs
 //   gsr::photometric_loss_forward / _backward -> gsr_loss_forward / gsr_loss_backward
 //   gsr::depth_loss_forward / _backward, gsr::training_loss_terms -> gsr_depth_loss_forward / _backward / _forward_terms
 //   gsr::adam_step            -> gsr_adam_step
@@ -180,6 +182,65 @@ std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tenso
         g_last = {image, binning, meta, dims};
     }
     return {color, radii, depth, alpha, geom, image, binning, meta, clamped, visible};
+}
+
+// gsr::importance_pass -> gsr_importance_accumulate over the outputs of a rasterize_forward of the same inputs on this stream (the second
+// half of gsr::importance_accumulate below, on its own for callers that keep the forward's buffers).  Mutates acc only.
+void importance_pass(Tensor& acc, const Tensor& means3D_, const Tensor& sh_, const Tensor& sh_rest_, const Tensor& campos_, const Tensor& xf_,
+                     const Tensor& color, const Tensor& geom, const Tensor& image, const Tensor& binning, const Tensor& meta, int64_t H, int64_t W,
+                     int64_t sh_degree, const c10::optional<Tensor>& sh_origin_)
+{
+    TORCH_CHECK(means3D_.is_cuda() && has(sh_), "importance_pass: a model with SH coefficients on a ROCm/HIP device expected");
+    const c10::hip::HIPGuardMasqueradingAsCUDA guard(means3D_.device());
+    const Tensor means3D = f32c(means3D_), sh = f32c(sh_), rest = f32c(sh_rest_), campos = f32c(campos_), xf = f32c(xf_);
+    const Tensor sh_origin = sh_origin_arg(sh_origin_);
+    const int64_t N = means3D.size(0), M = sh.size(1) + (has(rest) ? rest.size(1) : 0);
+    TORCH_CHECK(acc.is_cuda() && acc.scalar_type() == at::kFloat && acc.is_contiguous() && acc.dim() == 3 && acc.size(0) == N && acc.size(1) == M &&
+                    acc.size(2) == 3, "importance: acc must be a contiguous float32 [N, M, 3] tensor (M = stored SH coefficients)");
+    TORCH_CHECK(color.is_contiguous() && color.scalar_type() == at::kFloat && color.numel() == 3 * H * W && meta.numel() == 3 &&
+                    geom.numel() == (int64_t)gsr_geom_bytes((int32_t)N) && image.numel() == (int64_t)gsr_image_bytes((int32_t)W, (int32_t)H),
+                "importance_pass: the buffers do not come from a single-model rasterize_forward of this model and image size");
+    GsrForwardArgs a{};
+    a.N = (int32_t)N; a.M = (int32_t)M; a.D = (int32_t)sh_degree; a.W = (int32_t)W; a.H = (int32_t)H;
+    a.means3D = fp(means3D); a.shs = fp(sh); a.shs_rest = fp(rest); a.campos = fp(campos); a.points_transform = fp(xf);
+    a.sh_origin = fp(sh_origin);
+    a.out_color = color.data_ptr<float>(); a.geom = geom.data_ptr(); a.image = image.data_ptr();
+    GsrForwardOut out{};
+    const int64_t* mp = meta.data_ptr<int64_t>();
+    out.num_rendered = mp[0]; out.binning_capacity = mp[1]; out.forward_flags = mp[2];
+    out.binning = has(binning) ? binning.data_ptr() : nullptr;
+    if (out.binning) TORCH_CHECK(binning.numel() >= (int64_t)gsr_binning_bytes(mp[1] > 0 ? mp[1] : mp[0], (int32_t)W, (int32_t)H), "importance_pass: binning buffer too small");
+    Tensor scratch = at::empty({(int64_t)gsr_importance_scratch_bytes((int32_t)N)}, means3D.options().dtype(at::kByte));
+    check(gsr_importance_accumulate(&a, &out, acc.data_ptr<float>(), scratch.data_ptr(), c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream()),
+          "gsr_importance_accumulate");
+}
+
+// gsr::importance_accumulate -> gsr_forward + gsr_importance_accumulate: one view's colour importance added to `acc` [N,M,3] in place
+// (include/gsr.h, version 113; what hierarchy.calc_importance's kernel route runs per view).  The render goes through rasterize_forward
+// above -- the code path of gsr::rasterize -- with raw or activated parameters.  No autograd.  Returns the forward's
+// {color, radii, depth, alpha, geom, image, binning, meta}: an ordinary rasterize_backward over them is still valid.
+std::vector<Tensor> importance_accumulate(
+    Tensor& acc, const Tensor& means3D_, const Tensor& sh_, const Tensor& colors_, const Tensor& opacities_, const Tensor& scales_,
+    const Tensor& rotations_, const Tensor& cov3D_, const Tensor& sh_rest_, const Tensor& viewmatrix_, const Tensor& projmatrix_,
+    const Tensor& campos_, const Tensor& bg_, const Tensor& xf_, int64_t H, int64_t W, double tanfovx, double tanfovy,
+    double scale_modifier, int64_t sh_degree, bool raw_params, at::IntArrayRef batch_first_block, int64_t view_id,
+    const c10::optional<Tensor>& sh_origin_)
+{
+    TORCH_CHECK(means3D_.is_cuda(), "importance_accumulate: tensors must be on a ROCm/HIP device (no CPU fallback)");
+    const BatchArg batch(batch_first_block);
+    TORCH_CHECK(batch.B() == 1, "importance_accumulate: not served with a batch of B > 1");
+    TORCH_CHECK(has(sh_) && !has(colors_), "importance_accumulate: the model must carry SH coefficients (colors_precomp has none)");
+    const c10::hip::HIPGuardMasqueradingAsCUDA guard(means3D_.device());
+    const Tensor means3D = f32c(means3D_), sh = f32c(sh_), rest = f32c(sh_rest_), campos = f32c(campos_), xf = f32c(xf_);
+    const int64_t N = means3D.size(0), M = sh.size(1) + (has(rest) ? rest.size(1) : 0);
+    TORCH_CHECK(acc.is_cuda() && acc.scalar_type() == at::kFloat && acc.is_contiguous() && acc.dim() == 3 && acc.size(0) == N && acc.size(1) == M &&
+                    acc.size(2) == 3, "importance_accumulate: acc must be a contiguous float32 [N, M, 3] tensor (M = stored SH coefficients)");
+    auto f = rasterize_forward(means3D, sh, colors_, opacities_, scales_, rotations_, cov3D_, rest, viewmatrix_, projmatrix_, campos, bg_, xf, H, W,
+                               tanfovx, tanfovy, scale_modifier, sh_degree, raw_params, false, false, at::empty({0}, means3D.options().dtype(at::kByte)),
+                               batch_first_block, view_id, 0, sh_origin_);
+    const Tensor &color = std::get<0>(f), &geom = std::get<4>(f), &image = std::get<5>(f), &binning = std::get<6>(f), &meta = std::get<7>(f);
+    importance_pass(acc, means3D, sh, rest, campos, xf, color, geom, image, binning, meta, H, W, sh_degree, sh_origin_);
+    return {color, std::get<1>(f), std::get<2>(f), std::get<3>(f), geom, image, binning, meta};
 }
 
 struct BwdCommon {
@@ -984,6 +1045,12 @@ TORCH_LIBRARY(gsr, m)
           "int next_width, float next_tanfovx, float next_tanfovy, Tensor next_points_transform, int next_sh_degree, Tensor adam_commit, Tensor[] densify_stats, int[] batch_first_block, int view_id=0, int extras=0, "
           "Tensor? sh_origin=None) -> "
           "(Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)");
+    m.def("importance_accumulate(Tensor(a!) acc, Tensor means3D, Tensor sh, Tensor colors_precomp, Tensor opacities, Tensor scales, "
+          "Tensor rotations, Tensor cov3D_precomp, Tensor sh_rest, Tensor viewmatrix, Tensor projmatrix, Tensor campos, Tensor bg, "
+          "Tensor points_transform, int image_height, int image_width, float tanfovx, float tanfovy, float scale_modifier, int sh_degree, "
+          "bool raw_params, int[] batch_first_block, int view_id=0, Tensor? sh_origin=None) -> Tensor[]");
+    m.def("importance_pass(Tensor(a!) acc, Tensor means3D, Tensor sh, Tensor sh_rest, Tensor campos, Tensor points_transform, Tensor color, "
+          "Tensor geom, Tensor image, Tensor binning, Tensor meta, int image_height, int image_width, int sh_degree, Tensor? sh_origin=None) -> ()");
     m.def("mark_visible(Tensor means3D, Tensor viewmatrix, Tensor projmatrix) -> Tensor");
     m.def("photometric_loss_forward(Tensor render, Tensor target, float lambda_dssim, bool clamp) -> (Tensor, Tensor)");
     m.def("photometric_loss_backward(Tensor render, Tensor target, Tensor workspace, Tensor grad_loss, float lambda_dssim, bool clamp) -> Tensor");
@@ -1017,6 +1084,8 @@ TORCH_LIBRARY_IMPL(gsr, CUDA, m)   // the dispatch key of HIP tensors on a ROCm 
     m.impl("rasterize_forward", &rasterize_forward);
     m.impl("rasterize_backward", &rasterize_backward);
     m.impl("rasterize_backward_fused", &rasterize_backward_fused);
+    m.impl("importance_accumulate", &importance_accumulate);
+    m.impl("importance_pass", &importance_pass);
     m.impl("mark_visible", &mark_visible);
     m.impl("photometric_loss_forward", &photometric_loss_forward);
     m.impl("photometric_loss_backward", &photometric_loss_backward);

@@ -11,13 +11,14 @@ parallel), the source ships its **un-pruned** child with the drop mask, and the 
 which therefore also holds both un-pruned children as the frozen teachers of `train_nonleaf_3DGS_phase1`
 (:757, :866-883).  No collective is involved.
 """
+import os
 import time
 from typing import Dict, List, Optional
 
 import torch
 
 from . import segments
-from .rasterizer import GaussianRasterizationSettings, rasterize_gaussians_raw
+from .rasterizer import GaussianRasterizationSettings, importance_accumulate, rasterize_gaussians_raw
 
 
 def _elapsed_ms(t0: float, ref: torch.Tensor) -> float:
@@ -35,8 +36,60 @@ def render_raw(seg: Dict[str, torch.Tensor], rs: GaussianRasterizationSettings) 
         return color.clamp(0, 1)
 
 
-def calc_importance(seg: Dict[str, torch.Tensor], views: List[GaussianRasterizationSettings]) -> torch.Tensor:
-    """[N, 48] colour importance of a segment over `views` (each a full raster-settings tuple)."""
+# Which route calc_importance takes when its caller names none: "kernel" (a forward and the importance pass per view, include/gsr.h
+# gsr_importance_accumulate) or "autograd" (a render and a full backward per view).  Chosen by tools/importance_probe.py's rule: the
+# kernel route's median lies below the autograd route's by more than the same-arm spread at the headline scene and at stage A's size,
+# on dark and on brightened scenes (profiles/importance_probe.txt: 4.28 against 6.97 ms and 1.97 against 3.03 ms per eight views;
+# DESIGN.md section 6).  GSR_IMPORTANCE_ROUTE=autograd in the environment puts the old route back under every caller (A/B runs).
+DEFAULT_IMPORTANCE_ROUTE = os.environ.get("GSR_IMPORTANCE_ROUTE", "kernel")
+IMPORTANCE_ROUTES = ("kernel", "autograd")
+if DEFAULT_IMPORTANCE_ROUTE not in IMPORTANCE_ROUTES:
+    raise ValueError(f"GSR_IMPORTANCE_ROUTE={DEFAULT_IMPORTANCE_ROUTE!r}: one of {IMPORTANCE_ROUTES}")
+
+_SH_C0 = 0.28209479177387814
+_SH_C1 = 0.4886025119029199
+_SH_C2 = (1.0925484305920792, -1.0925484305920792, 0.31539156525252005, -1.0925484305920792, 0.5462742152960396)
+_SH_C3 = (-0.5900435899266435, 2.890611442640554, -0.4570457994644658, 0.3731763325901154, -0.4570457994644658, 1.445305721320277,
+          -0.5900435899266435)
+
+
+def sh_basis(dirs: torch.Tensor, degree: int) -> torch.Tensor:
+    """[N, (degree+1)^2] real SH basis in the unit directions `dirs` [N,3]: the factors that multiply the coefficients in the
+    kernels' colour evaluation (csrc/gsr_math.h sh_channel / sh_basis_dir), in `dirs`' dtype."""
+    x, y, z = dirs[:, 0], dirs[:, 1], dirs[:, 2]
+    b = [torch.full_like(x, _SH_C0)]
+    if degree > 0:
+        b += [-_SH_C1 * y, _SH_C1 * z, -_SH_C1 * x]
+    if degree > 1:
+        xx, yy, zz, xy, yz, xz = x * x, y * y, z * z, x * y, y * z, x * z
+        b += [_SH_C2[0] * xy, _SH_C2[1] * yz, _SH_C2[2] * (2 * zz - xx - yy), _SH_C2[3] * xz, _SH_C2[4] * (xx - yy)]
+    if degree > 2:
+        b += [_SH_C3[0] * y * (3 * xx - yy), _SH_C3[1] * xy * z, _SH_C3[2] * y * (4 * zz - xx - yy),
+              _SH_C3[3] * z * (2 * zz - 3 * xx - 3 * yy), _SH_C3[4] * x * (4 * zz - xx - yy), _SH_C3[5] * z * (xx - yy),
+              _SH_C3[6] * x * (xx - 3 * yy)]
+    return torch.stack(b, 1)
+
+
+def importance_from_sums(S: torch.Tensor, dirs: torch.Tensor, colours: torch.Tensor, degree: int, M: int) -> torch.Tensor:
+    """One view's |dL/dSH| [N, M, 3] for L = sum clamp(image, 0, 1), from the per-Gaussian sums the importance pass takes:
+
+        |dL/dSH[n,k,c]| = |basis_k(dirs_n)| * [colours[n,c] > 0] * S[n,c],   S[n,c] = sum_pixels alpha T [0 <= out_color_c <= 1]
+
+    (S >= 0; "colour > 0" says that channel's SH colour was not clamped at 0).  The finishing kernel's formula
+    (csrc/gsr_kernels.hip k_importance_finish) in torch, in the kernel's order of operations: b = |basis_k|, then b * S[n,c] where the
+    gate is open, nothing where it is closed; coefficients k >= (degree+1)^2 stay zero.  Any device, any float dtype: S, dirs [N,3]
+    (unit view directions) and colours [N,3] are used in S's dtype."""
+    nc = (degree + 1) ** 2
+    if M < nc:
+        raise ValueError(f"M = {M} stored coefficients cannot hold degree {degree}")
+    b = sh_basis(dirs.to(S.dtype), degree).abs()                       # [N, nc]
+    gated = torch.where(colours.to(S.device) > 0, S, torch.zeros_like(S))   # [N, 3]
+    out = S.new_zeros((S.shape[0], M, 3))
+    out[:, :nc] = b[:, :, None] * gated[:, None, :]
+    return out
+
+
+def _calc_importance_autograd(seg, views):
     dc = seg["_features_dc"].detach().clone().requires_grad_(True)
     rest = seg["_features_rest"].detach().clone().requires_grad_(True)
     acc_dc, acc_rest = torch.zeros_like(dc), torch.zeros_like(rest)
@@ -51,6 +104,28 @@ def calc_importance(seg: Dict[str, torch.Tensor], views: List[GaussianRasterizat
         acc_rest += rest.grad.abs()
         num_pixels += int(rs.image_height) * int(rs.image_width)
     return (torch.cat([acc_dc, acc_rest], 1).flatten(-2) / max(num_pixels, 1)).detach()
+
+
+def _calc_importance_kernel(seg, views, points_transform=None, sh_origin=None, view_id=0):
+    """Per view one forward plus the importance pass into ONE [N, M, 3] accumulator; the single division by the pixel count at the end."""
+    dc, rest = seg["_features_dc"].detach(), seg["_features_rest"].detach()
+    acc = torch.zeros((dc.shape[0], dc.shape[1] + rest.shape[1], 3), dtype=torch.float32, device=dc.device)
+    num_pixels = 0
+    for rs in views:
+        importance_accumulate(acc, seg["_xyz"], dc, seg["_opacity"], seg["_scaling"], seg["_rotation"], rs, sh_rest=rest,
+                              raw_params=True, points_transform=points_transform, sh_origin=sh_origin, view_id=view_id)
+        num_pixels += int(rs.image_height) * int(rs.image_width)
+    return acc.flatten(-2) / max(num_pixels, 1)
+
+
+def calc_importance(seg: Dict[str, torch.Tensor], views: List[GaussianRasterizationSettings], route: Optional[str] = None) -> torch.Tensor:
+    """[N, 48] colour importance of a segment over `views` (each a full raster-settings tuple), entry k * 3 + c.
+    route: "autograd" = per view a render and a full backward, |grad| of the SH tensors; "kernel" = per view a forward and the
+    importance pass (no backward, no autograd, no .grad left anywhere); None = DEFAULT_IMPORTANCE_ROUTE."""
+    route = DEFAULT_IMPORTANCE_ROUTE if route is None else route
+    if route not in IMPORTANCE_ROUTES:
+        raise ValueError(f"calc_importance: unknown route {route!r} (one of {IMPORTANCE_ROUTES})")
+    return _calc_importance_kernel(seg, views) if route == "kernel" else _calc_importance_autograd(seg, views)
 
 
 def prune_mask(importance: torch.Tensor, prune_ratio: float) -> torch.Tensor:

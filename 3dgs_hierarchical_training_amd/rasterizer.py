@@ -128,6 +128,79 @@ class _Workspace:
         return buf.data_ptr()
 
 
+class _CtypesForward:
+    """What one gsr_forward through the plain-FFI route leaves behind: outputs, the buffers a backward (or the importance pass) reads,
+    the prepared inputs they were computed from and the GsrForwardOut fields."""
+    __slots__ = ("means3D", "opacities", "sh", "colors_precomp", "scales", "rotations", "cov3Ds_precomp", "vm", "pm", "campos", "bg", "sh_rest",
+                 "xf", "color", "radii", "depth", "alpha", "geom", "image", "binning", "num_rendered", "binning_capacity", "forward_flags",
+                 "N", "M", "H", "W")
+
+
+def _ctypes_forward(means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings, sh_rest=None,
+                    raw_params=False, viewmatrix=None, projmatrix=None, campos=None, points_transform=None, view_id=0) -> _CtypesForward:
+    """gsr_forward over ctypes (shared by _RasterizeGaussians.forward and importance_accumulate's ctypes route)."""
+    lib = L.load()
+    rs = raster_settings
+    dev = means3D.device
+    if dev.type != "cuda":
+        raise RuntimeError("GaussianRasterizer: tensors must be on a ROCm/HIP device (no CPU fallback)")
+    means3D = _f32c(means3D)
+    N = means3D.shape[0]
+    sh, colors_precomp = _f32c(_empty_to_none(sh)), _f32c(_empty_to_none(colors_precomp))
+    scales, rotations = _f32c(_empty_to_none(scales)), _f32c(_empty_to_none(rotations))
+    cov3Ds_precomp = _f32c(_empty_to_none(cov3Ds_precomp))
+    opacities = _f32c(opacities)
+    vm = _f32c((viewmatrix if viewmatrix is not None else rs.viewmatrix).to(dev))
+    pm = _f32c((projmatrix if projmatrix is not None else rs.projmatrix).to(dev))
+    campos = _f32c((campos if campos is not None else rs.campos).to(dev))
+    bg = _f32c(rs.bg.to(dev))
+    H, W = int(rs.image_height), int(rs.image_width)
+    sh_rest = _f32c(_empty_to_none(sh_rest))
+    xf = None
+    if points_transform is not None:       # [3,4] or [4,4] rigid / affine transform applied to the means in-kernel
+        if tuple(points_transform.shape) not in ((3, 4), (4, 4)):
+            raise RuntimeError("points_transform must be a [3,4] or [4,4] tensor")
+        xf = _f32c(points_transform.to(dev)[:3])
+    M = (int(sh.shape[1]) + (int(sh_rest.shape[1]) if sh_rest is not None else 0)) if sh is not None else 0
+
+    color = torch.empty((3, H, W), dtype=torch.float32, device=dev)
+    depth = torch.empty((1, H, W), dtype=torch.float32, device=dev)
+    alpha = torch.empty((1, H, W), dtype=torch.float32, device=dev)
+    radii = torch.empty((N,), dtype=torch.int32, device=dev)
+    geom = torch.empty(lib.gsr_geom_bytes(N), dtype=torch.uint8, device=dev)
+    image = torch.empty(lib.gsr_image_bytes(W, H), dtype=torch.uint8, device=dev)
+    ws = _Workspace(dev)
+
+    a = L.GsrForwardArgs()
+    a.N, a.M, a.D, a.W, a.H = N, M, int(rs.sh_degree), W, H
+    a.prefiltered, a.debug = int(bool(rs.prefiltered)), int(bool(rs.debug))
+    a.scale_modifier, a.tanfovx, a.tanfovy = float(rs.scale_modifier), float(rs.tanfovx), float(rs.tanfovy)
+    a.means3D, a.scales, a.rotations, a.cov3D_precomp = _ptr(means3D), _ptr(scales), _ptr(rotations), _ptr(cov3Ds_precomp)
+    a.opacities, a.shs, a.colors_precomp = _ptr(opacities), _ptr(sh), _ptr(colors_precomp)
+    a.viewmatrix, a.projmatrix, a.campos, a.bg = _ptr(vm), _ptr(pm), _ptr(campos), _ptr(bg)
+    a.out_color, a.out_depth, a.out_alpha, a.radii = color.data_ptr(), depth.data_ptr(), alpha.data_ptr(), _ptr(radii)
+    a.geom, a.image = geom.data_ptr(), image.data_ptr()
+    a.alloc, a.alloc_user = ws.cb, None
+    a.shs_rest, a.raw_params = _ptr(sh_rest), int(bool(raw_params))
+    a.points_transform = _ptr(xf)
+    a.view_id = int(view_id)
+    out = L.GsrForwardOut()
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        L.check(lib.gsr_forward(C.byref(a), C.byref(out), C.c_void_p(stream)), "gsr_forward")
+    ws.scratch.clear()  # stream-ordered reuse by the caching allocator is safe: same stream
+
+    _LAST.update(num_rendered=int(out.num_rendered), image=image, W=W, H=H, B=1, binning=ws.binning,
+                 binning_capacity=int(out.binning_capacity))
+    f = _CtypesForward()
+    f.means3D, f.opacities, f.sh, f.colors_precomp, f.scales, f.rotations, f.cov3Ds_precomp = means3D, opacities, sh, colors_precomp, scales, rotations, cov3Ds_precomp
+    f.vm, f.pm, f.campos, f.bg, f.sh_rest, f.xf = vm, pm, campos, bg, sh_rest, xf
+    f.color, f.radii, f.depth, f.alpha, f.geom, f.image, f.binning = color, radii, depth, alpha, geom, image, ws.binning
+    f.num_rendered, f.binning_capacity, f.forward_flags = int(out.num_rendered), int(out.binning_capacity), int(out.forward_flags)
+    f.N, f.M, f.H, f.W = N, M, H, W
+    return f
+
+
 class _RasterizeGaussians(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings,
@@ -135,63 +208,17 @@ class _RasterizeGaussians(torch.autograd.Function):
                 points_transform=None, view_id=0):
         # viewmatrix / projmatrix / campos are ALSO passed as explicit tensor inputs (same objects as in
         # raster_settings) so that autograd can return their gradients: a NamedTuple cannot carry grads.
-        lib = L.load()
         rs = raster_settings
-        dev = means3D.device
-        if dev.type != "cuda":
-            raise RuntimeError("GaussianRasterizer: tensors must be on a ROCm/HIP device (no CPU fallback)")
-        means3D = _f32c(means3D)
-        N = means3D.shape[0]
-        sh, colors_precomp = _f32c(_empty_to_none(sh)), _f32c(_empty_to_none(colors_precomp))
-        scales, rotations = _f32c(_empty_to_none(scales)), _f32c(_empty_to_none(rotations))
-        cov3Ds_precomp = _f32c(_empty_to_none(cov3Ds_precomp))
-        opacities = _f32c(opacities)
-        vm = _f32c((viewmatrix if viewmatrix is not None else rs.viewmatrix).to(dev))
-        pm = _f32c((projmatrix if projmatrix is not None else rs.projmatrix).to(dev))
-        campos = _f32c((campos if campos is not None else rs.campos).to(dev))
-        bg = _f32c(rs.bg.to(dev))
-        H, W = int(rs.image_height), int(rs.image_width)
-        sh_rest = _f32c(_empty_to_none(sh_rest))
-        xf = None
-        if points_transform is not None:       # [3,4] or [4,4] rigid / affine transform applied to the means in-kernel
-            if tuple(points_transform.shape) not in ((3, 4), (4, 4)):
-                raise RuntimeError("points_transform must be a [3,4] or [4,4] tensor")
-            xf = _f32c(points_transform.to(dev)[:3])
-        M = (int(sh.shape[1]) + (int(sh_rest.shape[1]) if sh_rest is not None else 0)) if sh is not None else 0
-
-        color = torch.empty((3, H, W), dtype=torch.float32, device=dev)
-        depth = torch.empty((1, H, W), dtype=torch.float32, device=dev)
-        alpha = torch.empty((1, H, W), dtype=torch.float32, device=dev)
-        radii = torch.empty((N,), dtype=torch.int32, device=dev)
-        geom = torch.empty(lib.gsr_geom_bytes(N), dtype=torch.uint8, device=dev)
-        image = torch.empty(lib.gsr_image_bytes(W, H), dtype=torch.uint8, device=dev)
-        ws = _Workspace(dev)
-
-        a = L.GsrForwardArgs()
-        a.N, a.M, a.D, a.W, a.H = N, M, int(rs.sh_degree), W, H
-        a.prefiltered, a.debug = int(bool(rs.prefiltered)), int(bool(rs.debug))
-        a.scale_modifier, a.tanfovx, a.tanfovy = float(rs.scale_modifier), float(rs.tanfovx), float(rs.tanfovy)
-        a.means3D, a.scales, a.rotations, a.cov3D_precomp = _ptr(means3D), _ptr(scales), _ptr(rotations), _ptr(cov3Ds_precomp)
-        a.opacities, a.shs, a.colors_precomp = _ptr(opacities), _ptr(sh), _ptr(colors_precomp)
-        a.viewmatrix, a.projmatrix, a.campos, a.bg = _ptr(vm), _ptr(pm), _ptr(campos), _ptr(bg)
-        a.out_color, a.out_depth, a.out_alpha, a.radii = color.data_ptr(), depth.data_ptr(), alpha.data_ptr(), _ptr(radii)
-        a.geom, a.image = geom.data_ptr(), image.data_ptr()
-        a.alloc, a.alloc_user = ws.cb, None
-        a.shs_rest, a.raw_params = _ptr(sh_rest), int(bool(raw_params))
-        a.points_transform = _ptr(xf)
-        a.view_id = int(view_id)
-        out = L.GsrForwardOut()
-        with torch.cuda.device(dev):
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            L.check(lib.gsr_forward(C.byref(a), C.byref(out), C.c_void_p(stream)), "gsr_forward")
-        ws.scratch.clear()  # stream-ordered reuse by the caching allocator is safe: same stream
-
-        _LAST.update(num_rendered=int(out.num_rendered), image=image, W=W, H=H, B=1, binning=ws.binning,
-                     binning_capacity=int(out.binning_capacity))
+        f = _ctypes_forward(means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, rs, sh_rest, raw_params,
+                            viewmatrix, projmatrix, campos, points_transform, view_id)
+        means3D, opacities, sh, colors_precomp, scales, rotations, cov3Ds_precomp = f.means3D, f.opacities, f.sh, f.colors_precomp, f.scales, f.rotations, f.cov3Ds_precomp
+        vm, pm, campos, bg, sh_rest, xf = f.vm, f.pm, f.campos, f.bg, f.sh_rest, f.xf
+        color, radii, depth, alpha, geom, image = f.color, f.radii, f.depth, f.alpha, f.geom, f.image
+        N, M, H, W = f.N, f.M, f.H, f.W
         ctx.raster_settings = rs
-        ctx.num_rendered = int(out.num_rendered)
-        ctx.binning_capacity = int(out.binning_capacity)
-        ctx.forward_flags = int(out.forward_flags)
+        ctx.num_rendered = f.num_rendered
+        ctx.binning_capacity = f.binning_capacity
+        ctx.forward_flags = f.forward_flags
         ctx.dims = (N, M, H, W)
         ctx.has = (sh is not None, colors_precomp is not None, scales is not None, cov3Ds_precomp is not None)
         ctx.raw = (sh_rest is not None, bool(raw_params))
@@ -202,7 +229,7 @@ class _RasterizeGaussians(torch.autograd.Function):
         ctx.save_for_backward(means3D, opacities, sh if sh is not None else z, colors_precomp if colors_precomp is not None else z,
                               scales if scales is not None else z, rotations if rotations is not None else z,
                               cov3Ds_precomp if cov3Ds_precomp is not None else z, vm, pm, campos, bg, geom, image,
-                              ws.binning, sh_rest if sh_rest is not None else z, xf if xf is not None else z)
+                              f.binning, sh_rest if sh_rest is not None else z, xf if xf is not None else z)
         ctx.mark_non_differentiable(radii)
         ctx.set_materialize_grads(False)   # unused depth / alpha outputs arrive as None -> specialised backward
         return color, radii, depth, alpha
@@ -464,6 +491,58 @@ def rasterize_gaussians_raw(means3D, means2D, features_dc, features_rest, opacit
     e = torch.Tensor([])
     return _RasterizeGaussians.apply(means3D, means2D, features_dc, e, opacity_logit, log_scales, rotations_raw, e,
                                      raster_settings, features_rest, True, *_cam_inputs(raster_settings), fused_adam, points_transform, view_id)
+
+
+def importance_accumulate(acc, means3D, sh, opacities, scales, rotations, raster_settings, sh_rest=None, raw_params=False,
+                          cov3Ds_precomp=None, colors_precomp=None, points_transform=None, view_id=0, sh_origin=None,
+                          batch_first_block=None):
+    """One view's merge-time colour importance, added to `acc` [N, M, 3] in place WITHOUT a backward (include/gsr.h
+    gsr_importance_accumulate; /root/reference/trainer/ht3dgs_trainer.py:1427-1462 per view): one forward through the code path of
+    rasterize_gaussians / rasterize_gaussians_raw, a second walk of its tile lists in forward order that sums alpha T over the
+    pixels whose clamp gate is open, and |basis_k| [colour not clamped] S added per Gaussian.  No autograd, no .grad.
+    Returns the forward's (color, radii, depth, alpha, geom, image, binning, meta) -- an ordinary backward over them is still valid
+    (the extension binding; the ctypes binding returns the first four)."""
+    dev = means3D.device
+    if dev.type != "cuda":
+        raise RuntimeError("importance_accumulate: tensors must be on a ROCm/HIP device (no CPU fallback)")
+    rs = raster_settings
+    with torch.no_grad():
+        if not E.use_ctypes():
+            ops = E.load()
+            e = _e(dev)
+            pick = lambda t: e if (t is None or t.numel() == 0) else t.detach()
+            vm, pm, cp = rs.viewmatrix.to(dev), rs.projmatrix.to(dev), rs.campos.to(dev)
+            if sh_origin is not None:
+                sh_origin = sh_origin.detach().to(device=dev, dtype=torch.float32).reshape(3)
+            xf = e if points_transform is None else points_transform.detach().to(dev)[:3]
+            return tuple(ops.importance_accumulate(
+                acc, means3D.detach(), pick(sh), pick(colors_precomp), opacities.detach(), pick(scales), pick(rotations), pick(cov3Ds_precomp),
+                pick(sh_rest), vm, pm, cp, rs.bg.to(dev), xf, int(rs.image_height), int(rs.image_width), float(rs.tanfovx), float(rs.tanfovy),
+                float(rs.scale_modifier), int(rs.sh_degree), bool(raw_params),
+                [] if batch_first_block is None else [int(x) for x in batch_first_block], int(view_id), sh_origin))
+        # the plain-FFI route over the same C ABI: the ctypes forward above for its buffers, then the pass
+        if sh_origin is not None or batch_first_block is not None:
+            raise RuntimeError("sh_origin / batch_first_block are served by the PyTorch extension binding only")
+        lib = L.load()
+        f = _ctypes_forward(means3D.detach(), sh, colors_precomp, opacities.detach(), scales, rotations, cov3Ds_precomp, rs, sh_rest, raw_params,
+                            points_transform=points_transform, view_id=view_id)
+        N, M, H, W = f.N, f.M, f.H, f.W
+        if tuple(acc.shape) != (N, M, 3) or acc.dtype != torch.float32 or not acc.is_contiguous():
+            raise RuntimeError("importance_accumulate: acc must be a contiguous float32 [N, M, 3] tensor (M = stored SH coefficients)")
+        a = L.GsrForwardArgs()
+        a.N, a.M, a.D, a.W, a.H = N, M, int(rs.sh_degree), W, H
+        a.means3D, a.shs, a.shs_rest, a.colors_precomp = _ptr(f.means3D), _ptr(f.sh), _ptr(f.sh_rest), _ptr(f.colors_precomp)
+        a.campos, a.points_transform, a.raw_params = _ptr(f.campos), _ptr(f.xf), int(bool(raw_params))
+        a.out_color, a.geom, a.image = f.color.data_ptr(), f.geom.data_ptr(), f.image.data_ptr()
+        out = L.GsrForwardOut()
+        out.num_rendered, out.binning_capacity, out.forward_flags = f.num_rendered, f.binning_capacity, f.forward_flags
+        out.binning = _ptr(f.binning)
+        scratch = torch.empty(lib.gsr_importance_scratch_bytes(N), dtype=torch.uint8, device=dev)
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            L.check(lib.gsr_importance_accumulate(C.byref(a), C.byref(out), acc.data_ptr(), scratch.data_ptr(), C.c_void_p(stream)),
+                    "gsr_importance_accumulate")
+        return f.color, f.radii, f.depth, f.alpha
 
 
 class GaussianRasterizer(nn.Module):

@@ -47,6 +47,13 @@ Importing this module BEFORE the trainer swaps both for the HIP kernels of this 
     `max_radii2D[vis] = torch.max(max_radii2D[vis], radii[vis])` is one launch (gsr_masked_max) instead of three `nonzero`s;
     `utils.image_utils.psnr` (the training PSNR of every iteration) is two launches (gsr_psnr).  `GSR_AUTOPATCH_LAZY_MASK=0` /
     `GSR_AUTOPATCH_PSNR=0` switch those off.
+  * `trainer.ht3dgs_trainer.HTGaussianTrainer.calc_importance` (the colour-importance score of every merge, ht3dgs_trainer.py:1427-1462;
+    patched when that module is imported, now or later) runs, per camera, one forward and the importance pass
+    (`torch.ops.gsr.importance_accumulate`, include/gsr.h gsr_importance_accumulate) on the raw tensors instead of a render and a full
+    backward, and returns the same [N, 48] tensor.  One side effect differs: the reference leaves the summed |grad| in
+    `_features_dc.grad` / `_features_rest.grad`, the patched form leaves them None (`merge_two_3DGS` builds new tensors right after
+    and reads neither).  `compute_cov3D_python`, an override colour, `convert_SHs_python` without `view_dependent`, an unknown pose
+    object, CPU tensors or an unexpected layout run the ORIGINAL method; `GSR_AUTOPATCH_IMPORTANCE=0` leaves the method alone.
 
 `apply()` / `remove()` switch the patches on and off (importing the module calls `apply()`); `GSR_AUTOPATCH=0` disables them.
 The rasterizer itself needs no patch: `diff_gaussian_rasterization` IS this library's drop-in package.
@@ -70,6 +77,8 @@ _applied = False
 _patched_loss_classes = []          # [(class, original forward)]
 LOSS_MODULES = ("trainer.losses",)
 RENDER_MODULES = ("scene.gaussian_model_ht",)
+TRAINER_MODULES = ("trainer.ht3dgs_trainer",)
+_patched_trainer_classes = []       # [(class, attribute, original attribute as found in the class __dict__)]
 _patched_render_classes = []        # [(class, attribute, original function)]
 RAW_NAMES = ("_xyz", "_features_dc", "_features_rest", "_opacity", "_scaling", "_rotation")
 _REQUIRE_CUDA = True                # (tests drive the dispatch logic with CPU stand-ins and a recording rasterizer)
@@ -490,6 +499,66 @@ def render_fused(self, viewpoint_camera, scaling_modifier=1.0, invert_bg_color=F
             "visibility_filter": visible, "radii": radii}
 
 
+def calc_importance_fused(gs_render, cameras, pipe, override_color=None):
+    """Drop-in body of `HTGaussianTrainer.calc_importance` (/root/reference/trainer/ht3dgs_trainer.py:1427-1462; a staticmethod):
+    the same [N, 48] tensor -- sum over the cameras of |d sum(clamped render) / d SH|, over the pixel count -- from one forward and
+    the importance pass per camera (hierarchy.py calc_importance's kernel route) instead of a render and a full backward.  Raw
+    tensors, pose, SH origin and frame id are taken exactly as render_fused takes them; whatever render_fused would hand to the
+    original render hands this call to the original method.  `_features_dc.grad` / `_features_rest.grad` are left None (the
+    reference leaves the summed |grad| there; nobody reads it)."""
+    orig = next((f for c, a, f in _patched_trainer_classes if a == "calc_importance"), None)
+    orig = orig.__func__ if isinstance(orig, staticmethod) else orig
+    g = getattr(gs_render, "gaussians", None)
+    cov_py, sh_py = bool(getattr(pipe, "compute_cov3D_python", False)), bool(getattr(pipe, "convert_SHs_python", False))
+    python_sh = sh_py and getattr(gs_render, "view_dependent", False) is True and \
+        os.environ.get("GSR_AUTOPATCH_PYTHON_SH", "1") != "0" and _ext_binding()
+    ts = None
+    if override_color is None and not cov_py and (python_sh or not sh_py) and g is not None:
+        ts = _raw_tensors(g)
+    posed = ts is not None and (getattr(g, "rotate_xyz", False) or getattr(g, "rotate_xyz_inverse", False) or getattr(g, "rotate_seq", False))
+    if posed and os.environ.get("GSR_AUTOPATCH_POSE", "1") == "0":
+        ts = None
+    M = None
+    if ts is not None and posed:
+        try:
+            with torch.no_grad():
+                M = _pose_matrix(g)
+        except Exception:        # a pose object neither pose_opt nor lietorch's retr().matrix() reads: the original's own statement
+            ts = None
+    if ts is None:
+        if orig is None:
+            raise RuntimeError("gsr_autopatch.calc_importance_fused: this configuration needs the original HTGaussianTrainer.calc_importance")
+        return orig(gs_render, cameras, pipe) if override_color is None else orig(gs_render, cameras, pipe, override_color)
+    R = importlib.import_module("3dgs_hierarchical_training_amd.rasterizer")
+    xyz, f_dc, f_rest, opacity, scaling, rotation = ts
+    dev = xyz.device
+    f_dc.grad = None
+    f_rest.grad = None
+    acc = torch.zeros((xyz.shape[0], f_dc.shape[1] + f_rest.shape[1], 3), dtype=torch.float32, device=dev)
+    num_pixels = 0
+    for cam in cameras:
+        settings = R.GaussianRasterizationSettings(
+            image_height=int(cam.image_height), image_width=int(cam.image_width), tanfovx=math.tan(cam.FoVx * 0.5),
+            tanfovy=math.tan(cam.FoVy * 0.5), bg=gs_render.bg_color, scale_modifier=1.0, viewmatrix=cam.world_view_transform,
+            projmatrix=cam.full_proj_transform, sh_degree=g.active_sh_degree, campos=cam.camera_center, prefiltered=False, debug=False)
+        R.importance_accumulate(acc, xyz, f_dc, opacity, scaling, rotation, settings, sh_rest=f_rest, raw_params=True, points_transform=M,
+                                view_id=_view_id(cam, g), sh_origin=_sh_origin(g, cam, dev) if python_sh else None)
+        num_pixels += int(cam.image_height) * int(cam.image_width)
+    return (acc.flatten(-2) / num_pixels).detach()
+
+
+def _patch_trainer_module(mod):
+    # (on since the kernel route was measured faster than a render and a full backward per view at both sizes:
+    #  profiles/importance_probe.txt, DESIGN.md section 6)
+    if os.environ.get("GSR_AUTOPATCH_IMPORTANCE", "1") == "0":
+        return
+    cls = getattr(mod, "HTGaussianTrainer", None)
+    if cls is None or "calc_importance" not in vars(cls) or any(c is cls for c, _, _ in _patched_trainer_classes):
+        return
+    _patched_trainer_classes.append((cls, "calc_importance", vars(cls)["calc_importance"]))
+    cls.calc_importance = staticmethod(calc_importance_fused)
+
+
 def add_densification_stats_fused(self, viewspace_point_tensor, update_filter):
     """Drop-in body of `HTGaussianModel.add_densification_stats` (/root/reference/scene/gaussian_model_ht.py:718-721): the same
     sums as masked adds over N instead of three boolean-mask gathers / scatters (each a `nonzero` and a host synchronisation)."""
@@ -566,13 +635,15 @@ def _patch_loss_module(mod):
 
 
 class _PostImportFinder(importlib.abc.MetaPathFinder):
-    """Patches `trainer.losses` / `scene.gaussian_model_ht` right after they have been executed, whenever that import happens."""
+    """Patches `trainer.losses` / `scene.gaussian_model_ht` / `utils.image_utils` / `trainer.ht3dgs_trainer` right after they have
+    been executed, whenever that import happens."""
 
     def find_spec(self, fullname, path, target=None):
-        if (fullname not in LOSS_MODULES and fullname not in RENDER_MODULES and fullname not in IMAGE_UTILS_MODULES) or not _applied:
+        if (fullname not in LOSS_MODULES and fullname not in RENDER_MODULES and fullname not in IMAGE_UTILS_MODULES
+                and fullname not in TRAINER_MODULES) or not _applied:
             return None
         patch = _patch_loss_module if fullname in LOSS_MODULES else _patch_render_module if fullname in RENDER_MODULES \
-            else _patch_image_utils_module
+            else _patch_trainer_module if fullname in TRAINER_MODULES else _patch_image_utils_module
         for finder in sys.meta_path:
             if finder is self or not hasattr(finder, "find_spec"):
                 continue
@@ -614,6 +685,9 @@ def apply():
     for name in IMAGE_UTILS_MODULES:
         if name in sys.modules:
             _patch_image_utils_module(sys.modules[name])
+    for name in TRAINER_MODULES:
+        if name in sys.modules:
+            _patch_trainer_module(sys.modules[name])
 
 
 def remove():
@@ -634,6 +708,9 @@ def remove():
     while _patched_psnr:
         mod, attr, fn = _patched_psnr.pop()
         setattr(mod, attr, fn)
+    while _patched_trainer_classes:
+        cls, attr, fn = _patched_trainer_classes.pop()
+        setattr(cls, attr, fn)
 
 
 if os.environ.get("GSR_AUTOPATCH", "1") != "0":

@@ -274,12 +274,36 @@ int gsr_backward(const GsrBackwardArgs* args, void* stream);
 int gsr_mark_visible(int32_t N, const float* means3D, const float* viewmatrix, const float* projmatrix,
                      uint8_t* present, void* stream);
 
+/* ---- version 113: merge-time colour importance of one view WITHOUT a backward.
+ * Replaces, per view, the body of `HTGaussianTrainer.calc_importance` (/root/reference/trainer/ht3dgs_trainer.py:1427-1462: render,
+ * `rendering.sum().backward()` on the clamped image, `|grad|` of _features_dc / _features_rest through the hooks of :1436-1437).
+ * With L = sum clamp(image, 0, 1) the gradient of SH coefficient k, channel c of Gaussian n in one view is
+ *     dL/dSH[n,k,c] = basis_k(dir_n) * [colour_{n,c} not clamped at 0] * S[n,c],
+ *     S[n,c] = sum over pixels of alpha T * [0 <= out_color_c(pixel) <= 1],
+ * and alpha T is the weight the FORWARD blend forms for every contribution it takes; S >= 0, so the per-view |grad| is
+ * |basis_k| * gate * S.  The pass walks the forward's tile lists a second time in forward order with its out_color in hand (the same
+ * visit code as the forward blend: the same contributions) and sums S; a short per-Gaussian kernel then adds |basis_k| gate S to
+ * acc[n,k,c] for k < (D+1)^2.  No checkpoint, no back-to-front replay, no geometry gradient, no autograd.
+ *   fwd / out  the arguments and the result of the gsr_forward just run on the same stream.  Read: geom, image, binning, out_color,
+ *              means3D, campos, points_transform, sh_origin.  Written: acc and scratch only -- an ordinary gsr_backward of that
+ *              forward afterwards is still valid.
+ *   acc        [N,M,3] float, += (M = fwd->M, the stored coefficients).  Rows of Gaussians whose three sums are zero in this view are
+ *              neither read nor written; coefficients k >= (D+1)^2 are never touched.
+ *   scratch    gsr_importance_scratch_bytes(N) bytes; cleared by the pass itself (an asynchronous fill on the stream).
+ * Raw or activated parameters, shs alone or shs + shs_rest, cov3D_precomp, points_transform, sh_origin, any D <= 3 with any stored
+ * M >= (D+1)^2.  Refused (GSR_ERR_ARG): colors_precomp (no SH) and a batch of B > 1.  Float atomics: the sums of two runs may differ in
+ * the last bits.  Profile stages: "importance_blend", "importance_finish". */
+size_t gsr_importance_scratch_bytes(int32_t N);
+int gsr_importance_accumulate(const GsrForwardArgs* fwd, const GsrForwardOut* out, float* acc /* [N,M,3], += */, void* scratch,
+                              void* stream);
+
 const char* gsr_last_error(void);
 /* 100 * major + minor.  110 (round 6): GsrForwardArgs ends with view_id, out_color_clamped, visible (appended in round 5 under
  * version 100: a caller compiled against a shorter struct must be rebuilt -- check gsr_version() >= 110 AND
  * gsr_struct_bytes(0) == sizeof(GsrForwardArgs), gsr_struct_bytes(1) == sizeof(GsrBackwardArgs) at start-up).
  * 111: GsrForwardArgs and GsrBackwardArgs end with sh_origin.
- * 112: the depth term of the loss (gsr_depth_loss_*); no struct changed. */
+ * 112: the depth term of the loss (gsr_depth_loss_*); no struct changed.
+ * 113: gsr_importance_accumulate / gsr_importance_scratch_bytes; no struct changed. */
 int gsr_version(void);
 size_t gsr_struct_bytes(int32_t which); /* 0 GsrForwardArgs, 1 GsrBackwardArgs, 2 GsrForwardOut; anything else 0 */
 

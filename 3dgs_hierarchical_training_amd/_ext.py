@@ -176,10 +176,23 @@ def _register_fakes():
     def _(render, target, workspace, grad_loss, lambda_dssim, clamp):
         return torch.empty_like(render, dtype=torch.float32)
 
+    def _depth_images(depth):
+        """Images of a depth stack ([B,1,H,W], or [B,H,W] with B > 1); 0 for a plane [H,W] / [1,H,W]."""
+        return int(depth.shape[0]) if (depth.dim() == 4 or (depth.dim() == 3 and depth.shape[0] > 1)) else 0
+
     @torch.library.register_fake("gsr::depth_loss_forward")
     def _(depth, depth_gt, kind, clamp_lo, clamp_hi):
         H, W = depth.shape[-2:]
-        return depth.new_empty((6,), dtype=torch.float32), depth.new_empty((lib.gsr_depth_loss_workspace_bytes(int(H), int(W)),), dtype=torch.uint8)
+        B = _depth_images(depth)
+        nws = lib.gsr_depth_loss_workspace_bytes_batched(B, int(H), int(W)) if B else lib.gsr_depth_loss_workspace_bytes(int(H), int(W))
+        return depth.new_empty((B, 6) if B else (6,), dtype=torch.float32), depth.new_empty((nws,), dtype=torch.uint8)
+
+    @torch.library.register_fake("gsr::depth_loss_forward_stack")
+    def _(depth, depth_gt, kind, clamp_lo, clamp_hi):
+        H, W = depth.shape[-2:]
+        B = _depth_images(depth)
+        return (depth.new_empty((), dtype=torch.float32), depth.new_empty((B, 6), dtype=torch.float32),
+                depth.new_empty((lib.gsr_depth_loss_workspace_bytes_batched(B, int(H), int(W)),), dtype=torch.uint8))
 
     @torch.library.register_fake("gsr::depth_loss_backward")
     def _(depth, depth_gt, workspace, grad_loss, kind, clamp_lo, clamp_hi, lambda_depth):

@@ -81,6 +81,8 @@ EXPORTS = [
     "gsr_loss_workspace_bytes_batched", "gsr_loss_forward_batched", "gsr_loss_backward_batched", "gsr_loss_forward_terms", "gsr_pose_grad", "gsr_struct_bytes", "gsr_debug_list_cut_stats",
     "gsr_depth_loss_workspace_bytes", "gsr_depth_loss_forward", "gsr_depth_loss_backward", "gsr_depth_loss_forward_terms",
     "gsr_importance_scratch_bytes", "gsr_importance_accumulate",
+    "gsr_depth_loss_workspace_bytes_batched", "gsr_depth_loss_forward_batched", "gsr_depth_loss_backward_batched",
+    "gsr_depth_loss_forward_terms_batched",
 ]
 GSR_DEPTH_LOSS_L1, GSR_DEPTH_LOSS_INVARIANT = 0, 1
 
@@ -129,6 +131,16 @@ def load():
     lib.gsr_depth_loss_backward.argtypes = _depth + [C.c_void_p, C.c_void_p, C.c_void_p]            # grad_loss, d_depth, stream
     lib.gsr_depth_loss_forward_terms.restype = C.c_int
     lib.gsr_depth_loss_forward_terms.argtypes = _depth + [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]   # out6, terms6, loss_copy, stream
+    lib.gsr_depth_loss_workspace_bytes_batched.restype = C.c_size_t
+    lib.gsr_depth_loss_workspace_bytes_batched.argtypes = [C.c_int32, C.c_int32, C.c_int32]
+    # (depth, depth_gt, images, H, W, kind, clamp_lo, clamp_hi, lambda_depth, workspace, ...)
+    _depth_b = _depth[:2] + [C.c_int32] + _depth[2:]
+    lib.gsr_depth_loss_forward_batched.restype = C.c_int
+    lib.gsr_depth_loss_forward_batched.argtypes = _depth_b + [C.c_void_p, C.c_void_p, C.c_void_p]          # out6 [images,6], out_sum, stream
+    lib.gsr_depth_loss_backward_batched.restype = C.c_int
+    lib.gsr_depth_loss_backward_batched.argtypes = _depth_b + [C.c_void_p, C.c_void_p, C.c_void_p]         # grad_loss, d_depth, stream
+    lib.gsr_depth_loss_forward_terms_batched.restype = C.c_int
+    lib.gsr_depth_loss_forward_terms_batched.argtypes = _depth_b + [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]   # out6, terms6, loss_copy, stream
     lib.gsr_knn_scratch_bytes.restype = C.c_size_t
     lib.gsr_knn_scratch_bytes.argtypes = [C.c_int32]
     lib.gsr_knn_mean_dist2.restype = C.c_int

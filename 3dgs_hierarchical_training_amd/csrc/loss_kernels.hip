@@ -348,6 +348,7 @@ __global__ __launch_bounds__(256) void k_loss_bwd(const float* __restrict__ raw,
 constexpr int kDS1 = 256;          // workgroups of k_depth_sums at most (one partial row per thread of the consumers)
 constexpr int kDS2 = 1024;         // workgroups of k_depth_terms at most
 constexpr int kDV = 5;             // values per partial row
+constexpr int kDepthImagesMax = 65535;   // images of a stack: one grid row each
 constexpr float kDepthValid = 0.02f;   // mask = depth_gt > 0.02 (losses.py:92; a constant of the reference, not the clamp bound)
 // workspace: coefficients | partial rows of k_depth_sums | partial rows of k_depth_terms
 enum { kDcS = 0, kDcT, kDcInvM, kDcU0, kDcU1, kDcLs, kDcLt, kDcLoss, kDcSums /* 5 */, kDcDet = kDcSums + kDV, kDcLambda, kDcN = 16 };
@@ -396,11 +397,17 @@ __device__ __forceinline__ void depth_rows_sum(const double* __restrict__ rows, 
     __syncthreads();
 }
 
-// pass 1: the five sums of the normal equations (kind 1) or sum |pc - g| (kind 0); grid <= kDS1, one partial row per workgroup
+// pass 1: the five sums of the normal equations (kind 1) or sum |pc - g| (kind 0); grid <= kDS1, one partial row per workgroup.
+// blockIdx.y = the image of a stack [images,H,W] (gsr_depth_loss_*_batched): plane b at b P floats, its rows in ws[b]; nothing is
+// shared between images.  vec = which elements a lane adds: 1 = four consecutive elements per lane per trip, then the scalar tail
+// (what an aligned single plane has always taken), 0 = one element per lane per trip (a misaligned single plane).  The two group the
+// float64 additions differently, so a stack ALWAYS walks with vec = 1 -- plane b of a stack is 16-byte aligned only when b P is a
+// multiple of 4 -- and only the WIDTH of the loads follows the plane's address: an image's bits do not depend on where it lies.
 __global__ __launch_bounds__(256) void k_depth_sums(const float* __restrict__ p, const float* __restrict__ g, size_t P, int vec, int kind,
-                                                    float lo, float hi, double* __restrict__ part)
+                                                    float lo, float hi, DepthWs* __restrict__ ws)
 {
     __shared__ double s_red[4 * kDV];
+    p += (size_t)blockIdx.y * P; g += (size_t)blockIdx.y * P;
     double v[kDV] = {0.0, 0.0, 0.0, 0.0, 0.0};
     auto acc = [&](float pr, float gr) {
         const double pc = (double)depth_clamp(pr, lo, hi), gd = (double)gr;
@@ -409,25 +416,29 @@ __global__ __launch_bounds__(256) void k_depth_sums(const float* __restrict__ p,
     };
     const size_t stride = (size_t)gridDim.x * 256, first = (size_t)blockIdx.x * 256 + threadIdx.x;
     const size_t n4 = vec ? P / 4 : 0;
-    for (size_t i = first; i < n4; i += stride) {   // 16-byte loads
-        const float4 a = reinterpret_cast<const float4*>(p)[i], b = reinterpret_cast<const float4*>(g)[i];
+    const bool wide = (((uintptr_t)p | (uintptr_t)g) & 15) == 0;   // (uniform over the workgroup)
+    for (size_t i = first; i < n4; i += stride) {
+        float4 a, b;
+        if (wide) { a = reinterpret_cast<const float4*>(p)[i]; b = reinterpret_cast<const float4*>(g)[i]; }   // 16-byte loads
+        else { a = make_float4(p[4 * i], p[4 * i + 1], p[4 * i + 2], p[4 * i + 3]); b = make_float4(g[4 * i], g[4 * i + 1], g[4 * i + 2], g[4 * i + 3]); }
         acc(a.x, b.x); acc(a.y, b.y); acc(a.z, b.z); acc(a.w, b.w);
     }
     for (size_t i = n4 * 4 + first; i < P; i += stride) acc(p[i], g[i]);
-    depth_block_sum(v, s_red, part + (size_t)blockIdx.x * kDV);
+    depth_block_sum(v, s_red, ws[blockIdx.y].p1 + (size_t)blockIdx.x * kDV);
 }
 
 // pass 2 (kind 1): every workgroup reduces the partial rows in the same order and solves the 2x2 in float64 -- the same (s, t)
 // everywhere -- then walks its pixels with the neighbour to the right and the one below.  Partial row: sum d^2, sum |d_b - d_a|,
 // sum sgn(d_b - d_a) (pc_b - pc_a) (= M d reg / ds), sum d pc, sum d (= M d data / ds, dt; zero up to rounding at the fit).
 __global__ __launch_bounds__(256) void k_depth_terms(const float* __restrict__ p, const float* __restrict__ g, int H, int W, float lo,
-                                                     float hi, const double* __restrict__ part1, int n1, double* __restrict__ coef,
-                                                     double* __restrict__ part2)
+                                                     float hi, int n1, DepthWs* __restrict__ ws)
 {
     __shared__ double s_buf[kDV * 256];
     __shared__ double s_red[4 * kDV];
+    DepthWs& w = ws[blockIdx.y];            // blockIdx.y = the image of a stack: its own plane, rows, fit and coefficients
+    double* __restrict__ coef = w.coef;
     double S[kDV];
-    depth_rows_sum<256>(part1, n1, s_buf, S);
+    depth_rows_sum<256>(w.p1, n1, s_buf, S);
     const double det = S[0] * S[2] - S[1] * S[1];
     double s = 0.0, t = 0.0;
     if (det != 0.0) { s = (S[2] * S[3] - S[1] * S[4]) / det; t = (-S[1] * S[3] + S[0] * S[4]) / det; }   // losses.py:273-279
@@ -438,6 +449,7 @@ __global__ __launch_bounds__(256) void k_depth_terms(const float* __restrict__ p
     }
     double v[kDV] = {0.0, 0.0, 0.0, 0.0, 0.0};
     const size_t P = (size_t)H * W, stride = (size_t)gridDim.x * 256;
+    p += (size_t)blockIdx.y * P; g += (size_t)blockIdx.y * P;
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < P; i += stride) {
         const float gi = g[i];
         if (!(gi > kDepthValid)) continue;
@@ -462,20 +474,40 @@ __global__ __launch_bounds__(256) void k_depth_terms(const float* __restrict__ p
             }
         }
     }
-    depth_block_sum(v, s_red, part2 + (size_t)blockIdx.x * kDV);
+    depth_block_sum(v, s_red, w.p2 + (size_t)blockIdx.x * kDV);
 }
 
-// single workgroup: out6 = {loss_depth, s, t, M, data, reg} and the backward's coefficients.  With dL/ds = Ls, dL/dt = Lt and the
-// normal matrix A = [[a00, a01], [a01, a11]]: u = A^-1 (Ls, Lt), and pixel i adds -u0 (d_i + s pc_i) - u1 s (the closed form of
-// ds/dpc_i, dt/dpc_i contracted with (Ls, Lt)).  terms6 (may be NULL): the six-float vector of gsr_loss_forward_terms -- the weighted
-// depth term is added to its total and slot 5 receives the unweighted term; loss_dup: a second place for the total.
-__global__ __launch_bounds__(1024) void k_depth_finish(const double* __restrict__ part1, int n1, const double* __restrict__ part2, int n2,
-                                                       int kind, double npix, double lambda, double* __restrict__ coef,
-                                                       float* __restrict__ out6, float* __restrict__ terms6, float* __restrict__ loss_dup)
+// the stack's totals from the images' finished coefficients, one thread: *out_sum (may be NULL) = the SUM of the images' unweighted
+// terms, added in float64 in index order.  terms6 (may be NULL): the six-float vector of gsr_loss_forward_terms, completed as
+// k_loss_finish completes it for a stack -- the weighted SUM is added to its total, slot 5 receives the MEAN of the unweighted terms;
+// loss_dup: a second place for the total.  (images == 1: sum = mean = the image's term.)
+__device__ __forceinline__ void depth_total(const DepthWs* __restrict__ ws, int images, double lambda, float* __restrict__ out_sum,
+                                            float* __restrict__ terms6, float* __restrict__ loss_dup)
+{
+    double loss = 0.0;
+    for (int b = 0; b < images; b++) loss += ws[b].coef[kDcLoss];
+    if (out_sum) *out_sum = (float)loss;
+    if (terms6) {
+        terms6[0] = (float)((double)terms6[0] + lambda * loss);
+        terms6[5] = (float)(loss / (double)images);
+        if (loss_dup) *loss_dup = terms6[0];
+    }
+}
+
+// one workgroup per image: out6[b] = {loss_depth, s, t, M, data, reg} and the backward's coefficients.  With dL/ds = Ls, dL/dt = Lt
+// and the normal matrix A = [[a00, a01], [a01, a11]]: u = A^-1 (Ls, Lt), and pixel i adds -u0 (d_i + s pc_i) - u1 s (the closed form
+// of ds/dpc_i, dt/dpc_i contracted with (Ls, Lt)).  A single image (grid 1) finishes with depth_total here; a stack's totals need
+// every image's term and take a launch of their own (k_depth_total).
+__global__ __launch_bounds__(1024) void k_depth_finish(DepthWs* ws, int n1, int n2, int kind, double npix, double lambda,
+                                                       float* __restrict__ out6, float* __restrict__ out_sum, float* __restrict__ terms6,
+                                                       float* __restrict__ loss_dup)
 {
     __shared__ double s_buf[kDV * 1024];
+    DepthWs& w = ws[blockIdx.x];
+    double* coef = w.coef;                  // (not __restrict__: depth_total below reads what is stored through it)
+    out6 += 6 * (size_t)blockIdx.x;
     double T[kDV];
-    depth_rows_sum<1024>(kind == 0 ? part1 : part2, kind == 0 ? n1 : n2, s_buf, T);
+    depth_rows_sum<1024>(kind == 0 ? w.p1 : w.p2, kind == 0 ? n1 : n2, s_buf, T);
     if (threadIdx.x != 0) return;
     double loss = 0.0, s = 0.0, t = 0.0, M = npix, data = 0.0, reg = 0.0, invM = 0.0, u0 = 0.0, u1 = 0.0, Ls = 0.0, Lt = 0.0;
     if (kind == 0) loss = T[0] / npix;
@@ -494,23 +526,28 @@ __global__ __launch_bounds__(1024) void k_depth_finish(const double* __restrict_
     coef[kDcS] = s; coef[kDcT] = t; coef[kDcInvM] = kind == 0 ? 1.0 / npix : invM; coef[kDcU0] = u0; coef[kDcU1] = u1;
     coef[kDcLs] = Ls; coef[kDcLt] = Lt; coef[kDcLoss] = loss; coef[kDcLambda] = lambda;
     out6[0] = (float)loss; out6[1] = (float)s; out6[2] = (float)t; out6[3] = (float)M; out6[4] = (float)data; out6[5] = (float)reg;
-    if (terms6) {
-        terms6[0] = (float)((double)terms6[0] + lambda * loss);
-        terms6[5] = (float)loss;
-        if (loss_dup) *loss_dup = terms6[0];
-    }
+    if (gridDim.x == 1) depth_total(ws, 1, lambda, out_sum, terms6, loss_dup);
+}
+
+__global__ void k_depth_total(const DepthWs* __restrict__ ws, int images, double lambda, float* __restrict__ out_sum,
+                              float* __restrict__ terms6, float* __restrict__ loss_dup)
+{
+    if (threadIdx.x == 0) depth_total(ws, images, lambda, out_sum, terms6, loss_dup);
 }
 
 // d_p[i] = upstream * lambda * pass(p_i) * dL/dpc_i, one store per pixel.  pass: a pixel strictly outside [lo, hi] gets zero, one on a
 // bound passes (the masked assignments of :116-117).  invariant: m_i [ s/M (d_i + 0.5 stencil_i) - u0 (d_i + s pc_i) - u1 s ], stencil
-// = the signs of the pixel's four incident pairs.
+// = the signs of the pixel's four incident pairs.  blockIdx.y = the image of a stack, with ITS coefficients: the gradient of the SUM of
+// the images' terms, i.e. every image receives exactly the gradient of its own.
 __global__ __launch_bounds__(256) void k_depth_bwd(const float* __restrict__ p, const float* __restrict__ g, int H, int W, int kind, float lo,
-                                                   float hi, double lambda, const double* __restrict__ coef, const float* __restrict__ gscale,
+                                                   float hi, double lambda, const DepthWs* __restrict__ ws, const float* __restrict__ gscale,
                                                    float* __restrict__ d_p)
 {
+    const double* __restrict__ coef = ws[blockIdx.y].coef;
     const double up = (gscale ? (double)gscale[0] : 1.0) * lambda;
     const double s = coef[kDcS], t = coef[kDcT], invM = coef[kDcInvM], u0 = coef[kDcU0], u1 = coef[kDcU1];
     const size_t P = (size_t)H * W, stride = (size_t)gridDim.x * 256;
+    p += (size_t)blockIdx.y * P; g += (size_t)blockIdx.y * P; d_p += (size_t)blockIdx.y * P;
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < P; i += stride) {
         const float pi = p[i], gi = g[i];
         float out = 0.f;
@@ -595,55 +632,96 @@ int gsr_loss_backward(const float* render, const float* target, int32_t C, int32
     return gsr_loss_backward_batched(render, target, 1, C, H, W, lambda_dssim, clamp01_render, workspace, grad_loss, d_render, stream);
 }
 
-size_t gsr_depth_loss_workspace_bytes(int32_t H, int32_t W)
+size_t gsr_depth_loss_workspace_bytes_batched(int32_t images, int32_t H, int32_t W)
 {
-    (void)H; (void)W;   // coefficients + the two fixed grids' partial rows: the same size for every plane
-    return (sizeof(DepthWs) + 255) & ~(size_t)255;
+    (void)H; (void)W;   // per image: coefficients + the two fixed grids' partial rows, the same size for every plane
+    return ((size_t)std::max(images, 1) * sizeof(DepthWs) + 255) & ~(size_t)255;
 }
+size_t gsr_depth_loss_workspace_bytes(int32_t H, int32_t W) { return gsr_depth_loss_workspace_bytes_batched(1, H, W); }
 
-static int depth_loss_forward_impl(const float* depth, const float* depth_gt, int32_t H, int32_t W, int32_t kind, float clamp_lo, float clamp_hi,
-                                   float lambda_depth, void* workspace, float* out6, float* terms6, float* loss_copy, void* stream)
+// vec: the element-to-lane assignment of k_depth_sums.  A single plane takes the one its alignment has always selected; a stack takes
+// 1 for every plane, wherever it lies.
+static int depth_loss_forward_impl(const float* depth, const float* depth_gt, int32_t images, int32_t H, int32_t W, int vec, int32_t kind,
+                                   float clamp_lo, float clamp_hi, float lambda_depth, void* workspace, float* out6, float* out_sum, float* terms6,
+                                   float* loss_copy, void* stream)
 {
-    if (!depth || !depth_gt || !workspace || !out6 || H <= 0 || W <= 0 || (kind != GSR_DEPTH_LOSS_L1 && kind != GSR_DEPTH_LOSS_INVARIANT) ||
-        !(clamp_lo <= clamp_hi) || ((uintptr_t)workspace & 7) != 0)
+    if (!depth || !depth_gt || !workspace || !out6 || images <= 0 || images > kDepthImagesMax || H <= 0 || W <= 0 ||
+        (kind != GSR_DEPTH_LOSS_L1 && kind != GSR_DEPTH_LOSS_INVARIANT) || !(clamp_lo <= clamp_hi) || ((uintptr_t)workspace & 7) != 0)
         return GSR_ERR_ARG;
     DepthWs* ws = static_cast<DepthWs*>(workspace);
     const size_t P = (size_t)H * W;
-    const int vec = ((((uintptr_t)depth | (uintptr_t)depth_gt) & 15) == 0) ? 1 : 0;
     const int n1 = (int)std::min<size_t>(kDS1, (P + 1023) / 1024), n2 = (int)std::min<size_t>(kDS2, (P + 255) / 256);
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(k_depth_sums, dim3(n1), dim3(256), 0, st, depth, depth_gt, P, vec, (int)kind, clamp_lo, clamp_hi, ws->p1);
+    hipLaunchKernelGGL(k_depth_sums, dim3(n1, images), dim3(256), 0, st, depth, depth_gt, P, vec, (int)kind, clamp_lo, clamp_hi, ws);
     if (kind == GSR_DEPTH_LOSS_INVARIANT)
-        hipLaunchKernelGGL(k_depth_terms, dim3(n2), dim3(256), 0, st, depth, depth_gt, (int)H, (int)W, clamp_lo, clamp_hi, ws->p1, n1, ws->coef, ws->p2);
-    hipLaunchKernelGGL(k_depth_finish, dim3(1), dim3(1024), 0, st, ws->p1, n1, ws->p2, n2, (int)kind, (double)P, (double)lambda_depth, ws->coef,
-                       out6, terms6, loss_copy);
+        hipLaunchKernelGGL(k_depth_terms, dim3(n2, images), dim3(256), 0, st, depth, depth_gt, (int)H, (int)W, clamp_lo, clamp_hi, n1, ws);
+    hipLaunchKernelGGL(k_depth_finish, dim3(images), dim3(1024), 0, st, ws, n1, n2, (int)kind, (double)P, (double)lambda_depth, out6, out_sum,
+                       terms6, loss_copy);
+    if (images > 1 && (out_sum || terms6))
+        hipLaunchKernelGGL(k_depth_total, dim3(1), dim3(64), 0, st, ws, (int)images, (double)lambda_depth, out_sum, terms6, loss_copy);
     return hipGetLastError() == hipSuccess ? GSR_OK : GSR_ERR_HIP;
 }
+static int depth_plane_vec(const float* depth, const float* depth_gt) { return ((((uintptr_t)depth | (uintptr_t)depth_gt) & 15) == 0) ? 1 : 0; }
 
 int gsr_depth_loss_forward(const float* depth, const float* depth_gt, int32_t H, int32_t W, int32_t kind, float clamp_lo, float clamp_hi,
                            float lambda_depth, void* workspace, float* out6, void* stream)
 {
-    return depth_loss_forward_impl(depth, depth_gt, H, W, kind, clamp_lo, clamp_hi, lambda_depth, workspace, out6, nullptr, nullptr, stream);
+    return depth_loss_forward_impl(depth, depth_gt, 1, H, W, depth_plane_vec(depth, depth_gt), kind, clamp_lo, clamp_hi, lambda_depth, workspace, out6,
+                                   nullptr, nullptr, nullptr, stream);
 }
 
 int gsr_depth_loss_forward_terms(const float* depth, const float* depth_gt, int32_t H, int32_t W, int32_t kind, float clamp_lo, float clamp_hi,
                                  float lambda_depth, void* workspace, float* out6, float* terms6, float* loss_copy, void* stream)
 {
     if (!terms6) return GSR_ERR_ARG;
-    return depth_loss_forward_impl(depth, depth_gt, H, W, kind, clamp_lo, clamp_hi, lambda_depth, workspace, out6, terms6, loss_copy, stream);
+    return depth_loss_forward_impl(depth, depth_gt, 1, H, W, depth_plane_vec(depth, depth_gt), kind, clamp_lo, clamp_hi, lambda_depth, workspace, out6,
+                                   nullptr, terms6, loss_copy, stream);
+}
+
+int gsr_depth_loss_forward_batched(const float* depth, const float* depth_gt, int32_t images, int32_t H, int32_t W, int32_t kind, float clamp_lo,
+                                   float clamp_hi, float lambda_depth, void* workspace, float* out6, float* out_sum, void* stream)
+{
+    if (!out_sum) return GSR_ERR_ARG;
+    return depth_loss_forward_impl(depth, depth_gt, images, H, W, 1, kind, clamp_lo, clamp_hi, lambda_depth, workspace, out6, out_sum, nullptr,
+                                   nullptr, stream);
+}
+
+int gsr_depth_loss_forward_terms_batched(const float* depth, const float* depth_gt, int32_t images, int32_t H, int32_t W, int32_t kind,
+                                         float clamp_lo, float clamp_hi, float lambda_depth, void* workspace, float* out6, float* terms6,
+                                         float* loss_copy, void* stream)
+{
+    if (!terms6) return GSR_ERR_ARG;
+    return depth_loss_forward_impl(depth, depth_gt, images, H, W, 1, kind, clamp_lo, clamp_hi, lambda_depth, workspace, out6, nullptr, terms6,
+                                   loss_copy, stream);
+}
+
+static int depth_loss_backward_impl(const float* depth, const float* depth_gt, int32_t images, int32_t H, int32_t W, int32_t kind, float clamp_lo,
+                                    float clamp_hi, float lambda_depth, const void* workspace, const float* grad_loss, float* d_depth,
+                                    void* stream)
+{
+    if (!depth || !depth_gt || !workspace || !d_depth || images <= 0 || images > kDepthImagesMax || H <= 0 || W <= 0 ||
+        (kind != GSR_DEPTH_LOSS_L1 && kind != GSR_DEPTH_LOSS_INVARIANT))
+        return GSR_ERR_ARG;
+    const DepthWs* ws = static_cast<const DepthWs*>(workspace);
+    const size_t P = (size_t)H * W;
+    const int nb = (int)std::min<size_t>(2048, (P + 255) / 256);
+    hipLaunchKernelGGL(k_depth_bwd, dim3(nb, images), dim3(256), 0, (hipStream_t)stream, depth, depth_gt, (int)H, (int)W, (int)kind, clamp_lo,
+                       clamp_hi, (double)lambda_depth, ws, grad_loss, d_depth);
+    return hipGetLastError() == hipSuccess ? GSR_OK : GSR_ERR_HIP;
+}
+
+int gsr_depth_loss_backward_batched(const float* depth, const float* depth_gt, int32_t images, int32_t H, int32_t W, int32_t kind, float clamp_lo,
+                                    float clamp_hi, float lambda_depth, const void* workspace, const float* grad_loss, float* d_depth,
+                                    void* stream)
+{
+    if (((uintptr_t)workspace & 7) != 0) return GSR_ERR_ARG;
+    return depth_loss_backward_impl(depth, depth_gt, images, H, W, kind, clamp_lo, clamp_hi, lambda_depth, workspace, grad_loss, d_depth, stream);
 }
 
 int gsr_depth_loss_backward(const float* depth, const float* depth_gt, int32_t H, int32_t W, int32_t kind, float clamp_lo, float clamp_hi,
                             float lambda_depth, const void* workspace, const float* grad_loss, float* d_depth, void* stream)
 {
-    if (!depth || !depth_gt || !workspace || !d_depth || H <= 0 || W <= 0 || (kind != GSR_DEPTH_LOSS_L1 && kind != GSR_DEPTH_LOSS_INVARIANT))
-        return GSR_ERR_ARG;
-    const DepthWs* ws = static_cast<const DepthWs*>(workspace);
-    const size_t P = (size_t)H * W;
-    const int nb = (int)std::min<size_t>(2048, (P + 255) / 256);
-    hipLaunchKernelGGL(k_depth_bwd, dim3(nb), dim3(256), 0, (hipStream_t)stream, depth, depth_gt, (int)H, (int)W, (int)kind, clamp_lo, clamp_hi,
-                       (double)lambda_depth, ws->coef, grad_loss, d_depth);
-    return hipGetLastError() == hipSuccess ? GSR_OK : GSR_ERR_HIP;
+    return depth_loss_backward_impl(depth, depth_gt, 1, H, W, kind, clamp_lo, clamp_hi, lambda_depth, workspace, grad_loss, d_depth, stream);
 }
 
 }  // extern "C"

@@ -14,7 +14,8 @@
 //   gsr::importance_accumulate -> gsr_forward + gsr_importance_accumulate (merge-time colour importance, no backward)
 //   gsr::importance_pass      -> gsr_importance_accumulate over a rasterize_forward's outputs
 //   gsr::photometric_loss_forward / _backward -> gsr_loss_forward / gsr_loss_backward
-//   gsr::depth_loss_forward / _backward, gsr::training_loss_terms -> gsr_depth_loss_forward / _backward / _forward_terms
+//   gsr::depth_loss_forward / _forward_stack / _backward, gsr::training_loss_terms -> gsr_depth_loss_forward / _backward / _forward_terms
+//                                              and their _batched forms for stacks of planes
 //   gsr::adam_step            -> gsr_adam_step
 //   gsr::pose_step            -> gsr_pose_step (stage A: tangent-space Adam + exponential map between two renders)
 //   gsr::knn_mean_dist2       -> gsr_knn_mean_dist2
@@ -742,27 +743,57 @@ Tensor photometric_loss_no_grad(const Tensor& render, const Tensor& target, doub
     return std::get<0>(photometric_loss_forward(render, target.device() == render.device() ? target : target.to(render.device()), lambda_dssim, clamp)).select(0, 0);
 }
 
-// ---- the depth term of the loss (gsr_depth_loss_*): depth / depth_gt are [H,W] or [1,H,W] planes; kind 0 = 'l1', 1 = 'invariant'
-static void depth_dims(const Tensor& d, const Tensor& g, int32_t& H, int32_t& W)
+// ---- the depth term of the loss (gsr_depth_loss_*): kind 0 = 'l1', 1 = 'invariant'.  depth / depth_gt are [H,W] or [1,H,W] planes, or
+// stacks of B independent planes (gsr_depth_loss_*_batched): depth [B,1,H,W] (what a batched render returns) or [B,H,W] with B > 1,
+// depth_gt [B,H,W] or [B,1,H,W] of the same B.  Returns the number of images of a stack, 0 for a plane.
+static int32_t depth_dims(const Tensor& d, const Tensor& g, int32_t& H, int32_t& W)
 {
-    TORCH_CHECK((d.dim() == 2 || (d.dim() == 3 && d.size(0) == 1)) && d.numel() > 0 && g.numel() == d.numel() &&
-                g.size(-1) == d.size(-1) && g.size(-2) == d.size(-2), "fused_depth_loss: [H,W] or [1,H,W] depth and depth_gt of one size");
+    const bool plane = d.dim() == 2 || (d.dim() == 3 && d.size(0) == 1);
+    const bool stack = (d.dim() == 3 && d.size(0) > 1) || (d.dim() == 4 && d.size(1) == 1);
+    const bool gshape = !stack || ((g.dim() == 3 || (g.dim() == 4 && g.size(1) == 1)) && g.size(0) == d.size(0));
+    TORCH_CHECK((plane || stack) && gshape && d.numel() > 0 && g.numel() == d.numel() && g.size(-1) == d.size(-1) && g.size(-2) == d.size(-2),
+                "fused_depth_loss: [H,W] or [1,H,W] depth and depth_gt of one size, or stacks [B,1,H,W] / [B,H,W] of one B and one plane size");
     H = (int32_t)d.size(-2); W = (int32_t)d.size(-1);
+    return stack ? (int32_t)d.size(0) : 0;
 }
 inline Tensor on_device_of(const Tensor& t, const Tensor& like) { return t.device() == like.device() ? t : t.to(like.device()); }
 
-std::tuple<Tensor, Tensor> depth_loss_forward(const Tensor& depth_, const Tensor& gt_, int64_t kind, double clamp_lo, double clamp_hi)
+// {rows, workspace, sum}: a plane -> rows (6,), sum undefined (the plane's term is rows[0]); a stack -> rows [B,6], sum = the scalar
+// SUM of the images' terms (written by the chain's last launch)
+static std::tuple<Tensor, Tensor, Tensor> depth_loss_forward_any(const Tensor& depth_, const Tensor& gt_, int64_t kind, double clamp_lo, double clamp_hi)
 {
     TORCH_CHECK(depth_.is_cuda(), "fused_depth_loss: tensors must be on a ROCm/HIP device (no CPU fallback)");
     const c10::hip::HIPGuardMasqueradingAsCUDA guard(depth_.device());
     const Tensor depth = f32c(depth_), gt = f32c(on_device_of(gt_, depth_));
     int32_t H, W;
-    depth_dims(depth, gt, H, W);
-    Tensor ws = at::empty({(int64_t)gsr_depth_loss_workspace_bytes(H, W)}, depth.options().dtype(at::kByte));
-    Tensor out = at::empty({6}, depth.options());
-    check(gsr_depth_loss_forward(fp(depth), fp(gt), H, W, (int32_t)kind, (float)clamp_lo, (float)clamp_hi, 1.0f, ws.data_ptr(), out.data_ptr<float>(),
-                                 c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream()), "gsr_depth_loss_forward");
-    return {out, ws};
+    const int32_t B = depth_dims(depth, gt, H, W);
+    if (B == 0) {
+        Tensor ws = at::empty({(int64_t)gsr_depth_loss_workspace_bytes(H, W)}, depth.options().dtype(at::kByte));
+        Tensor out = at::empty({6}, depth.options());
+        check(gsr_depth_loss_forward(fp(depth), fp(gt), H, W, (int32_t)kind, (float)clamp_lo, (float)clamp_hi, 1.0f, ws.data_ptr(), out.data_ptr<float>(),
+                                     c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream()), "gsr_depth_loss_forward");
+        return {out, ws, Tensor()};
+    }
+    Tensor ws = at::empty({(int64_t)gsr_depth_loss_workspace_bytes_batched(B, H, W)}, depth.options().dtype(at::kByte));
+    Tensor out = at::empty({B, 6}, depth.options()), sum = at::empty({}, depth.options());
+    check(gsr_depth_loss_forward_batched(fp(depth), fp(gt), B, H, W, (int32_t)kind, (float)clamp_lo, (float)clamp_hi, 1.0f, ws.data_ptr(),
+                                         out.data_ptr<float>(), sum.data_ptr<float>(), c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream()),
+          "gsr_depth_loss_forward_batched");
+    return {out, ws, sum};
+}
+
+// (rows, workspace): rows (6,) for a plane, the per-image rows [B,6] for a stack -- no gradient
+std::tuple<Tensor, Tensor> depth_loss_forward(const Tensor& depth, const Tensor& gt, int64_t kind, double clamp_lo, double clamp_hi)
+{
+    auto out = depth_loss_forward_any(depth, gt, kind, clamp_lo, clamp_hi);
+    return {std::get<0>(out), std::get<1>(out)};
+}
+// (sum, rows, workspace) of a stack: what the autograd nodes (DepthLossFn here, loss._FusedDepthLoss on the plain-FFI route) call
+std::tuple<Tensor, Tensor, Tensor> depth_loss_forward_stack(const Tensor& depth, const Tensor& gt, int64_t kind, double clamp_lo, double clamp_hi)
+{
+    auto out = depth_loss_forward_any(depth, gt, kind, clamp_lo, clamp_hi);
+    TORCH_CHECK(std::get<2>(out).defined(), "depth_loss_forward_stack: a stack [B,1,H,W] or [B,H,W] (a plane goes through depth_loss_forward)");
+    return {std::get<2>(out), std::get<0>(out), std::get<1>(out)};
 }
 
 Tensor depth_loss_backward(const Tensor& depth_, const Tensor& gt_, const Tensor& ws, const Tensor& grad_loss_, int64_t kind, double clamp_lo,
@@ -771,22 +802,37 @@ Tensor depth_loss_backward(const Tensor& depth_, const Tensor& gt_, const Tensor
     const c10::hip::HIPGuardMasqueradingAsCUDA guard(depth_.device());
     const Tensor depth = f32c(depth_), gt = f32c(on_device_of(gt_, depth_)), g = f32c(grad_loss_);
     int32_t H, W;
-    depth_dims(depth, gt, H, W);
+    const int32_t B = depth_dims(depth, gt, H, W);
     Tensor d = at::empty_like(depth);
-    check(gsr_depth_loss_backward(fp(depth), fp(gt), H, W, (int32_t)kind, (float)clamp_lo, (float)clamp_hi, (float)lambda_depth, ws.data_ptr(), fp(g),
-                                  d.data_ptr<float>(), c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream()), "gsr_depth_loss_backward");
+    if (B == 0)
+        check(gsr_depth_loss_backward(fp(depth), fp(gt), H, W, (int32_t)kind, (float)clamp_lo, (float)clamp_hi, (float)lambda_depth, ws.data_ptr(), fp(g),
+                                      d.data_ptr<float>(), c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream()), "gsr_depth_loss_backward");
+    else {
+        TORCH_CHECK(ws.numel() >= (int64_t)gsr_depth_loss_workspace_bytes_batched(B, H, W), "fused_depth_loss: the workspace of another stack");
+        check(gsr_depth_loss_backward_batched(fp(depth), fp(gt), B, H, W, (int32_t)kind, (float)clamp_lo, (float)clamp_hi, (float)lambda_depth,
+                                              ws.data_ptr(), fp(g), d.data_ptr<float>(), c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream()),
+              "gsr_depth_loss_backward_batched");
+    }
     return d;
 }
+
+static bool depth_is_stack(const Tensor& d) { return (d.dim() == 3 && d.size(0) > 1) || d.dim() == 4; }
 
 class DepthLossFn : public torch::autograd::Function<DepthLossFn> {
    public:
     static Tensor forward(torch::autograd::AutogradContext* ctx, const Tensor& depth, const Tensor& gt, int64_t kind, double lo, double hi)
     {
         static auto op = c10::Dispatcher::singleton().findSchemaOrThrow("gsr::depth_loss_forward", "").typed<decltype(depth_loss_forward)>();
+        static auto ops = c10::Dispatcher::singleton().findSchemaOrThrow("gsr::depth_loss_forward_stack", "").typed<decltype(depth_loss_forward_stack)>();
         const Tensor d = f32c(depth), t = f32c(on_device_of(gt, depth));
+        ctx->saved_data["kind"] = kind; ctx->saved_data["lo"] = lo; ctx->saved_data["hi"] = hi;
+        if (depth_is_stack(d)) {      // the SUM of the images' terms
+            auto out = ops.call(d, t, kind, lo, hi);
+            ctx->save_for_backward({d, t, std::get<2>(out)});
+            return std::get<0>(out);
+        }
         auto out = op.call(d, t, kind, lo, hi);
         ctx->save_for_backward({d, t, std::get<1>(out)});
-        ctx->saved_data["kind"] = kind; ctx->saved_data["lo"] = lo; ctx->saved_data["hi"] = hi;
         return std::get<0>(out).select(0, 0);
     }
     static torch::autograd::variable_list backward(torch::autograd::AutogradContext* ctx, torch::autograd::variable_list g)
@@ -800,26 +846,37 @@ class DepthLossFn : public torch::autograd::Function<DepthLossFn> {
 Tensor depth_loss(const Tensor& depth, const Tensor& gt, int64_t kind, double lo, double hi) { return DepthLossFn::apply(depth, gt, kind, lo, hi); }
 Tensor depth_loss_no_grad(const Tensor& depth, const Tensor& gt, int64_t kind, double lo, double hi)
 {
-    return std::get<0>(depth_loss_forward(depth, gt, kind, lo, hi)).select(0, 0);
+    auto out = depth_loss_forward_any(depth, gt, kind, lo, hi);
+    return std::get<2>(out).defined() ? std::get<2>(out) : std::get<0>(out).select(0, 0);
 }
 
 // The whole of Loss.forward (/root/reference/trainer/losses.py:98-136) with a depth term: (loss, terms), terms = {total loss, mean SSIM,
-// mean L1, loss_rgb, loss_dssim, loss_depth (unweighted)} -- the photometric forward, then the depth chain whose finishing kernel completes
-// the vector.  ONE autograd node hands back d_render and d_depth.
+// mean L1, loss_rgb, loss_dssim, loss_depth (unweighted)} -- the photometric forward, then the depth chain whose last launch completes
+// the vector.  ONE autograd node hands back d_render and d_depth.  A stack [B,3,H,W] with depth [B,1,H,W] / [B,H,W]: loss = the SUM of
+// the images' losses (photometric and depth), terms[5] = the mean of the images' unweighted depth terms.
 static std::tuple<Tensor, Tensor, Tensor, Tensor> training_loss_forward(const Tensor& r, const Tensor& t, const Tensor& dp, const Tensor& dg,
                                                                         double lambda_dssim, double lambda_depth, int64_t kind, bool clamp,
                                                                         double lo, double hi)
 {
-    TORCH_CHECK(r.dim() == 3, "fused_training_loss_report: a single [C,H,W] render (the batched form has no depth term)");
     auto out = photometric_loss_forward_terms(r, t, lambda_dssim, clamp);
     const c10::hip::HIPGuardMasqueradingAsCUDA guard(r.device());
     int32_t H, W;
-    depth_dims(dp, dg, H, W);
+    const int32_t B = depth_dims(dp, dg, H, W);
+    TORCH_CHECK(r.dim() == 4 ? (B > 0 && r.size(0) == B) : B == 0,
+                "fused_training_loss_report: a [C,H,W] render with a depth plane, or a [B,C,H,W] stack with a depth stack [B,1,H,W] / [B,H,W] of the same B");
+    TORCH_CHECK(r.size(-2) == H && r.size(-1) == W, "fused_training_loss_report: render and depth of one image size");
     Tensor terms = std::get<0>(out), loss = std::get<2>(out);
-    Tensor dws = at::empty({(int64_t)gsr_depth_loss_workspace_bytes(H, W)}, r.options().dtype(at::kByte)), dout = at::empty({6}, r.options());
-    check(gsr_depth_loss_forward_terms(fp(dp), fp(dg), H, W, (int32_t)kind, (float)lo, (float)hi, (float)lambda_depth, dws.data_ptr(),
-                                       dout.data_ptr<float>(), terms.data_ptr<float>(), loss.data_ptr<float>(),
-                                       c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream()), "gsr_depth_loss_forward_terms");
+    if (B == 0) {
+        Tensor dws = at::empty({(int64_t)gsr_depth_loss_workspace_bytes(H, W)}, r.options().dtype(at::kByte)), dout = at::empty({6}, r.options());
+        check(gsr_depth_loss_forward_terms(fp(dp), fp(dg), H, W, (int32_t)kind, (float)lo, (float)hi, (float)lambda_depth, dws.data_ptr(),
+                                           dout.data_ptr<float>(), terms.data_ptr<float>(), loss.data_ptr<float>(),
+                                           c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream()), "gsr_depth_loss_forward_terms");
+        return {loss, terms, std::get<1>(out), dws};
+    }
+    Tensor dws = at::empty({(int64_t)gsr_depth_loss_workspace_bytes_batched(B, H, W)}, r.options().dtype(at::kByte)), dout = at::empty({B, 6}, r.options());
+    check(gsr_depth_loss_forward_terms_batched(fp(dp), fp(dg), B, H, W, (int32_t)kind, (float)lo, (float)hi, (float)lambda_depth, dws.data_ptr(),
+                                               dout.data_ptr<float>(), terms.data_ptr<float>(), loss.data_ptr<float>(),
+                                               c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream()), "gsr_depth_loss_forward_terms_batched");
     return {loss, terms, std::get<1>(out), dws};
 }
 class TrainingLossFn : public torch::autograd::Function<TrainingLossFn> {
@@ -1057,6 +1114,7 @@ TORCH_LIBRARY(gsr, m)
     m.def("photometric_loss(Tensor render, Tensor target, float lambda_dssim, bool clamp) -> Tensor");
     m.def("photometric_loss_terms(Tensor render, Tensor target, float lambda_dssim, bool clamp) -> (Tensor, Tensor)");
     m.def("depth_loss_forward(Tensor depth, Tensor depth_gt, int kind, float clamp_lo, float clamp_hi) -> (Tensor, Tensor)");
+    m.def("depth_loss_forward_stack(Tensor depth, Tensor depth_gt, int kind, float clamp_lo, float clamp_hi) -> (Tensor, Tensor, Tensor)");
     m.def("depth_loss_backward(Tensor depth, Tensor depth_gt, Tensor workspace, Tensor grad_loss, int kind, float clamp_lo, float clamp_hi, "
           "float lambda_depth) -> Tensor");
     m.def("depth_loss(Tensor depth, Tensor depth_gt, int kind, float clamp_lo, float clamp_hi) -> Tensor");
@@ -1103,6 +1161,7 @@ TORCH_LIBRARY_IMPL(gsr, CUDA, m)   // the dispatch key of HIP tensors on a ROCm 
     m.impl("photometric_loss", &photometric_loss_no_grad);
     m.impl("photometric_loss_terms", &photometric_loss_terms_no_grad);
     m.impl("depth_loss_forward", &depth_loss_forward);
+    m.impl("depth_loss_forward_stack", &depth_loss_forward_stack);
     m.impl("depth_loss_backward", &depth_loss_backward);
     m.impl("depth_loss", &depth_loss_no_grad);
     m.impl("training_loss_terms", &training_loss_terms_no_grad);

@@ -93,12 +93,21 @@ def _depth_kind(kind) -> int:
     return DEPTH_LOSS_KINDS[kind]
 
 
+def _depth_images(depth) -> int:
+    """Images of a depth stack ([B,1,H,W] -- what a batched render returns -- or [B,H,W] with B > 1); 0 for a plane [H,W] / [1,H,W]."""
+    return int(depth.shape[0]) if (depth.dim() == 4 or (depth.dim() == 3 and depth.shape[0] > 1)) else 0
+
+
 def _check_depth(depth, depth_gt):
+    plane = depth.dim() == 2 or (depth.dim() == 3 and depth.shape[0] == 1)
+    stack = (depth.dim() == 3 and depth.shape[0] > 1) or (depth.dim() == 4 and depth.shape[1] == 1)
+    if stack:       # depth_gt [B,H,W] or [B,1,H,W] of the same B
+        stack = (depth_gt.dim() == 3 or (depth_gt.dim() == 4 and depth_gt.shape[1] == 1)) and depth_gt.shape[0] == depth.shape[0]
+    if not (plane or stack) or tuple(depth_gt.shape[-2:]) != tuple(depth.shape[-2:]) or depth_gt.numel() != depth.numel():
+        raise RuntimeError("fused_depth_loss: depth and depth_gt must be [H,W] or [1,H,W] planes of one size, or stacks [B,1,H,W] / [B,H,W] "
+                           f"of one B and one plane size (got {tuple(depth.shape)} and {tuple(depth_gt.shape)})")
     if depth.device.type != "cuda":
         raise RuntimeError("fused_depth_loss: tensors must be on a ROCm/HIP device (no CPU fallback)")
-    if not (depth.dim() == 2 or (depth.dim() == 3 and depth.shape[0] == 1)) or tuple(depth_gt.shape[-2:]) != tuple(depth.shape[-2:]) \
-            or depth_gt.numel() != depth.numel():
-        raise RuntimeError("fused_depth_loss: depth and depth_gt must be [H,W] or [1,H,W] planes of one size")
 
 
 class _FusedDepthLoss(torch.autograd.Function):
@@ -107,9 +116,13 @@ class _FusedDepthLoss(torch.autograd.Function):
         ops = E.load()
         depth = depth.float().contiguous()
         depth_gt = depth_gt.to(depth.device).float().contiguous()
+        ctx.cfg = (kind, lo, hi)
+        if _depth_images(depth):      # a stack: the SUM of the images' terms
+            total, _rows, ws = ops.depth_loss_forward_stack(depth, depth_gt, kind, lo, hi)
+            ctx.save_for_backward(depth, depth_gt, ws)
+            return total
         out, ws = ops.depth_loss_forward(depth, depth_gt, kind, lo, hi)
         ctx.save_for_backward(depth, depth_gt, ws)
-        ctx.cfg = (kind, lo, hi)
         return out[0]
 
     @staticmethod
@@ -125,12 +138,25 @@ def fused_depth_loss(depth: torch.Tensor, depth_gt: torch.Tensor, kind: str = "i
     kind = the reference's depth_loss_type: 'l1', or 'invariant' = the scale-and-shift-invariant loss (alpha 0.5, one scale, mask
     depth_gt > 0.02) whose gradient flows through the fitted scale and shift.  Four short launches forward, one backward, float64
     fixed-order sums: bit-identical from run to run, no host synchronisation.  Autograd node in the extension (DepthLossFn); the
-    Python autograd.Function above states the same thing and serves the plain-FFI binding route."""
+    Python autograd.Function above states the same thing and serves the plain-FFI binding route.
+    A stack of B independent planes -- depth [B,1,H,W] (a batched render's depth) or [B,H,W], depth_gt [B,H,W] or [B,1,H,W] -- returns the
+    SUM of the images' terms, as the photometric loss does on a stack: every image has its own fit and its own M, the launches stay
+    four and one, and image b's term and gradient plane are bit for bit those of the plane alone (`fused_depth_loss_rows` reads the
+    per-image rows)."""
     _check_depth(depth, depth_gt)
     k, lo, hi = _depth_kind(kind), float(clamp[0]), float(clamp[1])
     if E.use_ctypes():
         return _FusedDepthLoss.apply(depth, depth_gt, k, lo, hi)
     return E.load().depth_loss(depth, depth_gt, k, lo, hi)
+
+
+def fused_depth_loss_rows(depth: torch.Tensor, depth_gt: torch.Tensor, kind: str = "invariant", clamp=DEPTH_CLAMP) -> torch.Tensor:
+    """{loss_depth, scale s, shift t, M, data term, regulariser} of the same forward, without a gradient: (6,) for a plane, one row per
+    image [B,6] for a stack (`torch.ops.gsr.depth_loss_forward`)."""
+    _check_depth(depth, depth_gt)
+    with torch.no_grad():
+        return E.load().depth_loss_forward(depth.float().contiguous(), depth_gt.to(depth.device).float().contiguous(), _depth_kind(kind),
+                                           float(clamp[0]), float(clamp[1]))[0]
 
 
 def fused_training_loss_report(render: torch.Tensor, target: torch.Tensor, depth: torch.Tensor = None, depth_gt: torch.Tensor = None,
@@ -140,11 +166,17 @@ def fused_training_loss_report(render: torch.Tensor, target: torch.Tensor, depth
     six-float vector {total loss, mean SSIM, mean L1, loss_rgb, loss_dssim, loss_depth (unweighted)}, i.e. every entry of the dict the
     reference returns -- from one dispatcher call; ONE autograd node hands back d_render and d_depth.  `clamp` is the render's
     clamp(0, 1) as in fused_photometric_loss; the depth plane is clamped to `depth_clamp` inside.  Without a depth_gt, or with
-    lambda_depth = 0, this is fused_photometric_loss_report: the same launches, the same bits.  Extension binding only."""
+    lambda_depth = 0, this is fused_photometric_loss_report: the same launches, the same bits.  Extension binding only.
+    Stacks: render / target [B,3,H,W] with depth [B,1,H,W] or [B,H,W] and depth_gt [B,H,W] or [B,1,H,W] of the same B -- loss = the SUM
+    of the images' losses, terms[5] = the mean of the images' unweighted depth terms (as terms[1], terms[2] are means), still one node."""
     if depth_gt is None or depth is None or float(lambda_depth) == 0.0:
         return fused_photometric_loss_report(render, target, lambda_dssim, clamp)
     if render.device.type != "cuda":
         raise RuntimeError("fused_photometric_loss: tensors must be on a ROCm/HIP device (no CPU fallback)")
     _check_depth(depth, depth_gt)
+    if (render.dim() == 4) != bool(_depth_images(depth)) or (render.dim() == 4 and render.shape[0] != depth.shape[0]) \
+            or tuple(render.shape[-2:]) != tuple(depth.shape[-2:]):
+        raise RuntimeError("fused_depth_loss: depth and depth_gt must be [H,W] or [1,H,W] planes of one size, or stacks [B,1,H,W] / [B,H,W] "
+                           f"of one B and one plane size, matching the render (got render {tuple(render.shape)}, depth {tuple(depth.shape)})")
     return E.load().training_loss_terms(render, target, depth, depth_gt, float(lambda_dssim), float(lambda_depth), _depth_kind(kind),
                                         bool(clamp), float(depth_clamp[0]), float(depth_clamp[1]))

@@ -130,17 +130,22 @@ def run_stage_a(n_frames: int, fit_fn: Callable[[int], torch.Tensor], device, ra
 
 
 def fit_pair(seq, p: int, device, n_points: int = 100_000, single_image_iters: int = 1000, pose_iters: int = 300,
-             pose_lr: float = 2e-3, seed: int = 0, init: str = "pixels", fused_pose_step: bool = True) -> torch.Tensor:
+             pose_lr: float = 2e-3, seed: int = 0, init: str = "pixels", fused_pose_step: bool = True, lambda_depth: float = 0.0,
+             depth_loss_type: str = "invariant") -> torch.Tensor:
     """compute_relative_pose(p+1, p) on the HIP rasterizer (:336-380): returns rel_pose_{p}_to_{p+1} [4,4] (CPU).
 
     1. single-image 3DGS of frame p in that frame's own camera coordinates (identity pose), initialised from the frame's
        un-projected depth (sequence.pixel_scene; :352-363), fused train step, no densification (:352-365; early exit on
        PSNR > 35 after 500 iterations as :300-301);
     2. freeze the Gaussians, fit delta in Exp(delta) (tangent at the identity, `init_RT(None)` :370) on frame p+1 with
-       Adam through `points_transform` (pose.py): loss = the same photometric loss."""
+       Adam through `points_transform` (pose.py): loss = the same photometric loss.
+    lambda_depth != 0: both phases add lambda_depth * the depth term (`depth_loss_type`, 'invariant' as the reference sets it for this
+    stage, ht3dgs_trainer.py:354, :392) on the render's depth against the frame's depth map (`seq.depth`): the image phase through
+    train_step, the pose phase through fused_training_loss_report, whose depth gradient reaches the transform through the blend's
+    depth instantiation.  0 (the default) leaves every launch as it is."""
     from . import pose as pose_mod
     from . import train_step as ts
-    from .loss import fused_photometric_loss
+    from .loss import fused_photometric_loss, fused_training_loss_report
     from .rasterizer import rasterize_gaussians_raw
     if init == "pixels":     # one Gaussian per strided pixel of frame p, un-projected with its depth (about n_points of them)
         stride = max(1, int(round((seq.W * seq.H / max(1, n_points)) ** 0.5)))
@@ -153,8 +158,16 @@ def fit_pair(seq, p: int, device, n_points: int = 100_000, single_image_iters: i
     params.active_sh_degree = 0
     ident = ts.with_sh_degree(seq.settings_for_pose(torch.eye(4)), 0)
     tgt0, tgt1 = seq.target(p), seq.target(p + 1)
+    with_depth = float(lambda_depth) != 0.0
+    dkw = dict(depth_gt=seq.depth(p), lambda_depth=float(lambda_depth), depth_loss_type=depth_loss_type) if with_depth else {}
+    dep1 = seq.depth(p + 1) if with_depth else None
+
+    def pose_loss(out):      # out = the render's (image, radii, depth, alpha)
+        if with_depth:
+            return fused_training_loss_report(out[0], tgt1, out[2], dep1, 0.2, float(lambda_depth), depth_loss_type, clamp=True)[0]
+        return fused_photometric_loss(out[0], tgt1, 0.2, clamp=True)
     for it in range(1, single_image_iters + 1):
-        pkg = ts.train_step(params, ident, tgt0, next_settings=ident)      # same view every step: its preprocess rides in the backward
+        pkg = ts.train_step(params, ident, tgt0, next_settings=ident, **dkw)      # same view every step: its preprocess rides in the backward
         if it > 500 and it % 50 == 0:
             with torch.no_grad():
                 mse = ((pkg["raw_image"].clamp(0, 1) - tgt0) ** 2).mean()
@@ -169,9 +182,9 @@ def fit_pair(seq, p: int, device, n_points: int = 100_000, single_image_iters: i
         for _ in range(pose_iters):
             opt.zero_grad(set_to_none=True)
             M = pose_mod.retr_matrix(delta, pose7)
-            img = rasterize_gaussians_raw(raw["_xyz"], m2d, raw["_features_dc"], raw["_features_rest"], raw["_opacity"],
-                                          raw["_scaling"], raw["_rotation"], ident, points_transform=M)[0]
-            fused_photometric_loss(img, tgt1, 0.2, clamp=True).backward()
+            out = rasterize_gaussians_raw(raw["_xyz"], m2d, raw["_features_dc"], raw["_features_rest"], raw["_opacity"],
+                                          raw["_scaling"], raw["_rotation"], ident, points_transform=M)
+            pose_loss(out).backward()
             opt.step()
         return pose_mod.retr_matrix(delta.detach(), pose7).cpu()
     # fused: one one-thread kernel between two renders (gsr_pose_step) takes dL/dM, applies Adam to the six tangent numbers and
@@ -185,9 +198,9 @@ def fit_pair(seq, p: int, device, n_points: int = 100_000, single_image_iters: i
     ops.pose_step(delta, m, v, none, none, M, pose_lr, 0.9, 0.999, 1e-8, 0)              # M = Exp(0) = identity
     for it in range(1, pose_iters + 1):
         Mi = M.detach().requires_grad_(True)
-        img = rasterize_gaussians_raw(raw["_xyz"], m2d, raw["_features_dc"], raw["_features_rest"], raw["_opacity"],
-                                      raw["_scaling"], raw["_rotation"], ident, points_transform=Mi)[0]
-        fused_photometric_loss(img, tgt1, 0.2, clamp=True).backward()
+        out = rasterize_gaussians_raw(raw["_xyz"], m2d, raw["_features_dc"], raw["_features_rest"], raw["_opacity"],
+                                      raw["_scaling"], raw["_rotation"], ident, points_transform=Mi)
+        pose_loss(out).backward()
         ops.pose_step(delta, m, v, Mi.grad, none, M, pose_lr, 0.9, 0.999, 1e-8, it)       # torch.optim.Adam's defaults
     out = torch.eye(4)
     out[:3] = M.detach().cpu()
@@ -195,22 +208,26 @@ def fit_pair(seq, p: int, device, n_points: int = 100_000, single_image_iters: i
 
 
 def fit_pairs_batched(seq, pairs: List[int], device, n_points: int = 100_000, single_image_iters: int = 1000, pose_iters: int = 300,
-                      pose_lr: float = 2e-3, seed: int = 0) -> Dict[int, torch.Tensor]:
+                      pose_lr: float = 2e-3, seed: int = 0, lambda_depth: float = 0.0,
+                      depth_loss_type: str = "invariant") -> Dict[int, torch.Tensor]:
     """`fit_pair` for several pairs AT ONCE: the B single-image models live in one parameter store and every step of the B fits is
     ONE launch chain (batched.BatchedGaussianParams / include/gsr.h GsrBatch) -- B renders, B losses, B Adam updates and the B
     hand-overs to the next step per pass over the kernels, instead of B chains of ~17 kernels that each fill a fraction of the
     chip.  Per model the arithmetic is what `fit_pair` does (bit-identical renders and updates, tests/test_gpu_batched.py); what
     differs is the early exit of the image phase: the reference leaves a model's loop when its PSNR passes 35 dB after 500
     iterations (ht3dgs_trainer.py:300-301), a batch runs until ALL its models have passed (or the iteration cap) -- a model that
-    is already there simply trains a little longer.  Returns {pair -> rel_pose [4,4] (CPU)}."""
+    is already there simply trains a little longer.  Returns {pair -> rel_pose [4,4] (CPU)}.
+    lambda_depth / depth_loss_type as in `fit_pair`: the depth term on the stack of the B depth planes (the sum of the images' terms,
+    each with its own fit -- every model gets exactly the gradient of its own loss)."""
     from . import batched as bt
     from . import train_step as ts
     from . import _ext
-    from .loss import fused_photometric_loss
+    from .loss import fused_photometric_loss, fused_training_loss_report
     from .rasterizer import rasterize_gaussians_raw
     B = len(pairs)
     if B == 1:
-        return {pairs[0]: fit_pair(seq, pairs[0], device, n_points, single_image_iters, pose_iters, pose_lr, seed)}
+        return {pairs[0]: fit_pair(seq, pairs[0], device, n_points, single_image_iters, pose_iters, pose_lr, seed,
+                                   lambda_depth=lambda_depth, depth_loss_type=depth_loss_type)}
     stride = max(1, int(round((seq.W * seq.H / max(1, n_points)) ** 0.5)))
     scenes = [seq.pixel_scene(p, stride=stride, seed=seed) for p in pairs]
     params = bt.BatchedGaussianParams(scenes, device)
@@ -219,8 +236,13 @@ def fit_pairs_batched(seq, pairs: List[int], device, n_points: int = 100_000, si
     ident = bt.batch_settings([ident1] * B, device)
     tgt0 = torch.stack([seq.target(p) for p in pairs])
     tgt1 = torch.stack([seq.target(p + 1) for p in pairs])
+    with_depth = float(lambda_depth) != 0.0
+    dkw = {}
+    if with_depth:
+        dkw = dict(depth_gt=torch.stack([seq.depth(p) for p in pairs]), lambda_depth=float(lambda_depth), depth_loss_type=depth_loss_type)
+        dep1 = torch.stack([seq.depth(p + 1) for p in pairs])
     for it in range(1, single_image_iters + 1):
-        pkg = ts.train_step(params, ident, tgt0, next_settings=ident)
+        pkg = ts.train_step(params, ident, tgt0, next_settings=ident, **dkw)
         if it > 500 and it % 50 == 0:
             with torch.no_grad():
                 mse = ((pkg["raw_image"].clamp(0, 1) - tgt0) ** 2).flatten(1).mean(dim=1)
@@ -237,9 +259,12 @@ def fit_pairs_batched(seq, pairs: List[int], device, n_points: int = 100_000, si
         ops.pose_step(delta[b], m[b], v[b], none, none, M[b], pose_lr, 0.9, 0.999, 1e-8, 0)              # M_b = Exp(0) = identity
     for it in range(1, pose_iters + 1):
         Mi = M.detach().requires_grad_(True)
-        img = rasterize_gaussians_raw(raw["_xyz"], m2d, raw["_features_dc"], raw["_features_rest"], raw["_opacity"], raw["_scaling"],
-                                      raw["_rotation"], ident, points_transform=Mi, batch_first_block=params.first_block)[0]
-        fused_photometric_loss(img, tgt1, 0.2, clamp=True).backward()          # sum of the B losses: every transform gets its own gradient
+        out = rasterize_gaussians_raw(raw["_xyz"], m2d, raw["_features_dc"], raw["_features_rest"], raw["_opacity"], raw["_scaling"],
+                                      raw["_rotation"], ident, points_transform=Mi, batch_first_block=params.first_block)
+        if with_depth:      # (image, radii, depth [B,1,H,W], alpha): photometric + depth on the stacks, one node for both gradients
+            fused_training_loss_report(out[0], tgt1, out[2], dep1, 0.2, float(lambda_depth), depth_loss_type, clamp=True)[0].backward()
+        else:
+            fused_photometric_loss(out[0], tgt1, 0.2, clamp=True).backward()    # sum of the B losses: every transform gets its own gradient
         g = Mi.grad
         for b in range(B):                                                        # one one-thread kernel per model (gsr_pose_step)
             ops.pose_step(delta[b], m[b], v[b], g[b], none, M[b], pose_lr, 0.9, 0.999, 1e-8, it)

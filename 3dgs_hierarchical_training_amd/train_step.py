@@ -68,7 +68,17 @@ def depth_loss(depth: torch.Tensor, depth_gt: torch.Tensor, kind: str = "invaria
     `depth` (float64-capable), differentiable through the fitted scale and shift -- but the three data-dependent branches (`det.nonzero()`,
     `if divisor == 0` twice) are `torch.where`, so nothing waits for the device.  The twin of `photometric_loss`: it serves
     fused_loss=False and is what the fused kernels (loss.fused_depth_loss) are tested against.
-    depth, depth_gt: [H,W] or [1,H,W].  return_fit=True: (loss, scale, shift, number of valid pixels)."""
+    depth, depth_gt: [H,W] or [1,H,W].  return_fit=True: (loss, scale, shift, number of valid pixels).
+    Stacks (depth [B,1,H,W] or [B,H,W] with B > 1, depth_gt [B,H,W] or [B,1,H,W]): the SUM of the images' losses, every image with its own
+    fit and its own M (return_fit: the sum and per-image lists) -- what loss.fused_depth_loss computes on a stack."""
+    if depth.dim() == 4 or (depth.dim() == 3 and depth.shape[0] > 1):      # a stack: the sum of the per-image losses
+        B = depth.shape[0]
+        if depth_gt.shape[0] != B or depth_gt.numel() != depth.numel() or tuple(depth_gt.shape[-2:]) != tuple(depth.shape[-2:]):
+            raise RuntimeError(f"depth_loss: stacks of one B and one plane size (got {tuple(depth.shape)} and {tuple(depth_gt.shape)})")
+        each = [depth_loss(depth[b], depth_gt[b], kind, clamp, return_fit) for b in range(B)]
+        if not return_fit:
+            return torch.stack(each).sum()
+        return torch.stack([e[0] for e in each]).sum(), [e[1] for e in each], [e[2] for e in each], [e[3] for e in each]
     p = depth.reshape(depth.shape[-2:])
     g = depth_gt.reshape(depth_gt.shape[-2:]).to(device=p.device, dtype=p.dtype)
     pc = p.clamp(float(clamp[0]), float(clamp[1]))        # (gradient: zero strictly outside the bounds, passed on them -- as the masked assignments)
@@ -460,7 +470,7 @@ def train_step(params: GaussianParams, settings: GaussianRasterizationSettings, 
     densifier (densify.Densifier) + iteration: the adaptive density control of ht3dgs_trainer.py:137-155 runs between
     backward() and optimizer.step(), as in the reference; on the iterations where it replaces parameter tensors the step is not
     fused into the backward, so that the update the reference drops there is dropped here too (densify.py).
-    depth_gt ([H,W] or [1,H,W]) with a non-zero lambda_depth: the loss is photometric + lambda_depth * depth term (`Loss.forward`,
+    depth_gt ([H,W] or [1,H,W]; [B,H,W] or [B,1,H,W] for a batch of B models) with a non-zero lambda_depth: the loss is photometric + lambda_depth * depth term (`Loss.forward`,
     losses.py:114-124; depth_loss_type 'l1' or 'invariant') on the render's depth plane, and the render's backward receives grad_depth
     -- on every route above (the blend's depth / alpha instantiation, then the depth terms of the per-Gaussian backward).  Without it
     nothing changes: the same launches, the same bits."""
@@ -495,10 +505,8 @@ def train_step(params: GaussianParams, settings: GaussianRasterizationSettings, 
     pkg = render(params, settings, clamp=not fused_loss, fused_activations=fused_activations, fused_adam=fused_adam,
                  next_settings=nxt, points_transform=xf, densify_stats=dstats, view_id=view_id,
                  next_points_transform=next_pose.M if (xf is not None and next_pose is not None and nxt is not None) else None)
-    if with_depth and pkg["depth"].dim() != 3:
-        raise RuntimeError("train_step: the depth term is not served for a batch of models")
     # (a batch hands [B,3,H,W] stacks: the fused loss is then the SUM of the models' losses, every image normalised on its own -- each
-    #  model gets exactly its own loss's gradient, bit-identical with training it alone)
+    #  model gets exactly its own loss's gradient, bit-identical with training it alone; the depth term likewise, on [B,1,H,W])
     if fused_loss and with_depth and not E_use_ctypes():      # one dispatcher call, one autograd node for d_render and d_depth
         loss = fused_training_loss_report(pkg["raw_image"], gt, pkg["depth"], depth_gt, lambda_dssim, lambda_depth, depth_loss_type, clamp=True)[0]
     elif fused_loss:

@@ -303,7 +303,8 @@ const char* gsr_last_error(void);
  * gsr_struct_bytes(0) == sizeof(GsrForwardArgs), gsr_struct_bytes(1) == sizeof(GsrBackwardArgs) at start-up).
  * 111: GsrForwardArgs and GsrBackwardArgs end with sh_origin.
  * 112: the depth term of the loss (gsr_depth_loss_*); no struct changed.
- * 113: gsr_importance_accumulate / gsr_importance_scratch_bytes; no struct changed. */
+ * 113: gsr_importance_accumulate / gsr_importance_scratch_bytes; no struct changed.
+ * 114: the depth term on a stack of planes (gsr_depth_loss_*_batched); no struct changed. */
 int gsr_version(void);
 size_t gsr_struct_bytes(int32_t which); /* 0 GsrForwardArgs, 1 GsrBackwardArgs, 2 GsrForwardOut; anything else 0 */
 
@@ -481,6 +482,32 @@ int gsr_depth_loss_backward(const float* depth, const float* depth_gt, int32_t H
  * new total to loss_copy (may be NULL) as well. */
 int gsr_depth_loss_forward_terms(const float* depth, const float* depth_gt, int32_t H, int32_t W, int32_t kind, float clamp_lo, float clamp_hi,
                                  float lambda_depth, void* workspace, float* out6, float* terms6, float* loss_copy, void* stream);
+
+/* The same over a stack of `images` independent planes [images, H, W] (version 114; the depth output of a batched render, GsrBatch):
+ * plane b lies at b H W floats, image b owns the b-th slice of the workspace (gsr_depth_loss_workspace_bytes_batched, 8-byte aligned)
+ * and nothing is shared between images -- every image has its own fit (s, t), its own M and its own determinant.  Still four short
+ * launches forward and one backward, whatever `images` is (the image index is a grid dimension).
+ * out6 = [images, 6], row b as gsr_depth_loss_forward writes it for plane b; *out_sum = the SUM of the images' unweighted terms, added
+ * in float64 in index order (no atomics).  The backward returns the gradient of that sum: d_depth[images,H,W], image b receives exactly
+ * grad_loss * lambda_depth * d loss_b / d depth_b.
+ * Position independence: row b and gradient plane b are, bit for bit, what the single-plane entries give on a separately allocated,
+ * 16-byte aligned copy of plane b -- whatever `images` is and wherever the plane lies (planes 1, 2, 3 ... of a stack are not 16-byte
+ * aligned when H W is not a multiple of 4: every lane then still adds the elements an aligned plane gives it, only the width of its
+ * loads follows the address).
+ * gsr_depth_loss_forward_terms_batched runs behind gsr_loss_forward_terms(..., images, ...) on the same stream and completes its
+ * six-float vector as that call's finishing kernel does for a stack: terms6[0] += lambda_depth * SUM_b loss_b, terms6[5] = the MEAN over
+ * the images of the unweighted term; loss_copy (may be NULL) receives the new total.
+ * GSR_ERR_ARG: images <= 0 (or more than 65535), a NULL pointer, a bad kind, a workspace that is not 8-byte aligned. */
+size_t gsr_depth_loss_workspace_bytes_batched(int32_t images, int32_t H, int32_t W);
+int gsr_depth_loss_forward_batched(const float* depth, const float* depth_gt, int32_t images, int32_t H, int32_t W, int32_t kind, float clamp_lo,
+                                   float clamp_hi, float lambda_depth, void* workspace, float* out6 /* [images,6] */, float* out_sum /* 1 float */,
+                                   void* stream);
+int gsr_depth_loss_backward_batched(const float* depth, const float* depth_gt, int32_t images, int32_t H, int32_t W, int32_t kind, float clamp_lo,
+                                    float clamp_hi, float lambda_depth, const void* workspace, const float* grad_loss,
+                                    float* d_depth /* [images,H,W] */, void* stream);
+int gsr_depth_loss_forward_terms_batched(const float* depth, const float* depth_gt, int32_t images, int32_t H, int32_t W, int32_t kind,
+                                         float clamp_lo, float clamp_hi, float lambda_depth, void* workspace, float* out6 /* [images,6] */,
+                                         float* terms6, float* loss_copy, void* stream);
 
 /* ---- "next" row f-2: multi-tensor Adam step in one launch ------------------------------------------------
  * Same update rule as torch.optim.Adam(l, lr=0.0, eps=1e-15) of /root/reference/scene/gaussian_model_ht.py:275-289

@@ -75,7 +75,7 @@ def _register_fakes():
           bg, points_transform, image_height, image_width, tanfovx, tanfovy, scale_modifier, sh_degree, raw_params, prefiltered, debug,
           cam_grad, adam_m, adam_v, adam_lr, beta1, beta2, eps, step, prepared, next_viewmatrix, next_projmatrix, next_campos,
           next_height, next_width, next_tanfovx, next_tanfovy, next_points_transform, next_sh_degree, adam_commit, densify_stats, batch_first_block, view_id=0, extras=0,
-          sh_origin=None):
+          sh_origin=None, frozen=-1):
         N, H, W = means3D.shape[0], image_height, image_width
         f = lambda *s: means3D.new_empty(s, dtype=torch.float32)
         nprep = lib.gsr_prepared_bytes(int(N)) if next_viewmatrix.numel() else 0
@@ -102,6 +102,19 @@ def _register_fakes():
                 f(N, M - 1, 3) if (has(sh) and has(sh_rest)) else none, f(*lead, 4, 4) if need_viewmatrix else none,
                 f(*lead, 4, 4) if need_projmatrix else none, f(*lead, 3) if need_campos else none,
                 f(*lead, 3, 4) if (need_points_transform and has(points_transform)) else none]
+
+    @torch.library.register_fake("gsr::rasterize_backward_frozen")
+    def _(means3D, sh, colors_precomp, opacities, scales, rotations, cov3D_precomp, sh_rest, viewmatrix, projmatrix, campos, bg,
+          points_transform, geom, image, binning, meta, grad_color, grad_depth, grad_alpha, image_height, image_width, tanfovx, tanfovy,
+          scale_modifier, sh_degree, raw_params, need_means2D, need_viewmatrix, need_projmatrix, need_campos, need_points_transform,
+          batch_first_block, sh_origin=None):
+        f = lambda *s: means3D.new_empty(s, dtype=torch.float32)
+        none = f(0)
+        B = len(batch_first_block) - 1 if len(batch_first_block) >= 3 else 1
+        lead = (B,) if B > 1 else ()
+        return [f(means3D.shape[0], 3) if need_means2D else none, f(*lead, 4, 4) if need_viewmatrix else none,
+                f(*lead, 4, 4) if need_projmatrix else none, f(*lead, 3) if need_campos else none,
+                f(*lead, 3, 4) if (need_points_transform and points_transform.numel() > 0) else none]
 
     @torch.library.register_fake("gsr::rasterize_backward_fused")
     def _(means3D, sh, sh_rest, opacities, scales, rotations, viewmatrix, projmatrix, campos, bg, points_transform, geom, image, binning,

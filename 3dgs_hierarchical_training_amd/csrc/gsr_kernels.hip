@@ -3604,7 +3604,14 @@ __device__ __forceinline__ void load_ggrad(const double* __restrict__ row, float
 
 // SHO (GsrBackwardArgs::sh_origin; not with PREP): the colour's direction is normalize(untransformed mean - sh_origin), so its share of
 // dL/dmean is added to d_means3D AFTER the R^T chain of points_transform and reaches neither d_points_transform nor d_campos.
-template <int DEG, bool RAW, bool CAM, bool ADAM, int PREP, bool SHO = false>
+//
+// FROZEN (the frozen call of include/gsr.h: no per-Gaussian gradient is wanted, only the camera's and the transform's; with CAM, without ADAM,
+// PREP or SHO): everything that feeds cg, xg and m2d runs in the same order of operations as in the full kernel -- a block's 47 partials are
+// the same bits -- and everything that only feeds a per-Gaussian gradient is left out: the chain rules of the raw opacity, scale and rotation,
+// the dSH rows and every per-Gaussian store but d_means2D (written when the pointer is set).  At DEG 0 the colour does not depend on the mean,
+// so no SH row is staged, sh_backward does not run and the barrier behind the staging goes with it; the host sends a call with sh_origin
+// (whose colour reaches d_means3D alone) or colors_precomp to that instantiation as well.
+template <int DEG, bool RAW, bool CAM, bool ADAM, int PREP, bool SHO = false, bool FROZEN = false>
 __global__ __launch_bounds__(kPreThreads) void k_preprocess_bwd(CamParams cp, int N, const float* means,
                                                                 const float* scales, const float* rots,
                                                                 const float* __restrict__ cov_pre, const float* shs,
@@ -3619,8 +3626,10 @@ __global__ __launch_bounds__(kPreThreads) void k_preprocess_bwd(CamParams cp, in
                                                                 const float* __restrict__ sh_origin = nullptr)
 {
     static_assert(!SHO || PREP < 0, "sh_origin is not served together with a next view");
+    static_assert(!FROZEN || (CAM && !ADAM && PREP < 0 && !SHO), "the frozen variant: camera gradients, no Adam, no next view, no sh_origin");
     constexpr int NC3 = 3 * (DEG + 1) * (DEG + 1);
-    __shared__ float s_sh[kPreThreads * kShStride];
+    constexpr bool kStageSh = !(FROZEN && DEG == 0);   // (FROZEN at degree 0 touches no SH row)
+    __shared__ float s_sh[kStageSh ? kPreThreads * kShStride : 1];
     __shared__ float s_cam[CAM ? (kPreThreads / 64) * kCamVals : 1];
     // PREP (with ADAM): the updated raw parameters of this thread's Gaussian, kept for the next-view tail
     float nmean[3] = {0.f, 0.f, 0.f}, nsc[3] = {0.f, 0.f, 0.f}, nrq[4] = {1.f, 0.f, 0.f, 0.f}, nop = 0.f;
@@ -3686,7 +3695,8 @@ __global__ __launch_bounds__(kPreThreads) void k_preprocess_bwd(CamParams cp, in
             e_op = opac_raw[i];
         }
     }
-    if (lin) {
+    if constexpr (!kStageSh) {
+    } else if (lin) {
         // every 16-byte piece of the block's rows is requested before the first one is waited for (round 5: the copy loop
         // `tile[v] = src[v]` has a run-time trip count, hipcc does not unroll it, and each of its twelve turns was a memory round trip
         // of its own -- a fifth of a wave's life in this kernel, tools/k9_timing.sh)
@@ -3773,6 +3783,7 @@ __global__ __launch_bounds__(kPreThreads) void k_preprocess_bwd(CamParams cp, in
             m2d[0] = o.mean2d[0]; m2d[1] = o.mean2d[1];
             dop = g1.y;
             grgb[0] = g1.z; grgb[1] = g1.w; grgb[2] = g2.x;
+            if constexpr (!FROZEN) {
             if (RAW) {   // chain through exp / normalize / sigmoid
                 const float sg = 1.0f / (1.0f + expf(-(ADAM ? e_op : opac_raw[i])));   // the activated opacity, as k_preprocess computes it
                 dop *= sg * (1.f - sg);
@@ -3788,14 +3799,19 @@ __global__ __launch_bounds__(kPreThreads) void k_preprocess_bwd(CamParams cp, in
             for (int k = 0; k < 4; k++) drq[k] = o.rot[k];
 #pragma unroll
             for (int k = 0; k < 6; k++) dcv[k] = o.cov[k];
+            }
             float dsho[3] = {0.f, 0.f, 0.f};   // SHO: the colour's share of dL/d(untransformed mean)
-            if (shs) {
+            if constexpr (!kStageSh) {
+            } else if (shs) {
                 if constexpr (SHO) {   // direction (raw mean - sh_origin)/|.|: the camera takes no part (cam is not read below)
 #pragma unroll
                     for (int k = 0; k < 3; k++) cam.cam[k] = sh_origin[k];
                     if (lin) sh_backward(cam, mraw, s_rest + tid * NRL - 3, 3, 1, grgb, s_rest + tid * NRL - 3, 3, 1, dsho, s_dc + tid * 3, s_dc + tid * 3);
                     else sh_backward(cam, mraw, &s_sh[tid * kShStride], 3, 1, grgb, &s_sh[tid * kShStride], 3, 1, dsho);
                 } else {
+                // (FROZEN: the dSH row is still written over the SH row in the tile, where nobody reads it -- twelve to 48 LDS words per live
+                //  Gaussian.  Leaving the writes out lets hipcc merge the two call sites, and the merged code contracts `dmean += t * inv_n`
+                //  into an fma where the full kernel, with its two call sites, multiplies and adds: dL/dcampos then differs in the last bit.)
                 if (lin) sh_backward(cam, mean, s_rest + tid * NRL - 3, 3, 1, grgb, s_rest + tid * NRL - 3, 3, 1, dmean, s_dc + tid * 3, s_dc + tid * 3);
                 else sh_backward(cam, mean, &s_sh[tid * kShStride], 3, 1, grgb, &s_sh[tid * kShStride], 3, 1, dmean);
                 if (CAM) {   // the view direction is (p - campos)/|.|: d/dcampos = -(its share of d/dp)
@@ -3811,14 +3827,17 @@ __global__ __launch_bounds__(kPreThreads) void k_preprocess_bwd(CamParams cp, in
                         xg[4 * r + 3] = dmean[r];
                     }
                 }
+                if constexpr (!FROZEN) {
                 const float d0 = dmean[0], d1 = dmean[1], d2 = dmean[2];
 #pragma unroll
                 for (int c = 0; c < 3; c++) dmean[c] = fmaf(cp.xf[c], d0, fmaf(cp.xf[4 + c], d1, cp.xf[8 + c] * d2));
+                }
             }
             if constexpr (SHO) {
 #pragma unroll
                 for (int k = 0; k < 3; k++) dmean[k] += dsho[k];
             }
+        } else if constexpr (FROZEN) {   // (no dSH row leaves the tile: nothing to clear)
         } else if (lin) {
             for (int e = 0; e < 3; e++) s_dc[tid * 3 + e] = 0.f;
             for (int e = 0; e < NRL; e++) s_rest[tid * NRL + e] = 0.f;
@@ -3826,6 +3845,9 @@ __global__ __launch_bounds__(kPreThreads) void k_preprocess_bwd(CamParams cp, in
             for (int e = 0; e < NC3; e++) s_sh[tid * kShStride + e] = 0.f;
         }
         K9_T(1);
+        if constexpr (FROZEN) {   // the only per-Gaussian row of a frozen call, and only when somebody wants it
+            if (d_means2d) { d_means2d[3 * (size_t)i] = m2d[0]; d_means2d[3 * (size_t)i + 1] = m2d[1]; d_means2d[3 * (size_t)i + 2] = 0.f; }
+        } else {
         d_means2d[3 * (size_t)i] = m2d[0]; d_means2d[3 * (size_t)i + 1] = m2d[1]; d_means2d[3 * (size_t)i + 2] = 0.f;
         if (ADAM) {   // (the statistics' words are requested with the small groups' moments and updated behind the streams)
             if (ds.radii) { e_rad = ds.radii[i]; e_ds[0] = ds.max_radii[i]; e_ds[1] = ds.grad_accum[i]; e_ds[2] = ds.denom[i]; }
@@ -3870,6 +3892,7 @@ __global__ __launch_bounds__(kPreThreads) void k_preprocess_bwd(CamParams cp, in
             for (int k = 0; k < 6; k++) d_cov[6 * (size_t)i + k] = dcv[k];
         }
         }
+        }
     }
     K9_T(2);
     if (CAM) {
@@ -3892,7 +3915,8 @@ __global__ __launch_bounds__(kPreThreads) void k_preprocess_bwd(CamParams cp, in
             cam_partial[(size_t)blockIdx.x * kCamVals + tid] = t;
         }
     }
-    if (ADAM) {
+    if constexpr (FROZEN) {   // (no gradient row leaves the tile)
+    } else if (ADAM) {
         lds_barrier();   // every thread's parameters are read, every gradient row is in LDS
         const size_t b = (size_t)base;
         const int rrow = cp.M * 3 - 3;
@@ -4293,7 +4317,7 @@ static int g_tile_map = 2;   // tile -> XCD map: 2 = 2x2 tile blocks interleaved
 static std::atomic<long long> g_spec_overflows{0}, g_spec_forwards{0}, g_exact_forwards{0}, g_depth_window_resorts{0};
 // host-side time accounting of the two entry points (gsr_get_counter): wall time inside the call, and the part of the forward
 // spent waiting for the instance count -- their difference is what the launching thread really works per call
-static std::atomic<long long> g_fwd_calls{0}, g_fwd_ns{0}, g_fwd_wait_ns{0}, g_bwd_calls{0}, g_bwd_ns{0};
+static std::atomic<long long> g_fwd_calls{0}, g_fwd_ns{0}, g_fwd_wait_ns{0}, g_bwd_calls{0}, g_bwd_ns{0}, g_frozen_bwd_calls{0};
 struct CallTimer {
     std::atomic<long long>&calls, &ns;
     std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
@@ -4440,7 +4464,7 @@ size_t gsr_prepared_bytes(int32_t N) { return prep_layout(N).bytes; }
 size_t gsr_prepared_radii_offset(int32_t N) { return prep_layout(N).radii; }
 int gsr_prepare_supported(int32_t M, int32_t D, int32_t raw_params) { return (raw_params && M == 16 && D >= 0 && D <= 3) ? 1 : 0; }
 const char* gsr_last_error(void) { return g_err; }
-int gsr_version(void) { return 114; }
+int gsr_version(void) { return 115; }
 size_t gsr_struct_bytes(int32_t which)
 {
     return which == 0 ? sizeof(GsrForwardArgs) : which == 1 ? sizeof(GsrBackwardArgs) : which == 2 ? sizeof(GsrForwardOut) : 0;
@@ -5169,6 +5193,23 @@ int gsr_backward(const GsrBackwardArgs* a, void* stream_)
     const int NB = bt.B;
     if (a->sh_origin && (!a->shs || NB > 1 || a->next_view))
         return fail(GSR_ERR_ARG, "sh_origin needs shs and is not served with a batch of B > 1 or a next_view%s");
+    // which gradients the caller wants (GsrBackwardArgs, "frozen call"): decided and checked here, in front of the first launch or memset
+    // of the call -- a refused call enqueues nothing
+    const bool want_cam = a->d_viewmatrix || a->d_projmatrix || a->d_campos || a->d_points_transform;
+    const bool want_other_pg = a->d_opacities || a->d_colors_precomp || a->d_shs || a->d_shs_rest || a->d_scales || a->d_rotations || a->d_cov3D_precomp;
+    const bool frozen = !a->fused_adam && !a->d_means3D && !want_other_pg && want_cam;
+    if (!a->fused_adam && !a->d_means3D && a->N > 0) {   // (N = 0: there is no gradient row to point at, the camera outputs are cleared below)
+        if (want_other_pg)
+            return fail(GSR_ERR_ARG, "d_means3D is NULL but another per-Gaussian gradient pointer is set: they come together, or none of them (frozen call)%s");
+        if (!want_cam)
+            return fail(GSR_ERR_ARG, "no gradient output: every per-Gaussian gradient pointer is NULL and so are d_viewmatrix, d_projmatrix, d_campos and "
+                                     "d_points_transform%s");
+        if (a->next_view || a->prepared_out)
+            return fail(GSR_ERR_ARG, "a frozen call (no per-Gaussian gradient pointer) cannot prepare a next view: next_view / prepared_out need fused_adam%s");
+        if (a->densify_stats)
+            return fail(GSR_ERR_ARG, "a frozen call (no per-Gaussian gradient pointer) cannot accumulate densify_stats: they are fed by the per-Gaussian "
+                                     "gradients it leaves out%s");
+    }
     {   // early R: a forward's count is held against its scan's own report as soon as that has arrived (no waiting here)
         int dev_id = 0;
         (void)hipGetDevice(&dev_id);
@@ -5202,7 +5243,7 @@ int gsr_backward(const GsrBackwardArgs* a, void* stream_)
         if (a->d_points_transform) GSR_HIP(hipMemsetAsync(a->d_points_transform, 0, 48 * NB, st));
         return GSR_OK;
     }
-    if (!a->geom || !a->image || !a->binning || !a->scratch || !a->d_means2D)
+    if (!a->geom || !a->image || !a->binning || !a->scratch || (!a->d_means2D && !frozen))   // (d_means2D is optional in a frozen call)
         return fail(GSR_ERR_ARG, "missing workspace / gradient pointer%s");
     const int tiles_x = (W + kTile - 1) / kTile, tiles_y = (H + kTile - 1) / kTile, T = tiles_x * tiles_y * NB;
     const Splat* splat = static_cast<const Splat*>(a->geom);
@@ -5294,7 +5335,6 @@ int gsr_backward(const GsrBackwardArgs* a, void* stream_)
     }
     CamParams cp = {a->viewmatrix, a->projmatrix, a->campos, a->tanfovx, a->tanfovy, a->scale_modifier, W, H, a->D, a->M, a->points_transform, bt};
     const int grid = (N + kPreThreads - 1) / kPreThreads;
-    const bool want_cam = a->d_viewmatrix || a->d_projmatrix || a->d_campos || a->d_points_transform;
     float* cam_partial = reinterpret_cast<float*>(static_cast<uint8_t*>(a->scratch) + align256((size_t)N * kGG * sizeof(double)));
     AdamDev ad = {};
     const GsrFusedAdam* fa = a->fused_adam;
@@ -5328,7 +5368,7 @@ int gsr_backward(const GsrBackwardArgs* a, void* stream_)
             }
         }
         ad.b1 = fa->beta1; ad.b2 = fa->beta2; ad.eps = fa->eps;
-    } else if (!a->d_means3D || !a->d_opacities)
+    } else if (!frozen && (!a->d_means3D || !a->d_opacities))
         return fail(GSR_ERR_ARG, "missing workspace / gradient pointer%s");
     DensDev ds = {};
     if (a->densify_stats) {
@@ -5366,8 +5406,9 @@ int gsr_backward(const GsrBackwardArgs* a, void* stream_)
             po.dh.clear_threads = (uint32_t)tail_blocks * kPreThreads;
         }
     }
-#define GSR_PREB_S(DEG, RAW, CAM, ADAM, PREP, SHO)                                                                                          \
-    hipLaunchKernelGGL((k_preprocess_bwd<DEG, RAW, CAM, ADAM, PREP, SHO>), dim3(grid), dim3(kPreThreads), 0, st, cp, N, a->means3D,         \
+#define GSR_PREB_S(DEG, RAW, CAM, ADAM, PREP, SHO) GSR_PREB_SF(DEG, RAW, CAM, ADAM, PREP, SHO, false)
+#define GSR_PREB_SF(DEG, RAW, CAM, ADAM, PREP, SHO, FROZEN)                                                                                 \
+    hipLaunchKernelGGL((k_preprocess_bwd<DEG, RAW, CAM, ADAM, PREP, SHO, FROZEN>), dim3(grid), dim3(kPreThreads), 0, st, cp, N, a->means3D, \
                        a->scales, a->rotations, a->cov3D_precomp, a->shs, a->shs_rest, a->opacities, ad, splat, gg, a->d_means3D,           \
                        a->d_means2D, a->d_opacities, a->d_colors_precomp, a->d_shs, a->d_shs_rest, a->d_scales, a->d_rotations,             \
                        a->d_cov3D_precomp, cam_partial, po, ds, a->sh_origin)
@@ -5379,6 +5420,7 @@ int gsr_backward(const GsrBackwardArgs* a, void* stream_)
         else { if (want_cam) GSR_PREB_S(DEG, false, true, false, -1, SHO); else GSR_PREB_S(DEG, false, false, false, -1, SHO); }           \
     } while (0)
 #define GSR_PREB(DEG) GSR_PREB_SO(DEG, false)
+#define GSR_PREB_FROZEN(DEG) do { if (a->raw_params) GSR_PREB_SF(DEG, true, true, false, -1, false, true); else GSR_PREB_SF(DEG, false, true, false, -1, false, true); } while (0)
 #define GSR_PREB_NEXT(DEG, NDEG) do { if (want_cam) GSR_PREB_(DEG, true, true, true, NDEG); else GSR_PREB_(DEG, true, false, true, NDEG); } while (0)
 #define GSR_PRE_TAIL(NDEG)                                                                                                               \
     hipLaunchKernelGGL((k_preprocess<NDEG, true>), dim3(1), dim3(kPreThreads), 0, st, po.cp, N, a->means3D, a->scales, a->rotations,       \
@@ -5408,6 +5450,16 @@ int gsr_backward(const GsrBackwardArgs* a, void* stream_)
                     default: GSR_PRE_TAIL(3); break;
                 }
             }
+        } else if (frozen) {
+            // the colour's share of dL/dmean reaches the camera and the transform only where the colour depends on the POSED mean: not at
+            // degree 0, not with colors_precomp and not with sh_origin (whose share goes to d_means3D alone) -- those run the degree-0 variant
+            g_frozen_bwd_calls.fetch_add(1, std::memory_order_relaxed);   // (gsr_get_counter "frozen_backward_calls": which route a caller took)
+            switch ((a->shs && !a->sh_origin) ? a->D : 0) {
+                case 0: GSR_PREB_FROZEN(0); break;
+                case 1: GSR_PREB_FROZEN(1); break;
+                case 2: GSR_PREB_FROZEN(2); break;
+                default: GSR_PREB_FROZEN(3); break;
+            }
         } else if (a->sh_origin) {   // (degree 0: the default kernel -- the colour does not depend on the direction)
         switch (a->D) {
             case 0: GSR_PREB(0); break;
@@ -5426,9 +5478,11 @@ int gsr_backward(const GsrBackwardArgs* a, void* stream_)
     }
 #undef GSR_PRE_TAIL
 #undef GSR_PREB_NEXT
+#undef GSR_PREB_FROZEN
 #undef GSR_PREB
 #undef GSR_PREB_SO
 #undef GSR_PREB_
+#undef GSR_PREB_SF
 #undef GSR_PREB_S
     if (want_cam)
         hipLaunchKernelGGL(k_cam_reduce, dim3(kCamVals, NB), dim3(256), 0, st, cam_partial, grid, a->d_viewmatrix, a->d_projmatrix, a->d_campos,
@@ -5564,6 +5618,7 @@ int64_t gsr_get_counter(const char* name)
     if (!strcmp(name, "forward_wait_ns")) return g_fwd_wait_ns.load();
     if (!strcmp(name, "backward_calls")) return g_bwd_calls.load();
     if (!strcmp(name, "backward_ns")) return g_bwd_ns.load();
+    if (!strcmp(name, "frozen_backward_calls")) return g_frozen_bwd_calls.load();
     if (!strcmp(name, "spec_callers")) { std::lock_guard<std::mutex> lk(g_state_mutex); return (int64_t)g_hints.size(); }
     return -1;
 }

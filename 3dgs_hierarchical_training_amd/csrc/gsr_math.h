@@ -586,6 +586,8 @@ struct GaussGrads {
 // accumulates dL/d(mean) through the colour and writes dL/dsh (coefficient k, channel ch at
 // dsh[k*dk + ch*dc]).  Coefficients >= (deg+1)^2 are written as zero up to M.
 // `sh0` / `dsh0` (optional): where coefficient 0 lives when it is stored apart from the rest (channel ch at sh0[ch*sc], dsh0[ch*dc]).
+// WRITE_DSH = false: dL/dsh is not written at all (dsh / dsh0 are not touched) -- the frozen-model backward wants dmean alone.
+template <bool WRITE_DSH = true>
 GSR_HD void sh_backward(const Camera& c, const float mean[3], const float* sh, int sk, int sc, const float g_rgb_in[3],
                         float* dsh, int dk, int dc, float dmean[3], const float* sh0 = nullptr, float* dsh0 = nullptr)
 {
@@ -631,11 +633,13 @@ GSR_HD void sh_backward(const Camera& c, const float mean[3], const float* sh, i
         if (k < nc) {
             for (int ch = 0; ch < 3; ch++) {
                 const float s = (k == 0 && sh0) ? sh0[ch * sc] : sh[k * sk + ch * sc];
-                if (k == 0 && dsh0) dsh0[ch * dc] = basis[k] * gr[ch];
-                else dsh[k * dk + ch * dc] = basis[k] * gr[ch];
+                if constexpr (WRITE_DSH) {
+                    if (k == 0 && dsh0) dsh0[ch * dc] = basis[k] * gr[ch];
+                    else dsh[k * dk + ch * dc] = basis[k] * gr[ch];
+                }
                 gdx += bx[k] * s * gr[ch]; gdy += by[k] * s * gr[ch]; gdz += bz[k] * s * gr[ch];
             }
-        } else if (k < c.M) {
+        } else if (WRITE_DSH && k < c.M) {
             for (int ch = 0; ch < 3; ch++) dsh[k * dk + ch * dc] = 0.f;
         }
     }

@@ -9,6 +9,7 @@
 //   gsr::rasterize            autograd-enabled entry (C++ torch::autograd::Function): what GaussianRasterizer.forward calls
 //   gsr::rasterize_forward    -> gsr_forward   (buffers come from at::empty inside the allocator callback: no Python)
 //   gsr::rasterize_backward   -> gsr_backward
+//   gsr::rasterize_backward_frozen -> gsr_backward, the frozen call: camera / points_transform gradients alone
 //   gsr::rasterize_backward_fused  -> gsr_backward with the in-kernel Adam step (parameters / moments updated in place)
 //   gsr::mark_visible         -> gsr_mark_visible
 //   gsr::importance_accumulate -> gsr_forward + gsr_importance_accumulate (merge-time colour importance, no backward)
@@ -325,6 +326,43 @@ std::vector<Tensor> rasterize_backward(
     return {d_means3D, d_means2D, d_sh, d_col, d_opac, d_scales, d_rot, d_cov, d_rest, d_vm, d_pm, d_cp, d_xf};
 }
 
+// The frozen call of gsr_backward (include/gsr.h, GsrBackwardArgs): the gradients of the camera and of points_transform alone -- no
+// per-Gaussian gradient tensor is allocated, d_means2D only when somebody wants it.  Returns {d_means2D or undefined, d_vm, d_pm, d_campos, d_xf}.
+std::vector<Tensor> rasterize_backward_frozen(
+    const Tensor& means3D, const Tensor& sh, const Tensor& colors, const Tensor& opac, const Tensor& scales, const Tensor& rots,
+    const Tensor& cov, const Tensor& rest, const Tensor& vm, const Tensor& pm, const Tensor& campos, const Tensor& bg, const Tensor& xf,
+    const Tensor& geom, const Tensor& image, const Tensor& binning, const Tensor& meta, const Tensor& grad_color, const Tensor& grad_depth,
+    const Tensor& grad_alpha, int64_t H, int64_t W, double tanfovx, double tanfovy, double scale_modifier, int64_t sh_degree,
+    bool raw_params, bool need_means2D, bool need_vm, bool need_pm, bool need_campos, bool need_xf, at::IntArrayRef batch_first_block,
+    const c10::optional<Tensor>& sh_origin_)
+{
+    const c10::hip::HIPGuardMasqueradingAsCUDA guard(means3D.device());
+    const BatchArg batch(batch_first_block);
+    const int64_t NB = batch.B();
+    BwdCommon b{means3D, sh, colors, opac, scales, rots, cov, rest, vm, pm, campos, bg, xf, f32c(grad_color), f32c(grad_depth), f32c(grad_alpha)};
+    const int64_t N = means3D.size(0);
+    const auto fo = means3D.options().dtype(at::kFloat);
+    Tensor none;
+    Tensor d_means2D = need_means2D ? at::empty({N, 3}, fo) : none;
+    auto cam_shape = [&](std::vector<int64_t> sh) { if (NB > 1) sh.insert(sh.begin(), NB); return sh; };
+    Tensor d_vm = need_vm ? at::empty(cam_shape({4, 4}), fo) : none, d_pm = need_pm ? at::empty(cam_shape({4, 4}), fo) : none;
+    Tensor d_cp = need_campos ? at::empty(cam_shape({3}), fo) : none;
+    Tensor d_xf = (need_xf && has(xf)) ? at::zeros(cam_shape({3, 4}), fo) : none;
+    TORCH_CHECK(d_vm.defined() || d_pm.defined() || d_cp.defined() || d_xf.defined(),
+                "rasterize_backward_frozen: no camera or points_transform gradient is wanted -- nothing to compute");
+    Tensor scratch = at::empty({(int64_t)gsr_backward_scratch_bytes((int32_t)N)}, means3D.options().dtype(at::kByte));
+    GsrBackwardArgs a{};
+    fill_backward_args(a, b, geom, image, binning, meta, H, W, tanfovx, tanfovy, scale_modifier, sh_degree, raw_params);
+    a.batch = batch.ptr();
+    const Tensor sh_origin = sh_origin_arg(sh_origin_);
+    a.sh_origin = fp(sh_origin);
+    a.d_means2D = fpm(d_means2D);
+    a.d_viewmatrix = fpm(d_vm); a.d_projmatrix = fpm(d_pm); a.d_campos = fpm(d_cp); a.d_points_transform = fpm(d_xf);
+    a.scratch = scratch.data_ptr();
+    check(gsr_backward(&a, c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream()), "gsr_backward");
+    return {d_means2D, d_vm, d_pm, d_cp, d_xf};
+}
+
 // Optimizer-in-backward (GsrFusedAdam): parameters (xyz, f_dc, f_rest, opacity, scaling, rotation) and their moments are
 // updated in place; returns {d_means2D, d_vm, d_pm, d_campos, d_xf}.
 std::vector<Tensor> rasterize_backward_fused(
@@ -421,6 +459,7 @@ struct Cfg {
     int64_t view_id = 0;                           // GsrForwardArgs::view_id
     int64_t extras = 0;                            // bit 0: clamped colour output, bit 1: visibility bytes
     Tensor sh_origin;                              // GsrForwardArgs::sh_origin (detached, not an autograd input), or undefined
+    int64_t frozen = -1;                           // the frozen backward (rasterize_backward_frozen): -1 = when no parameter wants a gradient, 0 = never, 1 = always
     double next_tanfovx = 0, next_tanfovy = 0;
 };
 
@@ -469,6 +508,7 @@ class RasterizeFn : public torch::autograd::Function<RasterizeFn> {
         ctx->saved_data["done"] = false;
         ctx->saved_data["prep_out"] = prep_out;
         ctx->saved_data["sh_origin"] = cfg.sh_origin.defined() ? cfg.sh_origin : x.new_empty({0});
+        ctx->saved_data["frozen"] = cfg.frozen;
         ctx->saved_data["next_cam"] = std::vector<Tensor>{has(cfg.next_vm) ? f32c(cfg.next_vm) : x, has(cfg.next_vm) ? f32c(cfg.next_pm) : x,
                                                           has(cfg.next_vm) ? f32c(cfg.next_campos) : x,
                                                           has(cfg.next_xf) ? f32c(cfg.next_xf) : x.new_empty({0})};
@@ -508,6 +548,15 @@ class RasterizeFn : public torch::autograd::Function<RasterizeFn> {
         const Tensor radii = ctx->saved_data["radii"].toTensor();
         const Tensor sho_t = ctx->saved_data["sh_origin"].toTensor();
         const c10::optional<Tensor> sho = has(sho_t) ? c10::optional<Tensor>(sho_t) : c10::nullopt;
+        // the frozen backward: nobody reads a per-Gaussian gradient (inputs means3D, sh, colors, opacities, scales, rotations, cov3D, sh_rest)
+        // and the camera or the transform wants one -- the pose phases of the reference, whose model does not move
+        const int64_t frozen = ctx->saved_data["frozen"].toInt();
+        const bool cam_wanted = need_vm || need_pm || need_cp || (need_xf && has(sv[12]));
+        bool param_wanted = false;
+        for (int q : {0, 2, 3, 4, 5, 6, 7, 8}) param_wanted = param_wanted || ctx->needs_input_grad(q);
+        TORCH_CHECK(frozen != 1 || (!n_adam && dens.empty() && cam_wanted),
+                    "frozen=True: not with fused_adam or densify_stats, and the camera or points_transform must require grad");
+        const bool take_frozen = frozen == 1 || (frozen < 0 && !n_adam && dens.empty() && !param_wanted && cam_wanted);
         if (n_adam) {
             // a second backward through the same forward would apply the optimizer step twice
             TORCH_CHECK(!ctx->saved_data["done"].toBool(), "fused_adam: backward() ran twice on the same render (retain_graph); the in-kernel "
@@ -528,6 +577,12 @@ class RasterizeFn : public torch::autograd::Function<RasterizeFn> {
                              ctx->saved_data["next_W"].toInt(), ctx->saved_data["next_tfx"].toDouble(), ctx->saved_data["next_tfy"].toDouble(),
                              ctx->saved_data["prep_out"].toTensor(), nc[3], ctx->saved_data["next_D"].toInt(), dens, radii, bfb, sho);
             commit_p[0] += 1;   // the update has been enqueued: the optimizer's step count advances (FusedAdam reconciles from this)
+            out[1] = r[0]; out[9] = r[1]; out[10] = r[2]; out[11] = r[3]; d_xf = r[4];
+        } else if (take_frozen) {
+            static auto op = c10::Dispatcher::singleton().findSchemaOrThrow("gsr::rasterize_backward_frozen", "").typed<decltype(rasterize_backward_frozen)>();
+            auto r = op.call(sv[0], sv[1], sv[2], sv[3], sv[4], sv[5], sv[6], sv[7], sv[8], sv[9], sv[10], sv[11], sv[12], sv[13], sv[14],
+                             sv[15], sv[16], orE(gc), orE(gd), orE(ga), H, W, tfx, tfy, smod, D, raw, ctx->needs_input_grad(1), need_vm, need_pm, need_cp,
+                             need_xf, bfb, sho);
             out[1] = r[0]; out[9] = r[1]; out[10] = r[2]; out[11] = r[3]; d_xf = r[4];
         } else {
             static auto op = c10::Dispatcher::singleton().findSchemaOrThrow("gsr::rasterize_backward", "").typed<decltype(rasterize_backward)>();
@@ -550,7 +605,7 @@ std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> rasterize(
     double beta2, double eps, int64_t step, const Tensor& prepared, const Tensor& next_vm, const Tensor& next_pm, const Tensor& next_campos,
     int64_t next_H, int64_t next_W, double next_tanfovx, double next_tanfovy, const Tensor& next_xf, int64_t next_sh_degree,
     const Tensor& adam_commit, at::TensorList densify_stats, at::IntArrayRef batch_first_block, int64_t view_id, int64_t extras,
-    const c10::optional<Tensor>& sh_origin)
+    const c10::optional<Tensor>& sh_origin, int64_t frozen)
 {
     Cfg cfg{H, W, sh_degree, step, tanfovx, tanfovy, scale_modifier, beta1, beta2, eps, raw_params, prefiltered, debug, cam_grad,
             std::vector<double>(adam_lr.begin(), adam_lr.end()), adam_m.vec(), adam_v.vec()};
@@ -559,6 +614,7 @@ std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> rasterize(
     cfg.batch.assign(batch_first_block.begin(), batch_first_block.end());
     cfg.view_id = view_id;
     cfg.extras = extras;
+    cfg.frozen = frozen;
     if (sh_origin.has_value() && sh_origin->defined()) cfg.sh_origin = sh_origin->detach();
     if (!adam_m.empty()) {
         TORCH_CHECK(has(adam_commit) && adam_commit.is_cpu() && adam_commit.scalar_type() == at::kLong, "fused_adam: adam_commit must be a CPU int64 tensor");
@@ -584,8 +640,9 @@ std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> rasterize_for
     double beta2, double eps, int64_t step, const Tensor& prepared, const Tensor& next_vm, const Tensor& next_pm, const Tensor& next_campos,
     int64_t next_H, int64_t next_W, double next_tanfovx, double next_tanfovy, const Tensor& next_xf, int64_t next_sh_degree,
     const Tensor& adam_commit, at::TensorList densify_stats, at::IntArrayRef batch_first_block, int64_t view_id, int64_t extras,
-    const c10::optional<Tensor>& sh_origin)
+    const c10::optional<Tensor>& sh_origin, int64_t frozen)
 {
+    (void)frozen;
     (void)means2D; (void)next_xf; (void)next_sh_degree; (void)adam_commit; (void)densify_stats; (void)cam_grad; (void)adam_m; (void)adam_v; (void)adam_lr; (void)beta1; (void)beta2; (void)eps; (void)step;
     (void)next_vm; (void)next_pm; (void)next_campos; (void)next_H; (void)next_W; (void)next_tanfovx; (void)next_tanfovy;
     auto out = rasterize_forward(means3D, sh, colors, opac, scales, rots, cov, rest, vm, pm, campos, bg, (has(xf) && xf.dim() == 2) ? xf.slice(0, 0, 3) : xf, H, W,
@@ -1086,6 +1143,12 @@ TORCH_LIBRARY(gsr, m)
           "int image_height, int image_width, float tanfovx, float tanfovy, float scale_modifier, int sh_degree, bool raw_params, "
           "bool need_viewmatrix, bool need_projmatrix, bool need_campos, bool need_points_transform, Tensor(a!)[] densify_stats, Tensor radii, int[] batch_first_block, "
           "Tensor? sh_origin=None) -> Tensor[]");
+    m.def("rasterize_backward_frozen(Tensor means3D, Tensor sh, Tensor colors_precomp, Tensor opacities, Tensor scales, Tensor rotations, "
+          "Tensor cov3D_precomp, Tensor sh_rest, Tensor viewmatrix, Tensor projmatrix, Tensor campos, Tensor bg, Tensor points_transform, "
+          "Tensor geom, Tensor image, Tensor binning, Tensor meta, Tensor grad_color, Tensor grad_depth, Tensor grad_alpha, "
+          "int image_height, int image_width, float tanfovx, float tanfovy, float scale_modifier, int sh_degree, bool raw_params, "
+          "bool need_means2D, bool need_viewmatrix, bool need_projmatrix, bool need_campos, bool need_points_transform, int[] batch_first_block, "
+          "Tensor? sh_origin=None) -> Tensor[]");
     m.def("rasterize_backward_fused(Tensor(a!) means3D, Tensor(b!) sh, Tensor(c!) sh_rest, Tensor(d!) opacities, Tensor(e!) scales, "
           "Tensor(f!) rotations, Tensor viewmatrix, Tensor projmatrix, Tensor campos, Tensor bg, Tensor points_transform, Tensor geom, "
           "Tensor image, Tensor binning, Tensor meta, Tensor grad_color, Tensor grad_depth, Tensor grad_alpha, int image_height, "
@@ -1100,7 +1163,7 @@ TORCH_LIBRARY(gsr, m)
           "bool prefiltered, bool debug, bool cam_grad, Tensor[] adam_m, Tensor[] adam_v, float[] adam_lr, float beta1, float beta2, "
           "float eps, int step, Tensor prepared, Tensor next_viewmatrix, Tensor next_projmatrix, Tensor next_campos, int next_height, "
           "int next_width, float next_tanfovx, float next_tanfovy, Tensor next_points_transform, int next_sh_degree, Tensor adam_commit, Tensor[] densify_stats, int[] batch_first_block, int view_id=0, int extras=0, "
-          "Tensor? sh_origin=None) -> "
+          "Tensor? sh_origin=None, int frozen=-1) -> "
           "(Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)");
     m.def("importance_accumulate(Tensor(a!) acc, Tensor means3D, Tensor sh, Tensor colors_precomp, Tensor opacities, Tensor scales, "
           "Tensor rotations, Tensor cov3D_precomp, Tensor sh_rest, Tensor viewmatrix, Tensor projmatrix, Tensor campos, Tensor bg, "
@@ -1142,6 +1205,7 @@ TORCH_LIBRARY_IMPL(gsr, CUDA, m)   // the dispatch key of HIP tensors on a ROCm 
     m.impl("rasterize_forward", &rasterize_forward);
     m.impl("rasterize_backward", &rasterize_backward);
     m.impl("rasterize_backward_fused", &rasterize_backward_fused);
+    m.impl("rasterize_backward_frozen", &rasterize_backward_frozen);
     m.impl("importance_accumulate", &importance_accumulate);
     m.impl("importance_pass", &importance_pass);
     m.impl("mark_visible", &mark_visible);

@@ -107,6 +107,52 @@ def _empty_to_none(t: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
     return None if (t is None or t.numel() == 0) else t
 
 
+# frozen=None: take the frozen backward whenever frozen_backward_route() says nobody reads a per-Gaussian gradient -- when this is True.
+# OFF by measurement (profiles/frozen_backward.txt, a pose iteration, frozen against full on one box): 0.714 against 0.739 ms at 1 M /
+# degree 3 and 2.135 against 2.176 ms for 8 x 130 k, but 0.439 against 0.443 ms at 130 k / degree 0, inside that size's same-arm spread of
+# 0.005 ms -- not faster at every size, so the keyword stays and the inference waits.  frozen=True takes the route (and its memory saving:
+# 62 against 310 bytes per Gaussian of backward allocations at 1 M) explicitly.
+FROZEN_BY_INFERENCE = False
+
+
+def frozen_backward_route(param_grad, means2D_grad, camera_grad, transform_grad, fused_adam=False, densify_stats=False, frozen=None) -> bool:
+    """Whether a backward takes the frozen call of gsr_backward (include/gsr.h, GsrBackwardArgs): the gradients of the camera and of
+    points_transform alone, no per-Gaussian gradient computed, allocated or stored.
+
+    param_grad      some of means3D, sh, colors_precomp, opacities, scales, rotations, cov3D_precomp, sh_rest needs a gradient
+    means2D_grad    means2D needs one (it does not change the route: the frozen call writes d_means2D when asked to)
+    camera_grad     some of viewmatrix, projmatrix, campos needs one
+    transform_grad  points_transform is given and needs one
+    frozen          None = by inference: no fused Adam, no densify_stats, no parameter wants a gradient and the camera or the transform does
+                    (the reference's pose phases after fix_position(): stage A's train_relative_pose, train_pose_only);
+                    False = never; True = always -- a parameter that requires grad then keeps .grad = None -- and a RuntimeError with
+                    fused_adam or densify_stats, or when neither the camera nor the transform wants a gradient."""
+    del means2D_grad
+    wanted = bool(camera_grad or transform_grad)
+    if frozen:
+        if fused_adam or densify_stats:
+            raise RuntimeError("frozen=True is not served together with fused_adam, prepare_next or densify_stats")
+        if not wanted:
+            raise RuntimeError("frozen=True: the camera or points_transform must require grad (a frozen backward computes nothing else)")
+        return True
+    if frozen is not None or not FROZEN_BY_INFERENCE:
+        return False
+    return wanted and not (param_grad or fused_adam or densify_stats)
+
+
+def _check_frozen(frozen, fused_adam=None, prepare_next=None, densify_stats=None):
+    """frozen=True with an argument that needs the per-Gaussian backward: refused before anything touches a device."""
+    if frozen and (fused_adam is not None or prepare_next is not None or densify_stats is not None):
+        raise RuntimeError("frozen=True is not served together with fused_adam, prepare_next or densify_stats")
+
+
+def _frozen_code(frozen) -> int:
+    """The `frozen` argument of torch.ops.gsr.rasterize: -1 by inference, 0 never, 1 always."""
+    if frozen is None:
+        return -1 if FROZEN_BY_INFERENCE else 0
+    return 1 if frozen else 0
+
+
 class _Workspace:
     """Allocator handed to gsr_forward: R-sized buffers come from torch's caching allocator."""
 
@@ -205,7 +251,7 @@ class _RasterizeGaussians(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings,
                 sh_rest=None, raw_params=False, viewmatrix=None, projmatrix=None, campos=None, fused_adam=None,
-                points_transform=None, view_id=0):
+                points_transform=None, view_id=0, frozen=None):
         # viewmatrix / projmatrix / campos are ALSO passed as explicit tensor inputs (same objects as in
         # raster_settings) so that autograd can return their gradients: a NamedTuple cannot carry grads.
         rs = raster_settings
@@ -223,6 +269,7 @@ class _RasterizeGaussians(torch.autograd.Function):
         ctx.has = (sh is not None, colors_precomp is not None, scales is not None, cov3Ds_precomp is not None)
         ctx.raw = (sh_rest is not None, bool(raw_params))
         ctx.fused_adam = fused_adam
+        ctx.frozen = frozen
         ctx.xf_shape = tuple(points_transform.shape) if points_transform is not None else None
         z = means3D.new_empty(0)
         # NOTE: depth is deliberately NOT saved -- the caller mutates it in place (ht3dgs_trainer.py:1290-1292).
@@ -246,7 +293,7 @@ class _RasterizeGaussians(torch.autograd.Function):
         dev = means3D.device
         grad_color, grad_depth, grad_alpha = _f32c(grad_color), _f32c(grad_depth), _f32c(grad_alpha)
         if grad_color is None and grad_depth is None and grad_alpha is None:
-            return (None,) * 17
+            return (None,) * 18
         need_vm, need_pm, need_cp = ctx.needs_input_grad[11], ctx.needs_input_grad[12], ctx.needs_input_grad[13]
         d_vm = torch.empty((4, 4), dtype=torch.float32, device=dev) if need_vm else None
         d_pm = torch.empty((4, 4), dtype=torch.float32, device=dev) if need_pm else None
@@ -255,10 +302,16 @@ class _RasterizeGaussians(torch.autograd.Function):
         d_xf = torch.zeros(ctx.xf_shape, dtype=torch.float32, device=dev) if (has_xf and ctx.needs_input_grad[15]) else None
 
         fused = ctx.fused_adam
-        d_means2D = torch.empty((N, 3), dtype=torch.float32, device=dev)
+        nig = ctx.needs_input_grad
+        take_frozen = frozen_backward_route(any(nig[q] for q in (0, 2, 3, 4, 5, 6, 7, 9)), nig[1], need_vm or need_pm or need_cp,
+                                            d_xf is not None, fused is not None, False, ctx.frozen)
+        # (the frozen call: d_means2D only when somebody wants it, none of the other per-Gaussian tensors)
+        d_means2D = torch.empty((N, 3), dtype=torch.float32, device=dev) if (nig[1] or not take_frozen) else None
         d_means3D = d_opac = d_sh = d_sh_rest = d_col = d_scales = d_rot = d_cov = None
         fa = None
-        if fused is not None:
+        if take_frozen:
+            pass
+        elif fused is not None:
             # optimizer-in-backward: the kernel applies the Adam step to the raw parameters in place; their gradients
             # are never materialised (the corresponding .grad stay None and optimizer.step() has nothing left to do)
             if not (raw_params and has_rest and has_sh and has_scale):
@@ -304,7 +357,7 @@ class _RasterizeGaussians(torch.autograd.Function):
             L.check(lib.gsr_backward(C.byref(a), C.c_void_p(stream)), "gsr_backward")
         if fused is not None:
             fused.fused_backward_applied()      # the update is enqueued: the optimizer's step count advances now, not at render time
-        return (d_means3D, d_means2D, d_sh, d_col, d_opac, d_scales, d_rot, d_cov, None, d_sh_rest, None, d_vm, d_pm, d_cp, None, d_xf, None)
+        return (d_means3D, d_means2D, d_sh, d_col, d_opac, d_scales, d_rot, d_cov, None, d_sh_rest, None, d_vm, d_pm, d_cp, None, d_xf, None, None)
 
 
 def _cam_inputs(rs):
@@ -333,9 +386,10 @@ def _ecpu():
 
 def _rasterize_ext(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, rs, sh_rest, raw_params,
                    fused_adam, points_transform, prepared=None, prepare_next=None, next_points_transform=None, densify_stats=None,
-                   batch_first_block=None, fused_adam_deferred=False, view_id=0, extras=0, sh_origin=None):
+                   batch_first_block=None, fused_adam_deferred=False, view_id=0, extras=0, sh_origin=None, frozen=None):
     """torch.ops.gsr.rasterize: empty tensors stand for None; the camera tensors of the settings tuple are ordinary inputs
     (their gradients are produced when one of them requires grad)."""
+    _check_frozen(frozen, fused_adam, prepare_next, densify_stats)
     ops = E.load()
     dev = means3D.device
     if dev.type != "cuda":
@@ -399,7 +453,7 @@ def _rasterize_ext(means3D, means2D, sh, colors_precomp, opacities, scales, rota
             e if (nx is None or next_points_transform is None) else next_points_transform.to(dev),
             -1 if nx is None else int(nx.sh_degree), _ecpu() if commit is None else commit,
             [] if densify_stats is None else list(densify_stats), [] if nb <= 1 else [int(x) for x in batch_first_block], int(view_id), int(extras),
-            sh_origin)
+            sh_origin, _frozen_code(frozen))
     if not rs.debug:
         out = ops.rasterize(*args)
         if extras:       # (color, radii, depth, alpha, clamped colour, visibility bytes)
@@ -419,18 +473,19 @@ def _rasterize_ext(means3D, means2D, sh, colors_precomp, opacities, scales, rota
 
 
 def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings,
-                        points_transform=None, view_id=0):
+                        points_transform=None, view_id=0, frozen: Optional[bool] = None):
+    """frozen: which backward runs -- see frozen_backward_route (None = by inference, False = the full one, True = the frozen one)."""
     if not E.use_ctypes():
         return _rasterize_ext(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings,
-                              None, False, None, points_transform, view_id=view_id)
+                              None, False, None, points_transform, view_id=view_id, frozen=frozen)
     return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                                     raster_settings, None, False, *_cam_inputs(raster_settings), None, points_transform, view_id)
+                                     raster_settings, None, False, *_cam_inputs(raster_settings), None, points_transform, view_id, frozen)
 
 
 def rasterize_gaussians_raw(means3D, means2D, features_dc, features_rest, opacity_logit, log_scales, rotations_raw,
                             raster_settings, fused_adam=None, points_transform=None, prepared=None, prepare_next=None,
                             next_points_transform=None, densify_stats=None, batch_first_block=None, fused_adam_deferred=False,
-                            view_id=0, extras=0, sh_origin=None):
+                            view_id=0, extras=0, sh_origin=None, frozen: Optional[bool] = None):
     """Extension ("next" row f-2): rasterize straight from HTGaussianModel's raw parameters (_xyz, _features_dc,
     _features_rest, _opacity, _scaling, _rotation; /root/reference/scene/gaussian_model_ht.py:74-82) with the
     activations of :49-65,128-133,176-188 fused into the HIP kernels; gradients are w.r.t. the raw tensors.
@@ -479,18 +534,26 @@ def rasterize_gaussians_raw(means3D, means2D, features_dc, features_rest, opacit
     means instead of normalize(posed mean - campos) -- the reference's `convert_SHs_python` render with `view_dependent`, whose origin
     is the camera centre in the model's own frame, `get_RT(uid).inverse()[:3, 3].detach()` (gaussian_model_ht.py:845-865).  The
     colour then sends no gradient to the pose or the camera; its direction gradient reaches means3D directly (include/gsr.h
-    GsrForwardArgs::sh_origin).  Not with batch_first_block, prepared or prepare_next."""
+    GsrForwardArgs::sh_origin).  Not with batch_first_block, prepared or prepare_next.
+
+    frozen = which backward runs (frozen_backward_route): None -- by inference, the frozen call of gsr_backward (include/gsr.h: camera and
+    points_transform gradients alone, no per-Gaussian gradient computed or allocated) when no parameter tensor requires grad and the
+    camera or points_transform does, which is every pose iteration against detached parameters (the reference after fix_position():
+    /root/reference/trainer/ht3dgs_trainer.py:307-335, 916-963); False -- always the full backward; True -- the frozen one even if a
+    parameter requires grad (its .grad then stays None); RuntimeError with fused_adam, prepare_next or densify_stats."""
+    _check_frozen(frozen, fused_adam, prepare_next, densify_stats)
     if not E.use_ctypes():
         return _rasterize_ext(means3D, means2D, features_dc, None, opacity_logit, log_scales, rotations_raw, None, raster_settings,
                               features_rest, True, fused_adam, points_transform, prepared, prepare_next, next_points_transform,
-                              densify_stats, batch_first_block, fused_adam_deferred, view_id, extras, sh_origin)
+                              densify_stats, batch_first_block, fused_adam_deferred, view_id, extras, sh_origin, frozen)
     if prepared is not None or extras or prepare_next is not None or densify_stats is not None or batch_first_block is not None or fused_adam_deferred \
             or sh_origin is not None:
         raise RuntimeError("prepared / prepare_next / densify_stats / batch_first_block / fused_adam_deferred / sh_origin are served by the "
                            "PyTorch extension binding only")
     e = torch.Tensor([])
     return _RasterizeGaussians.apply(means3D, means2D, features_dc, e, opacity_logit, log_scales, rotations_raw, e,
-                                     raster_settings, features_rest, True, *_cam_inputs(raster_settings), fused_adam, points_transform, view_id)
+                                     raster_settings, features_rest, True, *_cam_inputs(raster_settings), fused_adam, points_transform, view_id,
+                                     frozen)
 
 
 def importance_accumulate(acc, means3D, sh, opacities, scales, rotations, raster_settings, sh_rest=None, raw_params=False,
@@ -548,9 +611,12 @@ def importance_accumulate(acc, means3D, sh, opacities, scales, rotations, raster
 class GaussianRasterizer(nn.Module):
     """Callable exactly as at gaussian_model_ht.py:824,871-880 and gaussian_renderer/__init__.py:53,88-96."""
 
-    def __init__(self, raster_settings: GaussianRasterizationSettings):
+    def __init__(self, raster_settings: GaussianRasterizationSettings, frozen: Optional[bool] = None):
+        """frozen: which backward this module's renders run (frozen_backward_route: None = by inference, False = the full one, True = the
+        frozen one).  It lives here and as the attribute `frozen`: forward() keeps exactly the reference's keyword set."""
         super().__init__()
         self.raster_settings = raster_settings
+        self.frozen = frozen
 
     def markVisible(self, positions: torch.Tensor) -> torch.Tensor:
         """Frustum (near-plane) visibility mask; present in the module's API, unused by the reference."""
@@ -564,7 +630,7 @@ class GaussianRasterizer(nn.Module):
     def forward(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None,
                 cov3D_precomp=None):
         # (the keyword set is exactly the reference's; extensions such as points_transform live on the functions
-        #  rasterize_gaussians / rasterize_gaussians_raw)
+        #  rasterize_gaussians / rasterize_gaussians_raw, and `frozen` on the constructor)
         rs = self.raster_settings
         if (shs is None and colors_precomp is None) or (shs is not None and colors_precomp is not None):
             raise Exception("Please provide excatly one of either SHs or precomputed colors!")
@@ -575,4 +641,4 @@ class GaussianRasterizer(nn.Module):
         return rasterize_gaussians(means3D, means2D, shs if shs is not None else e,
                                    colors_precomp if colors_precomp is not None else e, opacities,
                                    scales if scales is not None else e, rotations if rotations is not None else e,
-                                   cov3D_precomp if cov3D_precomp is not None else e, rs)
+                                   cov3D_precomp if cov3D_precomp is not None else e, rs, frozen=self.frozen)

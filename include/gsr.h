@@ -202,6 +202,25 @@ typedef struct GsrDensifyStats {
     float* max_radii2D;
 } GsrDensifyStats;
 
+/* ---- version 115: the FROZEN CALL -- pose and camera gradients of a model that does not move.
+ * The reference optimises six pose numbers against fixed Gaussians in stage A's pose phase (train_relative_pose,
+ * /root/reference/trainer/ht3dgs_trainer.py:307-335, after training_setup_fix_position / fix_position,
+ * /root/reference/scene/gaussian_model_ht.py:321-343, 235-248), in train_pose_only (ht3dgs_trainer.py:916-963) and in the test-time
+ * pose fit of eval_nvs (:1018-1042): nobody reads a per-Gaussian gradient there.  A gsr_backward call is FROZEN when
+ *     fused_adam == NULL,
+ *     every per-Gaussian gradient pointer is NULL (d_means3D, d_opacities, d_colors_precomp, d_shs, d_shs_rest, d_scales, d_rotations,
+ *     d_cov3D_precomp), and
+ *     at least one of d_viewmatrix, d_projmatrix, d_campos, d_points_transform is set.
+ * It runs the same prologue and backward blend, then a variant of the per-Gaussian kernel that keeps what feeds the camera and transform
+ * gradients and leaves out the chain rules and the 62 floats per Gaussian of the parameter gradients; no buffer for them is needed.
+ * With the same blend result (option "deterministic_backward") its outputs are bit-identical with those of the full call.
+ * d_means2D is OPTIONAL in a frozen call: written when non-NULL, never required.  Accepted with raw or activated parameters, shs alone or
+ * shs + shs_rest, colors_precomp, cov3D_precomp, sh_origin, grad_depth / grad_alpha, any D <= 3 with any stored M, a GsrBatch of B <= 16.
+ * Refused with GSR_ERR_ARG (gsr_last_error() names the rule), before anything is enqueued on the stream:
+ *     a frozen call with next_view / prepared_out (they need fused_adam);
+ *     a frozen call with densify_stats (fed by the gradients it leaves out);
+ *     d_means3D == NULL while another per-Gaussian gradient pointer is set (without fused_adam they come together or not at all);
+ *     every per-Gaussian gradient pointer NULL and no camera / transform output either (nothing to compute). */
 typedef struct GsrBackwardArgs {
     int32_t N, M, D, W, H;
     float scale_modifier, tanfovx, tanfovy;
@@ -216,8 +235,8 @@ typedef struct GsrBackwardArgs {
     const float* grad_color; /* [3,H,W] or NULL */
     const float* grad_depth; /* [1,H,W] or NULL */
     const float* grad_alpha; /* [1,H,W] or NULL */
-    float* d_means3D;        /* [N,3] */
-    float* d_means2D;        /* [N,3]  (d/d ndc x, d/d ndc y, 0): gaussian_model_ht.py:718-721 */
+    float* d_means3D;        /* [N,3]; NULL together with every other per-Gaussian gradient pointer = frozen call (above) */
+    float* d_means2D;        /* [N,3]  (d/d ndc x, d/d ndc y, 0): gaussian_model_ht.py:718-721; may be NULL in a frozen call */
     float* d_opacities;      /* [N] */
     float* d_colors_precomp; /* [N,3] or NULL */
     float* d_shs;            /* [N,M,3] or NULL */
@@ -304,7 +323,8 @@ const char* gsr_last_error(void);
  * 111: GsrForwardArgs and GsrBackwardArgs end with sh_origin.
  * 112: the depth term of the loss (gsr_depth_loss_*); no struct changed.
  * 113: gsr_importance_accumulate / gsr_importance_scratch_bytes; no struct changed.
- * 114: the depth term on a stack of planes (gsr_depth_loss_*_batched); no struct changed. */
+ * 114: the depth term on a stack of planes (gsr_depth_loss_*_batched); no struct changed.
+ * 115: the frozen call of gsr_backward (camera / transform gradients alone, see GsrBackwardArgs); no struct changed. */
 int gsr_version(void);
 size_t gsr_struct_bytes(int32_t which); /* 0 GsrForwardArgs, 1 GsrBackwardArgs, 2 GsrForwardOut; anything else 0 */
 
@@ -405,7 +425,8 @@ int gsr_set_option(const char* name, int value);
  * gsr_forward) / "forward_wait_ns" (the part of it spent waiting for the instance count) and "backward_calls" / "backward_ns" --
  * (forward_ns - forward_wait_ns + backward_ns) / calls is what the launching thread works per forward + backward.  -1 for an
  * unknown name. */
-int64_t gsr_get_counter(const char* name);   /* + "blend_bwd_resident": workgroups of the backward blend the device holds at once; "depth_window_resorts" */
+int64_t gsr_get_counter(const char* name);   /* + "blend_bwd_resident": workgroups of the backward blend the device holds at once; "depth_window_resorts";
+                                                "frozen_backward_calls": gsr_backward calls that took the frozen route (GsrBackwardArgs) */
 /* Debug / test hook: copy the per-tile ranges (T x {begin, end} uint32) and the (tile, depth, id)-ordered Gaussian-id list
  * (num_rendered uint32) out of a forward's binning buffer into device buffers of the caller (either may be NULL). */
 int gsr_debug_read_binning(const void* binning, int64_t binning_capacity, int64_t num_rendered, int32_t W, int32_t H,

@@ -1,0 +1,477 @@
+"""GPU: the frozen call of gsr_backward (include/gsr.h, GsrBackwardArgs) -- the gradients of the camera and of points_transform alone,
+for a model that does not move -- against the full backward of the same forward.
+
+"Fixed order" is the option "deterministic_backward": the blend then hands both per-Gaussian kernels the same rows, and the frozen
+variant, which keeps the order of operations of everything that feeds the camera partials, must give the same BITS.  On the default
+accumulation the two are held to parity.same_accumulation()'s allowance, and the frozen outputs to the float64 oracle at the bars the
+full backward is held to (parity.GRAD_RTOL / ELEM_RTOL).  No tolerance of its own is introduced here.
+
+Scenes are parity.syn.make_scene at 70x50 (partial tiles on both axes); N = 1024 / 1000 / 100 take the three staging paths of the
+per-Gaussian kernel (whole blocks with linear SH tiles; a ragged last block whose rows are no whole 16-byte vectors; one ragged
+block).  The C ABI takes the transform as its 12 floats; the [4,4] form of the Python interface is covered through autograd below.
+"""
+import ctypes as C
+import importlib
+
+import numpy as np
+import pytest
+import torch
+
+import parity
+from oracle import binding
+
+pytestmark = pytest.mark.gpu
+ts = importlib.import_module("3dgs_hierarchical_training_amd.train_step")
+bt = importlib.import_module("3dgs_hierarchical_training_amd.batched")
+pose = importlib.import_module("3dgs_hierarchical_training_amd.pose")
+R = importlib.import_module("3dgs_hierarchical_training_amd.rasterizer")
+E = importlib.import_module("3dgs_hierarchical_training_amd._ext")
+L = importlib.import_module("3dgs_hierarchical_training_amd._lib")
+loss_mod = importlib.import_module("3dgs_hierarchical_training_amd.loss")
+
+DEV = torch.device("cuda:0")
+W, H = 70, 50
+PER_GAUSSIAN = ("d_means3D", "d_opacities", "d_colors_precomp", "d_shs", "d_shs_rest", "d_scales", "d_rotations", "d_cov3D_precomp")
+CAMERA = ("d_points_transform", "d_viewmatrix", "d_projmatrix", "d_campos")
+XF = [[0.9995, -0.02, 0.024, 0.03], [0.0205, 0.9996, -0.019, -0.02], [-0.0235, 0.0195, 0.9995, 0.05]]   # near a rotation: any affine map is served
+
+
+@pytest.fixture(autouse=True)
+def _inference_on(monkeypatch):
+    """rasterizer.FROZEN_BY_INFERENCE ships False (the route was not faster at every probed size): the inference itself is what these
+    tests hold, so it is switched on for them; test_the_shipped_default_keeps_the_full_backward covers the default."""
+    monkeypatch.setattr(R, "FROZEN_BY_INFERENCE", True)
+
+
+def _frozen_calls():
+    return int(L.load().gsr_get_counter(b"frozen_backward_calls"))
+
+
+class fixed_order:
+    def __enter__(self):
+        assert L.load().gsr_set_option(b"deterministic_backward", 1) == 0
+
+    def __exit__(self, *exc):
+        L.load().gsr_set_option(b"deterministic_backward", 0)
+
+
+def _tensors(N, deg, raw, layout, seed=5, posed=True):
+    """Device tensors of one C-ABI case.  layout: 'split' (shs [N,1,3] + shs_rest [N,15,3], M = 16), 'single' (shs [N,(deg+1)^2,3]),
+    'pre' (colors_precomp + cov3D_precomp), 'sho' (split + sh_origin)."""
+    sc = parity.syn.make_scene(N, W, H, sh_degree=deg, seed=seed, posed=posed)
+    e = torch.empty(0, device=DEV)
+    t = dict(N=N, D=deg, raw=bool(raw), sc=sc, means3D=sc["means3D"].to(DEV), sh=e, rest=e, colors=e, cov=e, scales=e, rots=e, sho=None)
+    t["opac"] = sc["opacities"].to(DEV)
+    if layout == "pre":
+        assert not raw
+        kw = parity.scene_kwargs(sc, "pre")
+        t["colors"], t["cov"] = kw["colors_precomp"].to(DEV), kw["cov3D_precomp"].to(DEV)
+    else:
+        t["scales"], t["rots"] = sc["scales"].to(DEV), sc["rotations"].to(DEV)
+        if layout == "single":
+            t["sh"] = sc["shs"][:, :(deg + 1) ** 2].contiguous().to(DEV)
+        else:
+            t["sh"], t["rest"] = sc["shs"][:, :1].contiguous().to(DEV), sc["shs"][:, 1:].contiguous().to(DEV)
+        if layout == "sho":
+            t["sho"] = torch.tensor([0.1, -0.2, -0.5], device=DEV)
+    if raw:
+        t["opac"] = ts.inverse_sigmoid(t["opac"].clamp(1e-4, 1 - 1e-4))
+        t["scales"], t["rots"] = torch.log(t["scales"]), (1.7 * t["rots"]).contiguous()
+    t["vm"], t["pm"], t["campos"] = sc["viewmatrix"].to(DEV), sc["projmatrix"].to(DEV), sc["campos"].to(DEV)
+    t["bg"] = torch.tensor([0.1, 0.2, 0.3], device=DEV)
+    return t
+
+
+def _forward(t, xf):
+    """gsr_forward through torch.ops.gsr.rasterize_forward (it serves sh_origin): the outputs and the buffers a backward reads."""
+    ops = E.load()
+    sc = t["sc"]
+    out = ops.rasterize_forward(t["means3D"], t["sh"], t["colors"], t["opac"], t["scales"], t["rots"], t["cov"], t["rest"], t["vm"], t["pm"],
+                                t["campos"], t["bg"], xf if xf is not None else torch.empty(0, device=DEV), H, W, float(sc["tanfovx"]),
+                                float(sc["tanfovy"]), 1.0, t["D"], t["raw"], False, False, torch.empty(0, dtype=torch.uint8, device=DEV), [], 0, 0,
+                                t["sho"])
+    return dict(color=out[0], radii=out[1], depth=out[2], alpha=out[3], geom=out[4], image=out[5], binning=out[6], meta=out[7], xf=xf)
+
+
+def _upstream(with_da, seed=3):
+    gc, gd, ga = parity.upstream_grads(H, W, seed=seed)
+    g = [torch.from_numpy(gc).to(DEV), torch.from_numpy(gd).to(DEV).reshape(1, H, W), torch.from_numpy(ga).to(DEV).reshape(1, H, W)]
+    return g if with_da else [g[0], None, None]
+
+
+def _backward(t, f, up, frozen, want=CAMERA, means2D=True, check=True, **override):
+    """One gsr_backward over ctypes.  Every output starts as NaN (an entry the call left alone would be seen).  frozen: no per-Gaussian
+    gradient pointer is handed over.  Returns (rc, {name: tensor})."""
+    lib = L.load()
+    N = t["N"]
+    has = lambda x: x.numel() > 0
+    M = (t["sh"].shape[1] + (t["rest"].shape[1] if has(t["rest"]) else 0)) if has(t["sh"]) else 0
+    nan = lambda *s: torch.full(s, float("nan"), device=DEV)
+    out = {}
+    if means2D:
+        out["d_means2D"] = nan(N, 3)
+    if not frozen:
+        out.update(d_means3D=nan(N, 3), d_opacities=nan(N, 1))
+        if has(t["sh"]):
+            out["d_shs"] = nan(N, 1 if has(t["rest"]) else M, 3)
+        if has(t["rest"]):
+            out["d_shs_rest"] = nan(N, M - 1, 3)
+        if has(t["colors"]):
+            out["d_colors_precomp"] = nan(N, 3)
+        if has(t["scales"]):
+            out.update(d_scales=nan(N, 3), d_rotations=nan(N, 4))
+        if has(t["cov"]):
+            out["d_cov3D_precomp"] = nan(N, 6)
+    for k, shape in (("d_points_transform", (3, 4)), ("d_viewmatrix", (4, 4)), ("d_projmatrix", (4, 4)), ("d_campos", (3,))):
+        if k in want and (k != "d_points_transform" or f["xf"] is not None):
+            out[k] = nan(*shape)
+    scratch = torch.empty(lib.gsr_backward_scratch_bytes(N), dtype=torch.uint8, device=DEV)
+    p = lambda x: x.data_ptr() if (x is not None and x.numel() > 0) else None
+    a = L.GsrBackwardArgs()
+    a.N, a.M, a.D, a.W, a.H = N, M, t["D"], W, H
+    a.scale_modifier, a.tanfovx, a.tanfovy = 1.0, float(t["sc"]["tanfovx"]), float(t["sc"]["tanfovy"])
+    a.means3D, a.opacities, a.scales, a.rotations, a.cov3D_precomp = p(t["means3D"]), p(t["opac"]), p(t["scales"]), p(t["rots"]), p(t["cov"])
+    a.shs, a.shs_rest, a.colors_precomp, a.raw_params = p(t["sh"]), p(t["rest"]), p(t["colors"]), int(t["raw"])
+    a.viewmatrix, a.projmatrix, a.campos, a.bg = p(t["vm"]), p(t["pm"]), p(t["campos"]), p(t["bg"])
+    a.geom, a.image, a.binning = p(f["geom"]), p(f["image"]), p(f["binning"])
+    meta = f["meta"]
+    a.num_rendered, a.binning_capacity, a.forward_flags = int(meta[0]), int(meta[1]), int(meta[2])
+    a.grad_color, a.grad_depth, a.grad_alpha = p(up[0]), p(up[1]), p(up[2])
+    a.points_transform, a.sh_origin, a.scratch = p(f["xf"]), p(t["sho"]), scratch.data_ptr()
+    for k, v in out.items():
+        setattr(a, k, v.data_ptr())
+    for k, v in override.items():
+        setattr(a, k, v)
+    rc = lib.gsr_backward(C.byref(a), C.c_void_p(torch.cuda.current_stream(DEV).cuda_stream))
+    if check:
+        assert rc == 0, lib.gsr_last_error()
+        torch.cuda.synchronize()
+        for k, v in out.items():
+            assert bool(torch.isfinite(v).all()), (k, "not written, or not finite")
+    return rc, out
+
+
+# N | degree | raw | layout | grad_depth / grad_alpha | transform given | outputs wanted
+CASES = [
+    (1024, 3, True, "split", True, True, CAMERA),                                # whole blocks, linear tiles, everything
+    (1000, 3, True, "split", False, True, ("d_points_transform",)),              # ragged last block, the transform alone
+    (100, 1, False, "split", False, True, CAMERA[1:]),                           # one ragged block, the camera alone (a transform is applied)
+    (1000, 2, False, "single", True, True, CAMERA),                              # shs alone, M = 9: the non-linear path
+    (1024, 0, True, "split", False, True, CAMERA),                               # degree 0 of a 16-coefficient model (stage A): no SH row staged
+    (100, 0, False, "single", True, True, ("d_points_transform",)),              # M = 1
+    (1000, 1, True, "single", False, False, CAMERA[1:]),                         # M = 4, no transform at all
+    (1024, 3, False, "single", False, True, CAMERA),                             # shs alone with M = 16
+    (100, 2, True, "split", True, True, CAMERA),
+    (1024, 1, False, "pre", True, True, CAMERA),                                 # colors_precomp + cov3D_precomp
+    (1000, 2, True, "sho", False, True, CAMERA),                                 # sh_origin: the colour's share reaches d_means3D alone
+    (1000, 2, False, "sho", True, True, CAMERA[:2]),
+]
+
+
+@pytest.mark.parametrize("case", CASES, ids=lambda c: f"N{c[0]}-d{c[1]}-{'raw' if c[2] else 'act'}-{c[3]}-{'da' if c[4] else 'c'}-{'xf' if c[5] else 'noxf'}-{len(c[6])}out")
+def test_frozen_equals_full_bit_for_bit_in_fixed_order(case):
+    """One forward; full, frozen, frozen, full gsr_backward over it (both orders): every camera / transform output and d_means2D of the
+    frozen call equals the full call's, bit for bit.  On the parent commit the frozen call is refused with GSR_ERR_ARG."""
+    N, deg, raw, layout, with_da, with_xf, want = case
+    t = _tensors(N, deg, raw, layout)
+    up = _upstream(with_da)
+    xf = torch.tensor(XF, device=DEV) if with_xf else None
+    with fixed_order():
+        f = _forward(t, xf)
+        assert int(f["meta"][0]) > 0 and int((f["radii"] > 0).sum()) > N // 4
+        n0 = _frozen_calls()
+        runs = [_backward(t, f, up, frozen, want)[1] for frozen in (False, True, True, False)]
+        assert _frozen_calls() == n0 + 2
+    full = runs[0]
+    keys = [k for k in full if k in CAMERA or k == "d_means2D"]
+    assert len(keys) == len([k for k in want if with_xf or k != "d_points_transform"]) + 1
+    for k in keys:
+        # (dL/dcampos comes from the colour's view direction alone: zero at degree 0, with colors_precomp and with sh_origin)
+        if k != "d_campos" or (deg > 0 and layout in ("split", "single")):
+            assert float(full[k].abs().max()) > 0, k
+        for r in runs[1:]:
+            assert torch.equal(r[k], full[k]), (k, float((r[k] - full[k]).abs().max()))
+    for k in PER_GAUSSIAN:      # and the full call around the frozen ones is unchanged by them
+        if k in full:
+            assert torch.equal(runs[3][k], full[k]), k
+    # d_means2D is optional in a frozen call: without it the other outputs are the same
+    with fixed_order():
+        r = _backward(t, f, up, True, want, means2D=False)[1]
+    for k in r:
+        assert torch.equal(r[k], full[k]), k
+
+
+def test_default_accumulation_against_the_full_route_and_the_oracle():
+    """Default accumulation (float64 atomics in arrival order): the frozen outputs against the full call of the same forward under
+    parity.same_accumulation()'s allowance, and against the float64 oracle at the bars of the full backward (parity.check_grads:
+    GRAD_RTOL norm-wise, ELEM_RTOL element-wise).  The transform is the identity, so the oracle's posed means are the model's and its
+    dL/d(transform) is sum_i dL/dmean_i [p_i; 1]^T of its float64 dL/dmean."""
+    N, deg = 1000, 3
+    t = _tensors(N, deg, False, "single", seed=11)
+    kw = parity.scene_kwargs(t["sc"], "sh", bg=(0.1, 0.2, 0.3))
+    o = binding.OracleRender(**kw)
+    xf = torch.eye(4, device=DEV)[:3].contiguous()
+    got = {}
+
+    def run(grads):
+        f = _forward(t, xf)
+        res = dict(fwd=tuple(f[k].detach().cpu().numpy() for k in ("color", "radii", "depth", "alpha")))
+        if grads is not None:
+            up = [torch.from_numpy(np.ascontiguousarray(g, np.float32)).to(DEV) for g in grads]
+            got["full"] = _backward(t, f, up, False)[1]
+            got["frozen"] = _backward(t, f, up, True)[1]
+        return res
+    rep, _, ref = parity.oracle_case(o, run, parity.upstream_grads(H, W, seed=4), "frozen backward")
+    o.close()
+    keys = CAMERA + ("d_means2D",)
+    parity.same_accumulation({k: got["frozen"][k] for k in keys}, {k: got["full"][k] for k in keys}, "frozen vs full, default accumulation")
+    p1 = np.concatenate([t["sc"]["means3D"].double().numpy(), np.ones((N, 1))], axis=1)
+    ref = dict(ref, points_transform=np.asarray(ref["means3D"], np.float64).T @ p1)
+    mine = {k[2:]: got["frozen"][k].cpu().numpy() for k in CAMERA}
+    print(parity.check_grads(mine, ref, "frozen backward vs oracle"))
+
+
+def _autograd_case(frozen, params_need_grad, m2d_needs_grad, xf44=False, deg=3, N=1000):
+    sc = parity.syn.make_scene(N, W, H, sh_degree=deg, seed=5, posed=True)
+    settings = ts.make_settings(sc, DEV, deg, bg=torch.tensor([0.1, 0.2, 0.3]))
+    p = ts.GaussianParams(sc, DEV, optimizer="torch")
+    names = ("_xyz", "_features_dc", "_features_rest", "_opacity", "_scaling", "_rotation")
+    prm = [getattr(p, k) if params_need_grad else getattr(p, k).detach() for k in names]
+    Mx = torch.tensor(XF + [[0.0, 0.0, 0.0, 1.0]] if xf44 else XF, device=DEV, requires_grad=True)
+    m2d = torch.zeros(N, 3, device=DEV, requires_grad=m2d_needs_grad)
+    up = _upstream(True)
+    n0 = _frozen_calls()
+    color, radii, depth, alpha = R.rasterize_gaussians_raw(prm[0], m2d, *prm[1:], settings, points_transform=Mx, frozen=frozen)
+    ((color * up[0]).sum() + (depth * up[1]).sum() + (alpha * up[2]).sum()).backward()
+    torch.cuda.synchronize()
+    return dict(xf=Mx.grad, m2d=m2d.grad, grads={k: getattr(p, k).grad for k in names}, frozen_calls=_frozen_calls() - n0)
+
+
+@pytest.mark.parametrize("binding_route", ["extension", "ctypes"])
+def test_through_autograd_on_both_bindings(binding_route, monkeypatch):
+    """Detached parameters and a transform that requires grad: the frozen call ran (the library's counter), no parameter has a .grad,
+    means2D.grad is None unless means2D requires grad and then equals the full route's; frozen=False is today's behaviour;
+    frozen=True leaves the .grad of parameters that require grad None; a [4,4] transform keeps its zero last row."""
+    if binding_route == "ctypes":
+        monkeypatch.setenv("GSR_BINDING", "ctypes")
+    assert E.use_ctypes() == (binding_route == "ctypes")
+    with fixed_order():
+        full = _autograd_case(False, True, True)                     # today's route
+        assert full["frozen_calls"] == 0 and all(g is not None and float(g.abs().max()) > 0 for g in full["grads"].values())
+        inferred = _autograd_case(None, False, False)                # a pose iteration of stage_a.fit_pair
+        assert inferred["frozen_calls"] == 1 and inferred["m2d"] is None and all(g is None for g in inferred["grads"].values())
+        assert torch.equal(inferred["xf"], full["xf"]) and float(full["xf"].abs().max()) > 0
+        with_m2d = _autograd_case(None, False, True)
+        assert with_m2d["frozen_calls"] == 1 and torch.equal(with_m2d["m2d"], full["m2d"]) and torch.equal(with_m2d["xf"], full["xf"])
+        off = _autograd_case(False, False, False)                    # detached parameters, inference switched off: the full backward
+        assert off["frozen_calls"] == 0 and torch.equal(off["xf"], full["xf"])
+        needs = _autograd_case(None, True, True)                     # a parameter wants its gradient: no frozen call by inference
+        assert needs["frozen_calls"] == 0 and all(torch.equal(needs["grads"][k], full["grads"][k]) for k in full["grads"])
+        forced = _autograd_case(True, True, True)
+        assert forced["frozen_calls"] == 1 and all(g is None for g in forced["grads"].values())
+        assert torch.equal(forced["xf"], full["xf"]) and torch.equal(forced["m2d"], full["m2d"])
+        x44 = _autograd_case(None, False, False, xf44=True)
+        assert x44["frozen_calls"] == 1 and x44["xf"].shape == (4, 4) and float(x44["xf"][3].abs().max()) == 0.0
+        assert torch.equal(x44["xf"][:3], full["xf"])
+
+
+def test_the_shipped_default_keeps_the_full_backward(monkeypatch):
+    """With rasterizer.FROZEN_BY_INFERENCE False, frozen=None on detached parameters runs the full backward and frozen=True the frozen one."""
+    monkeypatch.setattr(R, "FROZEN_BY_INFERENCE", False)
+    with fixed_order():
+        a = _autograd_case(None, False, True)
+        b = _autograd_case(True, False, True)
+    assert a["frozen_calls"] == 0 and b["frozen_calls"] == 1
+    assert torch.equal(a["xf"], b["xf"]) and torch.equal(a["m2d"], b["m2d"])
+
+
+def test_camera_gradients_through_the_module_interface():
+    """GaussianRasterizer(settings, frozen=...) with a camera that requires grad and activated, detached parameters."""
+    import hip_runner
+    sc = parity.syn.make_scene(1000, W, H, sh_degree=2, seed=5, posed=True)
+    kw = parity.scene_kwargs(sc, "sh", bg=(0.1, 0.2, 0.3))
+    up = _upstream(False)
+    res = {}
+    with fixed_order():
+        for frozen in (False, None):
+            rs = hip_runner.settings_from(kw, DEV, cam_grad=True)
+            n0 = _frozen_calls()
+            out = R.GaussianRasterizer(rs, frozen=frozen)(means3D=kw["means3D"].to(DEV), means2D=torch.zeros(1000, 3, device=DEV), shs=kw["shs"].to(DEV),
+                                           opacities=kw["opacities"].to(DEV), scales=kw["scales"].to(DEV), rotations=kw["rotations"].to(DEV))
+            (out[0] * up[0]).sum().backward()
+            res[frozen] = (rs.viewmatrix.grad, rs.projmatrix.grad, rs.campos.grad)
+            assert _frozen_calls() - n0 == (0 if frozen is False else 1)
+    for a, b in zip(res[None], res[False]):
+        assert torch.equal(a, b) and float(b.abs().max()) > 0
+
+
+def test_memory_of_the_backward():
+    """N = 100 000, M = 16, degree 3: the peak growth of allocated bytes over backward() is below 128 N on the frozen route (the
+    80 N-byte scratch + the 47 partials per block + at most 12 N of d_means2D + the image-sized gradients of the loss) and above
+    248 N on the full one (which adds the 62 floats per Gaussian of the parameter gradients)."""
+    N = 100_000
+    sc = parity.syn.make_scene(N, 160, 120, sh_degree=3, seed=2, posed=True)
+    settings = ts.make_settings(sc, DEV, 3)
+    p = ts.GaussianParams(sc, DEV, optimizer="torch")
+    raw = p.raw()
+    w = torch.rand(3, 120, 160, device=DEV)
+    growth = {}
+    for frozen in (None, False):
+        Mx = torch.tensor(XF, device=DEV, requires_grad=True)
+        m2d = torch.zeros(N, 3, device=DEV, requires_grad=True)
+        loss = (R.rasterize_gaussians_raw(raw["_xyz"], m2d, raw["_features_dc"], raw["_features_rest"], raw["_opacity"], raw["_scaling"],
+                                          raw["_rotation"], settings, points_transform=Mx, frozen=frozen)[0] * w).sum()
+        torch.cuda.synchronize()
+        torch.cuda.reset_peak_memory_stats(DEV)
+        before = torch.cuda.memory_allocated(DEV)
+        loss.backward()
+        torch.cuda.synchronize()
+        growth[frozen] = torch.cuda.max_memory_allocated(DEV) - before
+        assert Mx.grad is not None and m2d.grad is not None
+        del loss, Mx, m2d
+    print(f"peak growth over backward(): frozen {growth[None] / N:.1f} N bytes, full {growth[False] / N:.1f} N bytes")
+    assert growth[None] < 128 * N, growth
+    assert growth[False] > 248 * N, growth
+
+
+def test_batch_of_three_models():
+    """B = 3 models of 256 / 128 / 384 Gaussians, each under its own camera and transform, fixed order: every model's frozen
+    d_points_transform and d_viewmatrix equal its own unbatched frozen call bit for bit, and permuting the models permutes them."""
+    sizes = (256, 128, 384)
+    scenes = [parity.syn.make_scene(n, W, H, sh_degree=3, seed=40 + k, posed=True) for k, n in enumerate(sizes)]
+    views = [ts.make_settings(sc, DEV, 3) for sc in scenes]
+    Ms = [pose.se3_exp(torch.tensor(v))[:3].contiguous().to(DEV) for v in
+          ([0.0] * 6, [0.02, -0.01, 0.015, 0.004, -0.003, 0.002], [-0.015, 0.01, 0.02, -0.002, 0.004, 0.001])]
+    w = torch.rand(3, 3, H, W, device=DEV)
+
+    def grad_cam(rs):
+        return rs._replace(viewmatrix=rs.viewmatrix.detach().clone().requires_grad_(True))
+
+    def batched(order):
+        batch = bt.BatchedGaussianParams([scenes[k] for k in order], DEV, optimizer="torch")
+        raw = batch.raw()
+        bset = grad_cam(bt.batch_settings([views[k] for k in order], DEV))
+        Mb = torch.stack([Ms[k] for k in order]).requires_grad_(True)
+        n0 = _frozen_calls()
+        img = R.rasterize_gaussians_raw(raw["_xyz"], torch.zeros_like(raw["_xyz"]), raw["_features_dc"], raw["_features_rest"], raw["_opacity"],
+                                        raw["_scaling"], raw["_rotation"], bset, points_transform=Mb, batch_first_block=batch.first_block)[0]
+        (img * w[list(order)]).sum().backward()
+        assert _frozen_calls() == n0 + 1
+        return Mb.grad, bset.viewmatrix.grad
+    with fixed_order():
+        gx, gv = batched((0, 1, 2))
+        for k in range(3):
+            r = ts.GaussianParams(scenes[k], DEV, optimizer="torch").raw()
+            rs = grad_cam(views[k])
+            Mk = Ms[k].clone().requires_grad_(True)
+            one = R.rasterize_gaussians_raw(r["_xyz"], torch.zeros_like(r["_xyz"]), r["_features_dc"], r["_features_rest"], r["_opacity"],
+                                            r["_scaling"], r["_rotation"], rs, points_transform=Mk)[0]
+            (one * w[k]).sum().backward()
+            assert float(Mk.grad.abs().max()) > 0 and float(rs.viewmatrix.grad.abs().max()) > 0
+            assert torch.equal(gx[k], Mk.grad) and torch.equal(gv[k], rs.viewmatrix.grad), k
+        order = (2, 0, 1)
+        px, pv = batched(order)
+        for slot, k in enumerate(order):
+            assert torch.equal(px[slot], gx[k]) and torch.equal(pv[slot], gv[k]), (slot, k)
+
+
+def test_a_forward_is_reused():
+    """Frozen twice over one forward: equal results.  Frozen, then full over the same forward: the full call's parameter gradients
+    equal those of a fresh forward + full backward (fixed order) -- the frozen call leaves the forward's buffers as a full one does."""
+    t = _tensors(1000, 3, True, "split")
+    up = _upstream(True)
+    xf = torch.tensor(XF, device=DEV)
+    with fixed_order():
+        f = _forward(t, xf)
+        a = _backward(t, f, up, True)[1]
+        b = _backward(t, f, up, True)[1]
+        full = _backward(t, f, up, False)[1]
+        fresh = _backward(t, _forward(t, xf), up, False)[1]
+    for k in a:
+        assert torch.equal(a[k], b[k]) and torch.equal(a[k], full[k]), k
+    for k in fresh:
+        assert torch.equal(full[k], fresh[k]), k
+    assert all(k in fresh for k in ("d_means3D", "d_opacities", "d_shs", "d_shs_rest", "d_scales", "d_rotations"))
+
+
+def test_pose_trajectory_is_the_full_routes():
+    """stage_a.fit_pair's fused pose loop (render -> fused_photometric_loss -> backward -> pose_step) for 20 iterations on 2 000
+    Gaussians at degree 0, fixed order: the transform after EVERY iteration is bit-identical between frozen=False and the inferred
+    route, which runs the frozen call each time.  The fit moves towards the truth, measured as
+    test_gpu_pose.py::test_pose_optimisation_recovers_the_transform measures it (photometric loss; |delta - true| / |true|): 20 Adam
+    steps of 2e-3 can cover at most 0.04 per tangent number of a |true| of 0.09, so what is asserted is that both fall."""
+    ops = E.load()
+    N, iters, lr = 2000, 20, 2e-3
+    sc = parity.syn.make_scene(N, W, H, sh_degree=0, seed=21, sigma_px=5.0, frac_behind=0.0)
+    settings = ts.make_settings(sc, DEV, 0)
+    raw = ts.GaussianParams(sc, DEV, optimizer="torch").raw()
+    m2d = torch.zeros_like(raw["_xyz"])
+    true_delta = torch.tensor([0.06, -0.04, 0.05, 0.02, -0.03, 0.015], device=DEV)
+    G = torch.tensor([0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 1.0], device=DEV)
+
+    def render(M, frozen=None):
+        return R.rasterize_gaussians_raw(raw["_xyz"], m2d, raw["_features_dc"], raw["_features_rest"], raw["_opacity"], raw["_scaling"],
+                                         raw["_rotation"], settings, points_transform=M, frozen=frozen)
+    with torch.no_grad():
+        target = render(pose.retr_matrix(true_delta, G))[0].clamp(0, 1)
+
+    def fit(frozen):
+        delta = torch.zeros(6, device=DEV)
+        m, v, none = torch.zeros(6, device=DEV), torch.zeros(6, device=DEV), torch.empty(0, device=DEV)
+        M = torch.zeros(3, 4, device=DEV)
+        ops.pose_step(delta, m, v, none, none, M, lr, 0.9, 0.999, 1e-8, 0)
+        traj, losses = [], []
+        n0 = _frozen_calls()
+        for it in range(1, iters + 1):
+            Mi = M.detach().requires_grad_(True)
+            loss = loss_mod.fused_photometric_loss(render(Mi, frozen)[0], target, 0.2, clamp=True)
+            loss.backward()
+            ops.pose_step(delta, m, v, Mi.grad, none, M, lr, 0.9, 0.999, 1e-8, it)
+            traj.append(M.clone())
+            losses.append(loss.detach())
+        with torch.no_grad():
+            losses.append(loss_mod.fused_photometric_loss(render(M)[0], target, 0.2, clamp=True))
+        return torch.stack(traj), torch.stack(losses), delta, _frozen_calls() - n0
+    with fixed_order():
+        tf, lf, df, nf = fit(False)
+        ti, li, di, ni = fit(None)
+    assert nf == 0 and ni == iters
+    assert torch.equal(ti, tf), int((ti != tf).flatten(1).any(1).nonzero()[0])
+    assert torch.equal(di, df)
+    err = float((di - true_delta).norm() / true_delta.norm())
+    print(f"loss {float(li[0]):.5f} -> {float(li[-1]):.5f}, relative pose error 1.000 -> {err:.3f}")
+    assert float(li[-1]) < float(li[0]) and err < 1.0
+
+
+def test_refusals_enqueue_nothing_and_name_their_rule():
+    """The four GSR_ERR_ARG cases of the frozen contract: each message distinct and non-empty, and after each a valid frozen call on the
+    same stream gives the result it gives without them."""
+    lib = L.load()
+    t = _tensors(1000, 3, True, "split")
+    up = _upstream(True)
+    xf = torch.tensor(XF, device=DEV)
+    junk = torch.zeros(1 << 16, device=DEV)       # somewhere to point: a refused call reads none of it
+    with fixed_order():
+        f = _forward(t, xf)
+        want = _backward(t, f, up, True)[1]
+        refused = [
+            ("next_view", dict(frozen=True, next_view=junk.data_ptr(), prepared_out=junk.data_ptr())),
+            ("densify_stats", dict(frozen=True, densify_stats=junk.data_ptr())),
+            ("d_means3D", dict(frozen=True, d_opacities=junk.data_ptr())),
+            ("no gradient output", dict(frozen=True, want=())),
+        ]
+        msgs = []
+        for word, kw in refused:
+            n0 = _frozen_calls()
+            rc, _ = _backward(t, f, up, kw.pop("frozen"), kw.pop("want", CAMERA), check=False, **kw)
+            msg = lib.gsr_last_error().decode()
+            assert rc == -1 and word in msg, (word, rc, msg)
+            assert _frozen_calls() == n0
+            msgs.append(msg)
+            again = _backward(t, f, up, True)[1]
+            for k in want:
+                assert torch.equal(again[k], want[k]), (word, k)
+        assert len(set(msgs)) == 4 and all(msgs)
+        # prepared_out alone is refused like next_view
+        rc, _ = _backward(t, f, up, True, check=False, prepared_out=junk.data_ptr())
+        assert rc == -1 and "next_view" in lib.gsr_last_error().decode()

@@ -53,6 +53,17 @@ def _register_fakes():
                 b(lib.gsr_image_bytes_batched(int(W), int(H), B)), b(nbin), torch.empty((3,), dtype=torch.int64),
                 f(*lead, 3, H, W) if (extras & 1) else f(0), b(N if ((extras & 2) and prepared.numel() == 0) else 0))
 
+    @torch.library.register_fake("gsr::render")
+    def _(means3D, sh, colors_precomp, opacities, scales, rotations, cov3D_precomp, sh_rest, viewmatrix, projmatrix, campos, bg,
+          points_transform, image_height, image_width, tanfovx, tanfovy, scale_modifier, sh_degree, raw_params, view_id=0, outputs=0,
+          sh_origin=None):
+        # (color, radii, depth, alpha, clamped, visible); outputs: bit 0 depth + alpha, bit 1 clamped colour, bit 2 visibility bytes
+        N, H, W = means3D.shape[0], image_height, image_width
+        f = lambda *s: means3D.new_empty(s, dtype=torch.float32)
+        return (f(3, H, W), means3D.new_empty((N,), dtype=torch.int32), f(1, H, W) if (outputs & 1) else f(0),
+                f(1, H, W) if (outputs & 1) else f(0), f(3, H, W) if (outputs & 2) else f(0),
+                means3D.new_empty((N if (outputs & 4) else 0,), dtype=torch.uint8))
+
     @torch.library.register_fake("gsr::importance_accumulate")
     def _(acc, means3D, sh, colors_precomp, opacities, scales, rotations, cov3D_precomp, sh_rest, viewmatrix, projmatrix, campos, bg,
           points_transform, image_height, image_width, tanfovx, tanfovy, scale_modifier, sh_degree, raw_params, batch_first_block,

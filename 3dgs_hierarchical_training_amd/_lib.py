@@ -26,8 +26,11 @@ class GsrForwardArgs(C.Structure):
         ("shs_rest", C.c_void_p), ("raw_params", C.c_int32),
         ("points_transform", C.c_void_p), ("prepared", C.c_void_p), ("batch", C.c_void_p),
         ("view_id", C.c_int64), ("out_color_clamped", C.c_void_p), ("visible", C.c_void_p),
-        ("sh_origin", C.c_void_p),
+        ("sh_origin", C.c_void_p), ("render_only", C.c_int32),
     ]
+
+
+GSR_FWD_FLAG_RENDER_ONLY = 1 << 14      # GsrForwardOut.forward_flags of a render-only forward (include/gsr.h)
 
 
 class GsrForwardOut(C.Structure):

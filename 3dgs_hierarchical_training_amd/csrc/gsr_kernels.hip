@@ -2159,7 +2159,11 @@ __device__ __forceinline__ float wave_reduce_three(float v0, float v1, float v2,
 // IMP = the importance pass over a finished forward (see ImpArgs): the same staging, the same visit arithmetic in the same order, so
 // the same contributions are taken (and a pixel takes nothing behind the forward's recorded `last`); no image state, checkpoint,
 // counter or output is written -- per taken visit the gated weights are summed over the wave into LDS, per batch they are added to S.
-template <bool REACH, bool IMP = false>
+// LEAN = the render-only forward (GsrForwardArgs::render_only): the image is all that leaves -- no checkpoint store (the branch is not
+// compiled, not tested per batch), no state planes, no staged word; HAS_DA = false on top of it: no depth / alpha accumulators (two FMAs
+// per taken visit) and no store of them.  The colour chain, the stop test and the reach bits are the full forward's statements in the
+// full forward's order: out_color, out_color_clamped (and out_depth / out_alpha under HAS_DA) are bit-identical with its.
+template <bool REACH, bool IMP = false, bool LEAN = false, bool HAS_DA = true>
 __device__ __forceinline__ void blend_fwd_item(const int xcd, const int kslot, float4 (*s_ab)[64], float2 (*s_c)[64],
                                                int W, int H, int tiles_x, int T, const uint2* __restrict__ ranges,
                                                const uint32_t* __restrict__ list, const Splat* __restrict__ splat,
@@ -2254,9 +2258,11 @@ __device__ __forceinline__ void blend_fwd_item(const int xcd, const int kslot, f
         if (__all(Tr < 0.f)) break;
         // (round 5, measured and not kept: the six stores moved behind the staging, so that they do not sit between the batch's record
         //  loads and their first use in the wave's in-order vmcnt queue -- 98-100 us against 97)
+        if constexpr (!LEAN) {
         if (ckpt && !(b & 1) && (b >> 1) >= kCkptFirst) {   // 128-instance boundary deep in a long list: checkpoint
             float* c = ckpt + ((size_t)(rg.x >> 7) + tile + (b >> 1) - kCkptFirst) * kCkptFloats + sub * 64 + lane;
             c[0] = fabsf(Tr); c[256] = C0; c[512] = C1; c[768] = C2; c[1024] = Dd; c[1280] = Aa;
+        }
         }
 #ifdef GSR_K6_TIMING
         dbg_mark = __builtin_readcyclecounter();
@@ -2326,7 +2332,7 @@ __device__ __forceinline__ void blend_fwd_item(const int xcd, const int kslot, f
             const float asel = pass ? am : 0.f;               // a lane that does not blend adds (+-)0 to everything below
             const float w = asel * Tr;
             C0 = fmaf(B.w, w, C0); C1 = fmaf(C.x, w, C1); C2 = fmaf(C.y, w, C2);
-            Dd = fmaf(B.z, w, Dd); Aa = fmaf(Tr, asel, Aa);   // (k_blend_fwd_w's `A += alpha * T` is contracted to this fma)
+            if constexpr (HAS_DA) { Dd = fmaf(B.z, w, Dd); Aa = fmaf(Tr, asel, Aa); }   // (k_blend_fwd_w's `A += alpha * T` is contracted to this fma)
             Tr = pass ? test_T : -fabsf(Tr);                  // first failure flips the sign: done, |T| kept
             last = (pass && hit) ? (uint32_t)(b * NT + j + 1) : last;
             if constexpr (IMP) {
@@ -2393,7 +2399,7 @@ __device__ __forceinline__ void blend_fwd_item(const int xcd, const int kslot, f
         }
     }
     if constexpr (IMP) return;
-    if (lane == 0) staged4[tile * 4 + sub] = (uint32_t)min(n, batches * NT);
+    if constexpr (!LEAN) { if (lane == 0) staged4[tile * 4 + sub] = (uint32_t)min(n, batches * NT); }
     if (cost_out && lane == 0) cost_out[xcd + 8 * kslot] = (uint16_t)min(visits, 65535u);
     if (cut_pass) {
         // what this tile needs of its list next time: the depth of the last instance any of its waves staged -- or everything, when a
@@ -2427,10 +2433,12 @@ __device__ __forceinline__ void blend_fwd_item(const int xcd, const int kslot, f
     if (inside) {
         const size_t Pl = (size_t)W * H, P = Pl * (size_t)(T / Tl), pl = (size_t)py * W + px, pid = (size_t)bimg * Pl + pl;
         const float Tf = fabsf(Tr);
-        img[pid] = Tf;
-        reinterpret_cast<uint32_t*>(img)[P + pid] = last;
-        img[2 * P + pid] = C0; img[3 * P + pid] = C1; img[4 * P + pid] = C2;
-        img[5 * P + pid] = Dd; img[6 * P + pid] = Aa;
+        if constexpr (!LEAN) {
+            img[pid] = Tf;
+            reinterpret_cast<uint32_t*>(img)[P + pid] = last;
+            img[2 * P + pid] = C0; img[3 * P + pid] = C1; img[4 * P + pid] = C2;
+            img[5 * P + pid] = Dd; img[6 * P + pid] = Aa;
+        }
         float* oc = out_color + (size_t)bimg * 3 * Pl + pl;   // outputs: [B, 3, H, W], [B, 1, H, W]
         const float o0 = C0 + Tf * bg[0], o1 = C1 + Tf * bg[1], o2 = C2 + Tf * bg[2];
         oc[0] = o0;
@@ -2442,11 +2450,29 @@ __device__ __forceinline__ void blend_fwd_item(const int xcd, const int kslot, f
             cc[Pl] = o1 < 0.f ? 0.f : (o1 > 1.f ? 1.f : o1);
             cc[2 * Pl] = o2 < 0.f ? 0.f : (o2 > 1.f ? 1.f : o2);
         }
-        out_depth[pid] = Dd;
-        out_alpha[pid] = Aa;
+        if constexpr (HAS_DA) {
+            out_depth[pid] = Dd;
+            out_alpha[pid] = Aa;
+        }
     }
 }
 
+
+// Balanced placement of a forward-blend workgroup (see balance_build): the slot -> item table of this render, and where this item's
+// visits are recorded.  `table` = false: dispatch order (the list cut's repair pass).  Shared by k_blend_fwd_w6 and k_blend_fwd_render.
+__device__ __forceinline__ void blend_fwd_slot(const BlendBalance& bb, const bool table, int& kslot, uint16_t*& cost_out)
+{
+    if (bb.hdr) {
+        const uint32_t* __restrict__ cur = bb.cur;
+        const uint16_t* __restrict__ perm = bb.perm;
+        const uint32_t e = cur[0];
+        if (table && cur[1 + (blockIdx.x & 7u)]) {       // this XCD's slice of the table was built (each builder workgroup says so itself)
+            const int k = (int)perm[blockIdx.x];
+            if (k < bb.nslots4) kslot = k;
+        }
+        if (e < (uint32_t)kVcEntries) cost_out = bb.cost + (size_t)e * bb.items;
+    }
+}
 
 template <bool REACH>
 __global__ __launch_bounds__(64) void k_blend_fwd_w6(int W, int H, int tiles_x, int T, const uint2* __restrict__ ranges,
@@ -2462,21 +2488,32 @@ __global__ __launch_bounds__(64) void k_blend_fwd_w6(int W, int H, int tiles_x, 
     // register and differ in the immediate offset
     __shared__ float4 s_ab[2 * kFwdBufs][64];
     __shared__ float2 s_c[kFwdBufs][64];
-    // balanced placement (see balance_build): the slot -> item table of this render, and where this item's visits are recorded
     int kslot = (int)(blockIdx.x >> 3);
     uint16_t* cost_out = nullptr;
-    if (bb.hdr) {
-        const uint32_t* __restrict__ cur = bb.cur;
-        const uint16_t* __restrict__ perm = bb.perm;
-        const uint32_t e = cur[0];
-        if (cut_pass != 2 && cur[1 + (blockIdx.x & 7u)]) {       // this XCD's slice of the table was built (each builder workgroup says so itself); the repair pass: dispatch order
-            const int k = (int)perm[blockIdx.x];
-            if (k < bb.nslots4) kslot = k;
-        }
-        if (e < (uint32_t)kVcEntries) cost_out = bb.cost + (size_t)e * bb.items;
-    }
+    blend_fwd_slot(bb, cut_pass != 2, kslot, cost_out);       // (the repair pass: dispatch order)
     blend_fwd_item<REACH>((int)(blockIdx.x & 7), kslot, s_ab, s_c, W, H, tiles_x, T, ranges, list, splat, bg, out_color, out_depth,
                           out_alpha, img, staged4, interleave, ckpt, kCkptFirst, tiles_y, cost_out, out_clamped, cut, cut_pass);
+}
+
+// The render-only forward blend (GsrForwardArgs::render_only, blend_fwd_item's LEAN): k_blend_fwd_w6<true>'s placement and walk, the image
+// alone written.  The parameter list is k_blend_fwd_w6's, so that the host launches either through one pointer; the state planes, the
+// staged counters, the checkpoint area and the list cut are not read (full lists: cut_pass 0).  The staging planes are the forward's.
+template <bool HAS_DA>
+__global__ __launch_bounds__(64) void k_blend_fwd_render(int W, int H, int tiles_x, int T, const uint2* __restrict__ ranges,
+                                                         const uint32_t* __restrict__ list, const Splat* __restrict__ splat,
+                                                         const float* __restrict__ bg, float* __restrict__ out_color,
+                                                         float* __restrict__ out_depth, float* __restrict__ out_alpha,
+                                                         float* __restrict__, uint32_t* __restrict__, int interleave,
+                                                         float* __restrict__, int, int tiles_y, const BlendBalance bb,
+                                                         float* __restrict__ out_clamped, const ListCut, const int)
+{
+    __shared__ float4 s_ab[2 * kFwdBufs][64];
+    __shared__ float2 s_c[kFwdBufs][64];
+    int kslot = (int)(blockIdx.x >> 3);
+    uint16_t* cost_out = nullptr;
+    blend_fwd_slot(bb, true, kslot, cost_out);   // this render reads the frame's table and records its visits like any other
+    blend_fwd_item<true, false, true, HAS_DA>((int)(blockIdx.x & 7), kslot, s_ab, s_c, W, H, tiles_x, T, ranges, list, splat, bg, out_color, out_depth,
+                                              out_alpha, nullptr, nullptr, interleave, nullptr, 0, tiles_y, cost_out, out_clamped, ListCut{}, 0);
 }
 
 // Importance blend (gsr_importance_accumulate): the forward blend's walk a second time -- blend_fwd_item<true, true> -- in dispatch order
@@ -4464,7 +4501,7 @@ size_t gsr_prepared_bytes(int32_t N) { return prep_layout(N).bytes; }
 size_t gsr_prepared_radii_offset(int32_t N) { return prep_layout(N).radii; }
 int gsr_prepare_supported(int32_t M, int32_t D, int32_t raw_params) { return (raw_params && M == 16 && D >= 0 && D <= 3) ? 1 : 0; }
 const char* gsr_last_error(void) { return g_err; }
-int gsr_version(void) { return 115; }
+int gsr_version(void) { return 116; }
 size_t gsr_struct_bytes(int32_t which)
 {
     return which == 0 ? sizeof(GsrForwardArgs) : which == 1 ? sizeof(GsrBackwardArgs) : which == 2 ? sizeof(GsrForwardOut) : 0;
@@ -4616,7 +4653,16 @@ int gsr_forward(const GsrForwardArgs* a, GsrForwardOut* out, void* stream_)
     if (!a || !out) return fail(GSR_ERR_ARG, "null args%s");
     int rc = check_common(a->N, a->M, a->D, a->W, a->H);
     if (rc) return rc;
-    if (!a->out_color || !a->out_depth || !a->out_alpha || !a->image || !a->bg || !a->alloc)
+    // the render-only call (GsrForwardArgs::render_only): its own rules come first; its workspace is asked for behind the last argument
+    // check (ro_workspace below), so a refused call has asked the allocator for nothing
+    const bool ro = a->render_only != 0;
+    if (ro) {
+        if ((a->out_depth == nullptr) != (a->out_alpha == nullptr))
+            return fail(GSR_ERR_ARG, "render_only: out_depth and out_alpha are given both or neither%s");
+        if ((a->batch && a->batch->B > 1) || a->prepared)
+            return fail(GSR_ERR_ARG, "render_only is not served with a batch of B > 1 or a prepared buffer%s");
+        if (!a->out_color || !a->bg || !a->alloc) return fail(GSR_ERR_ARG, "missing output / workspace pointer%s");
+    } else if (!a->out_color || !a->out_depth || !a->out_alpha || !a->image || !a->bg || !a->alloc)
         return fail(GSR_ERR_ARG, "missing output / workspace pointer%s");
     const int N = a->N, W = a->W, H = a->H;
     BatchDev bt;
@@ -4629,14 +4675,43 @@ int gsr_forward(const GsrForwardArgs* a, GsrForwardOut* out, void* stream_)
     if (a->sh_origin && (!a->shs || NB > 1 || a->prepared))
         return fail(GSR_ERR_ARG, "sh_origin needs shs and is not served with a batch of B > 1 or a prepared buffer%s");
     out->num_rendered = 0; out->binning = nullptr; out->binning_bytes = 0; out->binning_capacity = 0;
-    out->forward_flags = pack_fwd_flags(opt_ppt, opt_map, opt_ckpt);
+    out->forward_flags = pack_fwd_flags(opt_ppt, opt_map, opt_ckpt) | (ro ? GSR_FWD_FLAG_RENDER_ONLY : 0);
     uint64_t R = 0;
     BlendBalance bb = {};   // filled in front of k_tile_counts (whose extra workgroups build the placement the blend reads)
     ListCut lc = {};        // filled with it: the list cut lives in the same per-frame cache
     uint64_t lc_capacity = 0;   // capacity of the last launch_binning (the repair pass scatters against the same)
     Splat* splat = static_cast<Splat*>(a->geom);
     float* img = static_cast<float*>(a->image);
-    uint32_t* staged = reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(a->image) + image_staged_offset(W, H, NB));
+    // image workspace: the caller's (state planes | balanced-placement table | staged counters), or -- a render-only call without one --
+    // scratch of the library's own: through the lean kernel the table and the counters alone (the clears that ride in k_block_scan /
+    // k_chunk_scan2 and the builder of the table write there), under "blend_fwd_ppt" 6 the whole layout (the existing kernel fills it)
+    const bool lean = ro && opt_ppt == 7;
+    uint8_t* img_base = static_cast<uint8_t*>(a->image);
+    size_t balance_off = image_balance_offset(W, H, NB), staged_off = image_staged_offset(W, H, NB);
+    float *ro_depth = a->out_depth, *ro_alpha = a->out_alpha;
+    uint32_t* staged = img_base ? reinterpret_cast<uint32_t*>(img_base + staged_off) : nullptr;
+    // (the staged counters of a lean call are cleared like any other forward's -- the clear rides in kernels that run anyway -- though
+    //  nothing reads them: knowingly redundant, the price of leaving k_block_scan / k_chunk_scan2 and their ZeroJobs as they are)
+    auto ro_workspace = [&]() -> int {
+        if (!ro) return GSR_OK;
+        if (!img_base) {
+            if (lean) { staged_off -= balance_off; balance_off = 0; }
+            img_base = static_cast<uint8_t*>(a->alloc(staged_off + align256((size_t)T * 16), GSR_ALLOC_SCRATCH, a->alloc_user));
+            if (!img_base) return fail(GSR_ERR_ALLOC, "image workspace allocation failed%s");
+            img = reinterpret_cast<float*>(img_base);
+            staged = reinterpret_cast<uint32_t*>(img_base + staged_off);
+        }
+        if (!lean && !ro_depth) {   // (the existing kernel writes both planes)
+            ro_depth = static_cast<float*>(a->alloc(2 * align256((size_t)W * H * 4), GSR_ALLOC_SCRATCH, a->alloc_user));
+            if (!ro_depth) return fail(GSR_ERR_ALLOC, "depth / alpha scratch allocation failed%s");
+            ro_alpha = ro_depth + align256((size_t)W * H * 4) / 4;
+        }
+        if (!splat && N > 0) {
+            splat = static_cast<Splat*>(a->alloc(gsr_geom_bytes(N), GSR_ALLOC_SCRATCH, a->alloc_user));
+            if (!splat) return fail(GSR_ERR_ALLOC, "splat record allocation failed%s");
+        }
+        return GSR_OK;
+    };
     const FwdScratch L = fwd_scratch_layout(N);
     uint8_t* fs = nullptr;
     uint32_t* sorted_gid = nullptr;
@@ -4662,7 +4737,8 @@ int gsr_forward(const GsrForwardArgs* a, GsrForwardOut* out, void* stream_)
     uint2 *pairs = nullptr, *pairs_alt = nullptr;
     auto alloc_binning = [&](uint64_t capacity) -> int {
         B = bin_layout((int64_t)capacity, W, H, NB);
-        bin = static_cast<uint8_t*>(a->alloc(B.bytes, GSR_ALLOC_BINNING, a->alloc_user));
+        // (render-only: ranges and list alone -- the head of the layout, up to where the checkpoints would start -- as scratch)
+        bin = static_cast<uint8_t*>(ro ? a->alloc(B.ckpt, GSR_ALLOC_SCRATCH, a->alloc_user) : a->alloc(B.bytes, GSR_ALLOC_BINNING, a->alloc_user));
         if (!bin) return fail(GSR_ERR_ALLOC, "binning allocation failed%s");
         ranges = reinterpret_cast<uint2*>(bin + B.ranges);
         list = reinterpret_cast<uint32_t*>(bin + B.list);
@@ -4763,27 +4839,29 @@ int gsr_forward(const GsrForwardArgs* a, GsrForwardOut* out, void* stream_)
     auto launch_blend = [&](bool prezeroed) -> int {
         const int ppt = opt_ppt;   // default 7: one wave per 8x8 sub-tile, sign-encoded done + sub-tile reach bits (6: without the bits)
         if (!prezeroed) GSR_HIP(hipMemsetAsync(staged, 0, (size_t)T * 16, st));
-        float* ckpt = reinterpret_cast<float*>(bin + B.ckpt);
+        float* ckpt = ro ? nullptr : reinterpret_cast<float*>(bin + B.ckpt);
+        // the default kernel, or the render-only one with or without depth / alpha: one parameter list
+        auto k7 = lean ? (a->out_depth ? k_blend_fwd_render<true> : k_blend_fwd_render<false>) : k_blend_fwd_w6<true>;
         if (ppt == 7 && g_profile && (g_profile != 3 || g_profile_tick.fetch_add(1u) % 3u == 0u)) {
             // timed launch of the default kernel (bench.py's in-run roofline timing): the dispatch's OWN start / stop timestamps
             // (hipExtLaunchKernelGGL) instead of an event record in front of and behind it -- each of those is a barrier packet that
             // idles the queue for ~6 us (tools/api_timeline.sh: 12 us per step of the timed region went to the measurement)
             hipEvent_t ea = nullptr, eb = nullptr;
             if (hipEventCreate(&ea) != hipSuccess || hipEventCreate(&eb) != hipSuccess) return fail(GSR_ERR_HIP, "hipEventCreate failed%s");
-            hipExtLaunchKernelGGL(k_blend_fwd_w6<true>, dim3(8 * 4 * slots_per_xcd(opt_map, T, tiles_x)), dim3(64), 0, st, ea, eb, 0, W, H, tiles_x, T, ranges, list,
-                                  splat, a->bg, a->out_color, a->out_depth, a->out_alpha, img, staged, opt_map, ckpt, opt_ckpt, tiles_y, bb, a->out_color_clamped,
+            hipExtLaunchKernelGGL(k7, dim3(8 * 4 * slots_per_xcd(opt_map, T, tiles_x)), dim3(64), 0, st, ea, eb, 0, W, H, tiles_x, T, ranges, list,
+                                  splat, a->bg, a->out_color, ro_depth, ro_alpha, img, staged, opt_map, ckpt, opt_ckpt, tiles_y, bb, a->out_color_clamped,
                                   lc, lc.key ? 1 : 0);
             std::lock_guard<std::mutex> lk(g_prof_mutex);
             g_prof_events[P_BLEND_FWD].push_back({ea, eb});
         } else {
             ProfScope ps(ppt == 7 && g_profile == 3 ? P_COUNT : P_BLEND_FWD, st);   // (mode 3, an untimed launch: no events)
             if (ppt == 7)
-                hipLaunchKernelGGL(k_blend_fwd_w6<true>, dim3(8 * 4 * slots_per_xcd(opt_map, T, tiles_x)), dim3(64), 0, st, W, H, tiles_x, T, ranges, list, splat, a->bg,
-                                   a->out_color, a->out_depth, a->out_alpha, img, staged, opt_map, ckpt, opt_ckpt, tiles_y, bb, a->out_color_clamped,
+                hipLaunchKernelGGL(k7, dim3(8 * 4 * slots_per_xcd(opt_map, T, tiles_x)), dim3(64), 0, st, W, H, tiles_x, T, ranges, list, splat, a->bg,
+                                   a->out_color, ro_depth, ro_alpha, img, staged, opt_map, ckpt, opt_ckpt, tiles_y, bb, a->out_color_clamped,
                                    lc, lc.key ? 1 : 0);
             else
                 hipLaunchKernelGGL(k_blend_fwd_w6<false>, dim3(8 * 4 * slots_per_xcd(opt_map, T, tiles_x)), dim3(64), 0, st, W, H, tiles_x, T, ranges, list, splat, a->bg,
-                                   a->out_color, a->out_depth, a->out_alpha, img, staged, opt_map, ckpt, opt_ckpt, tiles_y, BlendBalance{}, a->out_color_clamped);
+                                   a->out_color, ro_depth, ro_alpha, img, staged, opt_map, ckpt, opt_ckpt, tiles_y, BlendBalance{}, a->out_color_clamped);
         }
         if (ppt == 7 && lc.key && lc_capacity > 0) {
             // the repair pass of the list cut: the same scatter over the chunks behind the flagged tiles' cuts and the same blend over
@@ -4801,23 +4879,26 @@ int gsr_forward(const GsrForwardArgs* a, GsrForwardOut* out, void* stream_)
     };
 
     if (N == 0) {
+        rc = ro_workspace();
+        if (rc) return rc;
         rc = alloc_binning(0);
         if (rc) return rc;
         rc = launch_binning(0, nullptr, false);
         if (rc) return rc;
         rc = launch_blend(false);
         if (rc) return rc;
-        out->binning = bin;
-        out->binning_bytes = B.bytes;
+        if (!ro) { out->binning = bin; out->binning_bytes = B.bytes; }
         return GSR_OK;
     }
 
-    if (!a->means3D || !a->opacities || !a->geom || !a->radii || !a->viewmatrix || !a->projmatrix)
+    if (!a->means3D || !a->opacities || (!ro && !a->geom) || !a->radii || !a->viewmatrix || !a->projmatrix)
         return fail(GSR_ERR_ARG, "missing input pointer%s");
     if ((a->shs == nullptr) == (a->colors_precomp == nullptr)) return fail(GSR_ERR_ARG, "provide exactly one of shs / colors_precomp%s");
     if ((a->cov3D_precomp == nullptr) == (a->scales == nullptr || a->rotations == nullptr))
         return fail(GSR_ERR_ARG, "provide exactly one of (scales, rotations) / cov3D_precomp%s");
     if (a->shs && (!a->campos || a->M < (a->D + 1) * (a->D + 1))) return fail(GSR_ERR_ARG, "shs needs campos and M >= (D+1)^2%s");
+    rc = ro_workspace();
+    if (rc) return rc;
 
     // ---- the instance count R only exists on the device.  Classic flow: read it back, synchronise, size the
     // R-dependent buffers and grids exactly.  That puts a host round trip (~35 us of idle GPU per frame) in the middle
@@ -5024,7 +5105,7 @@ int gsr_forward(const GsrForwardArgs* a, GsrForwardOut* out, void* stream_)
                     }
                 }
                 if (mem) {
-                    uint8_t* ib = static_cast<uint8_t*>(a->image) + image_balance_offset(W, H, NB);
+                    uint8_t* ib = img_base + balance_off;
                     bb.hdr = reinterpret_cast<ViewCostHdr*>(mem);
                     bb.cost = reinterpret_cast<uint16_t*>(mem + hdr_bytes);
                     bb.cur = reinterpret_cast<uint32_t*>(ib);
@@ -5033,7 +5114,8 @@ int gsr_forward(const GsrForwardArgs* a, GsrForwardOut* out, void* stream_)
                     bb.tol = 1e-6f * (float)g_view_pose_tol_e6;
                     bb.items = items; bb.nslots4 = nslots4; bb.W = W; bb.H = H;
                     // the list cut: the plain direct binning behind a global depth sort, one model, the default blend
-                    if (direct && !tsort && db.NC <= 16000 && T == db.T && (g_list_cut == 2 || (g_list_cut == 1 && N >= g_list_cut_min_n))) {
+                    // (not under a render-only call: the cut's repair pass reads state that call does not keep)
+                    if (!ro && direct && !tsort && db.NC <= 16000 && T == db.T && (g_list_cut == 2 || (g_list_cut == 1 && N >= g_list_cut_min_n))) {
                         uint8_t* dm = fs + align256(L.bytes);
                         lc.key = reinterpret_cast<uint32_t*>(mem + vc_cut);
                         lc.owner_n = reinterpret_cast<uint32_t*>(mem + vc_own);
@@ -5154,6 +5236,7 @@ int gsr_forward(const GsrForwardArgs* a, GsrForwardOut* out, void* stream_)
         if (g_hints.size() > 4096) g_hints.clear();   // (a runaway number of distinct callers: start over)
     }
     out->num_rendered = (int64_t)R;
+    if (ro) return GSR_OK;   // (binning NULL, its size and capacity 0, the flags with the render-only bit: set on entry)
     out->binning = bin;
     out->binning_bytes = B.bytes;
     out->binning_capacity = (int64_t)((speculative && R <= cap && !resorted) ? cap : R);
@@ -5184,6 +5267,8 @@ int gsr_backward(const GsrBackwardArgs* a, void* stream_)
     CallTimer call_timer(g_bwd_calls, g_bwd_ns);
     hipStream_t st = (hipStream_t)stream_;
     if (!a) return fail(GSR_ERR_ARG, "null args%s");
+    if (a->forward_flags & GSR_FWD_FLAG_RENDER_ONLY)
+        return fail(GSR_ERR_ARG, "gsr_backward: forward_flags come from a render-only forward, which keeps nothing a backward could read%s");
     int rc = check_common(a->N, a->M, a->D, a->W, a->H);
     if (rc) return rc;
     const int N = a->N, W = a->W, H = a->H;
@@ -5498,6 +5583,8 @@ int gsr_importance_accumulate(const GsrForwardArgs* a, const GsrForwardOut* out,
 {
     hipStream_t st = (hipStream_t)stream_;
     if (!a || !out) return fail(GSR_ERR_ARG, "null args%s");
+    if (out->forward_flags & GSR_FWD_FLAG_RENDER_ONLY)
+        return fail(GSR_ERR_ARG, "importance: forward_flags come from a render-only forward, which keeps no image state or lists for the pass%s");
     int rc = check_common(a->N, a->M, a->D, a->W, a->H);
     if (rc) return rc;
     if (a->colors_precomp || !a->shs) return fail(GSR_ERR_ARG, "importance: the model must carry SH coefficients (colors_precomp has none)%s");

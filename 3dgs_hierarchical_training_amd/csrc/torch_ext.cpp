@@ -11,6 +11,7 @@
 //   gsr::rasterize_backward   -> gsr_backward
 //   gsr::rasterize_backward_frozen -> gsr_backward, the frozen call: camera / points_transform gradients alone
 //   gsr::rasterize_backward_fused  -> gsr_backward with the in-kernel Adam step (parameters / moments updated in place)
+//   gsr::render               -> gsr_forward, the render-only call: an image, nothing kept, no autograd
 //   gsr::mark_visible         -> gsr_mark_visible
 //   gsr::importance_accumulate -> gsr_forward + gsr_importance_accumulate (merge-time colour importance, no backward)
 //   gsr::importance_pass      -> gsr_importance_accumulate over a rasterize_forward's outputs
@@ -652,6 +653,60 @@ std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> rasterize_for
             std::get<9>(out)};
 }
 
+// gsr::render -> gsr_forward with GsrForwardArgs::render_only = 1 (include/gsr.h, version 116): the image of a model nobody will run a
+// backward over -- a frozen teacher, an evaluation view.  No autograd registration and nothing saved: geom / image are NULL, so the
+// library takes its splat records, its list and its counters as scratch that dies with this call, and what the allocator holds
+// afterwards are the outputs.  outputs: bit 0 = depth + alpha, bit 1 = the clamped colour, bit 2 = the visibility bytes.
+// Returns (color, radii, depth, alpha, clamped, visible), empty tensors for what was not asked.  g_last is left alone: last_call_info()
+// and last_binning() keep describing the last FULL forward.
+std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> render(
+    const Tensor& means3D_, const Tensor& sh_, const Tensor& colors_, const Tensor& opacities_, const Tensor& scales_,
+    const Tensor& rotations_, const Tensor& cov3D_, const Tensor& sh_rest_, const Tensor& viewmatrix_, const Tensor& projmatrix_,
+    const Tensor& campos_, const Tensor& bg_, const Tensor& xf_, int64_t H, int64_t W, double tanfovx, double tanfovy,
+    double scale_modifier, int64_t sh_degree, bool raw_params, int64_t view_id, int64_t outputs, const c10::optional<Tensor>& sh_origin_)
+{
+    TORCH_CHECK(means3D_.is_cuda(), "render: tensors must be on a ROCm/HIP device (no CPU fallback)");
+    const c10::hip::HIPGuardMasqueradingAsCUDA guard(means3D_.device());
+    const Tensor means3D = f32c(means3D_.detach()), sh = f32c(sh_.detach()), colors = f32c(colors_.detach()), opac = f32c(opacities_.detach()),
+                 scales = f32c(scales_.detach()), rots = f32c(rotations_.detach()), cov = f32c(cov3D_.detach()), rest = f32c(sh_rest_.detach()),
+                 vm = f32c(viewmatrix_.detach()), pm = f32c(projmatrix_.detach()), campos = f32c(campos_.detach()), bg = f32c(bg_.detach()),
+                 xf = f32c(((has(xf_) && xf_.dim() == 2) ? xf_.slice(0, 0, 3) : xf_).detach());
+    const Tensor sh_origin = sh_origin_arg(sh_origin_);
+    const int64_t N = means3D.size(0);
+    const int64_t M = has(sh) ? sh.size(1) + (has(rest) ? rest.size(1) : 0) : 0;
+    const auto fo = means3D.options().dtype(at::kFloat);
+    const auto bo = means3D.options().dtype(at::kByte);
+    Tensor color = at::empty({3, H, W}, fo);
+    Tensor depth = (outputs & 1) ? at::empty({1, H, W}, fo) : at::empty({0}, fo);
+    Tensor alpha = (outputs & 1) ? at::empty({1, H, W}, fo) : at::empty({0}, fo);
+    Tensor clamped = (outputs & 2) ? at::empty({3, H, W}, fo) : at::empty({0}, fo);
+    Tensor visible = (outputs & 4) ? at::empty({N}, bo) : at::empty({0}, bo);
+    Tensor radii = at::empty({N}, means3D.options().dtype(at::kInt));
+    AllocCtx actx{bo, Tensor(), {}};
+
+    GsrForwardArgs a{};
+    a.N = (int32_t)N; a.M = (int32_t)M; a.D = (int32_t)sh_degree; a.W = (int32_t)W; a.H = (int32_t)H;
+    a.scale_modifier = (float)scale_modifier; a.tanfovx = (float)tanfovx; a.tanfovy = (float)tanfovy;
+    a.means3D = fp(means3D); a.scales = fp(scales); a.rotations = fp(rots); a.cov3D_precomp = fp(cov);
+    a.opacities = fp(opac); a.shs = fp(sh); a.colors_precomp = fp(colors);
+    a.viewmatrix = fp(vm); a.projmatrix = fp(pm); a.campos = fp(campos); a.bg = fp(bg);
+    a.out_color = color.data_ptr<float>(); a.out_depth = fpm(depth); a.out_alpha = fpm(alpha);
+    a.radii = N ? radii.data_ptr<int32_t>() : nullptr;
+    a.alloc = alloc_cb; a.alloc_user = &actx;
+    a.shs_rest = fp(rest); a.raw_params = raw_params;
+    a.points_transform = fp(xf);
+    a.view_id = view_id;
+    a.sh_origin = fp(sh_origin);
+    a.out_color_clamped = fpm(clamped);
+    a.visible = has(visible) ? visible.data_ptr<uint8_t>() : nullptr;
+    a.render_only = 1;
+    GsrForwardOut out{};
+    check(gsr_forward(&a, &out, c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream()), "gsr_forward");
+    TORCH_CHECK(!actx.binning.defined() && out.binning == nullptr, "render: a render-only forward asked for a binning buffer");
+    // (every scratch tensor dies here: stream-ordered reuse by the caching allocator is safe, same stream)
+    return {color, radii, depth, alpha, clamped, visible};
+}
+
 // ---------------------------------------------------------------------------------------------------------------
 Tensor mark_visible(const Tensor& means3D_, const Tensor& vm_, const Tensor& pm_)
 {
@@ -1165,6 +1220,10 @@ TORCH_LIBRARY(gsr, m)
           "int next_width, float next_tanfovx, float next_tanfovy, Tensor next_points_transform, int next_sh_degree, Tensor adam_commit, Tensor[] densify_stats, int[] batch_first_block, int view_id=0, int extras=0, "
           "Tensor? sh_origin=None, int frozen=-1) -> "
           "(Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)");
+    m.def("render(Tensor means3D, Tensor sh, Tensor colors_precomp, Tensor opacities, Tensor scales, Tensor rotations, Tensor cov3D_precomp, "
+          "Tensor sh_rest, Tensor viewmatrix, Tensor projmatrix, Tensor campos, Tensor bg, Tensor points_transform, int image_height, "
+          "int image_width, float tanfovx, float tanfovy, float scale_modifier, int sh_degree, bool raw_params, int view_id=0, int outputs=0, "
+          "Tensor? sh_origin=None) -> (Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)");
     m.def("importance_accumulate(Tensor(a!) acc, Tensor means3D, Tensor sh, Tensor colors_precomp, Tensor opacities, Tensor scales, "
           "Tensor rotations, Tensor cov3D_precomp, Tensor sh_rest, Tensor viewmatrix, Tensor projmatrix, Tensor campos, Tensor bg, "
           "Tensor points_transform, int image_height, int image_width, float tanfovx, float tanfovy, float scale_modifier, int sh_degree, "
@@ -1206,6 +1265,7 @@ TORCH_LIBRARY_IMPL(gsr, CUDA, m)   // the dispatch key of HIP tensors on a ROCm 
     m.impl("rasterize_backward", &rasterize_backward);
     m.impl("rasterize_backward_fused", &rasterize_backward_fused);
     m.impl("rasterize_backward_frozen", &rasterize_backward_frozen);
+    m.impl("render", &render);
     m.impl("importance_accumulate", &importance_accumulate);
     m.impl("importance_pass", &importance_pass);
     m.impl("mark_visible", &mark_visible);

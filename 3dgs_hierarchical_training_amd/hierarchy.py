@@ -18,7 +18,7 @@ from typing import Dict, List, Optional
 import torch
 
 from . import segments
-from .rasterizer import GaussianRasterizationSettings, importance_accumulate, rasterize_gaussians_raw
+from .rasterizer import GaussianRasterizationSettings, importance_accumulate, rasterize_gaussians_raw, render_gaussians_raw
 
 
 def _elapsed_ms(t0: float, ref: torch.Tensor) -> float:
@@ -29,11 +29,10 @@ def _elapsed_ms(t0: float, ref: torch.Tensor) -> float:
 
 def render_raw(seg: Dict[str, torch.Tensor], rs: GaussianRasterizationSettings) -> torch.Tensor:
     """Clamped image of a frozen model given by its six raw tensors (the teacher render of :877-883)."""
-    with torch.no_grad():
-        m2d = torch.zeros_like(seg["_xyz"])
-        color = rasterize_gaussians_raw(seg["_xyz"], m2d, seg["_features_dc"], seg["_features_rest"], seg["_opacity"],
-                                        seg["_scaling"], seg["_rotation"], rs)[0]
-        return color.clamp(0, 1)
+    # the render-only forward: the kernel's own clamped image (bit-identical with `color.clamp(0, 1)`, NaN stays NaN), no zero means2D,
+    # no state planes, checkpoints or binning buffer behind it -- nobody runs a backward over a teacher
+    return render_gaussians_raw(seg["_xyz"], seg["_features_dc"], seg["_features_rest"], seg["_opacity"], seg["_scaling"],
+                                seg["_rotation"], rs, clamped=True)[4]
 
 
 # Which route calc_importance takes when its caller names none: "kernel" (a forward and the importance pass per view, include/gsr.h

@@ -556,6 +556,98 @@ def rasterize_gaussians_raw(means3D, means2D, features_dc, features_rest, opacit
                                      frozen)
 
 
+def _render_only(means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, rs, sh_rest, raw_params, depth_alpha, clamped,
+                 visible, points_transform, view_id, sh_origin):
+    """The render-only forward (include/gsr.h GsrForwardArgs::render_only) on either binding: (color, radii, depth, alpha, clamped,
+    visible), None for what was not asked.  Nothing of the call but these tensors stays allocated."""
+    dev = means3D.device
+    if dev.type != "cuda":
+        raise RuntimeError("render_gaussians: tensors must be on a ROCm/HIP device (no CPU fallback)")
+    if points_transform is not None and tuple(points_transform.shape) not in ((3, 4), (4, 4)):
+        raise RuntimeError("points_transform must be a [3,4] or [4,4] tensor")
+    if sh_origin is not None and (sh_origin.numel() != 3 or _empty_to_none(sh) is None):
+        raise RuntimeError("sh_origin must hold three numbers (the origin of the SH view direction) and needs SH coefficients")
+    H, W = int(rs.image_height), int(rs.image_width)
+    with torch.no_grad():
+        if not E.use_ctypes():
+            ops = E.load()
+            e = _e(dev)
+            pick = lambda t: e if (t is None or t.numel() == 0) else t.detach()
+            if sh_origin is not None:
+                sh_origin = sh_origin.detach().to(device=dev, dtype=torch.float32).reshape(3)
+            xf = e if points_transform is None else points_transform.detach().to(dev)
+            color, radii, depth, alpha, cl, vis = ops.render(
+                means3D.detach(), pick(sh), pick(colors_precomp), opacities.detach(), pick(scales), pick(rotations), pick(cov3Ds_precomp),
+                pick(sh_rest), rs.viewmatrix.detach().to(dev), rs.projmatrix.detach().to(dev), rs.campos.detach().to(dev), rs.bg.detach().to(dev), xf,
+                H, W, float(rs.tanfovx), float(rs.tanfovy), float(rs.scale_modifier), int(rs.sh_degree), bool(raw_params), int(view_id),
+                (1 if depth_alpha else 0) | (2 if clamped else 0) | (4 if visible else 0), sh_origin)
+            return (color, radii, depth if depth_alpha else None, alpha if depth_alpha else None, cl if clamped else None,
+                    vis if visible else None)
+        # the plain-FFI route over the same C ABI: render_only = 1, geom = image = NULL, every buffer the library asks for is scratch
+        if sh_origin is not None:
+            raise RuntimeError("sh_origin is served by the PyTorch extension binding only")
+        lib = L.load()
+        means3D = _f32c(means3D.detach())
+        N = means3D.shape[0]
+        prep = lambda t: _f32c(_empty_to_none(None if t is None else t.detach()))
+        sh, colors_precomp, scales, rotations = prep(sh), prep(colors_precomp), prep(scales), prep(rotations)
+        cov3Ds_precomp, sh_rest, opacities = prep(cov3Ds_precomp), prep(sh_rest), _f32c(opacities.detach())
+        vm, pm, campos, bg = (_f32c(t.detach().to(dev)) for t in (rs.viewmatrix, rs.projmatrix, rs.campos, rs.bg))
+        xf = None if points_transform is None else _f32c(points_transform.detach().to(dev)[:3])
+        M = (int(sh.shape[1]) + (int(sh_rest.shape[1]) if sh_rest is not None else 0)) if sh is not None else 0
+        new = lambda shape, dtype=torch.float32: torch.empty(shape, dtype=dtype, device=dev)
+        color, radii = new((3, H, W)), new((N,), torch.int32)
+        depth, alpha = (new((1, H, W)), new((1, H, W))) if depth_alpha else (None, None)
+        cl = new((3, H, W)) if clamped else None
+        vis = new((N,), torch.uint8) if visible else None
+        ws = _Workspace(dev)
+        a = L.GsrForwardArgs()
+        a.N, a.M, a.D, a.W, a.H = N, M, int(rs.sh_degree), W, H
+        a.scale_modifier, a.tanfovx, a.tanfovy = float(rs.scale_modifier), float(rs.tanfovx), float(rs.tanfovy)
+        a.means3D, a.scales, a.rotations, a.cov3D_precomp = _ptr(means3D), _ptr(scales), _ptr(rotations), _ptr(cov3Ds_precomp)
+        a.opacities, a.shs, a.colors_precomp = _ptr(opacities), _ptr(sh), _ptr(colors_precomp)
+        a.viewmatrix, a.projmatrix, a.campos, a.bg = _ptr(vm), _ptr(pm), _ptr(campos), _ptr(bg)
+        a.out_color, a.out_depth, a.out_alpha, a.radii = color.data_ptr(), _ptr(depth), _ptr(alpha), _ptr(radii)
+        a.geom, a.image = None, None
+        a.alloc, a.alloc_user = ws.cb, None
+        a.shs_rest, a.raw_params = _ptr(sh_rest), int(bool(raw_params))
+        a.points_transform = _ptr(xf)
+        a.view_id = int(view_id)
+        a.out_color_clamped, a.visible = _ptr(cl), _ptr(vis)
+        a.render_only = 1
+        out = L.GsrForwardOut()
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            L.check(lib.gsr_forward(C.byref(a), C.byref(out), C.c_void_p(stream)), "gsr_forward")
+        if ws.binning is not None or out.binning or not (int(out.forward_flags) & L.GSR_FWD_FLAG_RENDER_ONLY):
+            raise RuntimeError("render_gaussians: the library did not take the render-only route")
+        ws.scratch.clear()  # stream-ordered reuse by the caching allocator is safe: same stream
+        return color, radii, depth, alpha, cl, vis
+
+
+def render_gaussians(means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings, depth_alpha=False,
+                     clamped=False, visible=False, points_transform=None, view_id=0, sh_origin=None):
+    """The image of a model that no backward will ever visit -- a frozen teacher (/root/reference/trainer/ht3dgs_trainer.py:877-883), an
+    evaluation or novel-view render (:1050-1061) -- through the render-only forward (include/gsr.h GsrForwardArgs::render_only,
+    torch.ops.gsr.render): the inputs of rasterize_gaussians without means2D and the training keywords.  No autograd (inputs are
+    detached), no state planes, checkpoints or binning buffer: when the call returns the allocator holds the returned tensors and
+    nothing else of it.  Returns (color, radii, depth, alpha, clamped, visible): depth / alpha [1,H,W] with depth_alpha=True, the
+    clamped colour `clamp(color, 0, 1)` with clamped=True, the visibility bytes `radii > 0` (uint8 [N]) with visible=True, None for
+    what was not asked.  Every returned tensor is bit-identical with the full forward's.  points_transform, view_id, sh_origin: as in
+    rasterize_gaussians_raw (sh_origin: extension binding only).  last_call_info() / last_binning() keep describing the last full
+    forward: this call leaves them nothing to read."""
+    return _render_only(means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings, None, False,
+                        depth_alpha, clamped, visible, points_transform, view_id, sh_origin)
+
+
+def render_gaussians_raw(means3D, features_dc, features_rest, opacity_logit, log_scales, rotations_raw, raster_settings, depth_alpha=False,
+                         clamped=False, visible=False, points_transform=None, view_id=0, sh_origin=None):
+    """render_gaussians straight from HTGaussianModel's raw parameters (the inputs of rasterize_gaussians_raw without means2D and the
+    training keywords; the activations run in-kernel)."""
+    return _render_only(means3D, features_dc, None, opacity_logit, log_scales, rotations_raw, None, raster_settings, features_rest, True,
+                        depth_alpha, clamped, visible, points_transform, view_id, sh_origin)
+
+
 def importance_accumulate(acc, means3D, sh, opacities, scales, rotations, raster_settings, sh_rest=None, raw_params=False,
                           cov3Ds_precomp=None, colors_precomp=None, points_transform=None, view_id=0, sh_origin=None,
                           batch_first_block=None):

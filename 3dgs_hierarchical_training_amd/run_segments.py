@@ -328,7 +328,7 @@ class RankRunner:
         seg, tot = self.seg, 0.0
         with torch.no_grad():
             for f in seg.frames:
-                img = ts.render(seg.params, self._settings(seg, f))["image"]
+                img = ts.render_image(seg.params, self._settings(seg, f))[0]     # (the render-only forward: nothing kept behind the image)
                 mse = ((img - self.seq.target(f)) ** 2).mean().clamp_min(1e-12)
                 tot += float(-10.0 * torch.log10(mse))
         return tot / len(seg.frames)

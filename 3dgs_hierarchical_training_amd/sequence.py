@@ -93,8 +93,7 @@ class FrameSequence:
             from . import train_step as ts
             if self._gt_params is None:
                 self._gt_params = ts.GaussianParams(self.gt_scene, self.device, optimizer="torch")
-            with torch.no_grad():
-                self._targets[f] = ts.render(self._gt_params, self.settings_for_pose(self.w2c[f]))["image"].clone()
+            self._targets[f] = ts.render_image(self._gt_params, self.settings_for_pose(self.w2c[f]))[0]     # (render-only: the image alone)
         return self._targets[f]
 
     # ---- leaf initialisation -----------------------------------------------------------------------------------------
@@ -107,8 +106,8 @@ class FrameSequence:
         if self._gt_params is None:
             self._gt_params = ts.GaussianParams(self.gt_scene, self.device, optimizer="torch")
         with torch.no_grad():
-            pkg = ts.render(self._gt_params, self.settings_for_pose(self.w2c[f]))
-            cache[f] = (pkg["depth"][0] / pkg["alpha"][0].clamp_min(1e-3)).clone()
+            _, depth, alpha = ts.render_image(self._gt_params, self.settings_for_pose(self.w2c[f]), depth_alpha=True)
+            cache[f] = depth[0] / alpha[0].clamp_min(1e-3)
         return cache[f]
 
     def pixel_scene(self, f: int, stride: int = 2, seed: int = 0, depth_noise: float = 0.02) -> Dict:

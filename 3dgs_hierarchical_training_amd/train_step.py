@@ -18,7 +18,7 @@ import torch.nn.functional as F
 from ._ext import use_ctypes as E_use_ctypes
 from .loss import DEPTH_CLAMP, fused_depth_loss, fused_photometric_loss, fused_training_loss_report
 from .optim import FusedAdam
-from .rasterizer import GaussianRasterizationSettings, GaussianRasterizer, rasterize_gaussians_raw
+from .rasterizer import GaussianRasterizationSettings, GaussianRasterizer, rasterize_gaussians_raw, render_gaussians
 
 
 def inverse_sigmoid(x):
@@ -434,6 +434,19 @@ def render(params: GaussianParams, settings: GaussianRasterizationSettings, clam
     rendered_image, radii, rendered_depth, rendered_alpha = out
     return _LazyVisibility({"image": rendered_image.clamp(0, 1) if clamp else None, "raw_image": rendered_image,
                             "depth": rendered_depth, "alpha": rendered_alpha, "viewspace_points": screenspace_points, "radii": radii})
+
+
+def render_image(params: GaussianParams, settings: GaussianRasterizationSettings, depth_alpha: bool = False):
+    """The clamped image of a model nobody will run a backward over -- an evaluation view, a ground-truth target -- through the
+    render-only forward (rasterizer.render_gaussians: no state planes, checkpoints or binning buffer behind it).  Returns (image, depth,
+    alpha); depth / alpha are None unless asked for.  Bit-identical with `render(params, settings)` under torch.no_grad(): the same
+    activated tensors, the model's ACTIVE SH degree, the kernel's own clamp.  `render` itself is unchanged, under no_grad too:
+    last_call_info() / last_binning() describe ITS forwards, and this call leaves them nothing to read."""
+    settings = with_sh_degree(settings, params.active_sh_degree)
+    with torch.no_grad():
+        _, _, depth, alpha, image, _ = render_gaussians(params.get_xyz, params.get_features, None, params.get_opacity, params.get_scaling,
+                                                        params.get_rotation, None, settings, depth_alpha=depth_alpha, clamped=True)
+    return image, depth, alpha
 
 
 def _camera_versions(rs) -> tuple:

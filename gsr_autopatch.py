@@ -481,9 +481,17 @@ def render_fused(self, viewpoint_camera, scaling_modifier=1.0, invert_bg_color=F
     if _ext_binding() and os.environ.get("GSR_AUTOPATCH_EXTRAS", "1") != "0":
         # the clamped image and the visibility bytes come out of the kernels that hold the values (the blend's epilogue, the preprocess):
         # no torch launch for `clamp(0, 1)` / `radii > 0`
-        image_raw, radii, depth, alpha, image, vis8 = R.rasterize_gaussians_raw(
-            xyz, screenspace_points, f_dc, f_rest, opacity, scaling, rotation, settings, points_transform=M, fused_adam=opt if deferred else None,
-            fused_adam_deferred=deferred, view_id=_view_id(viewpoint_camera, g), extras=3, sh_origin=sh_origin)
+        if not torch.is_grad_enabled():
+            # a render no backward can follow -- the frozen teacher (trainer/ht3dgs_trainer.py:877-883), eval_nvs (:1050-1061),
+            # evaluate_on_training_images, render_nvs, all under torch.no_grad(): the render-only forward, the same six tensors bit for
+            # bit and no state, checkpoint or binning buffer behind them
+            image_raw, radii, depth, alpha, image, vis8 = R.render_gaussians_raw(
+                xyz, f_dc, f_rest, opacity, scaling, rotation, settings, depth_alpha=True, clamped=True, visible=True, points_transform=M,
+                view_id=_view_id(viewpoint_camera, g), sh_origin=sh_origin)
+        else:
+            image_raw, radii, depth, alpha, image, vis8 = R.rasterize_gaussians_raw(
+                xyz, screenspace_points, f_dc, f_rest, opacity, scaling, rotation, settings, points_transform=M, fused_adam=opt if deferred else None,
+                fused_adam_deferred=deferred, view_id=_view_id(viewpoint_camera, g), extras=3, sh_origin=sh_origin)
         visible = vis8.view(torch.bool) if vis8.numel() == radii.numel() else radii > 0
     else:
         image_raw, radii, depth, alpha = R.rasterize_gaussians_raw(xyz, screenspace_points, f_dc, f_rest, opacity, scaling, rotation,

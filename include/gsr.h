@@ -124,7 +124,29 @@ typedef struct GsrForwardArgs {
      * (GSR_ERR_ARG) with a batch of B > 1 or a `prepared` buffer.  At sh_degree 0 the colour does not depend on the direction: the
      * result is bit-identical to NULL. */
     const float* sh_origin;
+    /* ---- version 116: the RENDER-ONLY call -- an image is asked for and nothing else outlives the call.  0 = the call as above, byte for
+     * byte.  Callers that can never reach a backward: the frozen teacher of every virtual-view iteration of train_nonleaf_3DGS_phase1
+     * (/root/reference/trainer/ht3dgs_trainer.py:877-883), the eval_nvs loop (:1050-1061), evaluate_on_training_images and render_nvs, all
+     * under torch.no_grad() through CF3DGS_Render.render (/root/reference/scene/gaussian_model_ht.py:881-894).  With render_only = 1:
+     *   out_color is required; out_depth and out_alpha are given BOTH or NEITHER (one without the other: GSR_ERR_ARG);
+     *   out_color_clamped, visible, radii, points_transform, sh_origin, view_id, raw_params, shs_rest, colors_precomp, cov3D_precomp as above;
+     *   geom and image may be NULL: the library then takes the splat records (gsr_geom_bytes(N)) and a short image workspace -- the
+     *     balanced-placement table and the staged counters, no pixel state -- through alloc(..., GSR_ALLOC_SCRATCH, ...);
+     *   the R-sized buffer holds the list and the ranges only (4 R + 8 T bytes) and also comes under GSR_ALLOC_SCRATCH: nothing is
+     *     requested under GSR_ALLOC_BINNING, no checkpoint is written, no per-pixel state is kept;
+     *   GsrForwardOut: num_rendered = R, binning = NULL, binning_bytes = 0, binning_capacity = 0, forward_flags carries
+     *     GSR_FWD_FLAG_RENDER_ONLY -- gsr_backward and gsr_importance_accumulate refuse such flags (GSR_ERR_ARG) before anything is
+     *     enqueued;
+     *   a batch of B > 1 and `prepared` are refused (GSR_ERR_ARG);
+     *   the list cut ("list_cut") is not taken -- its repair pass reads state this call does not keep; the image is the same either way.
+     * Capacity hints, speculative binning, the early instance count and its late check, the choice of the list-building route and the
+     * balanced placement (its view-cost cache included) are read and updated as by any other forward.  out_color, out_color_clamped,
+     * out_depth, out_alpha, radii and visible are bit-identical with the full call's: the blend is the same chain of operations in the
+     * same order with the checkpoint stores, the state planes and (without out_depth / out_alpha) the two accumulators left out. */
+    int32_t render_only;
 } GsrForwardArgs;
+
+#define GSR_FWD_FLAG_RENDER_ONLY ((int64_t)1 << 14) /* GsrForwardOut::forward_flags of a render-only forward */
 
 typedef struct GsrForwardOut {
     int64_t num_rendered; /* R: (tile, Gaussian) instances */
@@ -324,7 +346,8 @@ const char* gsr_last_error(void);
  * 112: the depth term of the loss (gsr_depth_loss_*); no struct changed.
  * 113: gsr_importance_accumulate / gsr_importance_scratch_bytes; no struct changed.
  * 114: the depth term on a stack of planes (gsr_depth_loss_*_batched); no struct changed.
- * 115: the frozen call of gsr_backward (camera / transform gradients alone, see GsrBackwardArgs); no struct changed. */
+ * 115: the frozen call of gsr_backward (camera / transform gradients alone, see GsrBackwardArgs); no struct changed.
+ * 116: GsrForwardArgs ends with render_only (the render-only call). */
 int gsr_version(void);
 size_t gsr_struct_bytes(int32_t which); /* 0 GsrForwardArgs, 1 GsrBackwardArgs, 2 GsrForwardOut; anything else 0 */
 

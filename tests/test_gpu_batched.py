@@ -48,17 +48,27 @@ def test_batched_training_equals_training_each_model_alone_on_the_default_accumu
     _batched_training_case(sizes, deg, fixed_order=False)
 
 
-def _batched_training_case(sizes, deg, fixed_order):
+def _batched_training_case(sizes, deg, fixed_order, camera=None, steps=5):
+    """camera: None = every model under synthetic.make_camera's centred camera; else camera(k) -> dict(fx, fy, cx, cy) of model k
+    (tests/camera_common.py general_scene / general_camera; the focal lengths are shared by a batch, the principal point -- which
+    lives in projmatrix alone -- need not be): tests/test_gpu_camera_intrinsics.py."""
     lib = L.load()
     dev = torch.device("cuda:0")
     W, H = 330, 250            # ragged tile grid: the last tile row / column of every image is partial
-    scenes = _scenes(sizes, W, H, deg)
+    if camera is None:
+        scenes = _scenes(sizes, W, H, deg)
+    else:
+        import camera_common
+        scenes = [camera_common.general_scene(n, W, H, deg, 40 + k, camera(k), posed=True) for k, n in enumerate(sizes)]
     B = len(sizes)
     gts = [parity.syn.target_image(W, H, seed=10 + k).to(dev) for k in range(B)]
     # two cameras per model, alternating (the hand-over always prepares the other one)
     cams = []
     for k, sc in enumerate(scenes):
         alt = parity.syn.make_scene(8, W, H, sh_degree=deg, seed=70 + k, posed=True)
+        if camera is not None:
+            w2c = alt["viewmatrix"].t()
+            alt = camera_common.general_camera(W, H, R=w2c[:3, :3], t=w2c[:3, 3], **camera(k))
         sc2 = dict(sc)
         for key in ("viewmatrix", "projmatrix", "campos"):
             sc2[key] = alt[key]
@@ -70,7 +80,7 @@ def _batched_training_case(sizes, deg, fixed_order):
         assert batch.num_points % 128 == 0 and batch.first_block[-1] * 128 == batch.num_points
         bviews = [bt.batch_settings([cams[k][v] for k in range(B)], dev) for v in range(2)]
         gt_stack = torch.stack(gts)
-        for it in range(5):
+        for it in range(steps):
             v = it % 2
             pk = ts.train_step(batch, bviews[v], gt_stack, next_settings=bviews[1 - v])
             assert pk["raw_image"].shape == (B, 3, H, W) and pk["depth"].shape == (B, 1, H, W)

@@ -55,10 +55,11 @@ class fixed_order:
         L.load().gsr_set_option(b"deterministic_backward", 0)
 
 
-def _tensors(N, deg, raw, layout, seed=5, posed=True):
+def _tensors(N, deg, raw, layout, seed=5, posed=True, sc=None):
     """Device tensors of one C-ABI case.  layout: 'split' (shs [N,1,3] + shs_rest [N,15,3], M = 16), 'single' (shs [N,(deg+1)^2,3]),
-    'pre' (colors_precomp + cov3D_precomp), 'sho' (split + sh_origin)."""
-    sc = parity.syn.make_scene(N, W, H, sh_degree=deg, seed=seed, posed=posed)
+    'pre' (colors_precomp + cov3D_precomp), 'sho' (split + sh_origin).  sc: a scene of N Gaussians at W x H to use instead of
+    make_scene's (tests/test_gpu_camera_intrinsics.py)."""
+    sc = parity.syn.make_scene(N, W, H, sh_degree=deg, seed=seed, posed=posed) if sc is None else sc
     e = torch.empty(0, device=DEV)
     t = dict(N=N, D=deg, raw=bool(raw), sc=sc, means3D=sc["means3D"].to(DEV), sh=e, rest=e, colors=e, cov=e, scales=e, rots=e, sho=None)
     t["opac"] = sc["opacities"].to(DEV)

@@ -51,41 +51,10 @@ def test_parity_vs_oracle(case):
 
 
 def _pixel_gaussian_scene(W, H, stride, surface, seed=0):
-    """A stage-A single-image model as the reference initialises it (one Gaussian per strided pixel, un-projected with the frame's
-    depth into the frame's own camera, identity rotation, footprint-sized, band 0 of 16 stored SH coefficients:
-    /root/reference/trainer/ht3dgs_trainer.py:352-363, :172-212; 3dgs_hierarchical_training_amd/sequence.py pixel_scene) -- built on the
-    host from an analytic depth map.  surface = "plane": every Gaussian at EXACTLY the same depth (the whole depth order is the tie
-    rule: index order); "waves": a smooth surface (runs of nearly equal depths along its level lines)."""
-    import math
-    syn = parity.syn
-    cam = syn.make_camera(W, H)
-    g = torch.Generator().manual_seed(seed)
-    ys, xs = torch.meshgrid(torch.arange(stride // 2, H, stride), torch.arange(stride // 2, W, stride), indexing="ij")
-    ys, xs = ys.reshape(-1), xs.reshape(-1)
-    u, v = xs.float() / W, ys.float() / H
-    if surface == "plane":
-        z = torch.full(u.shape, 4.0)
-    else:
-        z = 3.0 + 0.8 * torch.sin(6.0 * u) * torch.cos(5.0 * v) + 0.5 * u
-    n = z.shape[0]
-    # (centres a fraction of a pixel off the pixel centres, as after the first iterations of the fit: ON the centres every 3-sigma rect
-    #  and every alpha threshold of the grid sits on a binary32 rounding edge at once -- a third of the pixels, measured)
-    x = (xs.float() + 0.5 - 0.5 * W + 0.6 * (torch.rand(n, generator=g) - 0.5)) / cam["fx"] * z
-    y = (ys.float() + 0.5 - 0.5 * H + 0.6 * (torch.rand(n, generator=g) - 0.5)) / cam["fy"] * z
-    sc = {k: cam[k] for k in ("image_width", "image_height", "tanfovx", "tanfovy", "viewmatrix", "projmatrix", "campos")}
-    sc["sh_degree"] = 0
-    sc["means3D"] = torch.stack((x, y, z), 1).float().contiguous()
-    # footprint-sized, a little anisotropic and a little turned: a model some iterations into its fit
-    sc["scales"] = ((0.7 * stride * z / cam["fx"])[:, None] * (0.8 + 0.4 * torch.rand(n, 3, generator=g))).float().contiguous()
-    rot = torch.zeros(n, 4); rot[:, 0] = 1.0
-    rot[:, 1:] = 0.05 * torch.randn(n, 3, generator=g)
-    sc["rotations"] = (rot / rot.norm(dim=1, keepdim=True)).contiguous()
-    sc["opacities"] = (0.5 + 0.4 * torch.rand(n, 1, generator=g)).contiguous()
-    shs = torch.zeros(n, 16, 3)
-    col = torch.stack((0.5 + 0.4 * torch.sin(9.0 * u), 0.5 + 0.4 * torch.cos(7.0 * v), 0.5 + 0.3 * torch.sin(5.0 * (u + v))), 1)
-    shs[:, 0] = (col - 0.5) / 0.28209479177387814
-    sc["shs"] = shs.contiguous()
-    return sc
+    """Stage A's single-image model under synthetic.make_camera's centred camera: the builder lives in tests/camera_common.py, where
+    tests/test_gpu_camera_intrinsics.py un-projects the same grid through cameras with real intrinsics."""
+    import camera_common
+    return camera_common.pixel_gaussian_scene(W, H, stride, surface, seed)
 
 
 @pytest.mark.parametrize("W,H,stride,surface", [(490, 272, 2, "plane"), (490, 272, 2, "waves"), (333, 250, 1, "waves"), (980, 545, 4, "plane")],

@@ -197,15 +197,20 @@ def test_pose_step_kernel_equals_torch_exp_map_autograd_and_adam(with_base):
     assert d_ref.detach().abs().max().item() > 0.05                # the trajectory actually moved (40 steps of lr 2e-3)
 
 
-def test_camera_pose_step_kernel_equals_torch_camera_chain_and_adam():
+@pytest.mark.parametrize("camera", ["centred", "both", "far-both"])
+def test_camera_pose_step_kernel_equals_torch_camera_chain_and_adam(camera):
     """gsr_pose_step_camera: dL/d(viewmatrix, projmatrix, campos) -> dL/dM -> dL/d(delta) -> Adam -> camera tensors rewritten in
-    place, against the torch statement (camera tensors built from pose.retr_matrix under autograd, torch.optim.Adam)."""
+    place, against the torch statement (camera tensors built from pose.retr_matrix under autograd, torch.optim.Adam).  projT of
+    synthetic.make_camera's centred camera, and of two cameras of tests/camera_common.py's table: unequal focal lengths and a principal
+    point off the centre put non-zero entries into projT's third row, which the centred camera leaves at zero."""
     import importlib
     _ext = importlib.import_module("3dgs_hierarchical_training_amd._ext")
     pose = importlib.import_module("3dgs_hierarchical_training_amd.pose")
     ops = _ext.load()
     dev = torch.device("cuda:0")
-    cam = parity.syn.make_camera(320, 240)
+    import camera_common
+    cam = parity.syn.make_camera(320, 240) if camera == "centred" else camera_common.named_camera(camera, 320, 240)
+    assert (camera == "centred") == (float(cam["projmatrix"][2, 0]) == 0.0 and float(cam["projmatrix"][2, 1]) == 0.0)
     projT = (torch.linalg.inv(cam["viewmatrix"].double()) @ cam["projmatrix"].double()).float().to(dev)
     g = torch.Generator().manual_seed(5)
     Wv, Wp, Wc = torch.randn(4, 4, generator=g).to(dev), torch.randn(4, 4, generator=g).to(dev), torch.randn(3, generator=g).to(dev)

@@ -71,6 +71,43 @@ def test_camera_convention_matches_reference_camera(golden_dir):
     assert np.abs(g["std_view"][3, :3] - g["T"]).max() < 1e-6 or np.abs(np.abs(g["std_view"][3, :3]) - np.abs(g["T"])).max() < 1e-6
 
 
+@pytest.mark.parametrize("tag,name", [("both", "both"), ("far_both", "far-both"), ("std", None)])
+def test_general_camera_matches_reference_camera_on_real_intrinsics(golden_dir, tag, name):
+    """tests/camera_common.py general_camera (fx != fy, principal point off the centre) reproduces scene/cameras.py: the co3d branch on
+    the intrinsics "both" and "far-both" of the camera table, and the non-co3d branch (FoVx, FoVy from unequal focal lengths; it ignores
+    K's principal point).  Bars of the centred camera test above.  The two principal-point entries of the projection -- exactly zero in
+    camera.npz and under synthetic.make_camera -- are held to the fixture in place, sign and value."""
+    import camera_common
+    g = _load(golden_dir, "camera_general.npz")
+    W, H = int(g["W"]), int(g["H"])
+    K, view = g[f"{tag}_K"], g[f"{tag}_view"]
+    R, t = torch.tensor(view.T[:3, :3]), torch.tensor(view.T[:3, 3])
+    if name is None:
+        fx, fy = 0.5 * W / np.tan(0.5 * float(g["std_fovx"])), 0.5 * H / np.tan(0.5 * float(g["std_fovy"]))
+        assert abs(fx - K[0, 0]) < 1e-4 * fx and abs(fy - K[1, 1]) < 1e-4 * fy and abs(fy / fx - 1.25 / 0.9) < 1e-5
+        cam = camera_common.general_camera(W, H, fx, fy, W / 2.0, H / 2.0, R=R, t=t)
+    else:
+        want = camera_common.intrinsics(name, W, H)          # the fixture was made on the table's numbers
+        assert np.abs(np.array([K[0, 0], K[1, 1], K[0, 2], K[1, 2]], np.float64) - np.array(want)).max() < 1e-4
+        cam = camera_common.general_camera(W, H, *want, R=R, t=t)
+        assert abs(cam["tanfovx"] - np.tan(0.5 * float(g[f"{tag}_fovx"]))) < 1e-6 and abs(cam["tanfovy"] - np.tan(0.5 * float(g[f"{tag}_fovy"]))) < 1e-6
+    assert np.abs(cam["viewmatrix"].numpy() - view).max() < 1e-6
+    assert np.abs(cam["projmatrix"].numpy() - g[f"{tag}_full"]).max() < 2e-5
+    assert np.abs(cam["campos"].numpy() - g[f"{tag}_campos"]).max() < 1e-5
+    # proj_T = view_T^-1 full: the principal point sits in row 2 (the transposed matrix's third ROW), columns 0 and 1
+    proj_T = np.linalg.solve(cam["viewmatrix"].double().numpy(), cam["projmatrix"].double().numpy())
+    ref_T = g[f"{tag}_proj"].astype(np.float64)
+    assert np.abs(proj_T - ref_T).max() < 2e-5
+    for j, (size, c) in enumerate(((W, cam["cx"]), (H, cam["cy"]))):
+        if name is None:
+            assert ref_T[2, j] == 0.0 and abs(proj_T[2, j]) < 1e-6
+            continue
+        assert abs(ref_T[2, j]) > 0.2 and abs(ref_T[2, j] - -(size - 2 * c) / size) < 1e-6          # the reference's own entry
+        assert np.sign(proj_T[2, j]) == np.sign(ref_T[2, j]) and abs(proj_T[2, j] - ref_T[2, j]) < 2e-6
+        assert ref_T[j, 2] == 0.0 and abs(proj_T[j, 2]) < 1e-6                                       # ... and not its transpose's place
+    assert abs(proj_T[0, 0] - 2 * cam["fx"] / W) < 2e-6 and abs(proj_T[1, 1] - 2 * cam["fy"] / H) < 2e-6 and proj_T[0, 0] != proj_T[1, 1]
+
+
 def test_boundary_capture_matches_our_api(golden_dir):
     g = _load(golden_dir, "boundary_args.npz")
     rast = importlib.import_module("3dgs_hierarchical_training_amd.rasterizer")

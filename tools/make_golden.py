@@ -7,6 +7,8 @@ What it pins, and with what:
                        values and autograd grads, degrees 0..3
     cov3d.npz          utils/general_utils.py:62-108 + gaussian_model_ht.py:50-55 (L L^T, strip_symmetric)
     camera.npz         scene/cameras.py:76-98 (co3d and non-co3d branches), utils/graphics_utils.py:57-141
+    camera_general.npz the same class on real intrinsics: co3d branch with fx != fy and an off-centre principal point (two cameras),
+                       non-co3d branch with FoVx, FoVy from unequal focal lengths
     boundary_args.npz  the exact kwargs/settings CF3DGS_Render.render (gaussian_model_ht.py:775-894) hands to
                        the rasterizer, captured with a recording stub under a CPU shim
     loss.npz           trainer/losses.py Loss / SSIM_V2 values for a fixed image pair (bench train-step loss)
@@ -193,6 +195,48 @@ def gen_camera(out):
                         f"{tag}_campos": t2n(cam.camera_center.contiguous())})
     res.update(R=Rn, T=Tn, K=K, fovx=np.float64(fovx), fovy=np.float64(fovy), W=np.int32(W), H=np.int32(H))
     np.savez_compressed(os.path.join(out, "camera.npz"), **res)
+
+
+def gen_camera_general(out):
+    """scene/cameras.py on cameras with REAL intrinsics (camera.npz holds the centred, square-pixel corner only): the co3d branch
+    with the intrinsics "both" and "far-both" of tests/camera_common.py's table at 96 x 64 (fx != fy, principal point off the centre by
+    a fractional number of pixels: the -(w - 2cx)/w, -(h - 2cy)/h entries are non-zero), and the non-co3d branch with FoVx, FoVy from
+    unequal focal lengths (it ignores K).  A random rotation and T."""
+    import math
+    from scene.cameras import Camera
+    from utils.graphics_utils import focal2fov
+    res = {}
+    g = torch.Generator().manual_seed(29)
+    W, H = 96, 64
+    img = torch.rand(3, H, W, generator=g)
+    A = torch.randn(3, 3, generator=g, dtype=torch.float64)
+    Q, _ = torch.linalg.qr(A)
+    if torch.det(Q) < 0:
+        Q[:, 0] = -Q[:, 0]
+    Rn = Q.numpy()
+    Tn = (0.5 * torch.randn(3, generator=g, dtype=torch.float64)).numpy()
+    f = 0.5 * W / math.tan(0.5 * 1.3541787529604106)          # synthetic.FOVX_FRANCIS
+    table = {"both": (0.85 * f, 1.2 * f, W / 2 + 0.125 * W, H / 2 - 0.135 * H),
+             "far_both": (0.8 * f, 1.3 * f, W / 2 - 0.23 * W, H / 2 + 0.2 * H)}
+    with _CudaToCpu():
+        for tag, (fx, fy, cx, cy) in table.items():
+            K = np.array([[fx, 0, cx], [0, fy, cy], [0, 0, 1]], dtype=np.float32)
+            fovx, fovy = focal2fov(fx, W), focal2fov(fy, H)
+            cam = Camera(colmap_id=0, R=Rn, T=Tn, FoVx=fovx, FoVy=fovy, image=img, gt_alpha_mask=None,
+                         image_name="x", uid=0, intrinsics=K, data_device="cpu", is_co3d=True)
+            res.update({f"{tag}_view": t2n(cam.world_view_transform.contiguous()), f"{tag}_proj": t2n(cam.projection_matrix.contiguous()),
+                        f"{tag}_full": t2n(cam.full_proj_transform.contiguous()), f"{tag}_campos": t2n(cam.camera_center.contiguous()),
+                        f"{tag}_K": K, f"{tag}_fovx": np.float64(fovx), f"{tag}_fovy": np.float64(fovy)})
+        fx, fy = 0.9 * f, 1.25 * f
+        K = np.array([[fx, 0, 31.7], [0, fy, 40.2], [0, 0, 1]], dtype=np.float32)     # (a principal point this branch must ignore)
+        fovx, fovy = focal2fov(fx, W), focal2fov(fy, H)
+        cam = Camera(colmap_id=0, R=Rn, T=Tn, FoVx=fovx, FoVy=fovy, image=img, gt_alpha_mask=None,
+                     image_name="x", uid=0, intrinsics=K, data_device="cpu", is_co3d=False)
+        res.update({"std_view": t2n(cam.world_view_transform.contiguous()), "std_proj": t2n(cam.projection_matrix.contiguous()),
+                    "std_full": t2n(cam.full_proj_transform.contiguous()), "std_campos": t2n(cam.camera_center.contiguous()),
+                    "std_K": K, "std_fovx": np.float64(fovx), "std_fovy": np.float64(fovy)})
+    res.update(R=Rn, T=Tn, W=np.int32(W), H=np.int32(H))
+    np.savez_compressed(os.path.join(out, "camera_general.npz"), **res)
 
 
 def gen_boundary(out, captured):
@@ -403,11 +447,12 @@ def main():
         gen_python_sh(OUT, captured)
         return
     if args.only:
-        {"gen_depth_loss": gen_depth_loss, "gen_loss": gen_loss}[args.only](OUT)
+        {"gen_depth_loss": gen_depth_loss, "gen_loss": gen_loss, "gen_camera_general": gen_camera_general}[args.only](OUT)
         return
     gen_sh(OUT)
     gen_cov3d(OUT)
     gen_camera(OUT)
+    gen_camera_general(OUT)
     gen_boundary(OUT, captured)
     gen_python_sh(OUT, captured)
     gen_loss(OUT)

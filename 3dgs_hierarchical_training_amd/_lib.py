@@ -57,6 +57,7 @@ class GsrBackwardArgs(C.Structure):
         ("binning_capacity", C.c_int64), ("forward_flags", C.c_int64),
         ("next_view", C.c_void_p), ("prepared_out", C.c_void_p), ("densify_stats", C.c_void_p), ("batch", C.c_void_p),
         ("sh_origin", C.c_void_p),
+        ("retired_at", C.c_void_p), ("retire_step", C.c_int64),
     ]
 
 
@@ -86,6 +87,7 @@ EXPORTS = [
     "gsr_importance_scratch_bytes", "gsr_importance_accumulate",
     "gsr_depth_loss_workspace_bytes_batched", "gsr_depth_loss_forward_batched", "gsr_depth_loss_backward_batched",
     "gsr_depth_loss_forward_terms_batched",
+    "gsr_batch_retire_scratch_bytes", "gsr_batch_retire", "gsr_forward_retire",
 ]
 GSR_DEPTH_LOSS_L1, GSR_DEPTH_LOSS_INVARIANT = 0, 1
 
@@ -144,6 +146,12 @@ def load():
     lib.gsr_depth_loss_backward_batched.argtypes = _depth_b + [C.c_void_p, C.c_void_p, C.c_void_p]         # grad_loss, d_depth, stream
     lib.gsr_depth_loss_forward_terms_batched.restype = C.c_int
     lib.gsr_depth_loss_forward_terms_batched.argtypes = _depth_b + [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]   # out6, terms6, loss_copy, stream
+    lib.gsr_batch_retire_scratch_bytes.restype = C.c_size_t
+    lib.gsr_batch_retire_scratch_bytes.argtypes = [C.c_int32]
+    lib.gsr_batch_retire.restype = C.c_int
+    # (render, target, B, C, H, W, mse_bar, exit_after, step, retired_at, mse_out, scratch, stream)
+    lib.gsr_batch_retire.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_int64, C.c_int64,
+                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.gsr_knn_scratch_bytes.restype = C.c_size_t
     lib.gsr_knn_scratch_bytes.argtypes = [C.c_int32]
     lib.gsr_knn_mean_dist2.restype = C.c_int
@@ -162,6 +170,8 @@ def load():
     lib.gsr_sort_scratch_bytes.argtypes = [C.c_uint32]
     lib.gsr_forward.restype = C.c_int
     lib.gsr_forward.argtypes = [C.POINTER(GsrForwardArgs), C.POINTER(GsrForwardOut), C.c_void_p]
+    lib.gsr_forward_retire.restype = C.c_int          # (args, retired_at, retire_step, out, stream): GsrForwardArgs keeps its version-116 layout
+    lib.gsr_forward_retire.argtypes = [C.POINTER(GsrForwardArgs), C.c_void_p, C.c_int64, C.POINTER(GsrForwardOut), C.c_void_p]
     lib.gsr_backward.restype = C.c_int
     lib.gsr_backward.argtypes = [C.POINTER(GsrBackwardArgs), C.c_void_p]
     lib.gsr_importance_accumulate.restype = C.c_int

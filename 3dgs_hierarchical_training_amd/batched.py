@@ -76,6 +76,9 @@ class BatchedGaussianParams(GaussianParams):
     def num_models(self) -> int:
         return len(self.counts)
 
+    # new_retire_table() / retired_sync() (train_step.GaussianParams): one entry per model of the batch.  Models cannot be REMOVED from a
+    # batch (prune_points below); a retired one stays in the store, culled from every render and skipped by every update.
+
     def model_rows(self, b: int) -> slice:
         """Rows of model b's own (un-padded) Gaussians."""
         lo = self.first_block[b] * BLOCK

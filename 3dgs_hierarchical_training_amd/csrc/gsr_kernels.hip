@@ -148,6 +148,35 @@ __device__ __forceinline__ int select_view(CamParams& p, int block)
     return b;
 }
 
+// The retire table of a launch chain (gsr_forward_retire / GsrBackwardArgs::retired_at, include/gsr.h): entry b = 0 while model b trains, otherwise the step at
+// which gsr_batch_retire retired it; `step` = the step s of the call.  table == nullptr: no table, every kernel as it was.
+struct RetireDev {
+    const int32_t* table;
+    int step;
+};
+// A block's entry, read once: every lane loads the same word with a vector load (the table was written by a kernel earlier on the stream)
+// and the value is made block-uniform, so the tests on it are scalar branches.  0 without a table.
+__device__ __forceinline__ int retire_entry(const RetireDev& rt, int model)
+{
+    if (!rt.table) return 0;
+    const int v = *reinterpret_cast<const volatile int32_t*>(rt.table + model);
+    return __builtin_amdgcn_readfirstlane(v);
+}
+// what k_preprocess leaves of a Gaussian that is not drawn, for every Gaussian of a culled model: an all-zero record, no tile
+__device__ __forceinline__ void culled_records(int i, int model, int tiles_y, Splat* __restrict__ splat, TileRec* __restrict__ tilerec,
+                                               int32_t* __restrict__ radii, uint32_t* __restrict__ dkey, uint32_t* __restrict__ gid)
+{
+    Splat z;
+    z.px = 0.f; z.py = 0.f; z.ca = 0.f; z.cb = 0.f; z.cc = 0.f; z.op = 0.f; z.depth = 0.f; z.r = 0.f; z.g = 0.f; z.b = 0.f; z.radius = 0; z.tiles = 0u;
+    splat[i] = z;
+    TileRec rec;
+    rec.mask = 0u; rec.rect = (1u << 24) + ((uint32_t)(model * tiles_y) << 12);
+    tilerec[i] = rec;
+    radii[i] = 0;
+    dkey[i] = 0xffffffffu;
+    gid[i] = (uint32_t)i;
+}
+
 // p' = M [p; 1]: the in-kernel form of `P.retr().act(xyz)` (/root/reference/scene/gaussian_model_ht.py:135-148)
 __device__ __forceinline__ void apply_points_transform(const float* __restrict__ xf, float m[3])
 {
@@ -467,7 +496,7 @@ __global__ __launch_bounds__(kPreThreads) void k_preprocess(CamParams cp, int N,
                                                             TileRec* __restrict__ tilerec, uint32_t* __restrict__ zero_words,
                                                             int zero_count, int block0, DepthHist dh, uint2* __restrict__ early_parts = nullptr,
                                                             uint32_t window_max = 0xffffffffu, uint8_t* __restrict__ visible = nullptr,
-                                                            const float* __restrict__ sh_origin = nullptr)
+                                                            const float* __restrict__ sh_origin = nullptr, RetireDev rt = {})
 {
     constexpr int NC3 = 3 * (DEG + 1) * (DEG + 1);
     __shared__ float s_sh[kPreThreads * kShStride];
@@ -478,6 +507,23 @@ __global__ __launch_bounds__(kPreThreads) void k_preprocess(CamParams cp, int N,
     const int model = select_view(cp, (int)blockIdx.x + block0);   // batched render: this block's model and its camera
     if (blockIdx.x == 0)   // rides along: clear the head of the depth sort's scratch (saves a fill launch)
         for (int q = tid; q < zero_count; q += kPreThreads) zero_words[q] = 0u;
+    if (rt.table) {   // the retire table: a model retired BEFORE this step is culled whole -- records and radii, no per-Gaussian arithmetic
+        const int ra = retire_entry(rt, model);
+        if (ra != 0 && ra < rt.step) {   // block-uniform
+            if (early_parts && tid == 0) early_parts[blockIdx.x + block0] = make_uint2(0u, 0u);   // no instance, no far key: the early count sees zero
+            if (dh.ghist && dh.clear_threads == 0u)
+                for (uint32_t q = tid; q < dh.status_words / 4; q += kPreThreads) reinterpret_cast<uint4*>(dh.status)[q] = make_uint4(0u, 0u, 0u, 0u);
+            if (i >= N) return;
+            culled_records(i, model, (cp.H + kTile - 1) / kTile, splat, tilerec, radii, dkey, gid);
+            if (visible) visible[i] = 0;
+            if (dh.ghist) {   // (as below: the single ragged block behind the next-view tail counts its keys' digits)
+                const uint32_t x = (uint32_t)i / onesweep_run_len<uint32_t>((uint32_t)N);
+#pragma unroll
+                for (int p = 0; p < 4; p++) atomicAdd(&dh.ghist[((size_t)p * kOsRanges + x) * 256 + 255u], 1u);
+            }
+            return;
+        }
+    }
     // ---- phase 0: SH rows.  Dense, aligned rows (the normal case) are only LOADED here -- into registers; the geometry
     // below does not need them, so the 180-192 bytes per Gaussian stream in underneath ~1500 instructions of float64
     // projection instead of in front of them (K1 was the sum of its HBM time and its VALU time: 0.073 ms without
@@ -3648,6 +3694,24 @@ __device__ __forceinline__ void load_ggrad(const double* __restrict__ row, float
 // the dSH rows and every per-Gaussian store but d_means2D (written when the pointer is set).  At DEG 0 the colour does not depend on the mean,
 // so no SH row is staged, sh_backward does not run and the barrier behind the staging goes with it; the host sends a call with sh_origin
 // (whose colour reaches d_means3D alone) or colors_precomp to that instantiation as well.
+// The hand-over records of a block whose model the NEXT render culls (the retire table, GsrBackwardArgs::retired_at): what k_preprocess's
+// culled path would write, its share of the next forward's early instance count (zero) and of the next depth sort's digit counts (every
+// key is 0xffffffff: digit 255 in all four passes) and of the status clear.  Every thread of the block calls it.
+__device__ __forceinline__ void culled_handover(const PrepOut& po, int i, int base, int N, int tid, int model2)
+{
+    if (po.early_parts && tid == 0) po.early_parts[blockIdx.x] = make_uint2(0u, 0u);
+    if (i < N) culled_records(i, model2, (po.cp.H + kTile - 1) / kTile, po.splat, po.rec, po.radii, po.dkey, po.gid);
+    if (po.dh.ghist) {
+        const uint32_t x = (uint32_t)base / onesweep_run_len<uint32_t>((uint32_t)N);
+        if (tid < 4) atomicAdd(&po.dh.ghist[((size_t)tid * kOsRanges + x) * 256 + 255u], (uint32_t)min(kPreThreads, N - base));
+        for (uint32_t q = blockIdx.x * kPreThreads + tid; q < po.dh.status_words / 4; q += po.dh.clear_threads)
+            reinterpret_cast<uint4*>(po.dh.status)[q] = make_uint4(0u, 0u, 0u, 0u);
+    }
+}
+
+// RETIRE TABLE (rt, with ADAM; GsrBackwardArgs::retired_at): a block of a model retired BEFORE this step issues none of its parameter, moment or
+// gradient-row streams -- it writes zero d_means2D rows, a zero camera partial (k_cam_reduce expects one from every block) and, with PREP,
+// culled hand-over records, and leaves.  A model retired AT this step (or earlier) gets culled hand-over records behind its update.
 template <int DEG, bool RAW, bool CAM, bool ADAM, int PREP, bool SHO = false, bool FROZEN = false>
 __global__ __launch_bounds__(kPreThreads) void k_preprocess_bwd(CamParams cp, int N, const float* means,
                                                                 const float* scales, const float* rots,
@@ -3660,7 +3724,7 @@ __global__ __launch_bounds__(kPreThreads) void k_preprocess_bwd(CamParams cp, in
                                                                 float* __restrict__ d_scales,
                                                                 float* __restrict__ d_rots, float* __restrict__ d_cov,
                                                                 float* __restrict__ cam_partial, PrepOut po, DensDev ds,
-                                                                const float* __restrict__ sh_origin = nullptr)
+                                                                const float* __restrict__ sh_origin = nullptr, RetireDev rt = {})
 {
     static_assert(!SHO || PREP < 0, "sh_origin is not served together with a next view");
     static_assert(!FROZEN || (CAM && !ADAM && PREP < 0 && !SHO), "the frozen variant: camera gradients, no Adam, no next view, no sh_origin");
@@ -3682,7 +3746,7 @@ __global__ __launch_bounds__(kPreThreads) void k_preprocess_bwd(CamParams cp, in
     unsigned long long k9t[8] = {0, 0, 0, 0, 0, 0, 0, 0}, k9t_last = __builtin_readcyclecounter();
     k9t[6] = k9t_last;   // start stamp (k9t[7] = end stamp)
 #endif
-    select_view(cp, (int)blockIdx.x);   // batched render: this block's model and its camera
+    const int model = select_view(cp, (int)blockIdx.x);   // batched render: this block's model and its camera
     CamGrads cg;
     float xg[12];   // dL/d(points_transform) share of this thread
     if (CAM) {
@@ -3703,6 +3767,22 @@ __global__ __launch_bounds__(kPreThreads) void k_preprocess_bwd(CamParams cp, in
     float* s_rest = s_sh + kPreThreads * 3;
     const bool lin = shs && shs_rest && cp.M == 16 && vec_ok(shs + (size_t)base * 3, nG * 3) &&
                      vec_ok(shs_rest + (size_t)base * NRL, nG * NRL);   // block-uniform
+    bool cull_next = false;   // (block-uniform) the next render culls this block's model: retired at or before this step
+    if constexpr (ADAM) {
+        if (rt.table) {
+            const int ra = retire_entry(rt, model);
+            if (ra != 0 && ra < rt.step) {   // retired before this step: the render was culled, every gradient is zero, the update is skipped
+                if (i < N) { d_means2d[3 * (size_t)i] = 0.f; d_means2d[3 * (size_t)i + 1] = 0.f; d_means2d[3 * (size_t)i + 2] = 0.f; }
+                if (CAM && tid < kCamVals) cam_partial[(size_t)blockIdx.x * kCamVals + tid] = 0.f;
+                if constexpr (PREP >= 0) {
+                    if (lin) culled_handover(po, i, base, N, tid, model);   // (a block without the tail: the host's k_preprocess launch culls it)
+                }
+                K9_T_FLUSH();
+                return;
+            }
+            cull_next = ra != 0 && ra <= rt.step;
+        }
+    }
     // the f_rest group's moments, first kAdamPrefetch elements of this thread's share of the update stream: requested NOW
     float4 pf_m[kAdamPrefetch > 0 ? kAdamPrefetch : 1], pf_v[kAdamPrefetch > 0 ? kAdamPrefetch : 1];
     bool pf_ok = false;
@@ -4017,6 +4097,11 @@ __global__ __launch_bounds__(kPreThreads) void k_preprocess_bwd(CamParams cp, in
             lds_barrier();
             const bool act = i < N;
             const int model2 = select_view(po.cp, (int)blockIdx.x);
+            if (cull_next) {   // retired at this step: the update above was its last, the next render culls it
+                culled_handover(po, i, base, N, tid, model2);
+                K9_T_FLUSH();
+                return;
+            }
             Camera cam2 = load_camera(po.cp);
             cam2.D = PREP < 0 ? 0 : PREP;
             Splat s2;
@@ -4501,7 +4586,7 @@ size_t gsr_prepared_bytes(int32_t N) { return prep_layout(N).bytes; }
 size_t gsr_prepared_radii_offset(int32_t N) { return prep_layout(N).radii; }
 int gsr_prepare_supported(int32_t M, int32_t D, int32_t raw_params) { return (raw_params && M == 16 && D >= 0 && D <= 3) ? 1 : 0; }
 const char* gsr_last_error(void) { return g_err; }
-int gsr_version(void) { return 116; }
+int gsr_version(void) { return 117; }
 size_t gsr_struct_bytes(int32_t which)
 {
     return which == 0 ? sizeof(GsrForwardArgs) : which == 1 ? sizeof(GsrBackwardArgs) : which == 2 ? sizeof(GsrForwardOut) : 0;
@@ -4646,7 +4731,7 @@ static bool direct_bin_geometry(int N, int T, DirectBin& db, DirectBinScratch& d
     return true;
 }
 
-int gsr_forward(const GsrForwardArgs* a, GsrForwardOut* out, void* stream_)
+static int forward_impl(const GsrForwardArgs* a, const int32_t* retired_at, int64_t retire_step, GsrForwardOut* out, void* stream_)
 {
     CallTimer call_timer(g_fwd_calls, g_fwd_ns);
     hipStream_t st = (hipStream_t)stream_;
@@ -4656,6 +4741,11 @@ int gsr_forward(const GsrForwardArgs* a, GsrForwardOut* out, void* stream_)
     // the render-only call (GsrForwardArgs::render_only): its own rules come first; its workspace is asked for behind the last argument
     // check (ro_workspace below), so a refused call has asked the allocator for nothing
     const bool ro = a->render_only != 0;
+    // the retire table (gsr_forward_retire): refused where nothing applies it, before anything is asked for or enqueued
+    if (retired_at) {
+        if (ro) return fail(GSR_ERR_ARG, "retired_at: a retire table is not served with render_only (no training step, nothing to retire)%s");
+        if (retire_step < 1 || retire_step > 0x7fffffffll) return fail(GSR_ERR_ARG, "retired_at: retire_step must be the 1-based step of the call%s");
+    }
     if (ro) {
         if ((a->out_depth == nullptr) != (a->out_alpha == nullptr))
             return fail(GSR_ERR_ARG, "render_only: out_depth and out_alpha are given both or neither%s");
@@ -4945,6 +5035,7 @@ int gsr_forward(const GsrForwardArgs* a, GsrForwardOut* out, void* stream_)
     const bool depth_onesweep = g_sort_algo != 0;
     CamParams cp = {a->viewmatrix, a->projmatrix, a->campos, a->tanfovx, a->tanfovy, a->scale_modifier, W, H, a->D, a->M, a->points_transform, bt};
     const int grid = (N + kPreThreads - 1) / kPreThreads;
+    const RetireDev rt = {retired_at, (int)retire_step};   // (a forward over a prepared buffer runs no preprocess: the backward culled for it)
     // block 0 of k_preprocess clears the head (digit histograms + tickets) of the depth sort's scratch
     uint32_t* zero_words = depth_onesweep ? reinterpret_cast<uint32_t*>(fs + L.sort) : nullptr;
     const int zero_count = depth_onesweep ? (int)kOnesweepHeadWordsMax : 0;   // (either layout of the depth sort's head)
@@ -4982,7 +5073,7 @@ int gsr_forward(const GsrForwardArgs* a, GsrForwardOut* out, void* stream_)
 #define GSR_PRE_(DEG, RAW, SHO)                                                                                                     \
     hipLaunchKernelGGL((k_preprocess<DEG, RAW, SHO>), dim3(grid), dim3(kPreThreads), 0, st, cp, N, a->means3D, a->scales,           \
                        a->rotations, a->cov3D_precomp, a->opacities, a->shs, a->shs_rest, a->colors_precomp, splat, a->radii, dkey, gid, \
-                       ntiles, zero_words, zero_count, 0, DepthHist{}, early_parts, early_window, a->visible, a->sh_origin)
+                       ntiles, zero_words, zero_count, 0, DepthHist{}, early_parts, early_window, a->visible, a->sh_origin, rt)
 #define GSR_PRE(DEG) do { if (a->raw_params) GSR_PRE_(DEG, true, false); else GSR_PRE_(DEG, false, false); } while (0)
     // sh_origin: degree 0 takes the default kernel (the colour does not depend on the direction)
 #define GSR_PRE_SHO(DEG) do { if (a->raw_params) GSR_PRE_(DEG, true, true); else GSR_PRE_(DEG, false, true); } while (0)
@@ -5245,6 +5336,12 @@ int gsr_forward(const GsrForwardArgs* a, GsrForwardOut* out, void* stream_)
 }
 
 // workgroups of the backward blend the device holds at once (occupancy x compute units), per kernel variant
+int gsr_forward(const GsrForwardArgs* a, GsrForwardOut* out, void* stream_) { return forward_impl(a, nullptr, 0, out, stream_); }
+int gsr_forward_retire(const GsrForwardArgs* a, const int32_t* retired_at, int64_t retire_step, GsrForwardOut* out, void* stream_)
+{
+    return forward_impl(a, retired_at, retire_step, out, stream_);
+}
+
 static int blend_bwd_resident(int has_da, int ppt = 2)
 {
     static int cached[2][2] = {{0, 0}, {0, 0}};
@@ -5283,6 +5380,15 @@ int gsr_backward(const GsrBackwardArgs* a, void* stream_)
     const bool want_cam = a->d_viewmatrix || a->d_projmatrix || a->d_campos || a->d_points_transform;
     const bool want_other_pg = a->d_opacities || a->d_colors_precomp || a->d_shs || a->d_shs_rest || a->d_scales || a->d_rotations || a->d_cov3D_precomp;
     const bool frozen = !a->fused_adam && !a->d_means3D && !want_other_pg && want_cam;
+    if (a->retired_at) {   // the retire table (GsrBackwardArgs::retired_at) is applied by the optimizer-in-backward alone
+        if (frozen) return fail(GSR_ERR_ARG, "retired_at: a retire table is not served on the frozen backward (no update to gate)%s");
+        if (!a->fused_adam) return fail(GSR_ERR_ARG, "retired_at: a retire table needs fused_adam (the update it gates runs in this call)%s");
+        if (a->retire_step < 1 || a->retire_step > 0x7fffffffll) return fail(GSR_ERR_ARG, "retired_at: retire_step must be the 1-based step of the call%s");
+        if (a->densify_stats) return fail(GSR_ERR_ARG, "retired_at: a retire table is not served with densify_stats%s");
+        for (int q = 0; q < 6; q++)
+            if (a->fused_adam->param_out[q] || a->fused_adam->exp_avg_out[q] || a->fused_adam->exp_avg_sq_out[q])
+                return fail(GSR_ERR_ARG, "retired_at: a retire table is not served with the deferred step (GsrFusedAdam::param_out)%s");
+    }
     if (!a->fused_adam && !a->d_means3D && a->N > 0) {   // (N = 0: there is no gradient row to point at, the camera outputs are cleared below)
         if (want_other_pg)
             return fail(GSR_ERR_ARG, "d_means3D is NULL but another per-Gaussian gradient pointer is set: they come together, or none of them (frozen call)%s");
@@ -5420,6 +5526,8 @@ int gsr_backward(const GsrBackwardArgs* a, void* stream_)
     }
     CamParams cp = {a->viewmatrix, a->projmatrix, a->campos, a->tanfovx, a->tanfovy, a->scale_modifier, W, H, a->D, a->M, a->points_transform, bt};
     const int grid = (N + kPreThreads - 1) / kPreThreads;
+    const RetireDev rt = {a->retired_at, (int)a->retire_step};
+    const RetireDev rt_next = {a->retired_at, (int)a->retire_step + 1};   // the test of the render this call prepares
     float* cam_partial = reinterpret_cast<float*>(static_cast<uint8_t*>(a->scratch) + align256((size_t)N * kGG * sizeof(double)));
     AdamDev ad = {};
     const GsrFusedAdam* fa = a->fused_adam;
@@ -5496,7 +5604,7 @@ int gsr_backward(const GsrBackwardArgs* a, void* stream_)
     hipLaunchKernelGGL((k_preprocess_bwd<DEG, RAW, CAM, ADAM, PREP, SHO, FROZEN>), dim3(grid), dim3(kPreThreads), 0, st, cp, N, a->means3D, \
                        a->scales, a->rotations, a->cov3D_precomp, a->shs, a->shs_rest, a->opacities, ad, splat, gg, a->d_means3D,           \
                        a->d_means2D, a->d_opacities, a->d_colors_precomp, a->d_shs, a->d_shs_rest, a->d_scales, a->d_rotations,             \
-                       a->d_cov3D_precomp, cam_partial, po, ds, a->sh_origin)
+                       a->d_cov3D_precomp, cam_partial, po, ds, a->sh_origin, rt)
 #define GSR_PREB_(DEG, RAW, CAM, ADAM, PREP) GSR_PREB_S(DEG, RAW, CAM, ADAM, PREP, false)
 #define GSR_PREB_SO(DEG, SHO)                                                                                                               \
     do {                                                                                                                                    \
@@ -5510,7 +5618,8 @@ int gsr_backward(const GsrBackwardArgs* a, void* stream_)
 #define GSR_PRE_TAIL(NDEG)                                                                                                               \
     hipLaunchKernelGGL((k_preprocess<NDEG, true>), dim3(1), dim3(kPreThreads), 0, st, po.cp, N, a->means3D, a->scales, a->rotations,       \
                        (const float*)nullptr, a->opacities, a->shs, a->shs_rest, (const float*)nullptr, po.splat, po.radii, po.dkey,     \
-                       po.gid, po.rec, (uint32_t*)nullptr, 0, grid - 1, po.dh, po.early_parts, po.early_window)
+                       po.gid, po.rec, (uint32_t*)nullptr, 0, grid - 1, po.dh, po.early_parts, po.early_window, (uint8_t*)nullptr,            \
+                       (const float*)nullptr, rt_next)
     {
         ProfScope ps(P_PRE_BWD, st);
         if (nv) {   // (this render's degree, the next render's): equal, or one step up (checked above)

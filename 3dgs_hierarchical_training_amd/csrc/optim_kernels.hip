@@ -435,6 +435,63 @@ __global__ __launch_bounds__(64) void k_psnr_finish(const float* __restrict__ pa
         out[c] = 20.f * log10f(1.0f / sqrtf(mse));
     }
 }
+
+// ---- the per-model exit decision of a launch chain (gsr_batch_retire, include/gsr.h): MSE of clamp(render, 0, 1) against the target per
+// image, in float64, then the retire rule.  Two launches in the manner of k_psnr_partial / k_psnr_finish, but per image (blockIdx.y) and with
+// every sum in a fixed order: lane `t` of block `k` of an image adds the quads k * 256 + t, + kRetireBlocks * 256, ... of THAT image in index
+// order, the lanes of a wave are folded by a xor butterfly, the four waves and then the blocks in index order.  Nothing depends on where the
+// image lies in the stack: an image whose first element is not 16-byte aligned (C H W no multiple of 4) reads the same quads with four
+// scalar loads instead of one float4.
+constexpr int kRetireBlocks = 64;   // blocks per image (a fixed grid: the order of the sums is part of the result)
+
+__device__ __forceinline__ double retire_sq(float x, float y)
+{
+#pragma clang fp contract(off)
+    const float c = x < 0.f ? 0.f : (x > 1.f ? 1.f : x);   // clamp(render, 0, 1); a NaN stays a NaN
+    const double d = (double)c - (double)y;
+    return d * d;
+}
+
+__global__ __launch_bounds__(256) void k_retire_partial(const float* __restrict__ render, const float* __restrict__ target, long long n,
+                                                        double* __restrict__ partial /*[B][kRetireBlocks]*/)
+{
+#pragma clang fp contract(off)
+    __shared__ double s_red[4];
+    const int tid = threadIdx.x;
+    const float* a = render + (size_t)blockIdx.y * (size_t)n;
+    const float* b = target + (size_t)blockIdx.y * (size_t)n;
+    const bool vec = ((((uintptr_t)a) | ((uintptr_t)b)) & 15) == 0;   // block-uniform
+    const long long quads = n >> 2;
+    double acc = 0.0;
+    for (long long q = (long long)blockIdx.x * 256 + tid; q < quads; q += (long long)kRetireBlocks * 256) {
+        float4 x, y;
+        if (vec) { x = reinterpret_cast<const float4*>(a)[q]; y = reinterpret_cast<const float4*>(b)[q]; }
+        else {
+            x = make_float4(a[4 * q], a[4 * q + 1], a[4 * q + 2], a[4 * q + 3]);
+            y = make_float4(b[4 * q], b[4 * q + 1], b[4 * q + 2], b[4 * q + 3]);
+        }
+        acc += retire_sq(x.x, y.x); acc += retire_sq(x.y, y.y); acc += retire_sq(x.z, y.z); acc += retire_sq(x.w, y.w);
+    }
+    if (blockIdx.x == 0 && tid < (int)(n & 3)) acc += retire_sq(a[4 * quads + tid], b[4 * quads + tid]);   // the last one to three elements
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off, 64);
+    if ((tid & 63) == 0) s_red[tid >> 6] = acc;
+    __syncthreads();
+    if (tid == 0) partial[(size_t)blockIdx.y * kRetireBlocks + blockIdx.x] = ((s_red[0] + s_red[1]) + s_red[2]) + s_red[3];
+}
+
+__global__ __launch_bounds__(64) void k_retire_finish(const double* __restrict__ partial, int B, long long n, double mse_bar, long long exit_after,
+                                                      long long step, int32_t* retired_at, double* __restrict__ mse_out)
+{
+#pragma clang fp contract(off)
+    const int b = blockIdx.x * 64 + threadIdx.x;
+    if (b >= B) return;
+    double sse = 0.0;
+    for (int k = 0; k < kRetireBlocks; k++) sse += partial[(size_t)b * kRetireBlocks + k];
+    const double mse = sse / (double)n;
+    mse_out[b] = mse;
+    if (retired_at[b] == 0 && step > exit_after && mse < mse_bar) retired_at[b] = (int32_t)step;   // sticky; strict; NaN never passes
+}
 }  // namespace gsr
 
 extern "C" int gsr_masked_max(float* dst, const int32_t* src, const uint8_t* mask, int32_t n, void* stream)
@@ -461,5 +518,20 @@ extern "C" int gsr_psnr(const float* a, const float* b, int32_t C, int64_t P, fl
     const int blocks = (int)std::min<int64_t>(256, (P + 255) / 256);
     hipLaunchKernelGGL(gsr::k_psnr_partial, dim3(blocks), dim3(256), 0, (hipStream_t)stream, a, b, C, (long long)P, static_cast<float*>(scratch));
     hipLaunchKernelGGL(gsr::k_psnr_finish, dim3(1), dim3(64), 0, (hipStream_t)stream, static_cast<const float*>(scratch), blocks, C, (long long)P, out);
+    return hipGetLastError() == hipSuccess ? GSR_OK : GSR_ERR_HIP;
+}
+
+extern "C" size_t gsr_batch_retire_scratch_bytes(int32_t B) { return (size_t)(B > 0 ? B : 1) * gsr::kRetireBlocks * sizeof(double); }
+
+extern "C" int gsr_batch_retire(const float* render, const float* target, int32_t B, int32_t C, int32_t H, int32_t W, double mse_bar, int64_t exit_after,
+                                int64_t step, int32_t* retired_at, double* mse_out, void* scratch, void* stream)
+{
+    if (!render || !target || !retired_at || !mse_out || !scratch || B < 1 || B > 65535 || C <= 0 || H <= 0 || W <= 0 || step < 1 ||
+        step > 0x7fffffffll || exit_after < 0 || (((uintptr_t)mse_out | (uintptr_t)scratch) & 7) != 0)
+        return GSR_ERR_ARG;
+    const long long n = (long long)C * H * W;
+    hipLaunchKernelGGL(gsr::k_retire_partial, dim3(gsr::kRetireBlocks, B), dim3(256), 0, (hipStream_t)stream, render, target, n, static_cast<double*>(scratch));
+    hipLaunchKernelGGL(gsr::k_retire_finish, dim3((B + 63) / 64), dim3(64), 0, (hipStream_t)stream, static_cast<const double*>(scratch), (int)B, n, mse_bar,
+                       (long long)exit_after, (long long)step, retired_at, mse_out);
     return hipGetLastError() == hipSuccess ? GSR_OK : GSR_ERR_HIP;
 }

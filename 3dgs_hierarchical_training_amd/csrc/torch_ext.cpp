@@ -19,6 +19,8 @@
 //   gsr::depth_loss_forward / _forward_stack / _backward, gsr::training_loss_terms -> gsr_depth_loss_forward / _backward / _forward_terms
 //                                              and their _batched forms for stacks of planes
 //   gsr::adam_step            -> gsr_adam_step
+//   gsr::batch_retire         -> gsr_batch_retire (the per-model exit decision of a launch chain, written into the retire table)
+//   gsr::retire_attach        attaches a retire table + step to the NEXT gsr::rasterize / render / importance_accumulate of the calling thread
 //   gsr::pose_step            -> gsr_pose_step (stage A: tangent-space Adam + exponential map between two renders)
 //   gsr::knn_mean_dist2       -> gsr_knn_mean_dist2
 //
@@ -102,6 +104,32 @@ std::vector<Tensor> debug_last()
 }
 
 // ---------------------------------------------------------------------------------------------------------------
+// The retire table (gsr_forward_retire / GsrBackwardArgs::retired_at, version 117).  The schema strings of the existing ops stay as they are, so the table travels
+// beside them: gsr::retire_attach(table, step) leaves it with the calling THREAD and the next forward-side op of that thread (rasterize /
+// rasterize_forward, render, importance_accumulate) takes it -- single use.  gsr::rasterize keeps it with its autograd node, whose backward
+// (another thread: autograd's device worker) attaches it again in front of the backward op it calls.  An empty tensor detaches.
+struct RetirePending {
+    Tensor table;
+    int64_t step = 0;
+};
+thread_local RetirePending g_retire;
+
+void retire_attach(const Tensor& retired_at, int64_t step)
+{
+    if (!has(retired_at)) { g_retire = RetirePending{}; return; }
+    TORCH_CHECK(retired_at.is_cuda() && retired_at.scalar_type() == at::kInt && retired_at.is_contiguous() && retired_at.dim() == 1,
+                "retire_attach: retired_at must be a contiguous int32 vector on the device (one entry per model)");
+    g_retire.table = retired_at;
+    g_retire.step = step;
+}
+
+RetirePending take_retire()
+{
+    RetirePending r = g_retire;
+    g_retire = RetirePending{};
+    return r;
+}
+
 // GsrForwardArgs::sh_origin as a contiguous float32 [3] tensor (undefined = none)
 Tensor sh_origin_arg(const c10::optional<Tensor>& o)
 {
@@ -117,9 +145,12 @@ std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tenso
     double scale_modifier, int64_t sh_degree, bool raw_params, bool prefiltered, bool debug, const Tensor& prepared,
     at::IntArrayRef batch_first_block, int64_t view_id, int64_t extras, const c10::optional<Tensor>& sh_origin_)
 {
+    const RetirePending retire = take_retire();
     TORCH_CHECK(means3D_.is_cuda(), "GaussianRasterizer: tensors must be on a ROCm/HIP device (no CPU fallback)");
     const BatchArg batch(batch_first_block);
     const int64_t NB = batch.B();
+    TORCH_CHECK(!retire.table.defined() || (retire.table.numel() == NB && retire.table.device() == means3D_.device()),
+                "retired_at: one int32 entry per model of the batch, on the models' device");
     const c10::hip::HIPGuardMasqueradingAsCUDA guard(means3D_.device());
     const Tensor means3D = f32c(means3D_), sh = f32c(sh_), colors = f32c(colors_), opac = f32c(opacities_), scales = f32c(scales_),
                  rots = f32c(rotations_), cov = f32c(cov3D_), rest = f32c(sh_rest_), vm = f32c(viewmatrix_), pm = f32c(projmatrix_),
@@ -172,7 +203,10 @@ std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tenso
     a.out_color_clamped = has(clamped) ? clamped.data_ptr<float>() : nullptr;
     a.visible = has(visible) ? visible.data_ptr<uint8_t>() : nullptr;
     GsrForwardOut out{};
-    check(gsr_forward(&a, &out, c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream()), "gsr_forward");
+    if (retire.table.defined())
+        check(gsr_forward_retire(&a, retire.table.data_ptr<int32_t>(), retire.step, &out, c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream()), "gsr_forward_retire");
+    else
+        check(gsr_forward(&a, &out, c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream()), "gsr_forward");
     // (scratch tensors die here: stream-ordered reuse by the caching allocator is safe, same stream)
     Tensor meta = at::empty({3}, at::TensorOptions().dtype(at::kLong));   // CPU: R, capacity, flags
     int64_t* mp = meta.data_ptr<int64_t>();
@@ -230,6 +264,8 @@ std::vector<Tensor> importance_accumulate(
     const c10::optional<Tensor>& sh_origin_)
 {
     TORCH_CHECK(means3D_.is_cuda(), "importance_accumulate: tensors must be on a ROCm/HIP device (no CPU fallback)");
+    // (gsr_importance_accumulate has no way to take a table -- include/gsr.h: refused here rather than ignored, before anything is enqueued)
+    TORCH_CHECK(!take_retire().table.defined(), "importance_accumulate: a retire table (retired_at) is not served with the importance pass");
     const BatchArg batch(batch_first_block);
     TORCH_CHECK(batch.B() == 1, "importance_accumulate: not served with a batch of B > 1");
     TORCH_CHECK(has(sh_) && !has(colors_), "importance_accumulate: the model must carry SH coefficients (colors_precomp has none)");
@@ -319,6 +355,8 @@ std::vector<Tensor> rasterize_backward(
     a.d_means3D = fpm(d_means3D); a.d_means2D = fpm(d_means2D); a.d_opacities = fpm(d_opac);
     a.d_colors_precomp = fpm(d_col); a.d_shs = fpm(d_sh); a.d_scales = fpm(d_scales); a.d_rotations = fpm(d_rot);
     a.d_cov3D_precomp = fpm(d_cov); a.d_shs_rest = fpm(d_rest);
+    const RetirePending retire = take_retire();   // (refused by the library: a table needs the optimizer-in-backward)
+    if (retire.table.defined()) { a.retired_at = retire.table.data_ptr<int32_t>(); a.retire_step = retire.step; }
     a.d_viewmatrix = fpm(d_vm); a.d_projmatrix = fpm(d_pm); a.d_campos = fpm(d_cp); a.d_points_transform = fpm(d_xf);
     a.scratch = scratch.data_ptr();
     GsrDensifyStats dstat{};
@@ -360,6 +398,8 @@ std::vector<Tensor> rasterize_backward_frozen(
     a.d_means2D = fpm(d_means2D);
     a.d_viewmatrix = fpm(d_vm); a.d_projmatrix = fpm(d_pm); a.d_campos = fpm(d_cp); a.d_points_transform = fpm(d_xf);
     a.scratch = scratch.data_ptr();
+    const RetirePending retire = take_retire();   // (refused by the library: no update to gate on the frozen backward)
+    if (retire.table.defined()) { a.retired_at = retire.table.data_ptr<int32_t>(); a.retire_step = retire.step; }
     check(gsr_backward(&a, c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream()), "gsr_backward");
     return {d_means2D, d_vm, d_pm, d_cp, d_xf};
 }
@@ -417,6 +457,11 @@ std::vector<Tensor> rasterize_backward_fused(
     a.scratch = scratch.data_ptr();
     a.fused_adam = &fa;
     a.batch = batch.ptr();
+    const RetirePending retire = take_retire();
+    if (retire.table.defined()) {
+        TORCH_CHECK(retire.table.numel() == NB, "retired_at: one int32 entry per model of the batch");
+        a.retired_at = retire.table.data_ptr<int32_t>(); a.retire_step = retire.step;
+    }
     const Tensor sh_origin = sh_origin_arg(sh_origin_);
     a.sh_origin = fp(sh_origin);
     GsrNextView nv{};
@@ -479,6 +524,9 @@ class RasterizeFn : public torch::autograd::Function<RasterizeFn> {
                      rs = f32c(rest), v = f32c(vm), p = f32c(pm), cp = f32c(campos), b = f32c(bg),
                      x = f32c((has(xf) && xf.dim() == 2) ? xf.slice(0, 0, 3) : xf);   // [4,4] -> rows 0..2; a batch hands [B,3,4]
         Tensor none;
+        const RetirePending retire = g_retire;   // (peeked: rasterize_forward takes it; this node keeps it for its backward)
+        ctx->saved_data["retire"] = retire.table.defined() ? retire.table : m3.new_empty({0}, m3.options().dtype(at::kInt));
+        ctx->saved_data["retire_step"] = retire.step;
         auto out = op.call(m3, s, c, o, sc, r, cv, rs, v, p, cp, b, x, cfg.H, cfg.W, cfg.tanfovx, cfg.tanfovy, cfg.scale_modifier,
                            cfg.sh_degree, cfg.raw_params, cfg.prefiltered, cfg.debug, cfg.prepared.defined() ? cfg.prepared : x.new_empty({0}, x.options().dtype(at::kByte)),
                            cfg.batch, cfg.view_id, cfg.extras, cfg.sh_origin.defined() ? c10::optional<Tensor>(cfg.sh_origin) : c10::nullopt);
@@ -558,6 +606,8 @@ class RasterizeFn : public torch::autograd::Function<RasterizeFn> {
         TORCH_CHECK(frozen != 1 || (!n_adam && dens.empty() && cam_wanted),
                     "frozen=True: not with fused_adam or densify_stats, and the camera or points_transform must require grad");
         const bool take_frozen = frozen == 1 || (frozen < 0 && !n_adam && dens.empty() && !param_wanted && cam_wanted);
+        // the forward's retire table goes to whichever backward op runs below, on THIS thread (the op takes it; the library applies or refuses it)
+        if (const Tensor rt = ctx->saved_data["retire"].toTensor(); has(rt)) retire_attach(rt, ctx->saved_data["retire_step"].toInt());
         if (n_adam) {
             // a second backward through the same forward would apply the optimizer step twice
             TORCH_CHECK(!ctx->saved_data["done"].toBool(), "fused_adam: backward() ran twice on the same render (retain_graph); the in-kernel "
@@ -665,6 +715,7 @@ std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> render(
     const Tensor& campos_, const Tensor& bg_, const Tensor& xf_, int64_t H, int64_t W, double tanfovx, double tanfovy,
     double scale_modifier, int64_t sh_degree, bool raw_params, int64_t view_id, int64_t outputs, const c10::optional<Tensor>& sh_origin_)
 {
+    const RetirePending retire = take_retire();   // (refused by the library: a render-only call takes no table)
     TORCH_CHECK(means3D_.is_cuda(), "render: tensors must be on a ROCm/HIP device (no CPU fallback)");
     const c10::hip::HIPGuardMasqueradingAsCUDA guard(means3D_.device());
     const Tensor means3D = f32c(means3D_.detach()), sh = f32c(sh_.detach()), colors = f32c(colors_.detach()), opac = f32c(opacities_.detach()),
@@ -701,7 +752,10 @@ std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> render(
     a.visible = has(visible) ? visible.data_ptr<uint8_t>() : nullptr;
     a.render_only = 1;
     GsrForwardOut out{};
-    check(gsr_forward(&a, &out, c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream()), "gsr_forward");
+    if (retire.table.defined())   // (refused: the library's own text)
+        check(gsr_forward_retire(&a, retire.table.data_ptr<int32_t>(), retire.step, &out, c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream()), "gsr_forward_retire");
+    else
+        check(gsr_forward(&a, &out, c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream()), "gsr_forward");
     TORCH_CHECK(!actx.binning.defined() && out.binning == nullptr, "render: a render-only forward asked for a binning buffer");
     // (every scratch tensor dies here: stream-ordered reuse by the caching allocator is safe, same stream)
     return {color, radii, depth, alpha, clamped, visible};
@@ -1172,6 +1226,27 @@ void densify_stats_add_(Tensor accum, Tensor denom, const Tensor& grad, const Te
     torch::autograd::impl::bump_version(denom);
 }
 
+// gsr::batch_retire -> gsr_batch_retire: the per-model exit decision on the render a step just produced.  render / target: [B,C,H,W] (or
+// [C,H,W] for one model); retired_at: B int32 entries, updated in place on the stream; returns the images' MSEs (B doubles, device).  No host
+// synchronisation.
+Tensor batch_retire(const Tensor& render_, const Tensor& target_, Tensor retired_at, double mse_bar, int64_t exit_after, int64_t step)
+{
+    TORCH_CHECK(render_.is_cuda() && target_.is_cuda() && retired_at.is_cuda(), "batch_retire: tensors must be on a ROCm/HIP device (no CPU fallback)");
+    TORCH_CHECK((render_.dim() == 3 || render_.dim() == 4) && render_.numel() == target_.numel(), "batch_retire: render and target are [B,C,H,W] stacks (or [C,H,W]) of one size");
+    const c10::hip::HIPGuardMasqueradingAsCUDA guard(render_.device());
+    const Tensor render = f32c(render_.detach()), target = f32c(target_.detach());
+    const int64_t B = render.dim() == 4 ? render.size(0) : 1, C = render.size(-3), H = render.size(-2), W = render.size(-1);
+    TORCH_CHECK(retired_at.scalar_type() == at::kInt && retired_at.is_contiguous() && retired_at.numel() == B,
+                "batch_retire: retired_at must be a contiguous int32 tensor with one entry per image");
+    Tensor mse = at::empty({B}, render.options().dtype(at::kDouble));
+    Tensor scratch = at::empty({(int64_t)gsr_batch_retire_scratch_bytes((int32_t)B)}, render.options().dtype(at::kByte));
+    const int rc = gsr_batch_retire(render.data_ptr<float>(), target.data_ptr<float>(), (int32_t)B, (int32_t)C, (int32_t)H, (int32_t)W, mse_bar, exit_after, step,
+                                    retired_at.data_ptr<int32_t>(), mse.data_ptr<double>(), scratch.data_ptr(),
+                                    c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream());
+    TORCH_CHECK(rc == 0, "gsr_batch_retire failed (code ", rc, "): step >= 1, exit_after >= 0 and at most 65535 images expected");
+    return mse;
+}
+
 Tensor psnr(const Tensor& a, const Tensor& b)
 {
     TORCH_CHECK(a.is_cuda(), "psnr: tensors must be on a ROCm/HIP device (no CPU fallback)");
@@ -1257,6 +1332,8 @@ TORCH_LIBRARY(gsr, m)
     m.def("densify_stats_add_(Tensor(a!) accum, Tensor(b!) denom, Tensor grad, Tensor mask) -> ()");
     m.def("psnr(Tensor a, Tensor b) -> Tensor");
     m.def("debug_last() -> Tensor[]", &debug_last);
+    m.def("batch_retire(Tensor render, Tensor target, Tensor(a!) retired_at, float mse_bar, int exit_after, int step) -> Tensor");
+    m.def("retire_attach(Tensor retired_at, int step) -> ()", &retire_attach);
 }
 
 TORCH_LIBRARY_IMPL(gsr, CUDA, m)   // the dispatch key of HIP tensors on a ROCm build
@@ -1281,6 +1358,7 @@ TORCH_LIBRARY_IMPL(gsr, CUDA, m)   // the dispatch key of HIP tensors on a ROCm 
     m.impl("masked_max_", &masked_max_);
     m.impl("densify_stats_add_", &densify_stats_add_);
     m.impl("psnr", &psnr);
+    m.impl("batch_retire", &batch_retire);
     m.impl("rasterize", &rasterize_forward_only);
     m.impl("photometric_loss", &photometric_loss_no_grad);
     m.impl("photometric_loss_terms", &photometric_loss_terms_no_grad);

@@ -146,6 +146,42 @@ def _check_frozen(frozen, fused_adam=None, prepare_next=None, densify_stats=None
         raise RuntimeError("frozen=True is not served together with fused_adam, prepare_next or densify_stats")
 
 
+def _check_retire(retire, fused_adam=None, fused_adam_deferred=False, densify_stats=None, frozen=None):
+    """retire = (retired_at, step): the retire table of a launch chain (include/gsr.h gsr_forward_retire) and the 1-based step of this
+    call.  It is applied by the fused route alone -- the optimizer-in-backward with its hand-over; every other route REFUSES it rather than
+    ignore it, before anything touches a device: a separate `FusedAdam.step()` launch (no fused_adam here), the deferred step, densify_stats,
+    the frozen backward.  (The render-only call and the importance pass have no `retire` keyword; a table left with them through
+    torch.ops.gsr.retire_attach is refused by the library / the binding.)"""
+    if retire is None:
+        return None
+    table, step = retire
+    if not torch.is_tensor(table) or table.dtype != torch.int32 or table.dim() != 1 or not table.is_contiguous():
+        raise RuntimeError("retire: retired_at must be a contiguous int32 vector (one entry per model)")
+    if int(step) < 1:
+        raise RuntimeError("retire: the step of a call is 1-based (the counter the fused Adam receives)")
+    if fused_adam is None:
+        raise RuntimeError("retire: a retire table needs fused_adam -- an update applied by a separate FusedAdam.step() launch cannot be gated per model")
+    if fused_adam_deferred:
+        raise RuntimeError("retire: a retire table is not served with the deferred step (fused_adam_deferred)")
+    if densify_stats is not None:
+        raise RuntimeError("retire: a retire table is not served with densify_stats")
+    if frozen:
+        raise RuntimeError("retire: a retire table is not served on the frozen backward")
+    return table, int(step)
+
+
+def _call_with_retire(ops, retire, fn, *args):
+    """fn(*args) with the table attached to it (torch.ops.gsr.retire_attach: single use, this thread); a call that fails before it took the
+    table leaves none behind."""
+    if retire is None:
+        return fn(*args)
+    ops.retire_attach(retire[0], retire[1])
+    try:
+        return fn(*args)
+    finally:
+        ops.retire_attach(retire[0][:0], 0)
+
+
 def _frozen_code(frozen) -> int:
     """The `frozen` argument of torch.ops.gsr.rasterize: -1 by inference, 0 never, 1 always."""
     if frozen is None:
@@ -386,10 +422,11 @@ def _ecpu():
 
 def _rasterize_ext(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, rs, sh_rest, raw_params,
                    fused_adam, points_transform, prepared=None, prepare_next=None, next_points_transform=None, densify_stats=None,
-                   batch_first_block=None, fused_adam_deferred=False, view_id=0, extras=0, sh_origin=None, frozen=None):
+                   batch_first_block=None, fused_adam_deferred=False, view_id=0, extras=0, sh_origin=None, frozen=None, retire=None):
     """torch.ops.gsr.rasterize: empty tensors stand for None; the camera tensors of the settings tuple are ordinary inputs
     (their gradients are produced when one of them requires grad)."""
     _check_frozen(frozen, fused_adam, prepare_next, densify_stats)
+    retire = _check_retire(retire, fused_adam, fused_adam_deferred, densify_stats, frozen)
     ops = E.load()
     dev = means3D.device
     if dev.type != "cuda":
@@ -455,14 +492,14 @@ def _rasterize_ext(means3D, means2D, sh, colors_precomp, opacities, scales, rota
             [] if densify_stats is None else list(densify_stats), [] if nb <= 1 else [int(x) for x in batch_first_block], int(view_id), int(extras),
             sh_origin, _frozen_code(frozen))
     if not rs.debug:
-        out = ops.rasterize(*args)
+        out = _call_with_retire(ops, retire, ops.rasterize, *args)
         if extras:       # (color, radii, depth, alpha, clamped colour, visibility bytes)
             return out[:4] + (out[5], out[6])
         return out[:5] if prepare_next is not None else out[:4]
     # raster_settings.debug = True: what the public module does -- on an error in the native forward, dump the arguments to
     # snapshot_fw.dump for offline inspection and re-raise (the reference always passes debug=False, gaussian_model_ht.py:821)
     try:
-        out = ops.rasterize(*args)
+        out = _call_with_retire(ops, retire, ops.rasterize, *args)
         if extras:
             return out[:4] + (out[5], out[6])
         return out[:5] if prepare_next is not None else out[:4]
@@ -485,7 +522,7 @@ def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales,
 def rasterize_gaussians_raw(means3D, means2D, features_dc, features_rest, opacity_logit, log_scales, rotations_raw,
                             raster_settings, fused_adam=None, points_transform=None, prepared=None, prepare_next=None,
                             next_points_transform=None, densify_stats=None, batch_first_block=None, fused_adam_deferred=False,
-                            view_id=0, extras=0, sh_origin=None, frozen: Optional[bool] = None):
+                            view_id=0, extras=0, sh_origin=None, frozen: Optional[bool] = None, retire=None):
     """Extension ("next" row f-2): rasterize straight from HTGaussianModel's raw parameters (_xyz, _features_dc,
     _features_rest, _opacity, _scaling, _rotation; /root/reference/scene/gaussian_model_ht.py:74-82) with the
     activations of :49-65,128-133,176-188 fused into the HIP kernels; gradients are w.r.t. the raw tensors.
@@ -540,12 +577,21 @@ def rasterize_gaussians_raw(means3D, means2D, features_dc, features_rest, opacit
     points_transform gradients alone, no per-Gaussian gradient computed or allocated) when no parameter tensor requires grad and the
     camera or points_transform does, which is every pose iteration against detached parameters (the reference after fix_position():
     /root/reference/trainer/ht3dgs_trainer.py:307-335, 916-963); False -- always the full backward; True -- the frozen one even if a
-    parameter requires grad (its .grad then stays None); RuntimeError with fused_adam, prepare_next or densify_stats."""
+    parameter requires grad (its .grad then stays None); RuntimeError with fused_adam, prepare_next or densify_stats.
+
+    retire = (retired_at, step): the retire table of the launch chain -- B int32 entries on the device (one for a single model), 0 = active,
+    otherwise the step at which torch.ops.gsr.batch_retire retired the model -- and the 1-based step s of this call (include/gsr.h
+    gsr_forward_retire; the reference's per-model exit, /root/reference/trainer/ht3dgs_trainer.py:299-300).  The forward culls every
+    model with 0 < retired_at[b] < s (background image, zero depth / alpha, radii 0, no gradient); the backward skips the Adam update of
+    those models bit for bit and prepares the next render with the test at s + 1.  Needs fused_adam; refused (RuntimeError, before a device is
+    touched) with fused_adam_deferred, densify_stats or frozen=True."""
     _check_frozen(frozen, fused_adam, prepare_next, densify_stats)
     if not E.use_ctypes():
         return _rasterize_ext(means3D, means2D, features_dc, None, opacity_logit, log_scales, rotations_raw, None, raster_settings,
                               features_rest, True, fused_adam, points_transform, prepared, prepare_next, next_points_transform,
-                              densify_stats, batch_first_block, fused_adam_deferred, view_id, extras, sh_origin, frozen)
+                              densify_stats, batch_first_block, fused_adam_deferred, view_id, extras, sh_origin, frozen, retire)
+    if retire is not None:
+        raise RuntimeError("retire is served by the PyTorch extension binding only")
     if prepared is not None or extras or prepare_next is not None or densify_stats is not None or batch_first_block is not None or fused_adam_deferred \
             or sh_origin is not None:
         raise RuntimeError("prepared / prepare_next / densify_stats / batch_first_block / fused_adam_deferred / sh_origin are served by the "

@@ -129,9 +129,19 @@ def run_stage_a(n_frames: int, fit_fn: Callable[[int], torch.Tensor], device, ra
     return pose_dict_from_table(gather_pose_table(local, n_frames, rank, world, device, group), vfi)
 
 
+EARLY_EXIT_MODES = ("host", "device")
+_POLL_EVERY = 50      # iterations between two looks of the host at the exit condition (either mode)
+
+
+def _check_early_exit(early_exit: str):
+    if early_exit not in EARLY_EXIT_MODES:
+        raise ValueError(f"early_exit={early_exit!r}: 'host' or 'device'")
+
+
 def fit_pair(seq, p: int, device, n_points: int = 100_000, single_image_iters: int = 1000, pose_iters: int = 300,
              pose_lr: float = 2e-3, seed: int = 0, init: str = "pixels", fused_pose_step: bool = True, lambda_depth: float = 0.0,
-             depth_loss_type: str = "invariant") -> torch.Tensor:
+             depth_loss_type: str = "invariant", early_exit: str = "host", psnr_exit: float = 35.0, exit_after: int = 500,
+             info: Optional[dict] = None) -> torch.Tensor:
     """compute_relative_pose(p+1, p) on the HIP rasterizer (:336-380): returns rel_pose_{p}_to_{p+1} [4,4] (CPU).
 
     1. single-image 3DGS of frame p in that frame's own camera coordinates (identity pose), initialised from the frame's
@@ -142,7 +152,16 @@ def fit_pair(seq, p: int, device, n_points: int = 100_000, single_image_iters: i
     lambda_depth != 0: both phases add lambda_depth * the depth term (`depth_loss_type`, 'invariant' as the reference sets it for this
     stage, ht3dgs_trainer.py:354, :392) on the render's depth against the frame's depth map (`seq.depth`): the image phase through
     train_step, the pose phase through fused_training_loss_report, whose depth gradient reaches the transform through the blend's
-    depth instantiation.  0 (the default) leaves every launch as it is."""
+    depth instantiation.  0 (the default) leaves every launch as it is.
+    early_exit: how the image phase ends.  'host' (the default, as ever): the host computes the PSNR every 50 iterations past `exit_after`
+    and leaves the loop when it exceeds `psnr_exit`.  'device': the reference's rule at EVERY iteration, decided and applied on the device
+    (train_step's `retire`): the model is retired at the first iteration past `exit_after` whose render has PSNR > psnr_exit, that
+    iteration's update still applies, and from then on the model is frozen bit for bit; the host reads the table every 50 iterations and
+    leaves the loop once the entry is set -- when it looks does not change the result.  `fit_pairs_batched(early_exit='device')` returns
+    the same pose bit for bit, whichever pairs share a batch.  An unknown value raises ValueError before a device is touched.
+    info (a dict, optional): receives 'iterations' and, in 'device' mode, 'retired_at' (the iteration the model retired at, 0 = the cap)
+    and 'mse' ([iterations, 1] float64, the decision kernel's MSE of every step; a retired model's rows show the background image)."""
+    _check_early_exit(early_exit)
     from . import pose as pose_mod
     from . import train_step as ts
     from .loss import fused_photometric_loss, fused_training_loss_report
@@ -166,13 +185,27 @@ def fit_pair(seq, p: int, device, n_points: int = 100_000, single_image_iters: i
         if with_depth:
             return fused_training_loss_report(out[0], tgt1, out[2], dep1, 0.2, float(lambda_depth), depth_loss_type, clamp=True)[0]
         return fused_photometric_loss(out[0], tgt1, 0.2, clamp=True)
+    retire = params.new_retire_table(psnr_exit, exit_after) if early_exit == "device" else None
+    it, curve = 0, []
     for it in range(1, single_image_iters + 1):
+        if retire is not None:      # the rule on the device at every iteration; the host only looks now and then
+            ts.train_step(params, ident, tgt0, next_settings=ident, retire=retire, **dkw)
+            if info is not None:
+                curve.append(retire.mse)
+            if it % _POLL_EVERY == 0 and all(retire.retired_sync()):
+                break
+            continue
         pkg = ts.train_step(params, ident, tgt0, next_settings=ident, **dkw)      # same view every step: its preprocess rides in the backward
-        if it > 500 and it % 50 == 0:
+        if it > exit_after and it % _POLL_EVERY == 0:
             with torch.no_grad():
                 mse = ((pkg["raw_image"].clamp(0, 1) - tgt0) ** 2).mean()
-            if float(-10 * torch.log10(mse.clamp_min(1e-12))) > 35:
+            if float(-10 * torch.log10(mse.clamp_min(1e-12))) > psnr_exit:
                 break
+    if info is not None:
+        info["iterations"] = it
+        if retire is not None:
+            info["retired_at"] = retire.retired_sync()[0]
+            info["mse"] = torch.stack(curve).cpu() if curve else None      # [iterations, 1] float64: the decision kernel's MSE of every step
     raw = params.raw()
     m2d = torch.zeros_like(raw["_xyz"])
     if not fused_pose_step:      # the torch statement of the loop: exponential map + its autograd + torch.optim.Adam (~50 tiny kernels)
@@ -209,14 +242,23 @@ def fit_pair(seq, p: int, device, n_points: int = 100_000, single_image_iters: i
 
 def fit_pairs_batched(seq, pairs: List[int], device, n_points: int = 100_000, single_image_iters: int = 1000, pose_iters: int = 300,
                       pose_lr: float = 2e-3, seed: int = 0, lambda_depth: float = 0.0,
-                      depth_loss_type: str = "invariant") -> Dict[int, torch.Tensor]:
+                      depth_loss_type: str = "invariant", early_exit: str = "host", psnr_exit: float = 35.0, exit_after: int = 500,
+                      info: Optional[dict] = None) -> Dict[int, torch.Tensor]:
     """`fit_pair` for several pairs AT ONCE: the B single-image models live in one parameter store and every step of the B fits is
     ONE launch chain (batched.BatchedGaussianParams / include/gsr.h GsrBatch) -- B renders, B losses, B Adam updates and the B
     hand-overs to the next step per pass over the kernels, instead of B chains of ~17 kernels that each fill a fraction of the
     chip.  Per model the arithmetic is what `fit_pair` does (bit-identical renders and updates, tests/test_gpu_batched.py); what
-    differs is the early exit of the image phase: the reference leaves a model's loop when its PSNR passes 35 dB after 500
-    iterations (ht3dgs_trainer.py:300-301), a batch runs until ALL its models have passed (or the iteration cap) -- a model that
-    is already there simply trains a little longer.  Returns {pair -> rel_pose [4,4] (CPU)}.
+    can differ is the early exit of the image phase: the reference leaves a model's loop when its PSNR passes 35 dB after 500
+    iterations (ht3dgs_trainer.py:299-300).
+      early_exit='host' (the default): the batch runs until ALL its models have passed at one of the host's looks (every 50 iterations
+        past `exit_after`), or until the cap.  A model that is already there keeps training at full cost, so its pose is NOT the one
+        `fit_pair` returns for it whenever the models of the batch pass at different times: the result depends on which pairs share a batch.
+      early_exit='device': every model is retired on the device at its own first iteration past `exit_after` with PSNR > psnr_exit
+        (train_step's `retire`), receives that iteration's update and is frozen from then on -- culled from the renders, skipped by Adam.
+        Pair for pair the pose is `fit_pair(early_exit='device')`'s bit for bit, whatever the batch; the host reads the table every 50
+        iterations and leaves when every entry is set.  The loss the steps report still sums the retired images' terms.
+    Returns {pair -> rel_pose [4,4] (CPU)}.  info (a dict, optional): 'iterations' and, in 'device' mode, 'retired_at'
+    {pair -> iteration, 0 = the cap} and 'mse' [iterations, B].
     lambda_depth / depth_loss_type as in `fit_pair`: the depth term on the stack of the B depth planes (the sum of the images' terms,
     each with its own fit -- every model gets exactly the gradient of its own loss)."""
     from . import batched as bt
@@ -224,10 +266,19 @@ def fit_pairs_batched(seq, pairs: List[int], device, n_points: int = 100_000, si
     from . import _ext
     from .loss import fused_photometric_loss, fused_training_loss_report
     from .rasterizer import rasterize_gaussians_raw
+    _check_early_exit(early_exit)
     B = len(pairs)
     if B == 1:
-        return {pairs[0]: fit_pair(seq, pairs[0], device, n_points, single_image_iters, pose_iters, pose_lr, seed,
-                                   lambda_depth=lambda_depth, depth_loss_type=depth_loss_type)}
+        one = {} if info is not None else None
+        out = {pairs[0]: fit_pair(seq, pairs[0], device, n_points, single_image_iters, pose_iters, pose_lr, seed,
+                                  lambda_depth=lambda_depth, depth_loss_type=depth_loss_type, early_exit=early_exit, psnr_exit=psnr_exit,
+                                  exit_after=exit_after, info=one)}
+        if info is not None:
+            info["iterations"] = one["iterations"]
+            if "retired_at" in one:
+                info["retired_at"] = {pairs[0]: one["retired_at"]}
+                info["mse"] = one["mse"]
+        return out
     stride = max(1, int(round((seq.W * seq.H / max(1, n_points)) ** 0.5)))
     scenes = [seq.pixel_scene(p, stride=stride, seed=seed) for p in pairs]
     params = bt.BatchedGaussianParams(scenes, device)
@@ -241,13 +292,27 @@ def fit_pairs_batched(seq, pairs: List[int], device, n_points: int = 100_000, si
     if with_depth:
         dkw = dict(depth_gt=torch.stack([seq.depth(p) for p in pairs]), lambda_depth=float(lambda_depth), depth_loss_type=depth_loss_type)
         dep1 = torch.stack([seq.depth(p + 1) for p in pairs])
+    retire = params.new_retire_table(psnr_exit, exit_after) if early_exit == "device" else None
+    it, curve = 0, []
     for it in range(1, single_image_iters + 1):
+        if retire is not None:
+            ts.train_step(params, ident, tgt0, next_settings=ident, retire=retire, **dkw)
+            if info is not None:
+                curve.append(retire.mse)
+            if it % _POLL_EVERY == 0 and all(retire.retired_sync()):
+                break
+            continue
         pkg = ts.train_step(params, ident, tgt0, next_settings=ident, **dkw)
-        if it > 500 and it % 50 == 0:
+        if it > exit_after and it % _POLL_EVERY == 0:
             with torch.no_grad():
                 mse = ((pkg["raw_image"].clamp(0, 1) - tgt0) ** 2).flatten(1).mean(dim=1)
-            if float((-10 * torch.log10(mse.clamp_min(1e-12))).min()) > 35:
+            if float((-10 * torch.log10(mse.clamp_min(1e-12))).min()) > psnr_exit:
                 break
+    if info is not None:
+        info["iterations"] = it
+        if retire is not None:
+            info["retired_at"] = dict(zip(pairs, retire.retired_sync()))
+            info["mse"] = torch.stack(curve).cpu() if curve else None      # [iterations, B] float64
     raw = params.raw()
     m2d = torch.zeros_like(raw["_xyz"])
     ops = _ext.load()

@@ -108,8 +108,40 @@ def depth_loss(depth: torch.Tensor, depth_gt: torch.Tensor, kind: str = "invaria
     return (loss, s, t, a11) if return_fit else loss
 
 
+class RetireTable:
+    """The retire table of one launch chain and the rule that fills it (include/gsr.h gsr_forward_retire, gsr_batch_retire): the
+    reference leaves a single-image model's loop at the first iteration past `exit_after` where that model's PSNR exceeds `psnr_exit`, after
+    that iteration's optimizer step (train_single_image_3DGS, /root/reference/trainer/ht3dgs_trainer.py:299-300; 500 and 35 dB there).
+    `retired_at` holds one int32 per model on the device, 0 while the model trains, otherwise the step it retired at; `step` counts the train
+    steps taken with this table (train_step advances it); `mse` is the last decision's per-model MSE (float64, device).  Everything is decided
+    and applied on the device: train_step(..., retire=table) adds no host synchronisation -- `retired_sync()` is the one place that waits."""
+
+    def __init__(self, num_models: int, device, psnr_exit: float = 35.0, exit_after: int = 500):
+        if int(exit_after) < 0:
+            raise ValueError("RetireTable: exit_after must not be negative")
+        self.retired_at = torch.zeros(int(num_models), dtype=torch.int32, device=device)
+        self.psnr_exit, self.exit_after = float(psnr_exit), int(exit_after)
+        self.mse_bar = 10.0 ** (-self.psnr_exit / 10.0)      # PSNR > psnr_exit  <=>  MSE < 10^(-psnr_exit / 10)
+        self.step = 0
+        self.mse = None
+
+    def retired_sync(self):
+        """Host copy of the table as a list of ints (0 = still training).  SYNCHRONISES: the copy waits for every step enqueued so far."""
+        return [int(x) for x in self.retired_at.cpu().tolist()]
+
+
 class GaussianParams:
     """Raw (pre-activation) parameters, laid out as HTGaussianModel keeps them."""
+
+    def new_retire_table(self, psnr_exit: float = 35.0, exit_after: int = 500) -> RetireTable:
+        """A fresh retire table for this store: one entry per model (a batch: `num_models` entries), all active."""
+        return RetireTable(len(getattr(self, "counts", (0,))), self._xyz.device, psnr_exit, exit_after)
+
+    @staticmethod
+    def retired_sync(table: RetireTable):
+        """The host copy of a retire table (list of ints, 0 = still training).  SYNCHRONISES with the device -- the training loop itself never
+        needs it; stage A polls it every 50 iterations."""
+        return table.retired_sync()
 
     def __init__(self, scene: Dict, device, spatial_lr_scale: float = 1.0, optimizer: str = "hip"):
         d = device
@@ -388,13 +420,17 @@ class CameraPoseState:
 def render(params: GaussianParams, settings: GaussianRasterizationSettings, clamp: bool = True,
            fused_activations: bool = False, fused_adam=None, next_settings: GaussianRasterizationSettings = None,
            points_transform: torch.Tensor = None, next_points_transform: torch.Tensor = None, densify_stats=None,
-           view_id: int = 0) -> Dict:
+           view_id: int = 0, retire=None) -> Dict:
     """CF3DGS_Render.render with compute_cov3D_python = convert_SHs_python = False.
     view_id: the frame's id (non-zero; the reference's `viewpoint_camera.uid`) -- speed only (rasterize_gaussians_raw).
     fused_activations=True hands the raw parameters to the kernels (exp / sigmoid / normalize / cat in-kernel).
     next_settings (with fused_adam): the camera of the NEXT render of this model -- its preprocess then rides in this render's
     backward ("prepare in backward", rasterize_gaussians_raw) and the hand-over buffer is kept on `params` until a render with
-    that camera picks it up (single use; any parameter surgery drops it)."""
+    that camera picks it up (single use; any parameter surgery drops it).
+    retire = (retired_at, step): the retire table and the step of this call (rasterize_gaussians_raw); needs fused_activations + fused_adam."""
+    if retire is not None and not (fused_activations and fused_adam is not None):
+        raise RuntimeError("retire: a retire table needs the fused step (fused_activations with fused_adam); a separate FusedAdam.step() "
+                           "launch cannot be gated per model")
     settings = with_sh_degree(settings, params.active_sh_degree)     # gaussian_model_ht.py:818: sh_degree = the model's ACTIVE degree
     xyz = params.get_xyz
     # gaussian_model_ht.py:800-805 builds `zeros_like(xyz, requires_grad=True) + 0` every render only to receive
@@ -420,7 +456,7 @@ def render(params: GaussianParams, settings: GaussianRasterizationSettings, clam
                                       params._scaling, params._rotation, settings, fused_adam=fused_adam, prepared=use,
                                       prepare_next=want_next, points_transform=points_transform,
                                       next_points_transform=next_points_transform if want_next is not None else None,
-                                      densify_stats=densify_stats, batch_first_block=bfb, view_id=view_id)
+                                      densify_stats=densify_stats, batch_first_block=bfb, view_id=view_id, retire=retire)
         if want_next is not None:        # filled by this render's backward; train_step marks it valid once that has run
             nxf = next_points_transform if next_points_transform is not None else points_transform
             params._prepared = {"buf": out[4], "settings": want_next, "n": xyz.shape[0], "xyz": params._xyz, "valid": False,
@@ -467,7 +503,7 @@ def train_step(params: GaussianParams, settings: GaussianRasterizationSettings, 
                lambda_dssim: float = 0.2, fused_loss: bool = True, fused_activations: bool = True,
                fused_optimizer: bool = True, densifier=None, iteration: int = 0, next_settings=None,
                pose: "PoseState" = None, next_pose: "PoseState" = None, next_sh_degree: int = None, view_id: int = 0,
-               depth_gt: torch.Tensor = None, lambda_depth: float = 0.0, depth_loss_type: str = "invariant") -> Dict:
+               depth_gt: torch.Tensor = None, lambda_depth: float = 0.0, depth_loss_type: str = "invariant", retire: RetireTable = None) -> Dict:
     """render -> loss -> backward -> Adam step (ht3dgs_trainer.py:102-166 without densification).
     fused_loss=True evaluates clamp + L1 + SSIM in the HIP loss kernels; False uses the torch restatement.
     fused_activations=True runs exp / sigmoid / normalize / cat inside the rasterizer kernels.
@@ -486,7 +522,16 @@ def train_step(params: GaussianParams, settings: GaussianRasterizationSettings, 
     depth_gt ([H,W] or [1,H,W]; [B,H,W] or [B,1,H,W] for a batch of B models) with a non-zero lambda_depth: the loss is photometric + lambda_depth * depth term (`Loss.forward`,
     losses.py:114-124; depth_loss_type 'l1' or 'invariant') on the render's depth plane, and the render's backward receives grad_depth
     -- on every route above (the blend's depth / alpha instantiation, then the depth terms of the per-Gaussian backward).  Without it
-    nothing changes: the same launches, the same bits."""
+    nothing changes: the same launches, the same bits.
+    retire (RetireTable; `params.new_retire_table()`): per-model retirement inside the launch chain, decided and applied on the device with no
+    host synchronisation.  This call is step s = retire.step + 1: its render culls the models retired before s, the decision kernel
+    (torch.ops.gsr.batch_retire) then marks a model whose clamped render has MSE < 10^(-psnr_exit / 10) against `gt` when s > exit_after,
+    the backward applies the Adam update of step s to every model not retired BEFORE s (the update of the step a model retires at still
+    applies, ht3dgs_trainer.py:299-300) and hands the next render over with the models retired up to s culled.  A retired model's
+    parameters and moments stay untouched bit for bit.  The loss kernels are untouched: the reported loss still contains the retired
+    images' terms (background against target); nothing downstream of a culled model can carry their gradient.  Needs the fused step
+    (fused_activations, fused_optimizer, the "hip" optimizer) and no densifier; anything else raises before a device is touched.
+    pkg["retire_mse"] = this step's per-model MSEs (float64, device)."""
     with_depth = depth_gt is not None and float(lambda_depth) != 0.0
     fused_adam = params.optimizer if (fused_optimizer and fused_activations and isinstance(params.optimizer, FusedAdam)) else None
     # an iteration whose `after_backward` replaces parameter tensors (densify / prune, opacity reset) runs UNFUSED: the reference's
@@ -494,6 +539,13 @@ def train_step(params: GaussianParams, settings: GaussianRasterizationSettings, 
     # (ht3dgs_trainer.py:137-160; densify.py) -- an update applied inside the backward kernel could not be dropped any more
     if fused_adam is not None and densifier is not None and densifier.touches_parameters_at(iteration):
         fused_adam = None
+    rstep = None
+    if retire is not None:
+        if fused_adam is None or densifier is not None or E_use_ctypes():
+            raise RuntimeError("retire: per-model retirement runs on the fused step (fused_activations + fused_optimizer on the 'hip' optimizer, "
+                               "extension binding) without a densifier -- a separate FusedAdam.step() launch, the deferred step and "
+                               "densify_stats refuse a retire table")
+        rstep = retire.step + 1
     # pose refinement (the reference's camera_optimizer, ht3dgs_trainer.py:162-166): this frame's transform is an autograd leaf of
     # the render; the hand-over to the next render is skipped when that render is of THIS frame (its transform changes in between)
     cam_pose = isinstance(pose, CameraPoseState)
@@ -517,7 +569,13 @@ def train_step(params: GaussianParams, settings: GaussianRasterizationSettings, 
     dstats = densifier.fused_stats(iteration) if (densifier is not None and fused_activations and not E_use_ctypes()) else None
     pkg = render(params, settings, clamp=not fused_loss, fused_activations=fused_activations, fused_adam=fused_adam,
                  next_settings=nxt, points_transform=xf, densify_stats=dstats, view_id=view_id,
-                 next_points_transform=next_pose.M if (xf is not None and next_pose is not None and nxt is not None) else None)
+                 next_points_transform=next_pose.M if (xf is not None and next_pose is not None and nxt is not None) else None,
+                 retire=None if retire is None else (retire.retired_at, rstep))
+    if retire is not None:      # the decision on the render just produced: two short launches on the stream, nothing waited for
+        from . import _ext
+        with torch.no_grad():
+            retire.mse = _ext.load().batch_retire(pkg["raw_image"], gt, retire.retired_at, retire.mse_bar, retire.exit_after, rstep)
+        pkg["retire_mse"] = retire.mse
     # (a batch hands [B,3,H,W] stacks: the fused loss is then the SUM of the models' losses, every image normalised on its own -- each
     #  model gets exactly its own loss's gradient, bit-identical with training it alone; the depth term likewise, on [B,1,H,W])
     if fused_loss and with_depth and not E_use_ctypes():      # one dispatcher call, one autograd node for d_render and d_depth
@@ -544,5 +602,7 @@ def train_step(params: GaussianParams, settings: GaussianRasterizationSettings, 
         densifier.after_backward(iteration, pkg, stats_done=dstats is not None)
     params.optimizer.step()
     params.optimizer.zero_grad(set_to_none=True)
+    if retire is not None:
+        retire.step = rstep
     pkg["loss"] = loss.detach()
     return pkg

@@ -291,6 +291,17 @@ typedef struct GsrBackwardArgs {
      * untransformed mean: it is added to d_means3D after the R^T chain of points_transform and reaches none of d_points_transform,
      * d_campos, d_viewmatrix.  Needs shs; refused (GSR_ERR_ARG) with a batch of B > 1 or next_view. */
     const float* sh_origin;
+    /* version 117: the forward's retire table and step (see gsr_forward_retire; ht3dgs_trainer.py:299-300).  Needs fused_adam.
+     *   The Adam update of step s runs for model b exactly when retired_at[b] == 0 || retired_at[b] >= s -- the update of the step at which a
+     *   model retires still applies, as the reference steps its optimizer before it breaks.  A skipped model's parameters and both moments
+     *   stay untouched bit for bit (its blocks issue none of their parameter or moment streams), its d_means2D rows, d_points_transform and
+     *   camera entries are exact zeros.
+     *   The hand-over for the next render (next_view / prepared_out) is written CULLED for model b when retired_at[b] != 0 &&
+     *   retired_at[b] < s + 1: the forward that consumes the buffer sees the model as the render of step s + 1 must.
+     * Refused (GSR_ERR_ARG, before anything is enqueued): a table without fused_adam (the frozen call included), with deferred application
+     * (GsrFusedAdam::param_out), with densify_stats, or with retire_step < 1. */
+    const int32_t* retired_at;
+    int64_t retire_step;
 } GsrBackwardArgs;
 
 size_t gsr_geom_bytes(int32_t N);
@@ -311,6 +322,22 @@ size_t gsr_prepared_radii_offset(int32_t N);                /* where its int32 r
 int gsr_prepare_supported(int32_t M, int32_t D, int32_t raw_params); /* 1 when gsr_backward can prepare the next view */
 
 int gsr_forward(const GsrForwardArgs* args, GsrForwardOut* out, void* stream);
+/* ---- version 117: the forward of a launch chain with a RETIRE TABLE (stage A's per-model early exit, decided and applied on the device).
+ * The reference leaves a single-image model's loop at the first iteration past 500 where that model's PSNR exceeds 35 dB
+ * (train_single_image_3DGS, /root/reference/trainer/ht3dgs_trainer.py:299-300), AFTER that iteration's optimizer.step().  retired_at: B int32
+ * entries on the device (one entry with batch == NULL), 0 = active, otherwise the 1-based step at which gsr_batch_retire retired the model;
+ * retire_step = the step s of THIS call (>= 1, the counter GsrFusedAdam::step receives).  retired_at == NULL: gsr_forward itself, byte for byte
+ * (gsr_forward(args, out, stream) IS gsr_forward_retire(args, NULL, 0, out, stream)).
+ *   The render of step s CULLS model b exactly when retired_at[b] != 0 && retired_at[b] < s: every Gaussian of the model gets radius 0,
+ *   `visible` 0 and no instance; its image is the background, its depth and alpha planes are 0, and nothing downstream of it can carry a
+ *   gradient (the loss kernels are untouched: a reported loss sum still contains the retired images' terms, background against target).
+ *   A forward that takes a `prepared` buffer does not read the table: the backward that filled the buffer applied the same test
+ *   (GsrBackwardArgs::retired_at).
+ * The table travels beside GsrForwardArgs, not in it: that struct keeps its version-116 layout, which tests/test_render_only_cpu.py pins
+ * (render_only is its last field); GsrBackwardArgs carries the table as appended fields.  gsr_importance_accumulate takes a GsrForwardArgs and
+ * therefore no table: the pass cannot be given one.
+ * Refused (GSR_ERR_ARG, before anything is asked for or enqueued): a table with args->render_only, or with retire_step < 1. */
+int gsr_forward_retire(const GsrForwardArgs* args, const int32_t* retired_at, int64_t retire_step, GsrForwardOut* out, void* stream);
 int gsr_backward(const GsrBackwardArgs* args, void* stream);
 int gsr_mark_visible(int32_t N, const float* means3D, const float* viewmatrix, const float* projmatrix,
                      uint8_t* present, void* stream);
@@ -347,7 +374,8 @@ const char* gsr_last_error(void);
  * 113: gsr_importance_accumulate / gsr_importance_scratch_bytes; no struct changed.
  * 114: the depth term on a stack of planes (gsr_depth_loss_*_batched); no struct changed.
  * 115: the frozen call of gsr_backward (camera / transform gradients alone, see GsrBackwardArgs); no struct changed.
- * 116: GsrForwardArgs ends with render_only (the render-only call). */
+ * 116: GsrForwardArgs ends with render_only (the render-only call).
+ * 117: the retire table: gsr_forward_retire, GsrBackwardArgs ends with retired_at, retire_step, gsr_batch_retire; GsrForwardArgs unchanged. */
 int gsr_version(void);
 size_t gsr_struct_bytes(int32_t which); /* 0 GsrForwardArgs, 1 GsrBackwardArgs, 2 GsrForwardOut; anything else 0 */
 
@@ -605,6 +633,20 @@ int gsr_masked_max(float* dst, const int32_t* src, const uint8_t* mask, int32_t 
 int gsr_densify_stats_add(float* xyz_gradient_accum, float* denom, const float* viewspace_grad3, const uint8_t* mask, int32_t n, void* stream);
 size_t gsr_psnr_scratch_bytes(int32_t C);
 int gsr_psnr(const float* a, const float* b, int32_t C, int64_t P, float* out, void* scratch, void* stream);
+
+/* ---- version 117: the per-model exit decision of a launch chain (gsr_forward_retire), two launches: partial sums, finish.
+ * render, target: stacks [B,C,H,W] (B = 1: one image).  mse_b = mean over the C H W elements of image b of (clamp(render, 0, 1) - target)^2;
+ * every difference and square is formed in float64 from the float32 inputs and the values are added in a fixed order over a fixed grid
+ * (no atomics), the element -> lane assignment depending on the position INSIDE the image alone: mse_out[b] and the decision of image b are
+ * bit-identical whatever B is and wherever the image lies in the stack.  mse_out: B doubles, always written.  The finishing kernel sets
+ *     retired_at[b] = step   when   retired_at[b] == 0  &&  step > exit_after  &&  mse_b < mse_bar     (strict; a NaN never retires)
+ * and never changes an entry that is set (sticky).  mse_bar = 10^(-psnr_exit / 10) as a double; the reference's rule is exit_after = 500,
+ * psnr_exit = 35 (/root/reference/trainer/ht3dgs_trainer.py:299-300).  scratch: gsr_batch_retire_scratch_bytes(B) bytes, 8-byte aligned.
+ * GSR_ERR_ARG: a NULL pointer, B outside 1..65535, a non-positive C / H / W, step < 1 or beyond int32, exit_after < 0, mse_out or scratch
+ * not 8-byte aligned. */
+size_t gsr_batch_retire_scratch_bytes(int32_t B);
+int gsr_batch_retire(const float* render, const float* target, int32_t B, int32_t C, int32_t H, int32_t W, double mse_bar, int64_t exit_after,
+                     int64_t step, int32_t* retired_at, double* mse_out, void* scratch, void* stream);
 
 /* ---- "next" row f-1: simple_knn._C.distCUDA2 ----------------------------------------------------------------
  * out[i] = mean of the squared distances from points[i] to its 3 nearest other points (exact), the semantics of the

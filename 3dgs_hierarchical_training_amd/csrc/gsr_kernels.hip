@@ -3434,6 +3434,10 @@ struct AdamDev {
 };
 template <typename T>
 __device__ __forceinline__ T* adam_out(T* p, long long d) { return reinterpret_cast<T*>(reinterpret_cast<char*>(p) + d); }
+// In place (the destination is the source): a 128-byte line of stream elements the update left bit for bit as they were loaded is not
+// stored again (adam_unchanged4 / adam_line_changed, adam_math.h).  The out-of-place route (param_out ..., the deferred step's shadow buffers) always stores: its
+// destination holds something else.  Uniform over the block; the streams hoist it out of their loops.
+__device__ __forceinline__ bool adam_in_place(const AdamDev& ad, int grp) { return (ad.dp[grp] | ad.dm[grp] | ad.dv[grp]) == 0; }
 
 __device__ __forceinline__ void adam_rows(const float* s_g, int stride, int col0, int row, int nact, float* __restrict__ p,
                                           float* __restrict__ m, float* __restrict__ v, int nG, int tid, float step_size, float bc2,
@@ -3441,6 +3445,7 @@ __device__ __forceinline__ void adam_rows(const float* s_g, int stride, int col0
 {
     const int total = nG * row;
     float* const po = adam_out(p, ad.dp[grp]); float* const mo = adam_out(m, ad.dm[grp]); float* const vo = adam_out(v, ad.dv[grp]);
+    const bool inpl = adam_in_place(ad, grp);
     if (((((uintptr_t)p | (uintptr_t)m | (uintptr_t)v | (uintptr_t)po | (uintptr_t)mo | (uintptr_t)vo) & 15) == 0) && (total & 3) == 0) {
         float4* p4 = reinterpret_cast<float4*>(p);
         float4* m4 = reinterpret_cast<float4*>(m);
@@ -3450,6 +3455,7 @@ __device__ __forceinline__ void adam_rows(const float* s_g, int stride, int col0
         float4* vo4 = reinterpret_cast<float4*>(vo);
         for (int q = tid; q < total / 4; q += kPreThreads) {
             float4 pp = p4[q], mm = nt_load4(m4 + q), vv = nt_load4(v4 + q);   // moments are touched once per step: keep them out of L2
+            const float4 p0 = pp, m0 = mm, v0 = vv;
             const int f = 4 * q;
             int g = f / row, e = f - g * row;
             float gs[4];
@@ -3462,14 +3468,15 @@ __device__ __forceinline__ void adam_rows(const float* s_g, int stride, int col0
             adam_one(pp.y, gs[1], mm.y, vv.y, ad.b1, ad.b2, ad.eps, step_size, bc2);
             adam_one(pp.z, gs[2], mm.z, vv.z, ad.b1, ad.b2, ad.eps, step_size, bc2);
             adam_one(pp.w, gs[3], mm.w, vv.w, ad.b1, ad.b2, ad.eps, step_size, bc2);
-            nt_store4(po4 + q, pp); nt_store4(mo4 + q, mm); nt_store4(vo4 + q, vv);
+            if (adam_line_changed<8>(!(inpl && adam_unchanged4(p0, m0, v0, pp, mm, vv)), tid & 63)) { nt_store4(po4 + q, pp); nt_store4(mo4 + q, mm); nt_store4(vo4 + q, vv); }
         }
     } else {
         for (int f = tid; f < total; f += kPreThreads) {
             const int g = f / row, e = f - g * row;
             float pp = p[f], mm = m[f], vv = v[f];
+            const float p0 = pp, m0 = mm, v0 = vv;
             adam_one(pp, e < nact ? s_g[g * stride + col0 + e] : 0.f, mm, vv, ad.b1, ad.b2, ad.eps, step_size, bc2);
-            po[f] = pp; mo[f] = mm; vo[f] = vv;
+            if (!(inpl && adam_unchanged(p0, m0, v0, pp, mm, vv))) { po[f] = pp; mo[f] = mm; vo[f] = vv; }
         }
     }
 }
@@ -3497,6 +3504,7 @@ __device__ __forceinline__ void adam_rows_lin(float* s_g, int total, float* __re
     float4* po4 = reinterpret_cast<float4*>(po);
     float4* mo4 = reinterpret_cast<float4*>(mo);
     float4* vo4 = reinterpret_cast<float4*>(vo);
+    const bool inpl = adam_in_place(ad, grp);
     if ((((uintptr_t)m | (uintptr_t)v | (uintptr_t)po | (uintptr_t)mo | (uintptr_t)vo) & 15) == 0) {
         int q0 = tid;
         if constexpr (KP > 0) {
@@ -3505,12 +3513,13 @@ __device__ __forceinline__ void adam_rows_lin(float* s_g, int total, float* __re
                 const int q = tid + k * kPreThreads;
                 if (q < total / 4) {
                     float4 pp = p4[q], mm = pm[k], vv = pv[k];
+                    const float4 p0 = pp, m0 = mm, v0 = vv;
                     const float4 g = g4[q];
                     adam_one(pp.x, g.x, mm.x, vv.x, ad.b1, ad.b2, ad.eps, step_size, bc2);
                     adam_one(pp.y, g.y, mm.y, vv.y, ad.b1, ad.b2, ad.eps, step_size, bc2);
                     adam_one(pp.z, g.z, mm.z, vv.z, ad.b1, ad.b2, ad.eps, step_size, bc2);
                     adam_one(pp.w, g.w, mm.w, vv.w, ad.b1, ad.b2, ad.eps, step_size, bc2);
-                    nt_store4(po4 + q, pp); nt_store4(mo4 + q, mm); nt_store4(vo4 + q, vv);
+                    if (adam_line_changed<8>(!(inpl && adam_unchanged4(p0, m0, v0, pp, mm, vv)), tid & 63)) { nt_store4(po4 + q, pp); nt_store4(mo4 + q, mm); nt_store4(vo4 + q, vv); }
                     if (KEEP) g4[q] = pp;
                 }
             }
@@ -3519,19 +3528,21 @@ __device__ __forceinline__ void adam_rows_lin(float* s_g, int total, float* __re
 #pragma unroll GSR_K9_UNROLL
         for (int q = q0; q < total / 4; q += kPreThreads) {
             float4 pp = p4[q], mm = nt_load4(m4 + q), vv = nt_load4(v4 + q);
+            const float4 p0 = pp, m0 = mm, v0 = vv;
             const float4 g = g4[q];
             adam_one(pp.x, g.x, mm.x, vv.x, ad.b1, ad.b2, ad.eps, step_size, bc2);
             adam_one(pp.y, g.y, mm.y, vv.y, ad.b1, ad.b2, ad.eps, step_size, bc2);
             adam_one(pp.z, g.z, mm.z, vv.z, ad.b1, ad.b2, ad.eps, step_size, bc2);
             adam_one(pp.w, g.w, mm.w, vv.w, ad.b1, ad.b2, ad.eps, step_size, bc2);
-            nt_store4(po4 + q, pp); nt_store4(mo4 + q, mm); nt_store4(vo4 + q, vv);
+            if (adam_line_changed<8>(!(inpl && adam_unchanged4(p0, m0, v0, pp, mm, vv)), tid & 63)) { nt_store4(po4 + q, pp); nt_store4(mo4 + q, mm); nt_store4(vo4 + q, vv); }
             if (KEEP) g4[q] = pp;
         }
     } else {
         for (int f = tid; f < total; f += kPreThreads) {
             float pp = p[f], mm = m[f], vv = v[f];
+            const float p0 = pp, m0 = mm, v0 = vv;
             adam_one(pp, s_g[f], mm, vv, ad.b1, ad.b2, ad.eps, step_size, bc2);
-            po[f] = pp; mo[f] = mm; vo[f] = vv;
+            if (!(inpl && adam_unchanged(p0, m0, v0, pp, mm, vv))) { po[f] = pp; mo[f] = mm; vo[f] = vv; }
             if (KEEP) s_g[f] = pp;
         }
     }
@@ -3560,6 +3571,7 @@ __device__ __forceinline__ void adam_rows_lin_piped(float* s_g, float* p, float*
     float4* po4 = reinterpret_cast<float4*>(adam_out(p, ad.dp[grp]));
     float4* mo4 = reinterpret_cast<float4*>(adam_out(m, ad.dm[grp]));
     float4* vo4 = reinterpret_cast<float4*>(adam_out(v, ad.dv[grp]));
+    const bool inpl = adam_in_place(ad, grp);
     float4 P[D], M[D], V[D];
 #pragma unroll
     for (int k = 0; k < D && k < NE; k++) {
@@ -3574,6 +3586,7 @@ __device__ __forceinline__ void adam_rows_lin_piped(float* s_g, float* p, float*
     for (int k = 0; k < NE; k++) {
         const int q = tid + k * kPreThreads, sl = k % D;
         float4 pp = P[sl], mm = M[sl], vv = V[sl];
+        const float4 p0 = pp, m0 = mm, v0 = vv;
         if (k + D < NE) {
             const int qn = q + D * kPreThreads;
             if ((k + D + 1) * kPreThreads <= total4 || qn < total4) {
@@ -3588,7 +3601,7 @@ __device__ __forceinline__ void adam_rows_lin_piped(float* s_g, float* p, float*
             adam_one(pp.y, g.y, mm.y, vv.y, ad.b1, ad.b2, ad.eps, step_size, bc2);
             adam_one(pp.z, g.z, mm.z, vv.z, ad.b1, ad.b2, ad.eps, step_size, bc2);
             adam_one(pp.w, g.w, mm.w, vv.w, ad.b1, ad.b2, ad.eps, step_size, bc2);
-            nt_store4(po4 + q, pp); nt_store4(mo4 + q, mm); nt_store4(vo4 + q, vv);
+            if (adam_line_changed<8>(!(inpl && adam_unchanged4(p0, m0, v0, pp, mm, vv)), tid & 63)) { nt_store4(po4 + q, pp); nt_store4(mo4 + q, mm); nt_store4(vo4 + q, vv); }
             if (KEEP) g4[q] = pp;
         }
     }
@@ -3632,12 +3645,19 @@ __device__ __forceinline__ void adam_own_apply(float* p, float* m, float* v, Own
 {
     float* const po = adam_out(p, ad.dp[grp]); float* const mo = adam_out(m, ad.dm[grp]); float* const vo = adam_out(v, ad.dv[grp]);
     float pp[K];
+    uint32_t diff = adam_in_place(ad, grp) ? 0u : 1u;     // in place: did the update change any word of the row?
 #pragma unroll
-    for (int c = 0; c < K; c++) { pp[c] = s.p[c]; adam_one(pp[c], g[c], s.m[c], s.v[c], ad.b1, ad.b2, ad.eps, step_size, bc2); }
+    for (int c = 0; c < K; c++) {
+        const float m0 = s.m[c], v0 = s.v[c];
+        pp[c] = s.p[c]; adam_one(pp[c], g[c], s.m[c], s.v[c], ad.b1, ad.b2, ad.eps, step_size, bc2);
+        diff |= adam_unchanged(s.p[c], m0, v0, pp[c], s.m[c], s.v[c]) ? 0u : 1u;
+    }
     if (updated) {
 #pragma unroll
         for (int c = 0; c < K; c++) updated[c] = pp[c];
     }
+    // neighbouring lanes own neighbouring rows: 8 rows of 16 bytes, 32 rows of 4 or 12 bytes are whole 128-byte lines -- stored whole or not at all
+    if (!adam_line_changed<(K == 4 ? 8 : 32)>(diff != 0u, (int)(threadIdx.x & 63))) return;
     if (K == 4 && ((((uintptr_t)po | (uintptr_t)mo | (uintptr_t)vo) & 15) == 0)) {
         nt_store4(reinterpret_cast<float4*>(po), make_float4(pp[0], pp[1], pp[2], pp[K - 1]));
         nt_store4(reinterpret_cast<float4*>(mo), make_float4(s.m[0], s.m[1], s.m[2], s.m[K - 1]));
@@ -4056,13 +4076,16 @@ __global__ __launch_bounds__(kPreThreads) void k_preprocess_bwd(CamParams cp, in
                 if (tid < dc4) {
                     float4* g4 = reinterpret_cast<float4*>(s_dc);
                     const float4 g = g4[tid];
+                    const float4 p0 = dP, m0 = dM, v0 = dV;
                     adam_one(dP.x, g.x, dM.x, dV.x, ad.b1, ad.b2, ad.eps, ad.step_size[1], ad.inv_bc2s[1]);
                     adam_one(dP.y, g.y, dM.y, dV.y, ad.b1, ad.b2, ad.eps, ad.step_size[1], ad.inv_bc2s[1]);
                     adam_one(dP.z, g.z, dM.z, dV.z, ad.b1, ad.b2, ad.eps, ad.step_size[1], ad.inv_bc2s[1]);
                     adam_one(dP.w, g.w, dM.w, dV.w, ad.b1, ad.b2, ad.eps, ad.step_size[1], ad.inv_bc2s[1]);
-                    nt_store4(reinterpret_cast<float4*>(adam_out(pd, ad.dp[1])) + tid, dP);
-                    nt_store4(reinterpret_cast<float4*>(adam_out(ad.m[1] + b * 3, ad.dm[1])) + tid, dM);
-                    nt_store4(reinterpret_cast<float4*>(adam_out(ad.v[1] + b * 3, ad.dv[1])) + tid, dV);
+                    if (adam_line_changed<8>(!(adam_in_place(ad, 1) && adam_unchanged4(p0, m0, v0, dP, dM, dV)), tid & 63)) {
+                        nt_store4(reinterpret_cast<float4*>(adam_out(pd, ad.dp[1])) + tid, dP);
+                        nt_store4(reinterpret_cast<float4*>(adam_out(ad.m[1] + b * 3, ad.dm[1])) + tid, dM);
+                        nt_store4(reinterpret_cast<float4*>(adam_out(ad.v[1] + b * 3, ad.dv[1])) + tid, dV);
+                    }
                     if (PREP >= 0) g4[tid] = dP;
                 }
             } else {

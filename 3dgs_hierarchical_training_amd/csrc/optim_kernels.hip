@@ -52,10 +52,14 @@ __global__ __launch_bounds__(kAdamThreads) void k_adam(AdamBatch B)
 #pragma unroll
         for (int r = 0; r < 4; r++) {
             const uint64_t i = base + (uint64_t)(r * kAdamThreads + threadIdx.x) * kAdamVec;
+            const float4 p0 = p[r], m0 = m[r], v0 = v[r];
             adam_one(p[r].x, g[r].x, m[r].x, v[r].x, B.beta1, B.beta2, B.eps, step_size, inv_bc2s);
             adam_one(p[r].y, g[r].y, m[r].y, v[r].y, B.beta1, B.beta2, B.eps, step_size, inv_bc2s);
             adam_one(p[r].z, g[r].z, m[r].z, v[r].z, B.beta1, B.beta2, B.eps, step_size, inv_bc2s);
             adam_one(p[r].w, g[r].w, m[r].w, v[r].w, B.beta1, B.beta2, B.eps, step_size, inv_bc2s);
+            // the update is in place: a 128-byte line (eight lanes' elements) it left bit for bit as loaded is already in memory
+            // (adam_unchanged4 / adam_line_changed, adam_math.h)
+            if (!adam_line_changed<8>(!adam_unchanged4(p0, m0, v0, p[r], m[r], v[r]), (int)(threadIdx.x & 63))) continue;
             nt_store4(reinterpret_cast<float4*>(t.param + i), p[r]);
             nt_store4(reinterpret_cast<float4*>(t.exp_avg + i), m[r]);
             nt_store4(reinterpret_cast<float4*>(t.exp_avg_sq + i), v[r]);
@@ -71,17 +75,21 @@ __global__ __launch_bounds__(kAdamThreads) void k_adam(AdamBatch B)
             const float4 g = nt_load4(reinterpret_cast<const float4*>(t.grad + i));
             float4 m = nt_load4(reinterpret_cast<const float4*>(t.exp_avg + i));
             float4 v = nt_load4(reinterpret_cast<const float4*>(t.exp_avg_sq + i));
+            const float4 p0 = p, m0 = m, v0 = v;
             adam_one(p.x, g.x, m.x, v.x, B.beta1, B.beta2, B.eps, step_size, inv_bc2s);
             adam_one(p.y, g.y, m.y, v.y, B.beta1, B.beta2, B.eps, step_size, inv_bc2s);
             adam_one(p.z, g.z, m.z, v.z, B.beta1, B.beta2, B.eps, step_size, inv_bc2s);
             adam_one(p.w, g.w, m.w, v.w, B.beta1, B.beta2, B.eps, step_size, inv_bc2s);
+            if (!adam_line_changed<8>(!adam_unchanged4(p0, m0, v0, p, m, v), (int)(threadIdx.x & 63))) continue;
             nt_store4(reinterpret_cast<float4*>(t.param + i), p);
             nt_store4(reinterpret_cast<float4*>(t.exp_avg + i), m);
             nt_store4(reinterpret_cast<float4*>(t.exp_avg_sq + i), v);
         } else {
             for (uint64_t k = i; k < t.n && k < i + kAdamVec; k++) {
                 float p = t.param[k], m = t.exp_avg[k], v = t.exp_avg_sq[k];
+                const float p0 = p, m0 = m, v0 = v;
                 adam_one(p, t.grad[k], m, v, B.beta1, B.beta2, B.eps, step_size, inv_bc2s);
+                if (adam_unchanged(p0, m0, v0, p, m, v)) continue;
                 t.param[k] = p; t.exp_avg[k] = m; t.exp_avg_sq[k] = v;
             }
         }

@@ -383,9 +383,9 @@ size_t gsr_struct_bytes(int32_t which); /* 0 GsrForwardArgs, 1 GsrBackwardArgs, 
  *   "blend_fwd_ppt"        forward blend kernel: 7 = one wave per 8x8 sub-tile, finished pixels encoded in the sign of T,
  *                          instances the sub-tile cannot see skipped by reach bits (default); 6 = without the reach bits.
  *                          Any other value is refused (the A/B kernels rounds 1-4 selected with 1-5 left the tree in round 5)
- *   "blend_bwd_ppt"        backward blend kernel: 2 (default; 0 = default) = two pixels per lane, packed math, two waves per tile; 1 = one pixel per lane,
- *                          four waves per tile, four reach bits per staged instance (k_blend_bwd1: same results within rounding; -7 % of the kernel
- *                          on random scenes of up to ~130 k Gaussians, +2 % on pixel-sized splats, equal from 300 k on)
+ *   "blend_bwd_ppt"        backward blend kernel: 0 or 2 = two pixels per lane, packed math, two waves per tile -- the only backward
+ *                          blend, so setting it changes nothing.  Any other value is refused (the one-pixel-per-lane kernel that 1
+ *                          selected left the tree)
  *   "ab_variants"          query kept for callers of the round-4 ABI: always returns 0 (no A/B kernels in the library)
  *   "sort_algo"            2 = onesweep for both sorts (default); 1 = onesweep depth sort only; 0 = hist + scan + scatter
  *   "bwd_split"            1 = the backward of a tile is ONE work item (off); anything else (default 0) = one item per 128-instance
@@ -454,9 +454,7 @@ size_t gsr_struct_bytes(int32_t which); /* 0 GsrForwardArgs, 1 GsrBackwardArgs, 
  *                          a second kernel sums each Gaussian's slots in list order, in float64; several times slower.  The
  *                          default adds the same float32 parts with float64 atomics in arrival order, and those sums are exact
  *                          (order-independent) while the parts' exponent span plus log2(count) fits in 29 bits: the default gives
- *                          the same bits as this mode apart from rare rounding-boundary flips of inexact sums.  "blend_bwd_ppt" 1
- *                          does not: its four waves add a tile's part into LDS in float32, in arrival order (this mode always runs
- *                          the two-pixel kernel)
+ *                          the same bits as this mode apart from rare rounding-boundary flips of inexact sums
  *   "profile"              1 = HIP events around every stage on the caller's stream (an event pair costs ~10 us of stream
  *                          bubble per stage), 2 = only the forward blend kernel is timed, through the start / stop timestamps of
  *                          its own dispatch (hipExtLaunchKernelGGL: still ~11 us of idle queue around the launch), 3 = as 2 on

@@ -131,8 +131,8 @@ def test_options_from_the_environment_at_load():
     code = ("import importlib, sys; sys.path.insert(0, '.'); L = importlib.import_module('3dgs_hierarchical_training_amd._lib'); "
             "lib = L.load(); print('loaded', lib.gsr_set_option(b'tile_sort', 1))")
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    ok = subprocess.run([sys.executable, "-c", code], cwd=root, env={**os.environ, "GSR_OPTS": "tile_sort=2, blend_bwd_ppt=1"}, capture_output=True, text=True)
+    ok = subprocess.run([sys.executable, "-c", code], cwd=root, env={**os.environ, "GSR_OPTS": "tile_sort=2, blend_bwd_ppt=2"}, capture_output=True, text=True)
     assert ok.returncode == 0 and "loaded 0" in ok.stdout, ok.stderr[-400:]
-    for bad in ("no_such_option=1", "tile_sort=7"):
+    for bad in ("no_such_option=1", "tile_sort=7", "blend_bwd_ppt=1"):
         r = subprocess.run([sys.executable, "-c", code], cwd=root, env={**os.environ, "GSR_OPTS": bad}, capture_output=True, text=True)
         assert r.returncode != 0 and "GSR_OPTS" in r.stderr, (bad, r.stdout, r.stderr[-400:])

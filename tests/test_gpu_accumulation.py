@@ -1,8 +1,7 @@
 """GPU: the default blend backward equals the fixed-order one, bit for bit.
 
-With `blend_bwd_ppt` at its default the default backward and the fixed-order mode ("deterministic_backward") run the same kernel,
-k_blend_bwd2, whose two waves add into a tile's LDS row commutatively: both form the same float32 part per (tile, Gaussian).  They
-differ only in how those parts are summed into the Gaussian's 10-double row (kGG, csrc/blend_common.h): float64 atomics in arrival
+The default backward and the fixed-order mode ("deterministic_backward") run the same kernel, k_blend_bwd2 (the only backward blend),
+whose two waves add into a tile's LDS row commutatively: both form the same float32 part per (tile, Gaussian).  They differ only in how those parts are summed into the Gaussian's 10-double row (kGG, csrc/blend_common.h): float64 atomics in arrival
 order (default: the flush of k_blend_bwd2, the prologue's fill of the rows, the `v != 0` skip) or float64 in list order (k_det_reduce
 over a slot per (tile, instance)).  Exact sums give the same bits either way, so every gradient the product returns -- means2D and
 the camera / points_transform gradients included -- must be equal, apart from rare rounding-boundary flips of inexact sums

@@ -52,8 +52,6 @@ namespace gsr {
 // ------------------------------------------------------------------------------------------------
 static thread_local char g_err[512] = "";
 static int g_blend_ppt = 0;   // 0 = default
-// 1 (default) = onesweep (decoupled look-back) for the depth sort over N, histogram+scan+scatter for the tile
-// sort over R (measured: 115 vs 140 us and 164 vs 157 us); 0 = three-kernel passes everywhere; 2 = onesweep everywhere
 // prepare in backward: up to this many Gaussians the per-Gaussian backward kernel also counts the digits of the next depth sort
 // (saves that sort's histogram launch: ~7 us + a launch gap on small models); above, its ~2 global adds per key cost more inside
 // the HBM-bound kernel than the histogram kernel does on its own (1 M: +20 us against -8 us).  Both sides of the hand-over
@@ -64,7 +62,6 @@ static int g_small_sort9 = 1;   // smallest N for which a forward with its own p
 static inline bool prep_counts_digits(int N) { return N <= g_prep_hist_max_n; }
 static int g_poll_iters = 400000;   // bound of gsr_forward's busy-wait for R in units of ~50 ns (20 ms); 0 = no polling: hipStreamSynchronize at once
 static int g_emit_hist = 1;   // 1: k_emit counts the tile sort's digits (no histogram launch); 0: k_radix_ghist
-static int g_sort_algo = 2;   // 2: onesweep for both sorts; 1: onesweep depth sort + hist/scan/scatter tile sort; 0: hist/scan/scatter
 
 static int fail(int code, const char* fmt, const char* detail = "")
 {
@@ -4076,7 +4073,7 @@ static FwdScratch fwd_scratch_layout(int32_t N)
     s.block_sums = o; o += align256(((n + kEmitThreads - 1) / kEmitThreads) * 4);
     s.total = o; o += 256;
     s.early = o; o += align256(((n + kPreThreads - 1) / kPreThreads) * sizeof(uint2));   // k_preprocess's per-block shares of R (OsRider)
-    s.sort = o; o += radix_scratch_bytes((uint32_t)n);
+    s.sort = o; o += onesweep_scratch_bytes((uint32_t)n);
     s.bytes = o;
     return s;
 }
@@ -4110,7 +4107,7 @@ static BinScratch bin_scratch_layout(int64_t R, int key_bytes = 4)
     s.tile = o; o += align256(r * (size_t)key_bytes);
     s.tile_alt = o; o += align256(r * (size_t)key_bytes);
     s.gid_alt = o; o += align256(r * 4);
-    s.sort = o; o += radix_scratch_bytes((uint32_t)r);
+    s.sort = o; o += onesweep_scratch_bytes((uint32_t)r);
     s.bytes = o;
     return s;
 }
@@ -4253,6 +4250,18 @@ static int check_common(int32_t N, int32_t M, int32_t D, int32_t W, int32_t H)
     return GSR_OK;
 }
 
+// gsr_sort_pairs_u32 / _u16: the bit range lies inside the key, the scratch holds gsr_sort_scratch_bytes(n)
+template <typename KeyT>
+static int sort_pairs_entry(KeyT* keys, uint32_t* vals, KeyT* keys_alt, uint32_t* vals_alt, uint32_t n, int begin_bit, int end_bit, void* scratch,
+                            size_t scratch_bytes, int* result_in_alt, void* stream)
+{
+    if (!result_in_alt) return fail(GSR_ERR_ARG, "sort: result_in_alt is null%s");
+    if (scratch_bytes < onesweep_scratch_bytes(n)) return fail(GSR_ERR_ARG, "sort scratch too small%s");
+    if (begin_bit < 0 || end_bit <= begin_bit || end_bit > 8 * (int)sizeof(KeyT)) return fail(GSR_ERR_ARG, "sort bit range outside the key%s");
+    GSR_HIP(onesweep_sort_pairs<KeyT>(keys, vals, keys_alt, vals_alt, n, begin_bit, end_bit, scratch, result_in_alt, (hipStream_t)stream));
+    return GSR_OK;
+}
+
 }  // namespace gsr
 
 using namespace gsr;
@@ -4304,7 +4313,7 @@ size_t gsr_backward_scratch_bytes(int32_t N)
     const size_t n = (size_t)(N > 0 ? N : 1);
     return align256(n * kGG * sizeof(double)) + align256(((n + kPreThreads - 1) / kPreThreads) * kCamVals * 4);
 }
-size_t gsr_sort_scratch_bytes(uint32_t n) { return radix_scratch_bytes(n); }
+size_t gsr_sort_scratch_bytes(uint32_t n) { return onesweep_scratch_bytes(n); }
 size_t gsr_prepared_bytes(int32_t N) { return prep_layout(N).bytes; }
 size_t gsr_prepared_radii_offset(int32_t N) { return prep_layout(N).radii; }
 int gsr_prepare_supported(int32_t M, int32_t D, int32_t raw_params) { return (raw_params && M == 16 && D >= 0 && D <= 3) ? 1 : 0; }
@@ -4402,7 +4411,8 @@ int gsr_set_option(const char* name, int value)
     if (!strcmp(name, "small_sort9")) { if (value < 0) return GSR_ERR_ARG; g_small_sort9 = value; return GSR_OK; }
     if (!strcmp(name, "poll_iters")) { g_poll_iters = value < 0 ? 0 : value; return GSR_OK; }
     if (!strcmp(name, "emit_hist")) { g_emit_hist = value ? 1 : 0; return GSR_OK; }
-    if (!strcmp(name, "sort_algo")) { if (value < 0 || value > 2) return GSR_ERR_ARG; g_sort_algo = value; return GSR_OK; }
+    // 2 = onesweep, the only sort: nothing to set (the name stays for callers that pass it through)
+    if (!strcmp(name, "sort_algo")) return value == 2 ? GSR_OK : GSR_ERR_ARG;
     // 0 or 2 = the packed two-pixel kernel, the only backward blend: nothing to set (the name stays for callers that pass it through)
     if (!strcmp(name, "blend_bwd_ppt")) return (value == 0 || value == 2) ? GSR_OK : GSR_ERR_ARG;
     return GSR_ERR_ARG;
@@ -4538,9 +4548,9 @@ static int forward_impl(const GsrForwardArgs* a, const int32_t* retired_at, int6
     // direct binning (k_chunk_counts ... k_chunk_scatter) where the frame's tile tables fit a wave's LDS; else emit + tile sort
     DirectBin db = {};
     DirectBinScratch dbs = {};
-    const bool direct = g_direct_bin && g_sort_algo == 2 && !wide_keys && direct_bin_geometry(N, T, db, dbs);
+    const bool direct = g_direct_bin && !wide_keys && direct_bin_geometry(N, T, db, dbs);
     // tile-sort route (round 5): the binning runs over the Gaussians in index order and k_tile_sort orders every tile's pairs by depth:
-    // single renders whose tile tables fit one wave, onesweep configuration
+    // single renders whose tile tables fit one wave
     bool tsort = false;   // (decided below, once the caller's capacity hint is known)
     uint2* ranges = nullptr;
     uint32_t* list = nullptr;
@@ -4582,7 +4592,7 @@ static int forward_impl(const GsrForwardArgs* a, const int32_t* retired_at, int6
         uint32_t* v0 = (tile_passes & 1) ? gid_alt2 : list;
         uint32_t* v1 = (tile_passes & 1) ? list : gid_alt2;
         // the emission counts the tile sort's digits itself when that sort's head is known to be zero (cleared by k_block_scan)
-        const bool emit_hist = g_sort_algo == 2 && prezeroed && g_emit_hist;
+        const bool emit_hist = prezeroed && g_emit_hist;
         EmitHist eh = {};
         if (emit_hist) {
             eh.ghist = reinterpret_cast<uint32_t*>(bs + S.sort);
@@ -4600,10 +4610,8 @@ static int forward_impl(const GsrForwardArgs* a, const int32_t* retired_at, int6
         int in_alt = 0;
         {
             ProfScope ps(P_SORT_TILE, st);
-            GSR_HIP(g_sort_algo == 2 ? onesweep_sort_pairs<KeyT>(tkey, v0, tkey_alt, v1, (uint32_t)capacity, 0, bits, bs + S.sort,
-                                                                 &in_alt, st, n_dev, prezeroed, emit_hist)
-                                     : radix_sort_pairs<KeyT>(tkey, v0, tkey_alt, v1, (uint32_t)capacity, 0, tile_passes * 8, bs + S.sort,
-                                                              &in_alt, st));
+            GSR_HIP(onesweep_sort_pairs<KeyT>(tkey, v0, tkey_alt, v1, (uint32_t)capacity, 0, bits, bs + S.sort, &in_alt, st, n_dev, prezeroed,
+                                              emit_hist));
         }
         const KeyT* skey = in_alt ? tkey_alt : tkey;
         {
@@ -4726,17 +4734,17 @@ static int forward_impl(const GsrForwardArgs* a, const int32_t* retired_at, int6
         if (g_hint_override > 0) { hint = (uint64_t)g_hint_override; g_hint_override = -1; }
         else { auto it = g_hints.find(hint_key); if (it != g_hints.end()) hint = it->second; }
     }
-    const bool speculative = g_speculate && g_sort_algo == 2 && hint > 0;
+    const bool speculative = g_speculate && hint > 0;
     const uint64_t cap = speculative ? hint : 0;
     {
         const int ts_mode = g_tile_sort;
         const uint64_t avg = (hint > 0 ? hint : (uint64_t)N * 4u) / (uint64_t)T;
-        // (behind the direct binning: single renders whose tile tables fit one wave; behind the emit path -- batched renders, frames above
-        //  4 096 tiles -- wherever both sorts are the onesweep ones)
+        // (behind the direct binning: single renders whose tile tables fit one wave; behind the emit path: batched renders, frames above
+        //  4 096 tiles)
         // (on the emit path the keys are gathered per pair and the lists of a large model spread widely: measured at 1920x1080, 300 k
         //  Gaussians -1.7 % of the step, 1 M +1 ... +12 %; eight stage-A models in one launch chain -2.5 %: small models only)
         const bool auto_ok = ts_mode == 1 && avg <= (uint64_t)g_tile_sort_max_avg && (direct || N / std::max(1, NB) <= g_tile_sort_emit_max_n);
-        tsort = (ts_mode == 2 || auto_ok) && g_sort_algo == 2 && (direct ? NB == 1 : true);
+        tsort = (ts_mode == 2 || auto_ok) && (direct ? NB == 1 : true);
     }
 
     fs = static_cast<uint8_t*>(a->alloc(align256(L.bytes) + (direct ? dbs.bytes : 0), GSR_ALLOC_SCRATCH, a->alloc_user));   // (+ the chunk tables of the direct binning)
@@ -4752,13 +4760,12 @@ static int forward_impl(const GsrForwardArgs* a, const int32_t* retired_at, int6
     TileRec* ntiles = reinterpret_cast<TileRec*>(fs + L.ntiles);
     uint32_t* block_sums = reinterpret_cast<uint32_t*>(fs + L.block_sums);
     unsigned long long* total = reinterpret_cast<unsigned long long*>(fs + L.total);
-    const bool depth_onesweep = g_sort_algo != 0;
     CamParams cp = {a->viewmatrix, a->projmatrix, a->campos, a->tanfovx, a->tanfovy, a->scale_modifier, W, H, a->D, a->M, a->points_transform, bt};
     const int grid = (N + kPreThreads - 1) / kPreThreads;
     const RetireDev rt = {retired_at, (int)retire_step};   // (a forward over a prepared buffer runs no preprocess: the backward culled for it)
     // block 0 of k_preprocess clears the head (digit histograms + tickets) of the depth sort's scratch
-    uint32_t* zero_words = depth_onesweep ? reinterpret_cast<uint32_t*>(fs + L.sort) : nullptr;
-    const int zero_count = depth_onesweep ? (int)kOnesweepHeadWordsMax : 0;   // (either layout of the depth sort's head)
+    uint32_t* zero_words = reinterpret_cast<uint32_t*>(fs + L.sort);
+    const int zero_count = (int)kOnesweepHeadWordsMax;   // (either layout of the depth sort's head)
     uint8_t* depth_scratch = fs + L.sort;
     bool depth_hist_done = false;
     // early R (round 5): a speculative forward that runs its own preprocess learns R from k_preprocess's per-block shares, summed and
@@ -4766,7 +4773,7 @@ static int forward_impl(const GsrForwardArgs* a, const int32_t* retired_at, int6
     // ends ~10 us into the forward instead of behind sort + counts + scan, and the caller can enqueue its loss and its backward while
     // the forward is still running.  (A forward that takes a prepared buffer finds the shares in it: the backward that ran its
     // preprocess left them there, k_preprocess_bwd's next-view tail.)
-    const bool early_r = g_early_r && speculative && depth_onesweep;
+    const bool early_r = g_early_r && speculative;
     uint2* early_parts = early_r ? reinterpret_cast<uint2*>(a->prepared ? static_cast<uint8_t*>(a->prepared) + prep_layout(N).early : fs + L.early) : nullptr;
     // visible depth keys beyond the 27-bit window of the three-pass sort are counted whenever this forward MAY sort on it
     const uint32_t early_window = (N > g_prep_hist_max_n || (g_small_sort9 && !a->prepared && N >= g_small_sort9)) ? (1u << 27) - 1u : 0xffffffffu;
@@ -4783,7 +4790,8 @@ static int forward_impl(const GsrForwardArgs* a, const int32_t* retired_at, int6
         // the depth sort's scratch is the buffer's too: its head was cleared in the backward (no memset here), and for small
         // models the backward also counted the digits and cleared the status words, so the sort starts with its first pass
         // (onesweep_sort_pairs hist_done)
-        if (depth_onesweep) { depth_scratch = pb + PL.sort; depth_hist_done = prep_counts_digits(N); }
+        depth_scratch = pb + PL.sort;
+        depth_hist_done = prep_counts_digits(N);
         // radii: a caller that takes them straight from the buffer (gsr_prepared_radii_offset) passes its own pointer into it
         // and nothing at all runs in front of the sort; otherwise a 4 N-byte copy kernel
         if (a->radii != reinterpret_cast<const int32_t*>(pb + PL.radii))
@@ -4825,7 +4833,7 @@ static int forward_impl(const GsrForwardArgs* a, const int32_t* retired_at, int6
     // the full sort.
     // (round 5: a forward that runs its own preprocess launches a digit histogram anyway, so below the threshold too three 9-bit passes
     //  behind it beat four 8-bit ones -- one latency-bound pass less; "small_sort9" = the smallest model that takes them, 0 = off)
-    bool wide_depth = depth_onesweep && g_depth_sort9 && !depth_hist_done && (N > g_prep_hist_max_n || (g_small_sort9 && N >= g_small_sort9));
+    bool wide_depth = g_depth_sort9 && !depth_hist_done && (N > g_prep_hist_max_n || (g_small_sort9 && N >= g_small_sort9));
     if (wide_depth) {
         std::lock_guard<std::mutex> lk(g_state_mutex);
         auto it = g_full_depth_sort.find(hint_key);
@@ -4849,9 +4857,8 @@ static int forward_impl(const GsrForwardArgs* a, const int32_t* retired_at, int6
     ts_rec = ntiles; ts_dkey = dkey;
     if (!tsort) {
         ProfScope ps(P_SORT_DEPTH, st);
-        GSR_HIP(depth_onesweep ? onesweep_sort_pairs<uint32_t>(dkey, gid, dkey_alt, gid_alt, (uint32_t)N, 0, wide_depth ? 27 : 32, depth_scratch, &in_alt, st,
-                                                               nullptr, true, depth_hist_done, wide_depth ? 9 : 8, kDepthKeyBias, early_r ? &rider : nullptr)
-                               : radix_sort_pairs<uint32_t>(dkey, gid, dkey_alt, gid_alt, (uint32_t)N, 0, 32, fs + L.sort, &in_alt, st));
+        GSR_HIP(onesweep_sort_pairs<uint32_t>(dkey, gid, dkey_alt, gid_alt, (uint32_t)N, 0, wide_depth ? 27 : 32, depth_scratch, &in_alt, st, nullptr, true,
+                                              depth_hist_done, wide_depth ? 9 : 8, kDepthKeyBias, early_r ? &rider : nullptr));
     }
     sorted_gid = tsort ? nullptr : (in_alt ? gid_alt : gid);
     // tiles-touched in depth order: R to the pinned slot, and what the binning needs (block offsets / the chunk tables)
@@ -5212,7 +5219,7 @@ int gsr_backward(const GsrBackwardArgs* a, void* stream_)
             o_part = o; o += align256((size_t)Rn * kDetStride * 4);
             o_k0 = o; o += align256((size_t)Rn * 4); o_k1 = o; o += align256((size_t)Rn * 4);
             o_v0 = o; o += align256((size_t)Rn * 4); o_v1 = o; o += align256((size_t)Rn * 4);
-            o_sort = o; o += radix_scratch_bytes(Rn);
+            o_sort = o; o += onesweep_scratch_bytes(Rn);
             det_bytes = o;
             GSR_HIP(hipMallocAsync((void**)&det_mem, det_bytes, st));
             det_part = reinterpret_cast<float*>(det_mem + o_part);
@@ -5229,7 +5236,7 @@ int gsr_backward(const GsrBackwardArgs* a, void* stream_)
             int nbits = 1;
             while ((1ll << nbits) < (long long)N) nbits++;
             int in_alt = 0;
-            GSR_HIP(radix_sort_pairs<uint32_t>(k0, v0, k1, v1, Rn, 0, ((nbits + 7) / 8) * 8, det_mem + o_sort, &in_alt, st));
+            GSR_HIP(onesweep_sort_pairs<uint32_t>(k0, v0, k1, v1, Rn, 0, ((nbits + 7) / 8) * 8, det_mem + o_sort, &in_alt, st));
             hipLaunchKernelGGL(k_det_reduce, dim3((Rn + 255) / 256), dim3(256), 0, st, Rn, in_alt ? k1 : k0, in_alt ? v1 : v0, det_part, gg);
             GSR_HIP(hipFreeAsync(det_mem, st));
         }
@@ -5542,23 +5549,13 @@ int gsr_mark_visible(int32_t N, const float* means3D, const float* viewmatrix, c
 int gsr_sort_pairs_u32(uint32_t* keys, uint32_t* vals, uint32_t* keys_alt, uint32_t* vals_alt, uint32_t n, int begin_bit, int end_bit,
                        void* scratch, size_t scratch_bytes, int* result_in_alt, void* stream)
 {
-    if (scratch_bytes < radix_scratch_bytes(n) || !result_in_alt) return fail(GSR_ERR_ARG, "sort scratch too small%s");
-    if (g_sort_algo && end_bit - begin_bit <= 32)
-        GSR_HIP(onesweep_sort_pairs<uint32_t>(keys, vals, keys_alt, vals_alt, n, begin_bit, end_bit, scratch, result_in_alt, (hipStream_t)stream));
-    else
-        GSR_HIP(radix_sort_pairs<uint32_t>(keys, vals, keys_alt, vals_alt, n, begin_bit, end_bit, scratch, result_in_alt, (hipStream_t)stream));
-    return GSR_OK;
+    return sort_pairs_entry<uint32_t>(keys, vals, keys_alt, vals_alt, n, begin_bit, end_bit, scratch, scratch_bytes, result_in_alt, stream);
 }
 
 int gsr_sort_pairs_u16(uint16_t* keys, uint32_t* vals, uint16_t* keys_alt, uint32_t* vals_alt, uint32_t n, int begin_bit, int end_bit,
                        void* scratch, size_t scratch_bytes, int* result_in_alt, void* stream)
 {
-    if (scratch_bytes < radix_scratch_bytes(n) || !result_in_alt) return fail(GSR_ERR_ARG, "sort scratch too small%s");
-    if (g_sort_algo)
-        GSR_HIP(onesweep_sort_pairs<uint16_t>(keys, vals, keys_alt, vals_alt, n, begin_bit, end_bit, scratch, result_in_alt, (hipStream_t)stream));
-    else
-        GSR_HIP(radix_sort_pairs<uint16_t>(keys, vals, keys_alt, vals_alt, n, begin_bit, end_bit, scratch, result_in_alt, (hipStream_t)stream));
-    return GSR_OK;
+    return sort_pairs_entry<uint16_t>(keys, vals, keys_alt, vals_alt, n, begin_bit, end_bit, scratch, scratch_bytes, result_in_alt, stream);
 }
 
 }  // extern "C"

@@ -4,14 +4,13 @@
 // and calls it on every model initialisation (:211-216) with an exact SciPy fallback that pins the semantics
 // (:31-36: KDTree.query(k=4), drop the point itself, mean of the squared distances).  The native module is an
 // un-vendored submodule (/root/reference/.gitmodules:1-3).  This is our own EXACT 3-NN for gfx950:
-//   1. bounding box (two-stage min/max), 2. 30-bit Morton codes, 3. radix sort (the rasterizer's own sort),
+//   1. bounding box (two-stage min/max), 2. 30-bit Morton codes, 3. radix sort (the rasterizer's own: gsr_sort_pairs_u32),
 //   4. AABB per box of 1024 Morton-consecutive points, 5. one lane per point: scan its own box, then every box
 //   whose AABB is closer than the current third-best distance.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "../../include/gsr.h"
-#include "radix_sort.h"
 
 namespace gsr {
 
@@ -152,7 +151,7 @@ size_t gsr_knn_scratch_bytes(int32_t N)
 {
     const size_t n = (size_t)(N > 0 ? N : 1);
     const size_t nboxes = (n + kKnnBox - 1) / kKnnBox;
-    return 4 * a256(n * 4) + a256(n * 16) + a256(nboxes * 24) + a256(256 * 24) + 256 + radix_scratch_bytes((uint32_t)n);
+    return 4 * a256(n * 4) + a256(n * 16) + a256(nboxes * 24) + a256(256 * 24) + 256 + gsr_sort_scratch_bytes((uint32_t)n);
 }
 
 int gsr_knn_mean_dist2(const float* points, int32_t N, float* out, void* scratch, size_t scratch_bytes, void* stream)
@@ -172,12 +171,13 @@ int gsr_knn_mean_dist2(const float* points, int32_t N, float* out, void* scratch
     float* partial = reinterpret_cast<float*>(s); s += a256(256 * 24);
     float* bbox = reinterpret_cast<float*>(s); s += 256;
     void* sort_scratch = s;
+    const size_t sort_bytes = gsr_sort_scratch_bytes((uint32_t)N);
     const int nb = (int)((n + 255) / 256 < 256 ? (n + 255) / 256 : 256);
     hipLaunchKernelGGL(k_knn_minmax_partial, dim3(nb), dim3(256), 0, st, points, N, partial);
     hipLaunchKernelGGL(k_knn_minmax_finish, dim3(1), dim3(64), 0, st, partial, nb, bbox);
     hipLaunchKernelGGL(k_knn_morton, dim3((N + 255) / 256), dim3(256), 0, st, points, N, bbox, keys, vals);
     int in_alt = 0;
-    if (radix_sort_pairs<uint32_t>(keys, vals, keys2, vals2, (uint32_t)N, 0, 32, sort_scratch, &in_alt, st) != hipSuccess) return GSR_ERR_HIP;
+    if (gsr_sort_pairs_u32(keys, vals, keys2, vals2, (uint32_t)N, 0, 32, sort_scratch, sort_bytes, &in_alt, stream) != GSR_OK) return GSR_ERR_HIP;
     const uint32_t* order = in_alt ? vals2 : vals;
     hipLaunchKernelGGL(k_knn_boxes, dim3(nboxes), dim3(256), 0, st, points, order, N, sorted, boxes);
     hipLaunchKernelGGL(k_knn_search, dim3((N + 255) / 256), dim3(256), 0, st, sorted, N, boxes, nboxes, out);

@@ -1,14 +1,14 @@
-// radix_sort.h -- stable LSD radix sort of (key, u32 value) pairs for gfx950, hand-written.
+// radix_sort.h -- stable LSD radix sort of (key, u32 value) pairs for gfx950, hand-written: the onesweep sort.
 //
-// Used twice per forward (DESIGN.md "binning"): 32-bit depth keys over the N Gaussians, then 16-bit tile
-// keys over the R instances.  One pass = 8 bits = three launches:
-//   k_radix_hist     per-block digit histogram (block = 4096 keys)        -> hist[digit][block]
-//   k_radix_scan     one workgroup per digit: exclusive scan over blocks + digit base
-//   k_radix_scatter  stable in-block ranking (wave_rank below), LDS-staged so that the global writes of one
-//                    digit run are consecutive lanes -> coalesced
-// Stability inside a block comes from an explicit (wave, round, lane) order: wave w owns keys
-// [w*1024, (w+1)*1024) of the tile, ranks them round by round against its own running per-digit count, and the
-// per-wave counts are prefix-summed in wave order.
+// Every sort of the library goes through onesweep_sort_pairs: per forward (DESIGN.md "binning") the 32-bit depth keys over
+// the N Gaussians and the 16-bit tile keys over the R instances; the fixed-order backward's instance positions; and,
+// through the exported gsr_sort_pairs_u32, the Morton keys of the KNN.  One launch (k_radix_ghist) counts the digits of
+// ALL passes up front; then one launch per pass of at most 8 bits (k_onesweep; 9 bits for the depth window) ranks a tile
+// of keys, finds its global offsets by decoupled look-back, and scatters it LDS-staged, so that the global writes of one
+// digit run are consecutive lanes -> coalesced.
+// Stability inside a tile comes from an explicit (wave, round, lane) order: wave w owns a contiguous slice of the tile,
+// ranks its keys round by round against its own running per-digit count (wave_rank below), and the per-wave counts are
+// prefix-summed in wave order.
 #pragma once
 #include <map>
 #include <mutex>
@@ -17,11 +17,6 @@
 #include <stdint.h>
 
 namespace gsr {
-
-constexpr int kSortThreads = 256;
-constexpr int kSortIPT = 16;                                // items per thread
-constexpr int kSortTile = kSortThreads * kSortIPT;          // 4096 keys per block
-constexpr int kSortWaves = kSortThreads / 64;
 
 __device__ __forceinline__ unsigned long long lanemask_lt()
 {
@@ -38,7 +33,8 @@ __device__ __forceinline__ unsigned long long lanemask_lt()
 // order, so "read, xor, read" needs no barrier; nothing is ever reset (a round only looks at the difference).
 // s_cnt[digit] is the wave's running count of the digit over the rounds done so far.
 // rnk[r] = number of this wave's keys with the same digit that precede key r in (round, lane) order.
-template <int IPT, int NB = 256>
+// NB = size of the digit tables.
+template <int IPT, int NB>
 __device__ __forceinline__ void wave_rank(unsigned long long* s_mask, uint32_t* s_cnt, const uint32_t (&dig)[IPT],
                                           uint32_t (&rnk)[IPT], int lane)
 {
@@ -89,152 +85,16 @@ __device__ __forceinline__ uint32_t block_scan_excl(uint32_t v, uint32_t* s_wsum
     return add + inc - v;
 }
 
-template <typename KeyT>
-__global__ __launch_bounds__(kSortThreads) void k_radix_hist(const KeyT* __restrict__ keys, uint32_t n, int shift,
-                                                             uint32_t* __restrict__ hist, uint32_t nblocks,
-                                                             uint32_t* __restrict__ totals)
-{
-    __shared__ uint32_t h[256];
-    const int tid = threadIdx.x;
-    h[tid] = 0;
-    __syncthreads();
-    const uint32_t base = blockIdx.x * (uint32_t)kSortTile;
-    if (base + kSortTile <= n && (((uintptr_t)(keys + base)) & 15) == 0) {
-        // full tile: 16-byte loads (order is irrelevant for a histogram)
-        constexpr int KPV = 16 / (int)sizeof(KeyT);                 // keys per 16-byte vector
-        constexpr int NV = kSortTile / KPV / kSortThreads;           // vectors per thread
-        const uint4* v4 = reinterpret_cast<const uint4*>(keys + base);
-#pragma unroll
-        for (int r = 0; r < NV; r++) {
-            const uint4 q = v4[r * kSortThreads + tid];
-            const uint32_t w[4] = {q.x, q.y, q.z, q.w};
-#pragma unroll
-            for (int c = 0; c < 4; c++) {
-                if (sizeof(KeyT) == 4) atomicAdd(&h[(w[c] >> shift) & 0xffu], 1u);
-                else {
-                    atomicAdd(&h[((w[c] & 0xffffu) >> shift) & 0xffu], 1u);
-                    atomicAdd(&h[((w[c] >> 16) >> shift) & 0xffu], 1u);
-                }
-            }
-        }
-    } else {
-#pragma unroll
-        for (int r = 0; r < kSortIPT; r++) {
-            const uint32_t idx = base + r * kSortThreads + tid;
-            if (idx < n) atomicAdd(&h[((uint32_t)keys[idx] >> shift) & 0xffu], 1u);
-        }
-    }
-    __syncthreads();
-    hist[(uint32_t)tid * nblocks + blockIdx.x] = h[tid];
-    if (h[tid]) atomicAdd(&totals[tid], h[tid]);
-}
-
-// grid = 256 (one workgroup per digit).  hist[d][*] -> exclusive prefix over blocks, plus the
-// exclusive prefix over the totals of digits < d (totals[] accumulated by k_radix_hist).
-static __global__ __launch_bounds__(256) void k_radix_scan(uint32_t* __restrict__ hist, uint32_t nblocks,
-                                                    const uint32_t* __restrict__ totals)
-{
-    __shared__ uint32_t s_part[256];
-    const int tid = threadIdx.x;
-    const int d = blockIdx.x;
-    uint32_t digit_base = 0;
-    for (int k = 0; k < d; k++) digit_base += totals[k];   // uniform -> scalar loads
-    // scan this digit's row: each thread owns a contiguous chunk
-    uint32_t* row = hist + (size_t)d * nblocks;
-    const uint32_t chunk = (nblocks + 255u) / 256u;
-    const uint32_t lo = min(nblocks, (uint32_t)tid * chunk), hi = min(nblocks, lo + chunk);
-    uint32_t sum = 0;
-    for (uint32_t b = lo; b < hi; b++) sum += row[b];
-    s_part[tid] = sum;
-    __syncthreads();
-    // exclusive scan of the 256 partials (Hillis-Steele in LDS)
-    for (int off = 1; off < 256; off <<= 1) {
-        uint32_t v = (tid >= off) ? s_part[tid - off] : 0u;
-        __syncthreads();
-        s_part[tid] += v;
-        __syncthreads();
-    }
-    uint32_t run = digit_base + s_part[tid] - sum;
-    for (uint32_t b = lo; b < hi; b++) {
-        const uint32_t c = row[b];
-        row[b] = run;
-        run += c;
-    }
-}
-
-template <typename KeyT>
-__global__ __launch_bounds__(kSortThreads) void k_radix_scatter(const KeyT* __restrict__ kin, const uint32_t* __restrict__ vin,
-                                                                KeyT* __restrict__ kout, uint32_t* __restrict__ vout, uint32_t n,
-                                                                int shift, const uint32_t* __restrict__ hist, uint32_t nblocks)
-{
-    __shared__ unsigned long long s_mask[kSortWaves][256];
-    __shared__ uint32_t s_cnt[kSortWaves][256];
-    __shared__ KeyT s_keys[kSortTile];
-    __shared__ uint32_t s_vals[kSortTile];
-    __shared__ uint32_t s_start[256];    // block-local exclusive start of each digit
-    __shared__ uint32_t s_gbase[256];    // global base of each digit for this block minus s_start
-    __shared__ uint32_t s_wsum[kSortWaves];
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    const uint32_t base = blockIdx.x * (uint32_t)kSortTile;
-    const uint32_t valid = min((uint32_t)kSortTile, n - base);
-
-    KeyT key[kSortIPT];
-    uint32_t val[kSortIPT];
-    uint32_t dig[kSortIPT];
-    uint32_t rnk[kSortIPT];
-#pragma unroll
-    for (int r = 0; r < kSortIPT; r++) {
-        const uint32_t p = (uint32_t)(wave * (kSortIPT * 64) + r * 64 + lane);   // wave-major: see wave_rank
-        if (p < valid) {
-            key[r] = kin[base + p];
-            val[r] = vin[base + p];
-            dig[r] = ((uint32_t)key[r] >> shift) & 0xffu;
-        } else {
-            key[r] = (KeyT)~(KeyT)0; val[r] = 0u; dig[r] = 255u;   // padding sorts behind every real item
-        }
-    }
-    wave_rank<kSortIPT>(s_mask[wave], s_cnt[wave], dig, rnk, lane);
-    __syncthreads();
-    uint32_t mine = 0;   // thread = digit: exclusive prefix of the per-wave counts in wave order
-#pragma unroll
-    for (int w = 0; w < kSortWaves; w++) {
-        const uint32_t c = s_cnt[w][tid];
-        s_cnt[w][tid] = mine;
-        mine += c;
-    }
-    const uint32_t excl = block_scan_excl<kSortWaves>(mine, s_wsum, tid);
-    s_start[tid] = excl;
-    s_gbase[tid] = hist[(size_t)tid * nblocks + blockIdx.x] - excl;
-    __syncthreads();
-#pragma unroll
-    for (int r = 0; r < kSortIPT; r++) {
-        const uint32_t lp = s_start[dig[r]] + s_cnt[wave][dig[r]] + rnk[r];
-        s_keys[lp] = key[r];
-        s_vals[lp] = val[r];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int r = 0; r < kSortIPT; r++) {
-        const uint32_t p = r * kSortThreads + tid;
-        if (p < valid) {
-            const KeyT k = s_keys[p];
-            const uint32_t d = ((uint32_t)k >> shift) & 0xffu;
-            const uint32_t g = s_gbase[d] + p;
-            kout[g] = k;
-            vout[g] = s_vals[p];
-        }
-    }
-}
-
 // ------------------------------------------------------------------------------------------------
-// Onesweep variant: one launch per 8-bit pass (+ one launch that histograms ALL passes up front).
-// Each block takes a ticket (= which 4096-key tile it owns, so lower tiles are always already running), ranks
-// its keys exactly as k_radix_scatter does, publishes its per-digit counts and finds its global offsets by
+// Onesweep: one launch per 8-bit pass (+ one launch that histograms ALL passes up front).
+// Each block takes a ticket (= which tile of keys it owns, so lower tiles are always already running), ranks
+// its keys wave by wave (wave_rank), publishes its per-digit counts and finds its global offsets by
 // decoupled look-back over the earlier tiles' status words.  A status word is ONE 32-bit value
 // {flag:2, count:30} written and polled with relaxed agent-scope atomics (write-through / L1-bypassing on
 // gfx950): the data IS the flag, so no fence is needed (MI355X guide G16, form R2).  Every started block
 // publishes its LOCAL count before it waits on anything, so the look-back can always walk back to tile 0:
-// no circular wait.  Versus hist+scan+scatter this reads the keys once per pass and saves two launches.
+// no circular wait.  Versus a histogram, a scan and a scatter launch per pass (the sort this one replaced) it reads the
+// keys once per pass and saves two launches.
 // ------------------------------------------------------------------------------------------------
 // A pass runs WITHOUT tickets (blockIdx order = look-back order) when its whole grid is co-resident on the device; the
 // bound -- workgroups of this very kernel the device holds at once -- is asked of the runtime per device and kernel
@@ -448,9 +308,8 @@ __device__ __forceinline__ void onesweep_rider_publish(const OsRider& rd, unsign
     }
 }
 
-// 512 threads x 8 keys per tile: the same 4096-key tile as the three-kernel path, but half the ranking rounds per
-// wave and twice the waves to hide the LDS / look-back latency behind (a workgroup's latency chain, not bandwidth,
-// is what a pass costs)
+// Threads x keys per thread of a tile: fewer ranking rounds per wave and more waves to hide the LDS / look-back latency
+// behind (a workgroup's latency chain, not bandwidth, is what a pass costs).
 // Measured (1 M depth keys / 4.5 M tile keys): 256x16 0.100 / 0.111 ms, 512x8 0.084 / 0.103, 1024x4 0.081 / 0.116,
 // 512x4 (2048-key tiles) 0.086 / 0.127 -> the small latency-bound depth sort takes 1024 threads, the tile sort 512;
 // 512x10 (5120-key tiles) for the tile sort: 0.096 -> 0.094 (its 4.5 M keys then fit the 1024 resident workgroups at once).
@@ -628,7 +487,8 @@ inline size_t onesweep_scratch_bytes(uint32_t n)
     return ((w8 > w9 ? w8 : w9) * sizeof(uint32_t) + 255) & ~(size_t)255;
 }
 
-// begin_bit..end_bit in 8-bit passes (at most 4).  Same contract as radix_sort_pairs.  n_dev != nullptr: `n` is only a
+// Sorts bits [begin_bit, end_bit) in passes of at most 8 bits (at most 4 passes), ping-ponging between (keys, vals) and
+// (keys_alt, vals_alt); *in_alt = 1 if the result ended in the alt buffers.  n_dev != nullptr: `n` is only a
 // capacity (it sizes the grid and the scratch); the number of pairs is min(n, *n_dev), read on the device.
 template <typename KeyT>
 inline hipError_t onesweep_sort_pairs(KeyT* keys, uint32_t* vals, KeyT* keys_alt, uint32_t* vals_alt, uint32_t n, int begin_bit,
@@ -636,13 +496,12 @@ inline hipError_t onesweep_sort_pairs(KeyT* keys, uint32_t* vals, KeyT* keys_alt
                                       const unsigned long long* n_dev = nullptr, bool head_prezeroed = false, bool hist_done = false,
                                       int max_digit_bits = 8, uint32_t bias = 0u, const OsRider* rider = nullptr)
 {
-    const bool wide_ = max_digit_bits == 9;
-    const OsRider rd = (rider && (wide_ || !hist_done)) ? *rider : OsRider{};   // rides on the histogram launch ...
-    const OsRider rd0 = (rider && !wide_ && hist_done) ? *rider : OsRider{};      // ... or, when the producer counted the digits, on the first pass
+    const bool wide = max_digit_bits == 9;                    // 9-bit digits: 512-entry tables, table stride 512, own head layout
+    const OsRider rd = (rider && (wide || !hist_done)) ? *rider : OsRider{};   // rides on the histogram launch ...
+    const OsRider rd0 = (rider && !wide && hist_done) ? *rider : OsRider{};      // ... or, when the producer counted the digits, on the first pass
     *in_alt = 0;
     if (n == 0) return hipSuccess;
     const int bits = end_bit - begin_bit;
-    const bool wide = max_digit_bits == 9;                    // 9-bit digits: 512-entry tables, table stride 512, own head layout
     const int passes = (bits + (wide ? 9 : 8) - 1) / (wide ? 9 : 8);
     if (passes < 1 || passes > 4 || (wide && (passes != 3 || sizeof(KeyT) != 4 || hist_done || begin_bit != 0))) return hipErrorInvalidValue;
     const uint32_t GS = wide ? 512u : 256u;
@@ -699,43 +558,6 @@ inline hipError_t onesweep_sort_pairs(KeyT* keys, uint32_t* vals, KeyT* keys_alt
             hipLaunchKernelGGL((k_onesweep<KeyT, 256>), dim3(pgrid), dim3(OsCfg<KeyT>::kThreads), 0, stream, kin, vin, kout, vout, n,
                                begin_bit + dbits * p, ghist + p * kOsRanges * 256, status + (size_t)p * nblocks * 256, tk_p, n_dev, pmask, runs,
                                0u, 0xffffffffu, p == 0 ? rd0 : OsRider{});
-        KeyT* tk = kin; kin = kout; kout = tk;
-        uint32_t* tv = vin; vin = vout; vout = tv;
-        *in_alt ^= 1;
-    }
-    return hipGetLastError();
-}
-
-inline size_t radix_scratch_bytes(uint32_t n)
-{
-    const size_t nblocks = ((size_t)n + kSortTile - 1) / kSortTile;
-    const size_t osblocks = ((size_t)n + kOsTile - 1) / kOsTile;
-    const size_t three_kernel = ((256 * (nblocks ? nblocks : 1) + 8 * 256) * sizeof(uint32_t) + 255) & ~(size_t)255;   // hist + totals
-    const size_t onesweep = onesweep_scratch_bytes(n);   // (either digit-table layout)
-    (void)osblocks;
-    return three_kernel > onesweep ? three_kernel : onesweep;
-}
-
-// Sorts bits [begin_bit, end_bit) in 8-bit passes, ping-ponging between (keys,vals) and (keys_alt,vals_alt).
-// Returns 1 in *in_alt if the result ended in the alt buffers.
-template <typename KeyT>
-inline hipError_t radix_sort_pairs(KeyT* keys, uint32_t* vals, KeyT* keys_alt, uint32_t* vals_alt, uint32_t n, int begin_bit,
-                                   int end_bit, void* scratch, int* in_alt, hipStream_t stream)
-{
-    *in_alt = 0;
-    if (n == 0) return hipSuccess;
-    const uint32_t nblocks = (n + kSortTile - 1) / kSortTile;
-    uint32_t* hist = static_cast<uint32_t*>(scratch);
-    uint32_t* totals = hist + (size_t)256 * nblocks;
-    hipError_t e = hipMemsetAsync(totals, 0, 8 * 256 * sizeof(uint32_t), stream);
-    if (e != hipSuccess) return e;
-    KeyT *kin = keys, *kout = keys_alt;
-    uint32_t *vin = vals, *vout = vals_alt;
-    for (int shift = begin_bit; shift < end_bit; shift += 8, totals += 256) {
-        hipLaunchKernelGGL(k_radix_hist<KeyT>, dim3(nblocks), dim3(kSortThreads), 0, stream, kin, n, shift, hist, nblocks, totals);
-        hipLaunchKernelGGL(k_radix_scan, dim3(256), dim3(256), 0, stream, hist, nblocks, totals);
-        hipLaunchKernelGGL(k_radix_scatter<KeyT>, dim3(nblocks), dim3(kSortThreads), 0, stream, kin, vin, kout, vout, n, shift,
-                           hist, nblocks);
         KeyT* tk = kin; kin = kout; kout = tk;
         uint32_t* tv = vin; vin = vout; vout = tv;
         *in_alt ^= 1;

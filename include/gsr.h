@@ -387,7 +387,9 @@ size_t gsr_struct_bytes(int32_t which); /* 0 GsrForwardArgs, 1 GsrBackwardArgs, 
  *                          blend, so setting it changes nothing.  Any other value is refused (the one-pixel-per-lane kernel that 1
  *                          selected left the tree)
  *   "ab_variants"          query kept for callers of the round-4 ABI: always returns 0 (no A/B kernels in the library)
- *   "sort_algo"            2 = onesweep for both sorts (default); 1 = onesweep depth sort only; 0 = hist + scan + scatter
+ *   "sort_algo"            2 = onesweep, the only sort of the library, so setting it changes nothing.  Any other value is refused (the
+ *                          histogram + scan + scatter sort that 0 and 1 selected left the tree).  bench.py --sort-algo passes its
+ *                          value on without looking at the return code: with 0 or 1 it now measures the default
  *   "bwd_split"            1 = the backward of a tile is ONE work item (off); anything else (default 0) = one item per 128-instance
  *                          batch beyond the first "ckpt_first" (default 1) batches, each resuming from the per-pixel checkpoint the
  *                          forward leaves at every 128-instance boundary.  (Round 4: the items are listed by k_bwd_prologue and
@@ -659,7 +661,9 @@ int gsr_knn_mean_dist2(const float* points /*[N,3]*/, int32_t N, float* out /*[N
  * write rate is the practical HBM ceiling of the box for a streaming kernel. */
 int gsr_stream_copy(const void* src, void* dst, size_t bytes, int variant, int blocks, void* stream);
 
-/* Building blocks exported for the unit tests of tests/test_gpu_blocks.py (device pointers). */
+/* Building blocks exported for the unit tests of tests/test_gpu_blocks.py (device pointers): stable sort of (key, value) pairs on key
+ * bits [begin_bit, end_bit), 0 <= begin_bit < end_bit <= width of the key (anything else: GSR_ERR_ARG); the result is in the _alt
+ * buffers when *result_in_alt comes back 1.  gsr_knn_mean_dist2 sorts its Morton keys through gsr_sort_pairs_u32. */
 int gsr_sort_pairs_u32(uint32_t* keys, uint32_t* vals, uint32_t* keys_alt, uint32_t* vals_alt, uint32_t n,
                        int begin_bit, int end_bit, void* scratch, size_t scratch_bytes, int* result_in_alt,
                        void* stream);

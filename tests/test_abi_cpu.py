@@ -107,6 +107,17 @@ def test_direct_binning_geometry_invariants():
         assert lib.gsr_debug_direct_binning_geometry(N, T, out) == 0 and out[0] == 0
 
 
+def test_sort_scratch_bytes_closed_form():
+    """Scratch of a sort over n pairs (csrc/radix_sort.h onesweep_scratch_bytes), in 32-bit words over nb = max(1, ceil(n / 4096)) tiles:
+    four 8-bit passes -- head of 4 x 32 x 256 digit counts + 128 tickets, then 4 x 256 status words per tile -- or three 9-bit
+    passes -- 3 x 32 x 512 + 128, then 3 x 512 per tile -- whichever is larger, rounded up to 256 bytes.  No GPU needed."""
+    L = importlib.import_module("3dgs_hierarchical_training_amd._lib")
+    lib = L.load()
+    for n in (0, 1, 4096, 4097, 1_000_000, 30_000_000):
+        nb = max(1, -(-n // 4096))
+        want = (4 * max(32896 + 1024 * nb, 49280 + 1536 * nb) + 255) // 256 * 256
+        assert lib.gsr_sort_scratch_bytes(n) == want, n
+
 
 def test_tile_sort_option_values():
     """`tile_sort` takes 0 / 1 / 2 (off / where the lists are short / wherever the direct binning runs) and nothing else; its threshold
@@ -133,6 +144,6 @@ def test_options_from_the_environment_at_load():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     ok = subprocess.run([sys.executable, "-c", code], cwd=root, env={**os.environ, "GSR_OPTS": "tile_sort=2, blend_bwd_ppt=2"}, capture_output=True, text=True)
     assert ok.returncode == 0 and "loaded 0" in ok.stdout, ok.stderr[-400:]
-    for bad in ("no_such_option=1", "tile_sort=7", "blend_bwd_ppt=1"):
+    for bad in ("no_such_option=1", "tile_sort=7", "blend_bwd_ppt=1", "sort_algo=0"):
         r = subprocess.run([sys.executable, "-c", code], cwd=root, env={**os.environ, "GSR_OPTS": bad}, capture_output=True, text=True)
         assert r.returncode != 0 and "GSR_OPTS" in r.stderr, (bad, r.stdout, r.stderr[-400:])

@@ -10,12 +10,22 @@ pytestmark = pytest.mark.gpu
 L = importlib.import_module("3dgs_hierarchical_training_amd._lib")
 
 
+# `sort_algo` 0 is refused by the library (test_sort_algo_option) and the return code is not looked at here: both parametrisations
+# run the onesweep sort, the only one.
 @pytest.fixture(params=[0, 2], ids=["three-kernel", "onesweep"], autouse=True)
 def sort_algo(request):
     lib = L.load()
     lib.gsr_set_option(b"sort_algo", request.param)
     yield request.param
     lib.gsr_set_option(b"sort_algo", 2)
+
+
+def test_sort_algo_option():
+    """Onesweep is the only sort: 2 is accepted and changes nothing, every other value is refused."""
+    lib = L.load()
+    assert lib.gsr_set_option(b"sort_algo", 2) == 0
+    for v in (0, 1, 3):
+        assert lib.gsr_set_option(b"sort_algo", v) != 0
 
 
 def _sort(keys, vals, bits, u16=False):

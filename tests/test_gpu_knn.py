@@ -14,8 +14,9 @@ def _ref(points):
 
 
 @pytest.mark.parametrize("n,kind", [(2, "uniform"), (5, "uniform"), (1000, "uniform"), (20000, "clustered"), (200000, "surface"),
-                                    (3000, "duplicates")])
+                                    (3000, "duplicates"), (4096, "uniform"), (4097, "uniform")])
 def test_dist_cuda2_matches_kdtree(n, kind):
+    """(4 096 and 4 097 points: one full tile of the Morton sort, and one key more.)"""
     from simple_knn._C import distCUDA2
     rng = np.random.default_rng(n)
     if kind == "uniform":

@@ -233,3 +233,17 @@ def _register_fakes():
     @torch.library.register_fake("gsr::knn_mean_dist2")
     def _(points):
         return points.new_empty((points.shape[0],), dtype=torch.float32)
+
+    @torch.library.register_fake("gsr::depth_to_points")
+    def _(depth, image, fx, fy, cx, cy):
+        H, W = depth.shape[-2:]
+        return depth.new_empty((H * W, 3), dtype=torch.float32), depth.new_empty((H * W if image is not None else 0, 3), dtype=torch.float32)
+
+    @torch.library.register_fake("gsr::voxel_down_sample")
+    def _(points, colors, voxel_size):
+        # M (the number of occupied voxels) and `dropped` depend on the data: unbacked sizes.  The real op reads them back from the device
+        # (its one host synchronisation), so a compiled graph breaks here all the same.
+        ctx = torch.library.get_ctx()
+        M, dropped = ctx.new_dynamic_size(), ctx.new_dynamic_size()
+        return (points.new_empty((M, 3), dtype=torch.float32), points.new_empty((M if colors is not None else 0, 3), dtype=torch.float32),
+                points.new_empty((M,), dtype=torch.int32), dropped)

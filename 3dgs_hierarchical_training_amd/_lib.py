@@ -88,6 +88,7 @@ EXPORTS = [
     "gsr_depth_loss_workspace_bytes_batched", "gsr_depth_loss_forward_batched", "gsr_depth_loss_backward_batched",
     "gsr_depth_loss_forward_terms_batched",
     "gsr_batch_retire_scratch_bytes", "gsr_batch_retire", "gsr_forward_retire",
+    "gsr_depth_to_points", "gsr_voxel_scratch_bytes", "gsr_voxel_down_sample",
 ]
 GSR_DEPTH_LOSS_L1, GSR_DEPTH_LOSS_INVARIANT = 0, 1
 
@@ -156,6 +157,16 @@ def load():
     lib.gsr_knn_scratch_bytes.argtypes = [C.c_int32]
     lib.gsr_knn_mean_dist2.restype = C.c_int
     lib.gsr_knn_mean_dist2.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+    lib.gsr_depth_to_points.restype = C.c_int
+    # (depth, image, H, W, fx, fy, cx, cy, points, colors, stream)
+    lib.gsr_depth_to_points.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_float, C.c_float,
+                                        C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.gsr_voxel_scratch_bytes.restype = C.c_size_t
+    lib.gsr_voxel_scratch_bytes.argtypes = [C.c_int64]
+    lib.gsr_voxel_down_sample.restype = C.c_int
+    # (points, colors, N, voxel_size, out_points, out_colors, out_counts, meta, scratch, scratch_bytes, stream)
+    lib.gsr_voxel_down_sample.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.c_size_t, C.c_void_p]
     lib.gsr_adam_step.restype = C.c_int
     lib.gsr_adam_step.argtypes = [C.POINTER(GsrAdamTensor), C.c_int32, C.c_float, C.c_float, C.c_float, C.c_int64, C.c_void_p]
     lib.gsr_pose_step.restype = C.c_int

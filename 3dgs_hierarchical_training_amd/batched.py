@@ -22,7 +22,7 @@ BLOCK = 128
 def _pad_rows(t: torch.Tensor, n_pad: int, fill: torch.Tensor) -> torch.Tensor:
     if n_pad == 0:
         return t
-    return torch.cat((t, fill.to(t.dtype).expand((n_pad,) + tuple(t.shape[1:]))), dim=0)
+    return torch.cat((t, fill.to(device=t.device, dtype=t.dtype).expand((n_pad,) + tuple(t.shape[1:]))), dim=0)     # (scenes built on the device stay there)
 
 
 def concat_scenes(scenes: Sequence[Dict]) -> Dict:

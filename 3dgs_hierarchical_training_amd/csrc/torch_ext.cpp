@@ -23,6 +23,8 @@
 //   gsr::retire_attach        attaches a retire table + step to the NEXT gsr::rasterize / render / importance_accumulate of the calling thread
 //   gsr::pose_step            -> gsr_pose_step (stage A: tangent-space Adam + exponential map between two renders)
 //   gsr::knn_mean_dist2       -> gsr_knn_mean_dist2
+//   gsr::depth_to_points      -> gsr_depth_to_points (a depth map's pixels un-projected, colours gathered beside them)
+//   gsr::voxel_down_sample    -> gsr_voxel_down_sample (voxel-grid means; its read of `meta` is the one host synchronisation)
 //
 // Registered with TORCH_LIBRARY so the ops are visible to the dispatcher (torch.ops.gsr.*, fake kernels in _ext.py for
 // torch.compile).  An empty tensor (numel 0) stands for "None".  Everything runs on the current HIP stream of the
@@ -1196,6 +1198,68 @@ Tensor knn_mean_dist2(const Tensor& points_)
     return out;
 }
 
+// gsr::depth_to_points -> gsr_depth_to_points.  depth [H,W] (or [1,H,W] / [1,1,H,W]), image [3,H,W] or None -> (points [H*W,3],
+// colors [H*W,3], or [0,3] without an image).  No autograd: inputs are detached.  No host synchronisation.
+std::tuple<Tensor, Tensor> depth_to_points(const Tensor& depth_, const c10::optional<Tensor>& image_, double fx, double fy, double cx, double cy)
+{
+    TORCH_CHECK(depth_.is_cuda(), "depth_to_points: depth must be on a ROCm/HIP device (no CPU fallback)");
+    TORCH_CHECK(depth_.dim() >= 2 && depth_.numel() == depth_.size(-2) * depth_.size(-1), "depth_to_points: depth is one plane [H,W]");
+    const c10::hip::HIPGuardMasqueradingAsCUDA guard(depth_.device());
+    const Tensor depth = f32c(depth_.detach());
+    const int64_t H = depth.size(-2), W = depth.size(-1);
+    TORCH_CHECK(H > 0 && W > 0 && H * W < ((int64_t)1 << 31), "depth_to_points: an image of 1 .. 2^31 - 1 pixels expected");
+    const bool with_image = image_.has_value() && image_->defined();
+    Tensor image;
+    if (with_image) {
+        TORCH_CHECK(image_->is_cuda() && image_->device() == depth_.device(), "depth_to_points: image must be on the depth's device (no CPU fallback)");
+        TORCH_CHECK(image_->dim() == 3 && image_->size(0) == 3 && image_->size(1) == H && image_->size(2) == W, "depth_to_points: image is [3,H,W]");
+        image = f32c(image_->detach());
+    }
+    Tensor points = at::empty({H * W, 3}, depth.options());
+    Tensor colors = at::empty({with_image ? H * W : 0, 3}, depth.options());
+    check(gsr_depth_to_points(depth.data_ptr<float>(), with_image ? image.data_ptr<float>() : nullptr, (int32_t)H, (int32_t)W, (float)fx, (float)fy,
+                              (float)cx, (float)cy, points.data_ptr<float>(), with_image ? colors.data_ptr<float>() : nullptr,
+                              c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream()), "gsr_depth_to_points");
+    return {points, colors};
+}
+
+// gsr::voxel_down_sample -> gsr_voxel_down_sample.  points [N,3], colors [N,3] or None -> (points [M,3], colors [M,3] or [0,3], counts [M] int32,
+// dropped).  Scratch and the N-row outputs come from the allocator; the read of the four `meta` words is the one host synchronisation; the
+// outputs are the first M rows of the N-row buffers.  status != 0 (an index beyond 2^21) raises.  No autograd: inputs are detached.
+std::tuple<Tensor, Tensor, Tensor, int64_t> voxel_down_sample(const Tensor& points_, const c10::optional<Tensor>& colors_, double voxel_size)
+{
+    TORCH_CHECK(points_.is_cuda(), "voxel_down_sample: points must be on a ROCm/HIP device (no CPU fallback)");
+    TORCH_CHECK(points_.dim() == 2 && points_.size(1) == 3, "voxel_down_sample: points is [N,3]");
+    TORCH_CHECK(voxel_size > 0.0 && std::isfinite(voxel_size), "voxel_down_sample: voxel_size must be positive and finite");
+    const c10::hip::HIPGuardMasqueradingAsCUDA guard(points_.device());
+    const Tensor points = f32c(points_.detach());
+    const int64_t N = points.size(0);
+    TORCH_CHECK(N < ((int64_t)1 << 31), "voxel_down_sample: at most 2^31 - 1 points");
+    const bool with_colors = colors_.has_value() && colors_->defined();
+    Tensor colors;
+    if (with_colors) {
+        TORCH_CHECK(colors_->is_cuda() && colors_->device() == points_.device(), "voxel_down_sample: colors must be on the points' device (no CPU fallback)");
+        TORCH_CHECK(colors_->dim() == 2 && colors_->size(0) == N && colors_->size(1) == 3, "voxel_down_sample: colors is [N,3]");
+        colors = f32c(colors_->detach());
+    }
+    Tensor out_points = at::empty({N, 3}, points.options());
+    Tensor out_colors = at::empty({with_colors ? N : 0, 3}, points.options());
+    Tensor out_counts = at::empty({N}, points.options().dtype(at::kInt));
+    Tensor meta = at::empty({4}, points.options().dtype(at::kLong));
+    const size_t sb = gsr_voxel_scratch_bytes(N);
+    Tensor scratch = at::empty({(int64_t)sb}, points.options().dtype(at::kByte));
+    check(gsr_voxel_down_sample(N ? points.data_ptr<float>() : nullptr, (with_colors && N) ? colors.data_ptr<float>() : nullptr, N, voxel_size,
+                                N ? out_points.data_ptr<float>() : nullptr, (with_colors && N) ? out_colors.data_ptr<float>() : nullptr,
+                                N ? out_counts.data_ptr<int32_t>() : nullptr, meta.data_ptr<int64_t>(), N ? scratch.data_ptr() : nullptr, sb,
+                                c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream()), "gsr_voxel_down_sample");
+    const Tensor host = meta.cpu();      // the feature's single host synchronisation
+    const int64_t* h = host.data_ptr<int64_t>();
+    TORCH_CHECK(h[2] == 0, "voxel_down_sample: extent / voxel_size needs a voxel index of 2^21 or more on some axis (status ", h[2],
+                "): use a larger voxel_size or split the cloud");
+    const int64_t M = h[0];
+    return {out_points.narrow(0, 0, M), with_colors ? out_colors.narrow(0, 0, M) : out_colors, out_counts.narrow(0, 0, M), h[1]};
+}
+
 }  // namespace
 
 // ---- the trainer's per-iteration bookkeeping (gsr_masked_max / gsr_densify_stats_add / gsr_psnr; include/gsr.h) ------------------
@@ -1328,6 +1392,8 @@ TORCH_LIBRARY(gsr, m)
     m.def("pose_matrix_backward(Tensor delta, Tensor base, Tensor d_xf) -> Tensor");
     m.def("pose_matrix(Tensor delta, Tensor base) -> Tensor");
     m.def("knn_mean_dist2(Tensor points) -> Tensor");
+    m.def("depth_to_points(Tensor depth, Tensor? image, float fx, float fy, float cx, float cy) -> (Tensor, Tensor)");
+    m.def("voxel_down_sample(Tensor points, Tensor? colors, float voxel_size) -> (Tensor points, Tensor colors, Tensor counts, int dropped)");
     m.def("masked_max_(Tensor(a!) dst, Tensor src, Tensor mask) -> ()");
     m.def("densify_stats_add_(Tensor(a!) accum, Tensor(b!) denom, Tensor grad, Tensor mask) -> ()");
     m.def("psnr(Tensor a, Tensor b) -> Tensor");
@@ -1355,6 +1421,8 @@ TORCH_LIBRARY_IMPL(gsr, CUDA, m)   // the dispatch key of HIP tensors on a ROCm 
     m.impl("pose_matrix_backward", &pose_matrix_backward);
     m.impl("pose_matrix", &pose_matrix_forward);
     m.impl("knn_mean_dist2", &knn_mean_dist2);
+    m.impl("depth_to_points", &depth_to_points);
+    m.impl("voxel_down_sample", &voxel_down_sample);
     m.impl("masked_max_", &masked_max_);
     m.impl("densify_stats_add_", &densify_stats_add_);
     m.impl("psnr", &psnr);

@@ -99,6 +99,8 @@ class HTConfig:
                                                 # depth_loss_type 'invariant', ht3dgs_trainer.py:354, :392); 0 = photometric only
     stage_a_early_exit: str = "host"            # how a stage-A image phase ends (stage_a.fit_pair): 'host' = the host looks every 50 iterations (a
                                                 # batch waits for all its models); 'device' = each model retires at its own iteration, on the device
+    stage_a_init: str = "pixels"                # a stage-A model's initialisation: 'pixels' = sequence.pixel_scene (a strided pixel grid, built on the
+                                                # host); 'voxels' = sequence.depth_scene (every pixel, voxel grid 0.01, create_from_pcd: the reference's, on the device)
     fit_pose: bool = False                      # refine each frame's pose while training on it (training_setup(fit_pose=True), :733)
     pose_lr: float = 1e-5                       # Adam with eps 1e-15 moves a pose by ~lr per step whatever the gradient: on these
                                                 # frames (1-2 px of motion per frame) 5e-6..2e-5 gains 0.4-0.6 dB over fixed stage-A
@@ -407,12 +409,14 @@ def run_stage_a_on(seq, cfg, dev, spec, rank: int, world: int, group=None, log=N
     batch = max(1, min(batch, 16, 4095 // max(1, tiles_y)))
     table = stage_a.run_stage_a(cfg.frames, lambda p: stage_a.fit_pair(seq, p, dev, n_points=n_points, single_image_iters=image_iters,
                                                                         pose_iters=pose_iters, seed=cfg.seed,
-                                                                        lambda_depth=cfg.stage_a_lambda_depth, early_exit=cfg.stage_a_early_exit),
+                                                                        lambda_depth=cfg.stage_a_lambda_depth, early_exit=cfg.stage_a_early_exit,
+                                                                        init=cfg.stage_a_init),
                                 gather_device or dev, rank=rank, world=world, group=group, concurrency=conc, fit_device=dev,
                                 batch=batch,
                                 batch_fn=lambda ps: stage_a.fit_pairs_batched(seq, ps, dev, n_points=n_points, single_image_iters=image_iters,
                                                                               pose_iters=pose_iters, seed=cfg.seed,
-                                                                              lambda_depth=cfg.stage_a_lambda_depth, early_exit=cfg.stage_a_early_exit))
+                                                                              lambda_depth=cfg.stage_a_lambda_depth, early_exit=cfg.stage_a_early_exit,
+                                                                              init=cfg.stage_a_init))
     if dev.type == "cuda":
         torch.cuda.synchronize(dev)
     err = max(float((table[f"rel_pose_{p}_to_{p + 1}"].cpu() - seq.true_rel_pose(p, p + 1)).abs().max()) for p in range(cfg.frames - 1))
@@ -510,6 +514,9 @@ def main():
                     help="end of a stage-A image phase: host = PSNR looked at by the host every 50 iterations, a batch runs until all its models "
                          "have passed (default); device = every model retires at its own first iteration past 500 with PSNR > 35 dB, decided "
                          "and applied on the device -- the pose table then does not depend on which pairs share a batch")
+    ap.add_argument("--stage-a-init", choices=("pixels", "voxels"), default="pixels",
+                    help="a stage-A model's initialisation: pixels = one Gaussian per strided pixel, built on the host (default); voxels = every "
+                         "pixel un-projected, voxel grid of 0.01, create_from_pcd -- the reference's initialisation, built on the device")
     ap.add_argument("--one-device", action="store_true", help="every rank on cuda:0 (with --backend gloo: the multi-process walk on a "
                                                               "one-GPU box; messages are staged through host memory)")
     ap.add_argument("--ranks", type=int, default=0, help="as a BARE command (WORLD_SIZE unset): start this many ranks of this very script "
@@ -524,7 +531,7 @@ def main():
         return launch_check(a)
     cfg = HTConfig(frames=a.frames, width=a.width, height=a.height, gt_gaussians=a.gt_gaussians, leaf_gaussians=a.leaf_gaussians,
                    leaf_iters_per_frame=a.leaf_iters, phase1_iters_per_frame=a.phase1_iters, phase2_iters_per_frame=[a.phase2_iters] * 3,
-                   importance_views=a.importance_views, densify=a.densify, fit_pose=a.fit_pose, stage_a_batch=a.stage_a_batch, stage_a_lambda_depth=a.stage_a_lambda_depth, stage_a_early_exit=a.stage_a_early_exit, sh_up_every=a.sh_up_every)
+                   importance_views=a.importance_views, densify=a.densify, fit_pose=a.fit_pose, stage_a_batch=a.stage_a_batch, stage_a_lambda_depth=a.stage_a_lambda_depth, stage_a_early_exit=a.stage_a_early_exit, stage_a_init=a.stage_a_init, sh_up_every=a.sh_up_every)
     if a.pose_lr is not None:
         cfg.pose_lr = a.pose_lr
     if not torch.cuda.is_available():

@@ -140,6 +140,23 @@ class FrameSequence:
         sc["shs"] = shs.contiguous()
         return sc
 
+    def intrinsics(self):
+        """(fx, fy, cx, cy) of every frame, in `pixel_scene`'s convention: pixel centre u sits at u + 0.5 - 0.5 * W of the optical axis."""
+        cam = syn.make_camera(self.W, self.H)
+        return cam["fx"], cam["fy"], 0.5 * self.W - 0.5, 0.5 * self.H - 0.5
+
+    def depth_scene(self, f: int, voxel_size: float = 0.01) -> Dict:
+        """The single-image model the reference trains in stage A, built on the device (pointcloud.scene_from_depth): EVERY pixel of frame
+        f un-projected with the frame's depth, one point per voxel of `voxel_size`, `create_from_pcd` on the result (trainer.py:646-671,
+        gaussian_model_ht.py:197-233).  Depth map and image never leave the device.  Pixels the ground truth does not cover (depth behind
+        the rasterizer's near cut, as `pixel_scene` drops them) are handed over as NaN, which the voxel grid drops."""
+        from . import pointcloud
+        dep = self.depth(f)
+        dep = torch.where(dep > 0.21, dep, torch.full_like(dep, float("nan")))
+        sc = dict(self.gt_scene)
+        sc.update(pointcloud.scene_from_depth(dep, self.target(f), self.intrinsics(), voxel_size=voxel_size))
+        return sc
+
     def leaf_scene(self, start_fidx: int, n_points: int, seed: int, noise: float = 1.0) -> Dict:
         """A perturbed subset of the ground truth, expressed in the camera frame of `start_fidx` (stands in for
         `init_leaf_3DGS` from monocular depth, :172-212): positions jittered, colours / opacities / scales off."""

@@ -159,7 +159,10 @@ def fit_pair(seq, p: int, device, n_points: int = 100_000, single_image_iters: i
     iteration's update still applies, and from then on the model is frozen bit for bit; the host reads the table every 50 iterations and
     leaves the loop once the entry is set -- when it looks does not change the result.  `fit_pairs_batched(early_exit='device')` returns
     the same pose bit for bit, whichever pairs share a batch.  An unknown value raises ValueError before a device is touched.
-    info (a dict, optional): receives 'iterations' and, in 'device' mode, 'retired_at' (the iteration the model retired at, 0 = the cap)
+    init: 'pixels' (the default; sequence.pixel_scene, a strided pixel grid built on the host), 'voxels' (sequence.depth_scene: the model the
+    reference trains -- every pixel un-projected, voxel grid of 0.01, create_from_pcd -- built on the device by pointcloud.py; n_points and seed
+    do not apply), anything else: a perturbed subset of the ground truth.
+    info (a dict, optional): receives 'iterations', 'loss_first' / 'loss_last' (the image phase's loss at its first and last iteration) and, in 'device' mode, 'retired_at' (the iteration the model retired at, 0 = the cap)
     and 'mse' ([iterations, 1] float64, the decision kernel's MSE of every step; a retired model's rows show the background image)."""
     _check_early_exit(early_exit)
     from . import pose as pose_mod
@@ -169,6 +172,8 @@ def fit_pair(seq, p: int, device, n_points: int = 100_000, single_image_iters: i
     if init == "pixels":     # one Gaussian per strided pixel of frame p, un-projected with its depth (about n_points of them)
         stride = max(1, int(round((seq.W * seq.H / max(1, n_points)) ** 0.5)))
         scene = seq.pixel_scene(p, stride=stride, seed=seed)
+    elif init == "voxels":   # the reference's own initialisation, on the device: every pixel un-projected, voxel grid, create_from_pcd
+        scene = seq.depth_scene(p)
     else:                    # a perturbed subset of the ground-truth cloud
         scene = seq.leaf_scene(p, n_points, seed=seed + p)
     params = ts.GaussianParams(scene, device)
@@ -186,16 +191,19 @@ def fit_pair(seq, p: int, device, n_points: int = 100_000, single_image_iters: i
             return fused_training_loss_report(out[0], tgt1, out[2], dep1, 0.2, float(lambda_depth), depth_loss_type, clamp=True)[0]
         return fused_photometric_loss(out[0], tgt1, 0.2, clamp=True)
     retire = params.new_retire_table(psnr_exit, exit_after) if early_exit == "device" else None
-    it, curve = 0, []
+    it, curve, loss_first, loss_last = 0, [], None, None
     for it in range(1, single_image_iters + 1):
         if retire is not None:      # the rule on the device at every iteration; the host only looks now and then
-            ts.train_step(params, ident, tgt0, next_settings=ident, retire=retire, **dkw)
+            pkg = ts.train_step(params, ident, tgt0, next_settings=ident, retire=retire, **dkw)
             if info is not None:
                 curve.append(retire.mse)
+                loss_first, loss_last = (pkg["loss"].clone() if loss_first is None else loss_first), pkg["loss"]
             if it % _POLL_EVERY == 0 and all(retire.retired_sync()):
                 break
             continue
         pkg = ts.train_step(params, ident, tgt0, next_settings=ident, **dkw)      # same view every step: its preprocess rides in the backward
+        if info is not None:
+            loss_first, loss_last = (pkg["loss"].clone() if loss_first is None else loss_first), pkg["loss"]
         if it > exit_after and it % _POLL_EVERY == 0:
             with torch.no_grad():
                 mse = ((pkg["raw_image"].clamp(0, 1) - tgt0) ** 2).mean()
@@ -203,6 +211,8 @@ def fit_pair(seq, p: int, device, n_points: int = 100_000, single_image_iters: i
                 break
     if info is not None:
         info["iterations"] = it
+        if loss_first is not None:      # the image phase's loss at its first and at its last iteration (read here, once)
+            info["loss_first"], info["loss_last"] = float(loss_first), float(loss_last)
         if retire is not None:
             info["retired_at"] = retire.retired_sync()[0]
             info["mse"] = torch.stack(curve).cpu() if curve else None      # [iterations, 1] float64: the decision kernel's MSE of every step
@@ -243,7 +253,7 @@ def fit_pair(seq, p: int, device, n_points: int = 100_000, single_image_iters: i
 def fit_pairs_batched(seq, pairs: List[int], device, n_points: int = 100_000, single_image_iters: int = 1000, pose_iters: int = 300,
                       pose_lr: float = 2e-3, seed: int = 0, lambda_depth: float = 0.0,
                       depth_loss_type: str = "invariant", early_exit: str = "host", psnr_exit: float = 35.0, exit_after: int = 500,
-                      info: Optional[dict] = None) -> Dict[int, torch.Tensor]:
+                      info: Optional[dict] = None, init: str = "pixels") -> Dict[int, torch.Tensor]:
     """`fit_pair` for several pairs AT ONCE: the B single-image models live in one parameter store and every step of the B fits is
     ONE launch chain (batched.BatchedGaussianParams / include/gsr.h GsrBatch) -- B renders, B losses, B Adam updates and the B
     hand-overs to the next step per pass over the kernels, instead of B chains of ~17 kernels that each fill a fraction of the
@@ -259,6 +269,7 @@ def fit_pairs_batched(seq, pairs: List[int], device, n_points: int = 100_000, si
         iterations and leaves when every entry is set.  The loss the steps report still sums the retired images' terms.
     Returns {pair -> rel_pose [4,4] (CPU)}.  info (a dict, optional): 'iterations' and, in 'device' mode, 'retired_at'
     {pair -> iteration, 0 = the cap} and 'mse' [iterations, B].
+    init: 'pixels' (the default) or 'voxels', as in `fit_pair` (anything else raises ValueError before a device is touched).
     lambda_depth / depth_loss_type as in `fit_pair`: the depth term on the stack of the B depth planes (the sum of the images' terms,
     each with its own fit -- every model gets exactly the gradient of its own loss)."""
     from . import batched as bt
@@ -267,10 +278,12 @@ def fit_pairs_batched(seq, pairs: List[int], device, n_points: int = 100_000, si
     from .loss import fused_photometric_loss, fused_training_loss_report
     from .rasterizer import rasterize_gaussians_raw
     _check_early_exit(early_exit)
+    if init not in ("pixels", "voxels"):
+        raise ValueError(f"init={init!r}: 'pixels' or 'voxels'")
     B = len(pairs)
     if B == 1:
         one = {} if info is not None else None
-        out = {pairs[0]: fit_pair(seq, pairs[0], device, n_points, single_image_iters, pose_iters, pose_lr, seed,
+        out = {pairs[0]: fit_pair(seq, pairs[0], device, n_points, single_image_iters, pose_iters, pose_lr, seed, init=init,
                                   lambda_depth=lambda_depth, depth_loss_type=depth_loss_type, early_exit=early_exit, psnr_exit=psnr_exit,
                                   exit_after=exit_after, info=one)}
         if info is not None:
@@ -280,7 +293,7 @@ def fit_pairs_batched(seq, pairs: List[int], device, n_points: int = 100_000, si
                 info["mse"] = one["mse"]
         return out
     stride = max(1, int(round((seq.W * seq.H / max(1, n_points)) ** 0.5)))
-    scenes = [seq.pixel_scene(p, stride=stride, seed=seed) for p in pairs]
+    scenes = [seq.depth_scene(p) if init == "voxels" else seq.pixel_scene(p, stride=stride, seed=seed) for p in pairs]
     params = bt.BatchedGaussianParams(scenes, device)
     params.active_sh_degree = 0          # fresh models: degree 0, 16 coefficients stored (see fit_pair)
     ident1 = ts.with_sh_degree(seq.settings_for_pose(torch.eye(4)), 0)

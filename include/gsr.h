@@ -375,7 +375,8 @@ const char* gsr_last_error(void);
  * 114: the depth term on a stack of planes (gsr_depth_loss_*_batched); no struct changed.
  * 115: the frozen call of gsr_backward (camera / transform gradients alone, see GsrBackwardArgs); no struct changed.
  * 116: GsrForwardArgs ends with render_only (the render-only call).
- * 117: the retire table: gsr_forward_retire, GsrBackwardArgs ends with retired_at, retire_step, gsr_batch_retire; GsrForwardArgs unchanged. */
+ * 117: the retire table: gsr_forward_retire, GsrBackwardArgs ends with retired_at, retire_step, gsr_batch_retire; GsrForwardArgs unchanged.
+ * 118: gsr_depth_to_points, gsr_voxel_scratch_bytes, gsr_voxel_down_sample; no struct changes (gsr_struct_bytes as in 117). */
 int gsr_version(void);
 size_t gsr_struct_bytes(int32_t which); /* 0 GsrForwardArgs, 1 GsrBackwardArgs, 2 GsrForwardOut; anything else 0 */
 
@@ -654,6 +655,49 @@ int gsr_batch_retire(const float* render, const float* target, int32_t B, int32_
 size_t gsr_knn_scratch_bytes(int32_t N);
 int gsr_knn_mean_dist2(const float* points /*[N,3]*/, int32_t N, float* out /*[N]*/, void* scratch, size_t scratch_bytes,
                        void* stream);
+
+/* ---- the single-image model's point cloud: depth map -> points -> voxel-grid means (version 118) --------------------------------------
+ * The two steps the reference runs in front of create_from_pcd for every frame of stage A and every leaf, on the host
+ * (/root/reference/trainer/trainer.py:646-671).  Neither kornia nor Open3D is available where this library is built and tested: both
+ * entries RESTATE the libraries' public definitions, they are not pinned against a run of them.  Both calls are
+ * fully asynchronous on `stream`.
+ *
+ * gsr_depth_to_points -- replaces `kornia.geometry.depth.depth_to_3d(depth[None,None], K[None], normalize_points=False)` at
+ * /root/reference/trainer/trainer.py:646-650.  For pixel column u = 0..W-1 and row v = 0..H-1 (integer pixel coordinates as float32) and
+ * d = depth[v,u]:
+ *     x = ((u - cx) / fx) * d      y = ((v - cy) / fy) * d      z = d
+ * all in float32 in exactly that order: a subtraction, a division, a product, each rounded once (nothing of it can contract to an FMA).
+ * points: row-major [H*W,3] (row v*W + u).  image [3,H,W] and colors [H*W,3] are given BOTH or NEITHER: colors[v*W+u, c] = image[c,v,u]
+ * (the reference's `image_np.reshape(-1, 3)` of the [H,W,3] image, :662; its points are reshaped the same way, :652).
+ * GSR_ERR_ARG (before anything is enqueued): depth or points NULL, H or W not positive, H*W >= 2^31, fx or fy equal to 0, image without
+ * colors or the reverse.
+ *
+ * gsr_voxel_down_sample -- replaces Open3D's `PointCloud::VoxelDownSample` (`pcd.voxel_down_sample(voxel_size=0.01)`,
+ * /root/reference/trainer/trainer.py:664-665; the `estimate_normals` before it, :663, produces normals nothing reads and has no counterpart):
+ *   * points and colours are widened to float64;
+ *   * min_bound = the per-axis minimum over the FINITE points (all three coordinates finite), origin = min_bound - 0.5 * voxel_size;
+ *   * the voxel index of a point per axis is floor((p - origin) / voxel_size) in float64;
+ *   * every occupied voxel yields one output point = the mean of its points and one colour = the mean of their colours, both accumulated in
+ *     float64 and rounded ONCE to float32; out_counts[m] = the number of points of voxel m;
+ *   * a point with a non-finite coordinate belongs to no voxel, does not enter the bound and is counted in `dropped`;
+ *   * output order: ascending (ix, iy, iz), lexicographic.  Open3D's own order is that of its hash map and unspecified; this one is defined
+ *     and repeatable.
+ * The sums are taken in a fixed order that depends on a voxel's point count alone (csrc/voxel_kernels.hip; no floating-point atomics): two
+ * calls on the same input are bit-identical, and voxels of up to 16 points are summed in input order.
+ * meta (device, 4 x int64, 8-byte aligned; the caller reads it): {M = number of voxels, dropped, status, 0}.  status = 1 when an axis needs
+ * an index >= 2^21 (extent / voxel_size too large for the 63-bit key ix<<42 | iy<<21 | iz): then M = 0 and no output row is to be relied on.
+ * out_points / out_colors / out_counts have room for N rows; rows [0, M) are written.  colors and out_colors are given BOTH or NEITHER;
+ * out_counts may be NULL.  scratch: gsr_voxel_scratch_bytes(N) bytes, 8-byte aligned -- a closed form in N, monotone, 0 for N <= 0.
+ * N == 0: returns 0, writes meta = {0,0,0,0} and launches nothing else (every other pointer may be NULL).
+ * GSR_ERR_ARG (before anything is enqueued): N < 0 or N >= 2^31, meta NULL or not 8-byte aligned, voxel_size <= 0 or not finite, colors
+ * without out_colors or the reverse, and for N > 0 points, out_points or scratch NULL, scratch misaligned or shorter than
+ * gsr_voxel_scratch_bytes(N). */
+int    gsr_depth_to_points(const float* depth /*[H,W]*/, const float* image /*[3,H,W] or NULL*/, int32_t H, int32_t W,
+                           float fx, float fy, float cx, float cy, float* points /*[H*W,3]*/, float* colors /*[H*W,3] or NULL*/, void* stream);
+size_t gsr_voxel_scratch_bytes(int64_t N);
+int    gsr_voxel_down_sample(const float* points /*[N,3]*/, const float* colors /*[N,3] or NULL*/, int64_t N, double voxel_size,
+                             float* out_points /*[N,3] capacity*/, float* out_colors /*[N,3] or NULL*/, int32_t* out_counts /*[N] or NULL*/,
+                             int64_t* meta /*device, 4 x int64: M, dropped, status, 0*/, void* scratch, size_t scratch_bytes, void* stream);
 
 /* Measurement hook (bench.py roofline.peak_measured): float4 streaming copy of `bytes` bytes (a multiple of 16, 16-byte aligned
  * pointers) with `blocks` workgroups of 256 threads.  variant 0 = plain loads / stores, 1 = nt bit, 2 = four loads in flight per

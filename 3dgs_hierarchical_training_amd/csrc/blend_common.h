@@ -1,5 +1,5 @@
 // blend_common.h -- what the blend kernels of gsr_kernels.hip share: image-state layout,
-// checkpoint layout, tile -> XCD maps, the wave64 DPP sum and the packed-float helpers.
+// checkpoint layout, tile -> XCD map, the wave64 DPP sum and the packed-float helpers.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -36,30 +36,21 @@ constexpr int kImgPlanes = 7;
 // floor(a) + floor(b) + 1 <= floor(a + b) + 1).
 constexpr int kCkptPlanes = 6, kCkptFloats = kCkptPlanes * kTile * kTile;
 
-__device__ __forceinline__ int xcd_tile(int b, int T)
+// tile handled by slot `s` of XCD `x` (0..7): 2x2 blocks of tiles are dealt round-robin to the XCDs (block j on XCD j % 8),
+// which spreads a spatially coherent hot region over all XCDs but keeps most of the tiles a splat touches behind one L2.
+// Returns -1 for a slot beyond the image (odd tile counts pad their last blocks).  (The banded map and the one that dealt single tiles
+// round-robin left the tree with their "tile_map" option: DESIGN_HISTORY.md.)
+__device__ __forceinline__ int slot_tile(int x, int s, int T, int tiles_x)
 {
-    const int per = (T + 7) >> 3;
-    return (b & 7) * per + (b >> 3);
-}
-
-// tile handled by slot `s` of XCD `x` (0..7).  map 0 "banded": XCD x owns the contiguous tiles [x per, (x+1) per);
-// map 1 "interleaved": tile t lives on XCD t % 8; map 2 "block-interleaved": 2x2 blocks of tiles are dealt round-robin to
-// the XCDs (block j on XCD j % 8), which still spreads a spatially coherent hot region over all XCDs but keeps most of
-// the tiles a splat touches behind one L2.  Returns -1 for a slot beyond the image.
-__device__ __forceinline__ int slot_tile(int map, int x, int s, int T, int tiles_x)
-{
-    if (map == 0) { const int per = (T + 7) >> 3; const int t = x * per + s; return (s < per && t < T) ? t : -1; }
-    if (map == 1) { const int t = s * 8 + x; return t < T ? t : -1; }
     const int tiles_y = T / tiles_x, bx_n = (tiles_x + 1) >> 1, by_n = (tiles_y + 1) >> 1;
     const int j = (s >> 2) * 8 + x, w = s & 3;
     if (j >= bx_n * by_n) return -1;
     const int tx = 2 * (j % bx_n) + (w & 1), ty = 2 * (j / bx_n) + (w >> 1);
     return (tx < tiles_x && ty < tiles_y) ? ty * tiles_x + tx : -1;
 }
-// slots per XCD that cover every tile under `map`
-static inline int slots_per_xcd(int map, int T, int tiles_x)
+// slots per XCD that cover every tile
+static inline int slots_per_xcd(int T, int tiles_x)
 {
-    if (map != 2) return (T + 7) / 8;
     const int tiles_y = T / tiles_x, nblk = ((tiles_x + 1) / 2) * ((tiles_y + 1) / 2);
     return 4 * ((nblk + 7) / 8);
 }

@@ -51,7 +51,6 @@ namespace gsr {
 // small helpers
 // ------------------------------------------------------------------------------------------------
 static thread_local char g_err[512] = "";
-static int g_blend_ppt = 0;   // 0 = default
 // prepare in backward: up to this many Gaussians the per-Gaussian backward kernel also counts the digits of the next depth sort
 // (saves that sort's histogram launch: ~7 us + a launch gap on small models); above, its ~2 global adds per key cost more inside
 // the HBM-bound kernel than the histogram kernel does on its own (1 M: +20 us against -8 us).  Both sides of the hand-over
@@ -2205,13 +2204,13 @@ __device__ __forceinline__ float wave_reduce_three(float v0, float v1, float v2,
 // compiled, not tested per batch), no state planes, no staged word; HAS_DA = false on top of it: no depth / alpha accumulators (two FMAs
 // per taken visit) and no store of them.  The colour chain, the stop test and the reach bits are the full forward's statements in the
 // full forward's order: out_color, out_color_clamped (and out_depth / out_alpha under HAS_DA) are bit-identical with its.
-template <bool REACH, bool IMP = false, bool LEAN = false, bool HAS_DA = true>
+template <bool IMP = false, bool LEAN = false, bool HAS_DA = true>
 __device__ __forceinline__ void blend_fwd_item(const int xcd, const int kslot, float4 (*s_ab)[64], float2 (*s_c)[64],
                                                int W, int H, int tiles_x, int T, const uint2* __restrict__ ranges,
                                                const uint32_t* __restrict__ list, const Splat* __restrict__ splat,
                                                const float* __restrict__ bg, float* __restrict__ out_color,
                                                float* __restrict__ out_depth, float* __restrict__ out_alpha,
-                                               float* __restrict__ img, uint32_t* __restrict__ staged4, int interleave,
+                                               float* __restrict__ img, uint32_t* __restrict__ staged4,
                                                float* __restrict__ ckpt, int kCkptFirst, int tiles_y, uint16_t* __restrict__ cost_out,
                                                float* __restrict__ out_clamped, const ListCut& cut, const int cut_pass,
                                                const ImpArgs imp = ImpArgs{})
@@ -2225,7 +2224,7 @@ __device__ __forceinline__ void blend_fwd_item(const int xcd, const int kslot, f
     uint32_t dbg_visits = 0u, dbg_taken = 0u;   // (wave, instance) visits / visits in which some pixel took the instance
     unsigned long long dbg_stage = 0ull, dbg_loop = 0ull, dbg_mark = 0ull;   // shader-clock cycles: staging (incl. the wait for the gather) / visit loops
 #endif
-    const int tile = slot_tile(interleave, xcd, kslot >> 2, T, tiles_x);
+    const int tile = slot_tile(xcd, kslot >> 2, T, tiles_x);
     const int sub = kslot & 3;
     const int lane = (int)(threadIdx.x & 63u);
     if (tile < 0) { if (cost_out && lane == 0) cost_out[xcd + 8 * kslot] = 0; return; }
@@ -2269,7 +2268,7 @@ __device__ __forceinline__ void blend_fwd_item(const int xcd, const int kslot, f
     }
     float4 ra = {0, 0, 0, 0}, rb = ra, rc = ra;
     constexpr float kL2E = 1.4426950408889634f;
-    // REACH: the staging lane also runs the exact box test of the tile culling (gsr_math.h box_accept: the minimum of the conic
+    // Reach bits: the staging lane also runs the exact box test of the tile culling (gsr_math.h box_accept: the minimum of the conic
     // form over the pixel box against 2 ln(255 o) + slack -- never rejects a box in which some pixel is reached) on THIS
     // wave's 8x8 block; the blend loop then visits only the instances whose bit is set.  An instance the tile accepted but
     // this sub-tile cannot see costs three scalar instructions instead of twelve vector ones.
@@ -2311,7 +2310,7 @@ __device__ __forceinline__ void blend_fwd_item(const int xcd, const int kslot, f
 #endif
         const int cnt = min(NT, n - b * NT);
         // first use of this batch's records (lanes beyond cnt hold stale ones: masked in the ballot, never visited)
-        const bool reach_me = REACH && box_accept(make_tile_test(ra.x, ra.y, ra.z, ra.w, rb.x, rb.y), sbx0, sby0, sbx1, sby1);
+        const bool reach_me = box_accept(make_tile_test(ra.x, ra.y, ra.z, ra.w, rb.x, rb.y), sbx0, sby0, sbx1, sby1);
         {
             const uint32_t lo = __float_as_uint(rc.w);
             ra.x = pixel_rel(ra.x, pixel_lo_x(lo), tox); ra.y = pixel_rel(ra.y, pixel_lo_y(lo), toy);
@@ -2320,8 +2319,8 @@ __device__ __forceinline__ void blend_fwd_item(const int xcd, const int kslot, f
         s_ab[buf][lane] = ra; s_ab[kFwdBufs + buf][lane] = rb;
         if constexpr (IMP) imp.s_id[lane] = id_rec;            // (the colour plane s_c is the forward's alone: the pass has none)
         else s_c[buf][lane] = make_float2(rc.x, rc.y);
-        const unsigned long long reach = REACH ? __ballot(reach_me && lane < cnt) : 0ull;
-        visits += REACH ? (uint32_t)__popcll(reach) : (uint32_t)cnt;
+        const unsigned long long reach = __ballot(reach_me && lane < cnt);
+        visits += (uint32_t)__popcll(reach);
         // the staging area belongs to this wave alone: LDS instructions of one wave execute in issue order, so the broadcast
         // reads below see the writes above -- only the compiler must be kept from reordering them (no s_barrier: the queue
         // kernel runs sixteen independent waves per workgroup)
@@ -2397,24 +2396,16 @@ __device__ __forceinline__ void blend_fwd_item(const int xcd, const int kslot, f
         // (evaluating two instances' alpha before either blend -- two v_exp_f32 in flight -- measured the same: 118 us;
         //  one 16-byte-stride array for the three staged planes, so that a visit needs one address register instead of two:
         //  one v_mov less per visit but 6 instead of 5 kB of LDS per wave -- 26 instead of 32 waves per CU -- 109 -> 113 us)
-        if (REACH) {
-            for (unsigned long long rm = reach; rm != 0ull;) {
-                const int j = (int)__builtin_ctzll(rm);
+        for (unsigned long long rm = reach; rm != 0ull;) {
+            const int j = (int)__builtin_ctzll(rm);
 #if defined(__HIP_DEVICE_COMPILE__)
-                asm("s_bitset0_b64 %0, %1" : "+s"(rm) : "s"(j));   // rm &= rm - 1 is s_add_u32 + s_addc_u32 + s_and_b64
+            asm("s_bitset0_b64 %0, %1" : "+s"(rm) : "s"(j));   // rm &= rm - 1 is s_add_u32 + s_addc_u32 + s_and_b64
 #else
-                rm &= rm - 1ull;
+            rm &= rm - 1ull;
 #endif
-                float p2;
-                const float a1 = alpha_of(j, p2);
-                blend(j, p2, a1);
-            }
-        } else {
-            for (int j = 0; j < cnt; j++) {
-                float p2;
-                const float a1 = alpha_of(j, p2);
-                blend(j, p2, a1);
-            }
+            float p2;
+            const float a1 = alpha_of(j, p2);
+            blend(j, p2, a1);
         }
 #ifdef GSR_K6_TIMING
         dbg_loop += __builtin_readcyclecounter() - dbg_mark;
@@ -2516,12 +2507,11 @@ __device__ __forceinline__ void blend_fwd_slot(const BlendBalance& bb, const boo
     }
 }
 
-template <bool REACH>
 __global__ __launch_bounds__(64) void k_blend_fwd_w6(int W, int H, int tiles_x, int T, const uint2* __restrict__ ranges,
                                                      const uint32_t* __restrict__ list, const Splat* __restrict__ splat,
                                                      const float* __restrict__ bg, float* __restrict__ out_color,
                                                      float* __restrict__ out_depth, float* __restrict__ out_alpha,
-                                                     float* __restrict__ img, uint32_t* __restrict__ staged4, int interleave,
+                                                     float* __restrict__ img, uint32_t* __restrict__ staged4,
                                                      float* __restrict__ ckpt, int kCkptFirst, int tiles_y, const BlendBalance bb,
                                                      float* __restrict__ out_clamped, const ListCut cut = ListCut{}, const int cut_pass = 0)
 {
@@ -2533,11 +2523,11 @@ __global__ __launch_bounds__(64) void k_blend_fwd_w6(int W, int H, int tiles_x, 
     int kslot = (int)(blockIdx.x >> 3);
     uint16_t* cost_out = nullptr;
     blend_fwd_slot(bb, cut_pass != 2, kslot, cost_out);       // (the repair pass: dispatch order)
-    blend_fwd_item<REACH>((int)(blockIdx.x & 7), kslot, s_ab, s_c, W, H, tiles_x, T, ranges, list, splat, bg, out_color, out_depth,
-                          out_alpha, img, staged4, interleave, ckpt, kCkptFirst, tiles_y, cost_out, out_clamped, cut, cut_pass);
+    blend_fwd_item((int)(blockIdx.x & 7), kslot, s_ab, s_c, W, H, tiles_x, T, ranges, list, splat, bg, out_color, out_depth,
+                   out_alpha, img, staged4, ckpt, kCkptFirst, tiles_y, cost_out, out_clamped, cut, cut_pass);
 }
 
-// The render-only forward blend (GsrForwardArgs::render_only, blend_fwd_item's LEAN): k_blend_fwd_w6<true>'s placement and walk, the image
+// The render-only forward blend (GsrForwardArgs::render_only, blend_fwd_item's LEAN): k_blend_fwd_w6's placement and walk, the image
 // alone written.  The parameter list is k_blend_fwd_w6's, so that the host launches either through one pointer; the state planes, the
 // staged counters, the checkpoint area and the list cut are not read (full lists: cut_pass 0).  The staging planes are the forward's.
 template <bool HAS_DA>
@@ -2545,7 +2535,7 @@ __global__ __launch_bounds__(64) void k_blend_fwd_render(int W, int H, int tiles
                                                          const uint32_t* __restrict__ list, const Splat* __restrict__ splat,
                                                          const float* __restrict__ bg, float* __restrict__ out_color,
                                                          float* __restrict__ out_depth, float* __restrict__ out_alpha,
-                                                         float* __restrict__, uint32_t* __restrict__, int interleave,
+                                                         float* __restrict__, uint32_t* __restrict__,
                                                          float* __restrict__, int, int tiles_y, const BlendBalance bb,
                                                          float* __restrict__ out_clamped, const ListCut, const int)
 {
@@ -2554,22 +2544,22 @@ __global__ __launch_bounds__(64) void k_blend_fwd_render(int W, int H, int tiles
     int kslot = (int)(blockIdx.x >> 3);
     uint16_t* cost_out = nullptr;
     blend_fwd_slot(bb, true, kslot, cost_out);   // this render reads the frame's table and records its visits like any other
-    blend_fwd_item<true, false, true, HAS_DA>((int)(blockIdx.x & 7), kslot, s_ab, s_c, W, H, tiles_x, T, ranges, list, splat, bg, out_color, out_depth,
-                                              out_alpha, nullptr, nullptr, interleave, nullptr, 0, tiles_y, cost_out, out_clamped, ListCut{}, 0);
+    blend_fwd_item<false, true, HAS_DA>((int)(blockIdx.x & 7), kslot, s_ab, s_c, W, H, tiles_x, T, ranges, list, splat, bg, out_color, out_depth,
+                                        out_alpha, nullptr, nullptr, nullptr, 0, tiles_y, cost_out, out_clamped, ListCut{}, 0);
 }
 
-// Importance blend (gsr_importance_accumulate): the forward blend's walk a second time -- blend_fwd_item<true, true> -- in dispatch order
+// Importance blend (gsr_importance_accumulate): the forward blend's walk a second time -- blend_fwd_item<true> -- in dispatch order
 // (no balanced placement: nothing records this launch's visits), one wave per 8x8 sub-tile.
 __global__ __launch_bounds__(64) void k_blend_importance(int W, int H, int tiles_x, int T, const uint2* __restrict__ ranges,
                                                          const uint32_t* __restrict__ list, const Splat* __restrict__ splat,
-                                                         float* __restrict__ img, uint32_t* __restrict__ staged4, int interleave, int tiles_y,
+                                                         float* __restrict__ img, uint32_t* __restrict__ staged4, int tiles_y,
                                                          const float* __restrict__ color, float* __restrict__ S)
 {
     __shared__ float4 s_ab[2 * kFwdBufs][64];
     __shared__ float s_sum[3][64];
     __shared__ uint32_t s_id[64];
-    blend_fwd_item<true, true>((int)(blockIdx.x & 7), (int)(blockIdx.x >> 3), s_ab, nullptr, W, H, tiles_x, T, ranges, list, splat, nullptr, nullptr, nullptr,
-                               nullptr, img, staged4, interleave, nullptr, 0, tiles_y, nullptr, nullptr, ListCut{}, 0, ImpArgs{color, S, s_sum, s_id});
+    blend_fwd_item<true>((int)(blockIdx.x & 7), (int)(blockIdx.x >> 3), s_ab, nullptr, W, H, tiles_x, T, ranges, list, splat, nullptr, nullptr, nullptr,
+                         nullptr, img, staged4, nullptr, 0, tiles_y, nullptr, nullptr, ListCut{}, 0, ImpArgs{color, S, s_sum, s_id});
 }
 
 // Finish of the importance pass: acc[n,k,c] += |basis_k(dir_n)| [colour_{n,c} > 0] S[n,c] for k < (D+1)^2 -- sixteen threads per
@@ -2634,7 +2624,7 @@ static_assert(sizeof(BwdItemHdr) <= kItemHdrBytes, "item header");
 constexpr int kItemBuckets = 32;   // batch indices 0..30 keep their own bucket of a list, deeper ones share the last
 
 __global__ __launch_bounds__(256) void k_bwd_prologue(float4* __restrict__ gg4, size_t n4, const uint32_t* __restrict__ staged4, int T,
-                                                      int tiles_x, int interleave, int tpad, int kCkptFirst, int split_ok,
+                                                      int tiles_x, int tpad, int kCkptFirst, int split_ok,
                                                       BwdItemHdr* __restrict__ hdr, uint2* __restrict__ items, uint32_t list_cap,
                                                       uint32_t first_pull, uint32_t* __restrict__ zero_words, int zero_count)
 {
@@ -2657,8 +2647,7 @@ __global__ __launch_bounds__(256) void k_bwd_prologue(float4* __restrict__ gg4, 
     if (tid < kItemBuckets) s_cur[tid] = 0u;
     __syncthreads();
     auto items_of = [&](int tile) -> int {      // the run [0, kCkptFirst) first, then one item per 128-instance batch
-        if (!split_ok) return 1;                // (no checkpoints -- a forward variant that leaves none, or "bwd_split" 1: the whole tile, whatever
-                                                //  the staged counters say: those variants do not all write them)
+        if (!split_ok) return 1;                // ("bwd_split" 1: the whole tile, whatever the staged counters say)
         const uint4 sd = *reinterpret_cast<const uint4*>(staged4 + 4 * tile);
         const int nbs = ((int)max(max(sd.x, sd.y), max(sd.z, sd.w)) + 127) / 128;
         if (nbs == 0) return 0;
@@ -2666,7 +2655,7 @@ __global__ __launch_bounds__(256) void k_bwd_prologue(float4* __restrict__ gg4, 
     };
     const int slots = tpad >> 3;
     for (int k = tid; k < slots; k += 256) {
-        const int tile = slot_tile(interleave, x, k, T, tiles_x);
+        const int tile = slot_tile(x, k, T, tiles_x);
         if (tile < 0) continue;
         const int ni = items_of(tile);
         for (int q = 0; q < ni; q++) atomicAdd(&s_cnt[min(q, kItemBuckets - 1)], 1u);
@@ -2681,7 +2670,7 @@ __global__ __launch_bounds__(256) void k_bwd_prologue(float4* __restrict__ gg4, 
     __syncthreads();
     uint2* const mine = items + (size_t)x * list_cap;
     for (int k = tid; k < slots; k += 256) {
-        const int tile = slot_tile(interleave, x, k, T, tiles_x);
+        const int tile = slot_tile(x, k, T, tiles_x);
         if (tile < 0) continue;
         const int ni = items_of(tile);
         for (int q = 0; q < ni; q++) {
@@ -2705,7 +2694,7 @@ __global__ __launch_bounds__(256) void k_bwd_prologue(float4* __restrict__ gg4, 
 // decisions are branch-free per pixel (masked alpha and G); only the whole-wave skip is a branch.
 // ------------------------------------------------------------------------------------------------
 struct BlendBwdArgs {
-    int W, H, tiles_x, tiles_y, T, interleave, kCkptFirst, pad;
+    int W, H, tiles_x, tiles_y, T, kCkptFirst;
     const uint2* ranges;
     const uint32_t* list;
     const Splat* splat;
@@ -4120,7 +4109,7 @@ static BinScratch bin_scratch_layout(int64_t R, int key_bytes = 4)
 // The pinned read-back slot belongs to ONE device (its device pointer is that device's mapping), and a slot is held by one
 // call at a time: callers on several threads / devices do not serialise on each other while they enqueue or wait.
 // the per-view cost cache of the balanced forward blend: one per (device, frame geometry), a handful at most
-struct ViewCostCache { int dev, W, H, map, items; uint8_t* mem; size_t bytes; };
+struct ViewCostCache { int dev, W, H, items; uint8_t* mem; size_t bytes; };
 static std::vector<ViewCostCache> g_view_costs;   // guarded by g_state_mutex
 static std::map<std::tuple<int, int, int, int>, bool> g_full_depth_sort;   // callers whose depths left the 27-bit window once: four 8-bit passes from then on
 
@@ -4155,7 +4144,6 @@ static int g_list_cut_margin_e3 = 50;   // ... x (1 + this / 1000) of the depth 
 static int g_list_cut_deep = 8;        // tiles whose own cut may lie behind the frame's (served by cut_chunk_tiles)
 static int g_early_r = 1;         // the host learns R from the preprocess's per-block shares (published by the depth sort's histogram kernel) instead of from the scan
 static int g_blend_balance = 1;   // forward blend: place the waves by the visits each took at the previous render of the same view (balance_build)
-static int g_tile_map = 2;   // tile -> XCD map: 2 = 2x2 tile blocks interleaved (default), 1 = tiles interleaved, 0 = banded
 static std::atomic<long long> g_spec_overflows{0}, g_spec_forwards{0}, g_exact_forwards{0}, g_depth_window_resorts{0};
 // host-side time accounting of the two entry points (gsr_get_counter): wall time inside the call, and the part of the forward
 // spent waiting for the instance count -- their difference is what the launching thread really works per call
@@ -4214,13 +4202,16 @@ struct PinLease {   // releases the slot on every exit path
     ~PinLease() { if (s) { std::lock_guard<std::mutex> lk(g_state_mutex); s->busy = false; } }
 };
 
-// What the forward fixed for its backward (GsrForwardOut::forward_flags): the blend kernel variant, the tile -> XCD map,
-// the first checkpointed batch and whether checkpoints were written at all.  gsr_backward reads them from the flags
-// instead of the process-wide options as they happen to be at backward time.
-static inline int64_t pack_fwd_flags(int ppt, int tile_map, int ckpt_first)
+// What the forward fixed for its backward (GsrForwardOut::forward_flags): the first checkpointed batch (bits 6..12), which gsr_backward
+// reads from the flags instead of the process-wide option as it happens to be at backward time, and the render-only bit (14).  Bits
+// 1..3, 4..5 and 13 once told the blend kernel variant, the tile -> XCD map and whether checkpoints were written: the layout stays,
+// the fields hold the one value left (7, 2, 1), and flags_from_forward refuses any other.
+static inline int64_t pack_fwd_flags(int ckpt_first)
 {
-    return 1 | ((int64_t)ppt << 1) | ((int64_t)tile_map << 4) | ((int64_t)ckpt_first << 6) | ((int64_t)(ppt >= 5) << 13);
+    return 1 | ((int64_t)7 << 1) | ((int64_t)2 << 4) | ((int64_t)ckpt_first << 6) | ((int64_t)1 << 13);
 }
+// flags with bit 0 set: do they carry the variant and the map this library writes?  (0 = the round-1 caller: the defaults)
+static inline bool flags_from_forward(int64_t flags) { return ((flags >> 1) & 7) == 7 && ((flags >> 4) & 3) == 2; }
 
 // GsrBatch -> the kernels' BatchDev; validates the block table against N.  nullptr / B <= 1: single model.
 static int batch_dev(const GsrBatch* bt, int32_t N, int32_t H, BatchDev& out)
@@ -4276,7 +4267,7 @@ static size_t image_balance_bytes(int32_t W, int32_t H, int32_t B)
 {
     if (B > 1) return 0;
     const int tiles_x = (W + kTile - 1) / kTile, T = tiles_x * ((H + kTile - 1) / kTile);
-    return 256 + align256((size_t)32 * slots_per_xcd(2, T, tiles_x) * sizeof(uint16_t) + 64);   // (map 2 has the most slots)
+    return 256 + align256((size_t)32 * slots_per_xcd(T, tiles_x) * sizeof(uint16_t) + 64);
 }
 static size_t image_staged_offset(int32_t W, int32_t H, int32_t B) { return image_balance_offset(W, H, B) + image_balance_bytes(W, H, B); }
 size_t gsr_image_staged_offset(int32_t W, int32_t H) { return image_staged_offset(W, H, 1); }
@@ -4362,16 +4353,13 @@ int gsr_debug_k8_timing(unsigned long long* host_dst, int blocks)
 int gsr_set_option(const char* name, int value)
 {
     if (!name) return GSR_ERR_ARG;
-    // 7 (default) / 6 = one wave per 8x8 sub-tile, with / without reach bits (the tile-per-workgroup A/B kernels of rounds 1-4, values
-    // 1-5, left the tree in round 5: they were compiled on request only and no default-build test reached them)
-    if (!strcmp(name, "blend_fwd_ppt")) {
-        if (value != 0 && value != 6 && value != 7) return GSR_ERR_ARG;
-        g_blend_ppt = value; return GSR_OK;
-    }
+    // 0 / 7 = one wave per 8x8 sub-tile with reach bits, the only forward blend (6, the same without the bits, and the tile-per-workgroup
+    // A/B kernels of rounds 1-4, values 1-5, have left the tree: DESIGN_HISTORY.md)
+    if (!strcmp(name, "blend_fwd_ppt")) return (value == 0 || value == 7) ? GSR_OK : GSR_ERR_ARG;
     if (!strcmp(name, "ab_variants")) return 0;   // query kept for callers of the round-4 ABI: no A/B kernels in the library
     if (!strcmp(name, "bwd_split")) { if (value < 0 || value > 64) return GSR_ERR_ARG; g_bwd_split = value; return GSR_OK; }
     if (!strcmp(name, "ckpt_first")) { if (value < 1 || value > 64) return GSR_ERR_ARG; g_ckpt_first = value; return GSR_OK; }
-    if (!strcmp(name, "tile_map")) { if (value < 0 || value > 2) return GSR_ERR_ARG; g_tile_map = value; return GSR_OK; }
+    if (!strcmp(name, "tile_map")) return value == 2 ? GSR_OK : GSR_ERR_ARG;   // 2x2 tile blocks dealt to the XCDs: the only map (blend_common.h)
     if (!strcmp(name, "blend_balance")) { g_blend_balance = value ? 1 : 0; return GSR_OK; }
     if (!strcmp(name, "early_r")) { g_early_r = value ? 1 : 0; return GSR_OK; }
     if (!strcmp(name, "list_cut")) { g_list_cut = value < 0 || value > 2 ? 1 : value; return GSR_OK; }
@@ -4490,12 +4478,12 @@ static int forward_impl(const GsrForwardArgs* a, const int32_t* retired_at, int6
     if (rc) return rc;
     const int NB = bt.B;   // images rendered by this call (batched render: a tall grid of NB * tiles_y tile rows)
     // the process-wide options as they are NOW: one forward uses one consistent set and hands it to its backward
-    const int opt_ppt = g_blend_ppt ? g_blend_ppt : 7, opt_map = g_tile_map, opt_ckpt = g_ckpt_first;
+    const int opt_ckpt = g_ckpt_first;
     const int tiles_x = (W + kTile - 1) / kTile, tiles_y = (H + kTile - 1) / kTile, T = tiles_x * tiles_y * NB;
     if (a->sh_origin && (!a->shs || NB > 1 || a->prepared))
         return fail(GSR_ERR_ARG, "sh_origin needs shs and is not served with a batch of B > 1 or a prepared buffer%s");
     out->num_rendered = 0; out->binning = nullptr; out->binning_bytes = 0; out->binning_capacity = 0;
-    out->forward_flags = pack_fwd_flags(opt_ppt, opt_map, opt_ckpt) | (ro ? GSR_FWD_FLAG_RENDER_ONLY : 0);
+    out->forward_flags = pack_fwd_flags(opt_ckpt) | (ro ? GSR_FWD_FLAG_RENDER_ONLY : 0);
     uint64_t R = 0;
     BlendBalance bb = {};   // filled in front of k_tile_counts (whose extra workgroups build the placement the blend reads)
     ListCut lc = {};        // filled with it: the list cut lives in the same per-frame cache
@@ -4503,28 +4491,21 @@ static int forward_impl(const GsrForwardArgs* a, const int32_t* retired_at, int6
     Splat* splat = static_cast<Splat*>(a->geom);
     float* img = static_cast<float*>(a->image);
     // image workspace: the caller's (state planes | balanced-placement table | staged counters), or -- a render-only call without one --
-    // scratch of the library's own: through the lean kernel the table and the counters alone (the clears that ride in k_block_scan /
-    // k_chunk_scan2 and the builder of the table write there), under "blend_fwd_ppt" 6 the whole layout (the existing kernel fills it)
-    const bool lean = ro && opt_ppt == 7;
+    // scratch of the library's own: the table and the counters alone (the clears that ride in k_block_scan / k_chunk_scan2 and the
+    // builder of the table write there; k_blend_fwd_render touches no state plane)
     uint8_t* img_base = static_cast<uint8_t*>(a->image);
     size_t balance_off = image_balance_offset(W, H, NB), staged_off = image_staged_offset(W, H, NB);
-    float *ro_depth = a->out_depth, *ro_alpha = a->out_alpha;
     uint32_t* staged = img_base ? reinterpret_cast<uint32_t*>(img_base + staged_off) : nullptr;
-    // (the staged counters of a lean call are cleared like any other forward's -- the clear rides in kernels that run anyway -- though
+    // (the staged counters of a render-only call are cleared like any other forward's -- the clear rides in kernels that run anyway -- though
     //  nothing reads them: knowingly redundant, the price of leaving k_block_scan / k_chunk_scan2 and their ZeroJobs as they are)
     auto ro_workspace = [&]() -> int {
         if (!ro) return GSR_OK;
         if (!img_base) {
-            if (lean) { staged_off -= balance_off; balance_off = 0; }
+            staged_off -= balance_off; balance_off = 0;
             img_base = static_cast<uint8_t*>(a->alloc(staged_off + align256((size_t)T * 16), GSR_ALLOC_SCRATCH, a->alloc_user));
             if (!img_base) return fail(GSR_ERR_ALLOC, "image workspace allocation failed%s");
             img = reinterpret_cast<float*>(img_base);
             staged = reinterpret_cast<uint32_t*>(img_base + staged_off);
-        }
-        if (!lean && !ro_depth) {   // (the existing kernel writes both planes)
-            ro_depth = static_cast<float*>(a->alloc(2 * align256((size_t)W * H * 4), GSR_ALLOC_SCRATCH, a->alloc_user));
-            if (!ro_depth) return fail(GSR_ERR_ALLOC, "depth / alpha scratch allocation failed%s");
-            ro_alpha = ro_depth + align256((size_t)W * H * 4) / 4;
         }
         if (!splat && N > 0) {
             splat = static_cast<Splat*>(a->alloc(gsr_geom_bytes(N), GSR_ALLOC_SCRATCH, a->alloc_user));
@@ -4655,33 +4636,29 @@ static int forward_impl(const GsrForwardArgs* a, const int32_t* retired_at, int6
         return wide_keys ? launch_binning_t(uint32_t{}, capacity, n_dev, prezeroed) : launch_binning_t(uint16_t{}, capacity, n_dev, prezeroed);
     };
     auto launch_blend = [&](bool prezeroed) -> int {
-        const int ppt = opt_ppt;   // default 7: one wave per 8x8 sub-tile, sign-encoded done + sub-tile reach bits (6: without the bits)
         if (!prezeroed) GSR_HIP(hipMemsetAsync(staged, 0, (size_t)T * 16, st));
         float* ckpt = ro ? nullptr : reinterpret_cast<float*>(bin + B.ckpt);
-        // the default kernel, or the render-only one with or without depth / alpha: one parameter list
-        auto k7 = lean ? (a->out_depth ? k_blend_fwd_render<true> : k_blend_fwd_render<false>) : k_blend_fwd_w6<true>;
-        if (ppt == 7 && g_profile && (g_profile != 3 || g_profile_tick.fetch_add(1u) % 3u == 0u)) {
-            // timed launch of the default kernel (bench.py's in-run roofline timing): the dispatch's OWN start / stop timestamps
+        // the forward blend (one wave per 8x8 sub-tile, sign-encoded done + sub-tile reach bits), or the render-only one with or without
+        // depth / alpha: one parameter list
+        auto k7 = ro ? (a->out_depth ? k_blend_fwd_render<true> : k_blend_fwd_render<false>) : k_blend_fwd_w6;
+        if (g_profile && (g_profile != 3 || g_profile_tick.fetch_add(1u) % 3u == 0u)) {
+            // timed launch (bench.py's in-run roofline timing): the dispatch's OWN start / stop timestamps
             // (hipExtLaunchKernelGGL) instead of an event record in front of and behind it -- each of those is a barrier packet that
             // idles the queue for ~6 us (tools/api_timeline.sh: 12 us per step of the timed region went to the measurement)
             hipEvent_t ea = nullptr, eb = nullptr;
             if (hipEventCreate(&ea) != hipSuccess || hipEventCreate(&eb) != hipSuccess) return fail(GSR_ERR_HIP, "hipEventCreate failed%s");
-            hipExtLaunchKernelGGL(k7, dim3(8 * 4 * slots_per_xcd(opt_map, T, tiles_x)), dim3(64), 0, st, ea, eb, 0, W, H, tiles_x, T, ranges, list,
-                                  splat, a->bg, a->out_color, ro_depth, ro_alpha, img, staged, opt_map, ckpt, opt_ckpt, tiles_y, bb, a->out_color_clamped,
+            hipExtLaunchKernelGGL(k7, dim3(8 * 4 * slots_per_xcd(T, tiles_x)), dim3(64), 0, st, ea, eb, 0, W, H, tiles_x, T, ranges, list,
+                                  splat, a->bg, a->out_color, a->out_depth, a->out_alpha, img, staged, ckpt, opt_ckpt, tiles_y, bb, a->out_color_clamped,
                                   lc, lc.key ? 1 : 0);
             std::lock_guard<std::mutex> lk(g_prof_mutex);
             g_prof_events[P_BLEND_FWD].push_back({ea, eb});
         } else {
-            ProfScope ps(ppt == 7 && g_profile == 3 ? P_COUNT : P_BLEND_FWD, st);   // (mode 3, an untimed launch: no events)
-            if (ppt == 7)
-                hipLaunchKernelGGL(k7, dim3(8 * 4 * slots_per_xcd(opt_map, T, tiles_x)), dim3(64), 0, st, W, H, tiles_x, T, ranges, list, splat, a->bg,
-                                   a->out_color, ro_depth, ro_alpha, img, staged, opt_map, ckpt, opt_ckpt, tiles_y, bb, a->out_color_clamped,
-                                   lc, lc.key ? 1 : 0);
-            else
-                hipLaunchKernelGGL(k_blend_fwd_w6<false>, dim3(8 * 4 * slots_per_xcd(opt_map, T, tiles_x)), dim3(64), 0, st, W, H, tiles_x, T, ranges, list, splat, a->bg,
-                                   a->out_color, ro_depth, ro_alpha, img, staged, opt_map, ckpt, opt_ckpt, tiles_y, BlendBalance{}, a->out_color_clamped);
+            ProfScope ps(g_profile == 3 ? P_COUNT : P_BLEND_FWD, st);   // (mode 3, an untimed launch: no events)
+            hipLaunchKernelGGL(k7, dim3(8 * 4 * slots_per_xcd(T, tiles_x)), dim3(64), 0, st, W, H, tiles_x, T, ranges, list, splat, a->bg,
+                               a->out_color, a->out_depth, a->out_alpha, img, staged, ckpt, opt_ckpt, tiles_y, bb, a->out_color_clamped,
+                               lc, lc.key ? 1 : 0);
         }
-        if (ppt == 7 && lc.key && lc_capacity > 0) {
+        if (lc.key && lc_capacity > 0) {
             // the repair pass of the list cut: the same scatter over the chunks behind the flagged tiles' cuts and the same blend over
             // the flagged tiles' full lists -- every workgroup of both launches reads one word and leaves unless a wave flagged a tile
             ProfScope ps(P_CUT_REPAIR, st);
@@ -4689,8 +4666,8 @@ static int forward_impl(const GsrForwardArgs* a, const int32_t* retired_at, int6
             hipLaunchKernelGGL((k_chunk_scatter<false, 2>), dim3(grid), dim3(64), (size_t)12 * db.Tp + 4 * kDbPairs, st, db, W, H,
                                tiles_x, tiles_y, sorted_gid, reinterpret_cast<const TileRec*>(fs + L.srec), splat, list, ranges,
                                (uint32_t)std::min<uint64_t>(lc_capacity, 0xffffffffull), (const uint32_t*)nullptr, (uint2*)nullptr, lc);
-            hipLaunchKernelGGL(k_blend_fwd_w6<true>, dim3(8 * 4 * slots_per_xcd(opt_map, T, tiles_x)), dim3(64), 0, st, W, H, tiles_x, T, ranges, list, splat, a->bg,
-                               a->out_color, a->out_depth, a->out_alpha, img, staged, opt_map, ckpt, opt_ckpt, tiles_y, bb, a->out_color_clamped, lc, 2);
+            hipLaunchKernelGGL(k_blend_fwd_w6, dim3(8 * 4 * slots_per_xcd(T, tiles_x)), dim3(64), 0, st, W, H, tiles_x, T, ranges, list, splat, a->bg,
+                               a->out_color, a->out_depth, a->out_alpha, img, staged, ckpt, opt_ckpt, tiles_y, bb, a->out_color_clamped, lc, 2);
         }
         GSR_HIP(hipGetLastError());
         return GSR_OK;
@@ -4889,11 +4866,11 @@ static int forward_impl(const GsrForwardArgs* a, const int32_t* retired_at, int6
             zj.p[1] = staged; zj.words[1] = (uint32_t)T * 4u;
             if (bs) { zj.p[2] = bs + S.sort; zj.words[2] = kOnesweepHeadWords; }
         }
-        // balanced placement of the forward blend (balance_build): single renders through the default kernel, frames of up to
+        // balanced placement of the forward blend (balance_build): single renders, frames of up to
         // 65 535 sub-tile waves; the per-view cost cache is a lazily allocated device buffer per (device, frame geometry)
         {
-            const int nslots4 = 4 * slots_per_xcd(opt_map, T, tiles_x), items = 8 * nslots4;
-            if (g_blend_balance && NB == 1 && opt_ppt == 7 && items <= 65535 && nslots4 <= 20 * kEmitThreads && a->viewmatrix) {
+            const int nslots4 = 4 * slots_per_xcd(T, tiles_x), items = 8 * nslots4;
+            if (g_blend_balance && NB == 1 && items <= 65535 && nslots4 <= 20 * kEmitThreads && a->viewmatrix) {
                 const size_t hdr_bytes = align256(sizeof(ViewCostHdr));
                 // header | visit counts [entries][items] | list cut: depth keys [entries][T], the model size they belong to [entries]
                 const size_t vc_cut = align256(hdr_bytes + (size_t)kVcEntries * items * sizeof(uint16_t));
@@ -4903,14 +4880,14 @@ static int forward_impl(const GsrForwardArgs* a, const int32_t* retired_at, int6
                 {
                     std::lock_guard<std::mutex> lk(g_state_mutex);
                     for (auto& c : g_view_costs)
-                        if (c.dev == dev_id && c.W == W && c.H == H && c.map == opt_map && c.items == items) mem = c.mem;
+                        if (c.dev == dev_id && c.W == W && c.H == H && c.items == items) mem = c.mem;
                     if (!mem && g_view_costs.size() < 64) {   // (frame geometries per process; round 6: 64 -- a test session renders more than 16 sizes)
                         if (hipMalloc((void**)&mem, vc_bytes) == hipSuccess) {
                             // cleared SYNCHRONOUSLY, once per (device, frame geometry), before anybody can look at it (with
                             // pose-keyed entries an uncleared header is not "garbage hashes = a miss" -- a key that reads 2 with pose
                             // floats inside the tolerance would be a hit on garbage cost tables); a failed clear = no cache
                             if (hipMemset(mem, 0, vc_bytes) == hipSuccess) {
-                                g_view_costs.push_back({dev_id, W, H, opt_map, items, mem, vc_bytes});
+                                g_view_costs.push_back({dev_id, W, H, items, mem, vc_bytes});
                             } else {
                                 (void)hipGetLastError();
                                 (void)hipFree(mem);
@@ -5058,8 +5035,7 @@ static int forward_impl(const GsrForwardArgs* a, const int32_t* retired_at, int6
     out->binning = bin;
     out->binning_bytes = B.bytes;
     out->binning_capacity = (int64_t)((speculative && R <= cap && !resorted) ? cap : R);
-    out->forward_flags = pack_fwd_flags(opt_ppt, opt_map, opt_ckpt);
-    return GSR_OK;
+    return GSR_OK;   // (forward_flags: set on entry)
 }
 
 int gsr_forward(const GsrForwardArgs* a, GsrForwardOut* out, void* stream_) { return forward_impl(a, nullptr, 0, out, stream_); }
@@ -5142,14 +5118,12 @@ int gsr_backward(const GsrBackwardArgs* a, void* stream_)
             return fail(GSR_ERR_HIP, msg);
         }
     }
-    // the forward's kernel variant / tile map / checkpoint layout travel with its output (forward_flags); a caller of the
-    // round-1 ABI (flags 0) gets the process-wide options as before.  (The forward blend's variant is range-checked only: 6 and 7
-    // leave the same state and checkpoints.)
-    int f_map = g_tile_map, f_ckpt = g_ckpt_first;
+    // the forward's checkpoint layout travels with its output (forward_flags); a caller of the round-1 ABI (flags 0) gets the
+    // process-wide option as before
+    int f_ckpt = g_ckpt_first;
     if (a->forward_flags & 1) {
-        const int f_ppt = (int)((a->forward_flags >> 1) & 7);
-        f_map = (int)((a->forward_flags >> 4) & 3); f_ckpt = (int)((a->forward_flags >> 6) & 127);
-        if (f_ppt < 1 || f_ppt > 7 || f_map > 2 || f_ckpt < 1) return fail(GSR_ERR_ARG, "forward_flags do not come from gsr_forward%s");
+        f_ckpt = (int)((a->forward_flags >> 6) & 127);
+        if (!flags_from_forward(a->forward_flags) || f_ckpt < 1) return fail(GSR_ERR_ARG, "forward_flags do not come from gsr_forward%s");
     }
     if (N == 0) {
         if (a->d_viewmatrix) GSR_HIP(hipMemsetAsync(a->d_viewmatrix, 0, 64 * NB, st));
@@ -5182,7 +5156,7 @@ int gsr_backward(const GsrBackwardArgs* a, void* stream_)
     int bwd_grid = 0;
     {
         const uint32_t* staged4 = reinterpret_cast<const uint32_t*>(static_cast<const uint8_t*>(a->image) + image_staged_offset(W, H, NB));
-        const int tpad = 8 * slots_per_xcd(f_map, T, tiles_x);
+        const int tpad = 8 * slots_per_xcd(T, tiles_x);
         const int want_split = g_bwd_split ? g_bwd_split : 16;
         const int split_ok = want_split > 1 ? 1 : 0;
         const size_t n4 = (size_t)N * kGG * sizeof(double) / sizeof(float4);
@@ -5199,7 +5173,7 @@ int gsr_backward(const GsrBackwardArgs* a, void* stream_)
         }
         const uint32_t list_cap = (uint32_t)bwd_list_cap(a->binning_capacity > 0 ? a->binning_capacity : a->num_rendered, (size_t)T);
         hipLaunchKernelGGL(k_bwd_prologue, dim3(fill_blocks + (blend_items ? 8 : 0)), dim3(256), 0, st, reinterpret_cast<float4*>(gg), n4,
-                           staged4, T, tiles_x, f_map, tpad, f_ckpt, split_ok, item_hdr, const_cast<uint2*>(items), list_cap,
+                           staged4, T, tiles_x, tpad, f_ckpt, split_ok, item_hdr, const_cast<uint2*>(items), list_cap,
                            (uint32_t)(bwd_grid / 8), blend_items ? prep_head : nullptr, (int)kOnesweepHeadWordsMax);
         prep_head_cleared = blend_items && prep_head != nullptr;
     }
@@ -5225,7 +5199,7 @@ int gsr_backward(const GsrBackwardArgs* a, void* stream_)
             det_part = reinterpret_cast<float*>(det_mem + o_part);
             GSR_HIP(hipMemsetAsync(det_part, 0, (size_t)Rn * kDetStride * 4, st));
         }
-        BlendBwdArgs ba = {W, H, tiles_x, tiles_y, T, f_map, f_ckpt, 0, ranges, list, splat, a->bg, img, a->grad_color, a->grad_depth,
+        BlendBwdArgs ba = {W, H, tiles_x, tiles_y, T, f_ckpt, ranges, list, splat, a->bg, img, a->grad_color, a->grad_depth,
                            a->grad_alpha, gg, ckpt, det_part, item_hdr, items};
         if (a->grad_depth || a->grad_alpha) hipLaunchKernelGGL(k_blend_bwd2<true>, dim3(bwd_grid), dim3(128), 0, st, ba);
         else hipLaunchKernelGGL(k_blend_bwd2<false>, dim3(bwd_grid), dim3(128), 0, st, ba);
@@ -5420,11 +5394,7 @@ int gsr_importance_accumulate(const GsrForwardArgs* a, const GsrForwardOut* out,
     if (N == 0) return GSR_OK;
     if (!acc || !scratch || !a->geom || !a->image || !a->out_color || !a->means3D) return fail(GSR_ERR_ARG, "missing workspace / accumulator pointer%s");
     if (out->num_rendered <= 0 || !out->binning) return GSR_OK;   // nothing was blended: every sum is zero, the accumulator keeps its bits
-    int f_map = g_tile_map;
-    if (out->forward_flags & 1) {
-        f_map = (int)((out->forward_flags >> 4) & 3);
-        if (f_map > 2) return fail(GSR_ERR_ARG, "forward_flags do not come from gsr_forward%s");
-    }
+    if ((out->forward_flags & 1) && !flags_from_forward(out->forward_flags)) return fail(GSR_ERR_ARG, "forward_flags do not come from gsr_forward%s");
     const int tiles_x = (W + kTile - 1) / kTile, tiles_y = (H + kTile - 1) / kTile, T = tiles_x * tiles_y;
     const Splat* splat = static_cast<const Splat*>(a->geom);
     const BinLayout B = bin_layout(out->binning_capacity > 0 ? out->binning_capacity : out->num_rendered, W, H, 1);
@@ -5437,8 +5407,8 @@ int gsr_importance_accumulate(const GsrForwardArgs* a, const GsrForwardOut* out,
     GSR_HIP(hipMemsetAsync(S, 0, (size_t)N * kImpStride * sizeof(float), st));
     {
         ProfScope ps(P_IMP_BLEND, st);
-        hipLaunchKernelGGL(k_blend_importance, dim3(8 * 4 * slots_per_xcd(f_map, T, tiles_x)), dim3(64), 0, st, W, H, tiles_x, T, ranges, list, splat,
-                           img, staged, f_map, tiles_y, (const float*)a->out_color, S);
+        hipLaunchKernelGGL(k_blend_importance, dim3(8 * 4 * slots_per_xcd(T, tiles_x)), dim3(64), 0, st, W, H, tiles_x, T, ranges, list, splat,
+                           img, staged, tiles_y, (const float*)a->out_color, S);
     }
     {
         ProfScope ps(P_IMP_FINISH, st);

@@ -83,7 +83,7 @@ __device__ __forceinline__ LossTile loss_tile()
 __global__ __launch_bounds__(256) void k_loss_fwd(const float* __restrict__ raw, const float* __restrict__ gt, int H, int W,
                                                   int do_clamp, float* __restrict__ maps, float* __restrict__ partial)
 {
-    __shared__ __attribute__((aligned(16))) float s_in[kIH * kStrIn2];   // (x, y) interleaved
+    __shared__ __attribute__((aligned(16))) float s_in[kIH * kStrIn2];   // (x, y) pairs
     __shared__ __attribute__((aligned(16))) float s_hA[kIH * kStrH2];    // row-filtered (x, y)
     __shared__ __attribute__((aligned(16))) float s_hB[kIH * kStrH2];    // row-filtered (x^2, y^2)
     __shared__ __attribute__((aligned(16))) float s_hC[kIH * kStrH1];    // row-filtered x y

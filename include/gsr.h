@@ -154,9 +154,11 @@ typedef struct GsrForwardOut {
     size_t binning_bytes;
     int64_t binning_capacity; /* instances the binning buffer was laid out for (>= R when the forward ran speculatively);
                                  pass to gsr_backward together with `binning` */
-    int64_t forward_flags;    /* what this forward fixed for its backward (blend kernel variant, tile -> XCD map, checkpoint
-                                 layout): pass to gsr_backward unchanged.  gsr_set_option calls between the two then cannot
-                                 make the backward read checkpoints the forward never wrote */
+    int64_t forward_flags;    /* what this forward fixed for its backward (the first checkpointed batch; the render-only bit):
+                                 pass to gsr_backward unchanged.  gsr_set_option calls between the two then cannot make the
+                                 backward read checkpoints the forward never wrote.  (The bits that once told the blend kernel
+                                 variant and the tile -> XCD map keep their place and hold the one value left; flags that
+                                 carry another are refused, GSR_ERR_ARG.) */
 } GsrForwardOut;
 
 /* Optimizer-in-backward: with raw_params = 1, shs (= _features_dc) + shs_rest given and this struct attached,
@@ -381,9 +383,11 @@ int gsr_version(void);
 size_t gsr_struct_bytes(int32_t which); /* 0 GsrForwardArgs, 1 GsrBackwardArgs, 2 GsrForwardOut; anything else 0 */
 
 /* Process-wide knobs (value 0 = default unless stated):
- *   "blend_fwd_ppt"        forward blend kernel: 7 = one wave per 8x8 sub-tile, finished pixels encoded in the sign of T,
- *                          instances the sub-tile cannot see skipped by reach bits (default); 6 = without the reach bits.
- *                          Any other value is refused (the A/B kernels rounds 1-4 selected with 1-5 left the tree in round 5)
+ *   "blend_fwd_ppt"        forward blend kernel: 0 or 7 = one wave per 8x8 sub-tile, finished pixels encoded in the sign of T,
+ *                          instances the sub-tile cannot see skipped by reach bits -- the only forward blend, so setting it changes
+ *                          nothing.  Any other value is refused (the A/B kernels rounds 1-4 selected with 1-5 left the tree in
+ *                          round 5, the kernel without reach bits that 6 selected after them).  bench.py --fwd-ppt passes its value
+ *                          on without looking at the return code: with 6 it now measures the default
  *   "blend_bwd_ppt"        backward blend kernel: 0 or 2 = two pixels per lane, packed math, two waves per tile -- the only backward
  *                          blend, so setting it changes nothing.  Any other value is refused (the one-pixel-per-lane kernel that 1
  *                          selected left the tree)
@@ -411,15 +415,15 @@ size_t gsr_struct_bytes(int32_t which); /* 0 GsrForwardArgs, 1 GsrBackwardArgs, 
  *   "tile_sort_max_avg"    (default 700) see "tile_sort"
  *   "blend_balance"        1 (default) = the forward blend places its sub-tile waves by the visits each took at the previous
  *                          render of the same frame (device-side cache of 128 frames per frame size, least recently used out; a
- *                          frame is recognised by GsrForwardArgs::view_id or, without one, by its pose; single renders through
- *                          the default kernel); 0 = dispatch order = tile order.  Same image either way
+ *                          frame is recognised by GsrForwardArgs::view_id or, without one, by its pose; single renders);
+ *                          0 = dispatch order = tile order.  Same image either way
  *   "small_sort9"          (default 1) smallest model for which a forward that runs its own preprocess sorts its depth keys in three
  *                          9-bit passes over the 27-bit window instead of four 8-bit ones (it launches a digit histogram either way);
  *                          0 = only models above 262 144 Gaussians.  Same order either way (a depth beyond the window is detected
  *                          and sorted again on all 32 bits)
  *   "list_cut"             1 (default) = for models of at least "list_cut_min_n" Gaussians (default 2 000 000: where it was measured to pay;
  *                          2 = whatever the size), on the plain direct-binning route (frames of up to 4 096 tiles behind the global depth sort,
- *                          single renders, default blend, "blend_balance" on) the tile lists are WRITTEN only up to where the tiles
+ *                          single renders, "blend_balance" on) the tile lists are WRITTEN only up to where the tiles
  *                          stopped at the previous render of the same frame (the frame is recognised as for "blend_balance"; a tile
  *                          remembers the view depth of the last instance any of its four waves staged, x (1 + "list_cut_margin_e3" /
  *                          1000), rounded up to a chunk of the depth order).  One cut for the frame -- the chunk behind which at
@@ -442,8 +446,10 @@ size_t gsr_struct_bytes(int32_t which); /* 0 GsrForwardArgs, 1 GsrBackwardArgs, 
  *                          (counters "late_checks", "late_mismatches"; "debug_late_bias": tests, falsifies the next remembered count)
  *   "view_pose_tol_e6"     (default 2000 = 2e-3) without a view id a render belongs to the cached frame whose view matrix and
  *                          points_transform are within this, x 1e-6, of its own in every entry (the nearest such frame)
- *   "tile_map"             how tiles are dealt to the eight XCDs: 2 (default) = 2x2 blocks of tiles round-robin, 1 = single
- *                          tiles round-robin (tile t on XCD t % 8), 0 = one contiguous band of tiles per XCD
+ *   "tile_map"             how tiles are dealt to the eight XCDs: 2 = 2x2 blocks of tiles round-robin, the only map of the library, so
+ *                          setting it changes nothing.  Any other value is refused (the single tiles round-robin that 1 selected and
+ *                          the contiguous band of tiles per XCD that 0 selected left the tree).  bench.py --tile-map passes its
+ *                          value on without looking at the return code: with 0 or 1 it now measures the default
  *   "speculative_binning"  1 (default) = R-dependent stages launched against a capacity, R read back late;
  *                          0 = read R, then launch
  *   "binning_capacity_hint" capacity of the NEXT forward, one shot (tests: force the overflow re-run).  The regular hints

@@ -251,9 +251,11 @@ long long hostemu_check_tight_rect(int count, unsigned seed, int W, int H, long 
 
 // Property check for the exact tile culling (gsr_math.h box_accept): whenever ANY pixel centre of a box receives a
 // contribution from the splat by the blend's own rule (pair_alpha: power <= 0 and o exp(power) >= 1/255), box_accept must
-// say yes -- for tiles (the culling of the binning), 16x8 halves (reach bits of the backward) and arbitrary sub-boxes.
+// say yes -- for tiles (the culling of the binning), 16x8 halves (reach bits of the backward), 8x8 blocks (reach bits of the forward
+// blend) and arbitrary sub-boxes.  Boxes are 1..max_side pixels per side: 16 covers all of these and their clamped remainders at the
+// right and bottom edge, 8 draws the forward's blocks and remainders alone.
 // Returns the number of violations (must be 0); *checked = boxes that had a contributing pixel.
-long long hostemu_check_box_accept(int count, unsigned seed, long long* checked)
+long long hostemu_check_box_accept(int count, unsigned seed, int max_side, long long* checked)
 {
     unsigned long long st = seed * 6364136223846793005ull + 1442695040888963407ull;
     auto rnd = [&]() { st = st * 6364136223846793005ull + 1442695040888963407ull; return (float)((st >> 40) & 0xffffff) / 16777216.0f; };
@@ -271,7 +273,7 @@ long long hostemu_check_box_accept(int count, unsigned seed, long long* checked)
         // a box near the 1/255 contour of the splat (that is where a wrong reject would hide)
         const float reach = sqrtf(fmaxf(0.f, 2.f * logf(255.f * op))) * s1;
         const float ang = rnd() * 6.2831853f, dist = reach * (0.6f + 0.8f * rnd());
-        const int bw = 1 + (int)(rnd() * 16.f), bh = 1 + (int)(rnd() * 16.f);
+        const int bw = 1 + (int)(rnd() * (float)max_side), bh = 1 + (int)(rnd() * (float)max_side);
         const float bx0 = floorf(px + dist * cosf(ang)) + 0.5f, by0 = floorf(py + dist * sinf(ang)) + 0.5f;   // pixel centres at k + 0.5
         const float bx1 = bx0 + (float)(bw - 1), by1 = by0 + (float)(bh - 1);
         bool any = false;

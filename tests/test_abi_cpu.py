@@ -144,6 +144,32 @@ def test_options_from_the_environment_at_load():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     ok = subprocess.run([sys.executable, "-c", code], cwd=root, env={**os.environ, "GSR_OPTS": "tile_sort=2, blend_bwd_ppt=2"}, capture_output=True, text=True)
     assert ok.returncode == 0 and "loaded 0" in ok.stdout, ok.stderr[-400:]
-    for bad in ("no_such_option=1", "tile_sort=7", "blend_bwd_ppt=1", "sort_algo=0"):
+    for bad in ("no_such_option=1", "tile_sort=7", "blend_bwd_ppt=1", "sort_algo=0", "blend_fwd_ppt=6", "tile_map=1"):
         r = subprocess.run([sys.executable, "-c", code], cwd=root, env={**os.environ, "GSR_OPTS": bad}, capture_output=True, text=True)
         assert r.returncode != 0 and "GSR_OPTS" in r.stderr, (bad, r.stdout, r.stderr[-400:])
+
+
+def test_forward_flags_of_a_retired_variant_or_map_are_refused():
+    """forward_flags keep their bit layout; the variant field (bits 1..3) holds 7 and the map field (bits 4..5) holds 2, the one forward
+    blend and the one tile -> XCD map.  Flags with bit 0 set that carry another value cannot come from this library: gsr_backward and
+    gsr_importance_accumulate refuse them before anything is enqueued.  The default's flags and flags 0 (the round-1 caller) pass that
+    check and stop at the next one, a missing pointer."""
+    L = importlib.import_module("3dgs_hierarchical_training_amd._lib")
+    lib = L.load()
+    fake = 0x1000          # never dereferenced: every call here is refused by an argument check
+    good = 1 | (7 << 1) | (2 << 4) | (1 << 6) | (1 << 13)
+    b = L.GsrBackwardArgs()
+    b.N, b.M, b.D, b.W, b.H, b.d_means3D = 128, 1, 0, 32, 32, fake
+    a = L.GsrForwardArgs()
+    a.N, a.M, a.D, a.W, a.H = 128, 16, 3, 32, 32
+    a.shs = a.campos = a.geom = a.image = a.out_color = a.means3D = fake
+    out = L.GsrForwardOut()
+    out.num_rendered, out.binning = 10, fake
+    for flags in (good & ~(7 << 1) | (6 << 1), good & ~(7 << 1) | (1 << 1), good & ~(3 << 4) | (1 << 4), good & ~(3 << 4)):
+        b.forward_flags = out.forward_flags = flags
+        assert lib.gsr_backward(C.byref(b), None) == -1 and "forward_flags do not come from gsr_forward" in lib.gsr_last_error().decode()
+        assert lib.gsr_importance_accumulate(C.byref(a), C.byref(out), fake, fake, None) == -1
+        assert "forward_flags do not come from gsr_forward" in lib.gsr_last_error().decode()
+    for flags in (good, 0):
+        b.forward_flags = flags
+        assert lib.gsr_backward(C.byref(b), None) == -1 and "missing workspace / gradient pointer" in lib.gsr_last_error().decode()

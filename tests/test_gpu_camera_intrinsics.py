@@ -93,14 +93,14 @@ def test_parity_vs_oracle_precomputed_covariance_under_real_intrinsics():
 
 
 # option, value, value that restores the default
-ROUTES = [("tile_sort", 0, 1), ("tile_sort", 2, 1), ("direct_binning", 0, 1), ("blend_fwd_ppt", 6, 0), ("blend_fwd_ppt", 7, 0),
+ROUTES = [("tile_sort", 0, 1), ("tile_sort", 2, 1), ("direct_binning", 0, 1), ("blend_fwd_ppt", 7, 0),
           ("deterministic_backward", 1, 0)]
 
 
 @pytest.mark.parametrize("route", ROUTES, ids=lambda r: f"{r[0]}={r[1]}")
 @pytest.mark.parametrize("name", ["both", "far"])
 def test_routes_vs_oracle_under_real_intrinsics(name, route):
-    """Each list-building route, both forward blends and the fixed-order accumulation against the oracle."""
+    """Each list-building route, the forward blend selected explicitly and the fixed-order accumulation against the oracle."""
     lib = L.load()
     opt, val, default = route
     kw, up = parity_inputs(name, SHAPE_A)

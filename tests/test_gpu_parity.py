@@ -170,19 +170,22 @@ def test_parity_color_loss_only(case):
     _run_case(*case, color_only=True)
 
 
-@pytest.mark.parametrize("ppt", [6, 7])
-def test_blend_variants_agree(ppt):
-    """The forward blend with (7, default) and without (6) its sub-tile reach bits -- a conservative skip -- against the oracle.  (The
-    tile-per-workgroup / lane-mask A/B kernels of rounds 1-4 left the tree in round 5: they needed a special build and no default-build
-    test reached them.)"""
+def test_blend_variants_agree():
+    """The forward blend, selected explicitly ("blend_fwd_ppt" 7: one wave per 8x8 sub-tile with its sub-tile reach bits -- a conservative
+    skip), against the oracle; then the option surface of the blend kernels.  (The tile-per-workgroup / lane-mask A/B kernels of rounds
+    1-4 left the tree in round 5, the kernel without reach bits -- 6 -- after it: none was ever the default.)"""
     import importlib
     L = importlib.import_module("3dgs_hierarchical_training_amd._lib")
     lib = L.load()
     try:
-        assert lib.gsr_set_option(b"blend_fwd_ppt", ppt) == 0
+        assert lib.gsr_set_option(b"blend_fwd_ppt", 7) == 0
         _run_case(20000, 330, 250, 3, True, "sh", (0.2, 0.3, 0.1))
     finally:
         lib.gsr_set_option(b"blend_fwd_ppt", 0)
+    # the forward blend has one kernel: its option takes the default's two spellings and refuses the retired ones
+    assert lib.gsr_set_option(b"blend_fwd_ppt", 0) == 0 and lib.gsr_set_option(b"blend_fwd_ppt", 7) == 0
+    for v in (6, 3, 1):
+        assert lib.gsr_set_option(b"blend_fwd_ppt", v) != 0
     assert lib.gsr_set_option(b"blend_fwd_ppt", 3) != 0 and lib.gsr_set_option(b"blend_bwd_ppt", 3) != 0 and lib.gsr_set_option(b"ab_variants", 0) == 0
     # the backward blend has one kernel: its option takes the default's two spellings and refuses the retired one-pixel kernel
     assert lib.gsr_set_option(b"blend_bwd_ppt", 0) == 0 and lib.gsr_set_option(b"blend_bwd_ppt", 2) == 0
@@ -281,18 +284,20 @@ def test_large_splats_take_the_per_wave_emission_path(scale):
     parity.check_grads(out["grads"], ref, f"large splats x{scale}")
 
 
-@pytest.mark.parametrize("tile_map", [0, 1, 2], ids=["banded", "interleaved", "blocks"])
-def test_tile_to_xcd_maps_agree(tile_map):
-    """The three tile -> XCD maps only change which workgroup processes which tile: identical image, parity gradients
-    (335x235: 21 x 15 tiles, odd counts in both directions exercise the padding slots of the 2x2-block map)."""
+def test_tile_to_xcd_maps_agree():
+    """The tile -> XCD map (2x2 blocks of tiles dealt round-robin) only decides which workgroup processes which tile: parity image and
+    gradients at 335x235 -- 21 x 15 tiles, odd counts in both directions exercise the padding slots of the 2x2-block map.  The banded
+    and the single-tile maps (0, 1) have left the library: the option takes 2 and refuses them."""
     import importlib
     L = importlib.import_module("3dgs_hierarchical_training_amd._lib")
     lib = L.load()
     try:
-        assert lib.gsr_set_option(b"tile_map", tile_map) == 0
+        assert lib.gsr_set_option(b"tile_map", 2) == 0
         _run_case(20000, 335, 235, 3, True, "sh", (0.2, 0.3, 0.1))
     finally:
         lib.gsr_set_option(b"tile_map", 2)
+    assert lib.gsr_set_option(b"tile_map", 0) != 0 and lib.gsr_set_option(b"tile_map", 1) != 0
+    assert lib.gsr_set_option(b"tile_map", 2) == 0
 
 
 @pytest.mark.parametrize("N,W,H,posed", [(20000, 320, 240, True), (300000, 980, 545, True), (1000000, 980, 545, False),
@@ -1169,26 +1174,6 @@ def test_backward_twice_over_one_render():
     g1 = torch.autograd.grad(loss, leaves, retain_graph=True)
     g2 = torch.autograd.grad(loss, leaves)
     parity.same_accumulation({str(i): b for i, b in enumerate(g2)}, {str(i): a for i, a in enumerate(g1)}, "second backward vs first")
-
-
-def test_reach_bits_change_nothing_in_the_forward_image():
-    """k_blend_fwd_w6<true> (default) skips the instances whose exact box test fails on the wave's 8x8 block; <false> visits them all:
-    a conservative skip, the images are EQUAL."""
-    import importlib
-    import hip_runner
-    L = importlib.import_module("3dgs_hierarchical_training_amd._lib")
-    lib = L.load()
-    sc = parity.syn.make_scene(300000, 980, 545, sh_degree=3, seed=5, posed=True)
-    kw = parity.scene_kwargs(sc, "sh", bg=(0.3, 0.2, 0.1))
-    outs = {}
-    try:
-        for v in (6, 7):
-            assert lib.gsr_set_option(b"blend_fwd_ppt", v) == 0
-            outs[v] = hip_runner.run_hip(kw)["fwd"]
-    finally:
-        lib.gsr_set_option(b"blend_fwd_ppt", 0)
-    for name, a, b in zip(("color", "radii", "depth", "alpha"), outs[6], outs[7]):
-        assert np.array_equal(a, b), (name, int((a != b).sum()), float(np.abs(a.astype(np.float64) - b).max()))
 
 
 def test_deterministic_backward_debug_mode():

@@ -453,23 +453,6 @@ def test_sequence_targets_and_depths_are_the_full_forwards():
         assert seq.target(f) is target and seq.depth(f) is depth
 
 
-def test_blend_fwd_ppt_6():
-    """Under "blend_fwd_ppt" 6 a render-only call runs the existing kernel without reach bits into scratch planes (the whole image layout,
-    scratch depth / alpha when none were asked, no checkpoint area): the same outputs as the full forward under that option."""
-    lib = L.load()
-    case = Case(parity.syn.make_scene(1024, W, H, sh_degree=3, seed=111, posed=True), "raw")
-    long_case = Case(_long_list_scene(), "sh")
-    try:
-        assert lib.gsr_set_option(b"blend_fwd_ppt", 6) == 0
-        for c, what in ((case, "ppt 6"), (long_case, "ppt 6, long list")):
-            full = c.full()
-            for depth_alpha in (False, True):
-                _same(c.lean(depth_alpha=depth_alpha, clamped=True, visible=True), full, depth_alpha, what)
-    finally:
-        lib.gsr_set_option(b"blend_fwd_ppt", 0)
-    _same(case.lean(depth_alpha=True, clamped=True, visible=True), case.full(), True, "back on the default kernel")
-
-
 def test_exact_and_overflowing_flows():
     """A render-only call as the FIRST forward of its caller (no capacity hint: the exact, read-then-launch flow) and one whose speculative
     capacity is too small (the binning and the blend run again): the flow is checked on the library's counters, the outputs against the

@@ -117,14 +117,18 @@ def test_tight_candidate_rect_never_loses_an_accepted_tile():
 
 
 def test_exact_box_culling_is_conservative():
-    """box_accept -- the test behind the image-preserving tile culling and the backward's reach bits -- may only reject a
-    box in which no pixel centre receives a contribution by the blend's own rule.  600 000 random (splat, box) pairs placed
-    around the splat's 1/255 contour, needles and threshold opacities included."""
+    """box_accept -- the test behind the image-preserving tile culling, the backward's reach bits (16x8 halves) and the 8x8 blocks
+    (reach bits of the forward blend) -- may only reject a box in which no pixel centre receives a contribution by the blend's own
+    rule.  600 000 random (splat, box) pairs placed around the splat's 1/255 contour, needles and threshold opacities included, with
+    boxes of 1..16 pixels per side, and 600 000 more with 1..8 per side: the forward's blocks and their clamped remainders at the right
+    and bottom edge.  This is what holds that the forward's reach bits skip only instances that contribute to no pixel of the block
+    (test_hip_takes_the_host_emulations_decisions holds the kernel against an emulation that has no reach bits)."""
     import ctypes as C
     lib = parity.hostemu_lib()
     lib.hostemu_check_box_accept.restype = C.c_longlong
-    lib.hostemu_check_box_accept.argtypes = [C.c_int, C.c_uint, C.POINTER(C.c_longlong)]
-    for seed in (11, 12, 13):
-        seen = C.c_longlong(0)
-        bad = lib.hostemu_check_box_accept(200000, seed, C.byref(seen))
-        assert bad == 0 and seen.value > 50000, (seed, bad, seen.value)
+    lib.hostemu_check_box_accept.argtypes = [C.c_int, C.c_uint, C.c_int, C.POINTER(C.c_longlong)]
+    for max_side in (16, 8):
+        for seed in (11, 12, 13):
+            seen = C.c_longlong(0)
+            bad = lib.hostemu_check_box_accept(200000, seed, max_side, C.byref(seen))
+            assert bad == 0 and seen.value > 50000, (max_side, seed, bad, seen.value)

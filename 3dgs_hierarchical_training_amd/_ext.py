@@ -247,3 +247,15 @@ def _register_fakes():
         M, dropped = ctx.new_dynamic_size(), ctx.new_dynamic_size()
         return (points.new_empty((M, 3), dtype=torch.float32), points.new_empty((M if colors is not None else 0, 3), dtype=torch.float32),
                 points.new_empty((M,), dtype=torch.int32), dropped)
+
+    @torch.library.register_fake("gsr::camera_from_pose")
+    def _(pose, fx, fy, cx, cy, W, H, znear=0.01, zfar=100.0):
+        f = lambda *s: pose.new_empty(s, dtype=torch.float32)
+        if pose.dim() == 2 and tuple(pose.shape) == (4, 4):
+            return f(4, 4), f(4, 4), f(3)
+        B = pose.shape[0]
+        return f(B, 4, 4), f(B, 4, 4), f(B, 3)
+
+    @torch.library.register_fake("gsr::pose_virtual_view")
+    def _(pose0, pose1, alpha, base=None):
+        return pose0.new_empty((4, 4), dtype=torch.float32), pose0.new_empty((4, 4) if base is not None else (0,), dtype=torch.float32)

@@ -89,6 +89,7 @@ EXPORTS = [
     "gsr_depth_loss_forward_terms_batched",
     "gsr_batch_retire_scratch_bytes", "gsr_batch_retire", "gsr_forward_retire",
     "gsr_depth_to_points", "gsr_voxel_scratch_bytes", "gsr_voxel_down_sample",
+    "gsr_camera_from_pose", "gsr_pose_virtual_view",
 ]
 GSR_DEPTH_LOSS_L1, GSR_DEPTH_LOSS_INVARIANT = 0, 1
 
@@ -167,6 +168,12 @@ def load():
     # (points, colors, N, voxel_size, out_points, out_colors, out_counts, meta, scratch, scratch_bytes, stream)
     lib.gsr_voxel_down_sample.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                           C.c_void_p, C.c_size_t, C.c_void_p]
+    lib.gsr_camera_from_pose.restype = C.c_int
+    # (pose, B, fx, fy, cx, cy, W, H, znear, zfar, viewmatrix, projmatrix, campos, stream)
+    lib.gsr_camera_from_pose.argtypes = [C.c_void_p, C.c_int32] + [C.c_double] * 4 + [C.c_int32, C.c_int32, C.c_double, C.c_double] + [C.c_void_p] * 4
+    lib.gsr_pose_virtual_view.restype = C.c_int
+    # (pose0, pose1, alpha, base, out, out_rel, stream)
+    lib.gsr_pose_virtual_view.argtypes = [C.c_void_p, C.c_void_p, C.c_double] + [C.c_void_p] * 4
     lib.gsr_adam_step.restype = C.c_int
     lib.gsr_adam_step.argtypes = [C.POINTER(GsrAdamTensor), C.c_int32, C.c_float, C.c_float, C.c_float, C.c_int64, C.c_void_p]
     lib.gsr_pose_step.restype = C.c_int

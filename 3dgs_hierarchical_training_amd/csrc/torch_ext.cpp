@@ -25,6 +25,8 @@
 //   gsr::knn_mean_dist2       -> gsr_knn_mean_dist2
 //   gsr::depth_to_points      -> gsr_depth_to_points (a depth map's pixels un-projected, colours gathered beside them)
 //   gsr::voxel_down_sample    -> gsr_voxel_down_sample (voxel-grid means; its read of `meta` is the one host synchronisation)
+//   gsr::camera_from_pose     -> gsr_camera_from_pose (view matrix, full projection and camera centre of up to 16 device poses, one launch)
+//   gsr::pose_virtual_view    -> gsr_pose_virtual_view (the interpolated pose between two device poses, and that pose relative to a base)
 //
 // Registered with TORCH_LIBRARY so the ops are visible to the dispatcher (torch.ops.gsr.*, fake kernels in _ext.py for
 // torch.compile).  An empty tensor (numel 0) stands for "None".  Everything runs on the current HIP stream of the
@@ -1260,6 +1262,55 @@ std::tuple<Tensor, Tensor, Tensor, int64_t> voxel_down_sample(const Tensor& poin
     return {out_points.narrow(0, 0, M), with_colors ? out_colors.narrow(0, 0, M) : out_colors, out_counts.narrow(0, 0, M), h[1]};
 }
 
+// gsr::camera_from_pose -> gsr_camera_from_pose.  pose [4,4] -> ([4,4], [4,4], [3]); pose [B,4,4] or [B,16] -> ([B,4,4], [B,4,4], [B,3]).
+// No autograd: the pose is detached.  No host synchronisation.
+std::tuple<Tensor, Tensor, Tensor> camera_from_pose(const Tensor& pose_, double fx, double fy, double cx, double cy, int64_t W, int64_t H,
+                                                    double znear, double zfar)
+{
+    TORCH_CHECK(pose_.is_cuda(), "camera_from_pose: pose must be on a ROCm/HIP device (no CPU fallback)");
+    const bool single = pose_.dim() == 2 && pose_.size(0) == 4 && pose_.size(1) == 4;
+    TORCH_CHECK(single || (pose_.dim() == 3 && pose_.size(1) == 4 && pose_.size(2) == 4) || (pose_.dim() == 2 && pose_.size(1) == 16),
+                "camera_from_pose: pose is [4,4], [B,4,4] or [B,16]");
+    const int64_t B = single ? 1 : pose_.size(0);
+    TORCH_CHECK(B >= 1 && B <= 16, "camera_from_pose: 1 to 16 poses per call, got ", B);
+    TORCH_CHECK(fx > 0.0 && fy > 0.0 && W > 0 && H > 0 && W < ((int64_t)1 << 31) && H < ((int64_t)1 << 31),
+                "camera_from_pose: fx, fy, W and H must be positive");
+    const c10::hip::HIPGuardMasqueradingAsCUDA guard(pose_.device());
+    const Tensor pose = f32c(pose_.detach());
+    Tensor view = single ? at::empty({4, 4}, pose.options()) : at::empty({B, 4, 4}, pose.options());
+    Tensor proj = at::empty_like(view);
+    Tensor campos = single ? at::empty({3}, pose.options()) : at::empty({B, 3}, pose.options());
+    check(gsr_camera_from_pose(pose.data_ptr<float>(), (int32_t)B, fx, fy, cx, cy, (int32_t)W, (int32_t)H, znear, zfar, view.data_ptr<float>(),
+                               proj.data_ptr<float>(), campos.data_ptr<float>(), c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream()),
+          "gsr_camera_from_pose");
+    return {view, proj, campos};
+}
+
+// gsr::pose_virtual_view -> gsr_pose_virtual_view.  pose0, pose1, base: [4,4] on one device; alpha in [0, 1].  Returns (out [4,4],
+// out_rel [4,4], or an empty tensor without a base).  No autograd, no host synchronisation.
+std::tuple<Tensor, Tensor> pose_virtual_view(const Tensor& pose0_, const Tensor& pose1_, double alpha, const c10::optional<Tensor>& base_)
+{
+    TORCH_CHECK(pose0_.is_cuda() && pose1_.is_cuda() && pose1_.device() == pose0_.device(),
+                "pose_virtual_view: poses must be on one ROCm/HIP device (no CPU fallback)");
+    TORCH_CHECK(pose0_.numel() == 16 && pose1_.numel() == 16, "pose_virtual_view: poses are [4,4]");
+    TORCH_CHECK(alpha >= 0.0 && alpha <= 1.0, "pose_virtual_view: alpha must lie in [0, 1]");
+    const bool with_base = base_.has_value() && base_->defined();
+    const c10::hip::HIPGuardMasqueradingAsCUDA guard(pose0_.device());
+    const Tensor p0 = f32c(pose0_.detach()), p1 = f32c(pose1_.detach());
+    Tensor base;
+    if (with_base) {
+        TORCH_CHECK(base_->is_cuda() && base_->device() == pose0_.device() && base_->numel() == 16,
+                    "pose_virtual_view: base is [4,4] on the poses' device (no CPU fallback)");
+        base = f32c(base_->detach());
+    }
+    Tensor out = at::empty({4, 4}, p0.options());
+    Tensor out_rel = with_base ? at::empty({4, 4}, p0.options()) : at::empty({0}, p0.options());
+    check(gsr_pose_virtual_view(p0.data_ptr<float>(), p1.data_ptr<float>(), alpha, with_base ? base.data_ptr<float>() : nullptr,
+                                out.data_ptr<float>(), with_base ? out_rel.data_ptr<float>() : nullptr,
+                                c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream()), "gsr_pose_virtual_view");
+    return {out, out_rel};
+}
+
 }  // namespace
 
 // ---- the trainer's per-iteration bookkeeping (gsr_masked_max / gsr_densify_stats_add / gsr_psnr; include/gsr.h) ------------------
@@ -1394,6 +1445,9 @@ TORCH_LIBRARY(gsr, m)
     m.def("knn_mean_dist2(Tensor points) -> Tensor");
     m.def("depth_to_points(Tensor depth, Tensor? image, float fx, float fy, float cx, float cy) -> (Tensor, Tensor)");
     m.def("voxel_down_sample(Tensor points, Tensor? colors, float voxel_size) -> (Tensor points, Tensor colors, Tensor counts, int dropped)");
+    m.def("camera_from_pose(Tensor pose, float fx, float fy, float cx, float cy, int W, int H, float znear=0.01, float zfar=100.0) -> "
+          "(Tensor viewmatrix, Tensor projmatrix, Tensor campos)");
+    m.def("pose_virtual_view(Tensor pose0, Tensor pose1, float alpha, Tensor? base=None) -> (Tensor out, Tensor out_rel)");
     m.def("masked_max_(Tensor(a!) dst, Tensor src, Tensor mask) -> ()");
     m.def("densify_stats_add_(Tensor(a!) accum, Tensor(b!) denom, Tensor grad, Tensor mask) -> ()");
     m.def("psnr(Tensor a, Tensor b) -> Tensor");
@@ -1423,6 +1477,8 @@ TORCH_LIBRARY_IMPL(gsr, CUDA, m)   // the dispatch key of HIP tensors on a ROCm 
     m.impl("knn_mean_dist2", &knn_mean_dist2);
     m.impl("depth_to_points", &depth_to_points);
     m.impl("voxel_down_sample", &voxel_down_sample);
+    m.impl("camera_from_pose", &camera_from_pose);
+    m.impl("pose_virtual_view", &pose_virtual_view);
     m.impl("masked_max_", &masked_max_);
     m.impl("densify_stats_add_", &densify_stats_add_);
     m.impl("psnr", &psnr);

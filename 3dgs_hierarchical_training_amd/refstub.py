@@ -128,6 +128,12 @@ class StubGaussians:
             return self.P[self.seq_idx].retr().act(self._xyz.clone())
         return self._xyz
 
+    def get_RT(self, idx=None):              # gaussian_model_ht.py:150-166
+        if getattr(self, "P", None) is None:
+            return torch.eye(4, device=self._xyz.device)
+        p = self.P[0] if self.rotate_xyz else self.P[self.seq_idx if idx is None else idx]
+        return p.retr().matrix().squeeze()
+
     get_scaling = property(lambda s: torch.exp(s._scaling))
     get_rotation = property(lambda s: torch.nn.functional.normalize(s._rotation))
     get_opacity = property(lambda s: torch.sigmoid(s._opacity))
@@ -226,3 +232,181 @@ class StubLoss:
         return {'loss': loss, 'loss_rgb': rgb_full_loss, 'loss_dssim': dssim_loss, 'loss_depth': depth_loss}
 
     __call__ = forward
+
+
+# ---- the frame loader: `GaussianTrainer.load_viewpoint_cam` and the `Camera` it builds per call --------------------------------------------
+# Written from what the reference's loader and camera DO per call (/root/reference/trainer/trainer.py:989-1142,
+# /root/reference/scene/cameras.py:17-101), with this project's helpers and names: the attribute names of the camera are its interface (the
+# trainer, the patched render and the frame cache read them), everything else is this file's own.
+def fov_of_focal(focal, pixels):
+    """Full opening angle of `pixels` seen through a pinhole of focal length `focal` (pixels)."""
+    return 2.0 * math.atan(0.5 * pixels / focal)
+
+
+def frame_to_float_image(frame):
+    """A decoded frame, numpy uint8 [H,W,3], as the float32 [3,H,W] image the trainer works on: scaled to [0,1] in float64 on the host
+    first, narrowed afterwards -- the order (and the cost: a float64 plane per call) of the reference's conversion."""
+    import numpy as np
+    scaled = np.true_divide(frame, 255.0)                       # float64
+    return torch.from_numpy(scaled).movedim(-1, 0).to(torch.float32)
+
+
+def float_image_to_frame(image):
+    """The way back, as the pre-loaded branch takes it on every call: the device image to the host, to 0..255, truncated to uint8."""
+    import numpy as np
+    return (image.movedim(0, -1).cpu().numpy() * 255).astype(np.uint8)
+
+
+def rigid_view_matrix(R, t):
+    """World-to-camera 4x4 of (R, t) after the round trip through its inverse that the reference's view-matrix helper makes (with no
+    recentring the two inversions cancel up to rounding, which is kept): numpy blocks -> float64 work, a float32 array; tensor blocks -> the
+    tensor's own dtype and device."""
+    import numpy as np
+    if torch.is_tensor(R):
+        M = torch.eye(4, dtype=R.dtype, device=R.device)
+        M[:3, :3] = R
+        M[:3, 3] = t
+        return torch.linalg.inv(torch.linalg.inv(M))
+    M = np.eye(4)
+    M[:3, :3] = R
+    M[:3, 3] = t
+    return np.linalg.inv(np.linalg.inv(M)).astype(np.float32)
+
+
+def pinhole_projection_T(K32, W, H, near, far):
+    """The transposed projection of a pinhole with intrinsics K32 (numpy float32 3x3, pixels) over a W x H frame and the depth range
+    [near, far], as a host float32 tensor: x and y scaled by twice the focal length over the frame size and shifted by the principal
+    point's offset from the centre, depth mapped to far / (far - near) * (z - near), w = z.  Entries are formed in float32, like the
+    reference's."""
+    import numpy as np
+    P = np.zeros((4, 4), dtype=np.float32)
+    two = np.float32(2.0)
+    P[0, 0], P[1, 1] = two * K32[0, 0] / W, two * K32[1, 1] / H
+    P[0, 2], P[1, 2] = -(W - two * K32[0, 2]) / W, -(H - two * K32[1, 2]) / H
+    depth_gain = far / (far - near)
+    P[2, 2], P[2, 3] = depth_gain, -near * depth_gain
+    P[3, 2] = 1.0
+    return torch.from_numpy(np.ascontiguousarray(P.T))
+
+
+class StubCameraFull(torch.nn.Module):
+    """Stand-in for the camera `load_viewpoint_cam` builds on every call (the reference's `Camera` in its co3d form): the attributes that
+    class exposes, filled by the same amount of work -- the image clamped on the host, uploaded and multiplied by a plane of ones on the
+    device; the view matrix and the projection built on the host and uploaded; one batched 4x4 product and one 4x4 inverse on the device,
+    whose row read waits for it.  This is the unpatched route the frame cache of `gsr_autopatch` is compared with and timed against."""
+    NEAR, FAR = 0.01, 100.0
+
+    def __init__(self, uid, R, T, fov_xy, image, image_name, intrinsics, device="cuda", vfi=None, alpha_mask=None):
+        import numpy as np
+        super().__init__()
+        self.uid = self.colmap_id = uid
+        self.image_name, self.vfi = image_name, vfi
+        self.R, self.T = R, T
+        self.FoVx, self.FoVy = fov_xy
+        self.intrinsics = np.asarray(intrinsics).astype(np.float32)
+        self.depth = self.optical_flow = self.mask_for_relative_pose = self.mask = None
+        self.znear, self.zfar, self.scale = self.NEAR, self.FAR, 1.0
+        self.trans = torch.zeros(3, dtype=R.dtype, device=R.device) if torch.is_tensor(R) else np.zeros(3)
+        self.data_device = torch.device(device)
+        self._take_image(image, alpha_mask)
+        self._build_matrices()
+        self.focal_x = 0.5 * self.image_width / math.tan(0.5 * self.FoVx)
+        self.focal_y = 0.5 * self.image_height / math.tan(0.5 * self.FoVy)
+
+    def _take_image(self, image, alpha_mask):
+        plane = torch.clamp(image, min=0.0, max=1.0).to(device=self.data_device)
+        self.image_height, self.image_width = int(plane.shape[-2]), int(plane.shape[-1])
+        weight = torch.ones((1, self.image_height, self.image_width), device=self.data_device) if alpha_mask is None \
+            else alpha_mask.to(device=self.data_device)
+        plane.mul_(weight)
+        self.original_image, self.gt_alpha_mask = plane, alpha_mask
+
+    def _build_matrices(self):
+        view = rigid_view_matrix(self.R, self.T)
+        view = view if torch.is_tensor(view) else torch.from_numpy(view).to(device=self.data_device)
+        self.world_view_transform = view.t()
+        self.projection_matrix = pinhole_projection_T(self.intrinsics, self.image_width, self.image_height, self.znear, self.zfar).to(
+            device=self.world_view_transform.device)
+        self.full_proj_transform = torch.bmm(self.world_view_transform[None], self.projection_matrix[None])[0]
+        self.camera_center = torch.linalg.inv(self.world_view_transform)[3, :3]
+
+
+class StubTrainer:
+    """Stand-in for the reference's `GaussianTrainer` as far as its frame loader goes, on frames held as numpy uint8 arrays [H,W,3] (what a
+    decoded image file is; the decode itself and the halving of frames above 1000 pixels have no counterpart here).  data_type 'custom':
+    every call converts the frame to a float image again.  data_type 'preloaded': `data[idx]` is a camera that already holds the float image
+    on the device, and every call copies that image back to the host (for the depth network) and builds a fresh camera around it.
+    `predict_depth` / `predict_vfi` stand for the two networks: a cheap deterministic function each, counted.  Side effects as in the
+    reference: `mono_depth[idx]` and `vfi["i_to_i+1"]` are filled the first time they are asked for."""
+
+    def __init__(self, frames, intrinsic, data_type="custom", device="cuda", near=0.01):
+        import numpy as np
+        if data_type not in ("custom", "preloaded"):
+            raise ValueError("data_type: 'custom' or 'preloaded'")
+        self.data_type, self.device, self.near = data_type, torch.device(device), near
+        self.intrinsic = np.asarray(intrinsic, dtype=np.float64)
+        self.mono_depth, self.vfi, self.rgb_images = {}, {}, {}
+        self.depth_calls = self.vfi_calls = 0
+        frames = [np.ascontiguousarray(f, dtype=np.uint8) for f in frames]
+        self.data = frames if data_type == "custom" else [self._camera(k, None, frame_to_float_image(f)) for k, f in enumerate(frames)]
+
+    # -- the two networks ------------------------------------------------------------------------------------------------------------------
+    def predict_depth(self, frame):
+        self.depth_calls += 1
+        return torch.from_numpy(frame.astype("float32").mean(axis=2) / 255.0 + 1.0)
+
+    def predict_vfi(self, image1, image2):
+        self.vfi_calls += 1
+        return (0.5 * (image1 + image2)).squeeze(0)
+
+    # -- pieces of a call ------------------------------------------------------------------------------------------------------------------
+    def _camera(self, idx, pose, image, trainable=False, vfi=None, like=None):
+        import numpy as np
+        if pose is None:
+            R, t = np.eye(3), np.zeros(3)
+        elif trainable:
+            R, t = pose[:3, :3], pose[:3, 3]                     # tensor blocks: the camera stays differentiable in the pose
+        else:
+            host = pose.numpy()                                  # a host pose is expected here, as in the reference: a device tensor raises
+            R, t = host[:3, :3], host[:3, 3]
+        if like is None:
+            h, w = image.shape[-2:]
+            fov, name, K = (fov_of_focal(self.intrinsic[0, 0], w), fov_of_focal(self.intrinsic[1, 1], h)), f"frame_{idx:05d}", self.intrinsic
+        else:
+            fov, name, K = (like.FoVx, like.FoVy), like.image_name, like.intrinsics
+        return StubCameraFull(idx, R, t, fov, image, name, K, device=self.device, vfi=vfi)
+
+    def _want_depth(self, idx, frame, floor=None):
+        if idx in self.mono_depth:
+            return
+        depth = self.predict_depth(frame)
+        if floor is not None:
+            depth.clamp_(min=floor)
+        self.mono_depth[idx] = depth.to(self.device)
+
+    def _interpolated(self, idx, image):
+        """The in-between image of frames idx and idx + 1, predicted once and kept; a plane of ones behind the last frame."""
+        if idx + 1 >= len(self.data):
+            self.vfi[idx] = torch.ones((3,) + tuple(image.shape[-2:]), device=self.device)
+            return self.vfi[idx]
+        key = f"{idx}_to_{idx + 1}"
+        if key not in self.vfi:
+            pair = [im.to(self.device)[None] for im in (image, self.data[idx + 1].original_image)]
+            self.vfi[key] = self.predict_vfi(*pair).to(self.device)
+        return self.vfi[key]
+
+    # -- the loader ------------------------------------------------------------------------------------------------------------------------
+    def load_viewpoint_cam(self, idx, pose=None, load_depth=False, pose_to_train=False, load_vfi=False):
+        if self.data_type == "custom":
+            frame = self.data[idx]
+            cam = self._camera(idx, pose, frame_to_float_image(frame))            # the conversion, every call
+            if load_depth:
+                self._want_depth(idx, frame)
+            return cam
+        held = self.data[idx]
+        frame = float_image_to_frame(held.original_image)                            # the float image back to the host, every call
+        vfi = self._interpolated(idx, held.original_image) if load_vfi else None
+        cam = self._camera(idx, pose, held.original_image, trainable=pose_to_train is True, vfi=vfi, like=held)
+        if load_depth:
+            self._want_depth(idx, frame, floor=self.near)
+        return cam

@@ -54,8 +54,9 @@ if __package__ in (None, ""):      # executed as a script: make the oddly named 
     pose_mod = importlib.import_module("3dgs_hierarchical_training_amd.pose")
     host_mod = importlib.import_module("3dgs_hierarchical_training_amd.host")
     stage_a = importlib.import_module("3dgs_hierarchical_training_amd.stage_a")
+    cameras = importlib.import_module("3dgs_hierarchical_training_amd.cameras")
 else:
-    from . import densify, hierarchy, segments, sequence
+    from . import cameras, densify, hierarchy, segments, sequence
     from . import host as host_mod
     from . import stage_a
     from . import pose as pose_mod
@@ -101,6 +102,9 @@ class HTConfig:
                                                 # batch waits for all its models); 'device' = each model retires at its own iteration, on the device
     stage_a_init: str = "pixels"                # a stage-A model's initialisation: 'pixels' = sequence.pixel_scene (a strided pixel grid, built on the
                                                 # host); 'voxels' = sequence.depth_scene (every pixel, voxel grid 0.01, create_from_pcd: the reference's, on the device)
+    device_cameras: bool = False                # phase 1's virtual views from poses kept on the device: cameras.virtual_view + settings_from_pose, two
+                                                # launches per view instead of host matrix work and eight uploads; a camera may differ from the host
+                                                # route's in the last float32 bit, so the default stays the host route
     fit_pose: bool = False                      # refine each frame's pose while training on it (training_setup(fit_pose=True), :733)
     pose_lr: float = 1e-5                       # Adam with eps 1e-15 moves a pose by ~lr per step whatever the gradient: on these
                                                 # frames (1-2 px of motion per frame) 5e-6..2e-5 gains 0.4-0.6 dB over fixed stage-A
@@ -173,6 +177,15 @@ class RankRunner:
         st = self.seq.settings_for_pose(pose)
         cache[f] = (pose, st)
         return st
+
+    def _device_pose(self, seg: Segment, f: int) -> torch.Tensor:
+        """Frame f's pose on the device, uploaded once per pose object (cfg.device_cameras)."""
+        cache = seg.__dict__.setdefault("_device_poses", {})
+        pose = seg.poses[f]
+        hit = cache.get(f)
+        if hit is None or hit[0] is not pose:
+            hit = cache[f] = (pose, pose.detach().float().contiguous().to(self.dev))
+        return hit[1]
 
     def _importance_views(self, seg: Segment):
         fr = seg.frames
@@ -306,10 +319,18 @@ class RankRunner:
                     f -= 1
                 if f + 1 not in seg.poses:
                     continue
-                p = pose_mod.interpolate_pose(seg.poses[f], seg.poses[f + 1], alpha)     # get_virtual_view, :462-479
                 teacher = next((t for t in self.teachers[::-1] if f >= t["start_fidx"] and f in t["frames"]), None)
                 if teacher is None:
                     raise ValueError(f"frame {f} belongs to no child")
+                if cfg.device_cameras:       # the view and its teacher-relative twin in one launch, a camera each in one more; nothing on the host
+                    p, p_wrt_teacher = cameras.virtual_view(self._device_pose(seg, f), self._device_pose(seg, f + 1), alpha,
+                                                            base=self._device_pose(seg, teacher["start_fidx"]))
+                    st_teacher = self.seq.settings_for_pose(p_wrt_teacher)
+                    pseudo = self.teacher_render_fn(teacher["seg"], ts.with_sh_degree(st_teacher, teacher["sh_degree"]) if self.step_fn is None else st_teacher)
+                    self._step(seg, self.seq.settings_for_pose(p), pseudo)
+                    virtual += 1
+                    continue
+                p = pose_mod.interpolate_pose(seg.poses[f], seg.poses[f + 1], alpha)     # get_virtual_view, :462-479
                 p_wrt_teacher = p @ torch.linalg.inv(seg.poses[teacher["start_fidx"]])    # :874
                 pseudo = self.teacher_render_fn(teacher["seg"], ts.with_sh_degree(self.seq.settings_for_pose(p_wrt_teacher), teacher["sh_degree"])
                                                 if self.step_fn is None else self.seq.settings_for_pose(p_wrt_teacher))
@@ -517,6 +538,9 @@ def main():
     ap.add_argument("--stage-a-init", choices=("pixels", "voxels"), default="pixels",
                     help="a stage-A model's initialisation: pixels = one Gaussian per strided pixel, built on the host (default); voxels = every "
                          "pixel un-projected, voxel grid of 0.01, create_from_pcd -- the reference's initialisation, built on the device")
+    ap.add_argument("--device-cameras", action="store_true",
+                    help="phase 1's virtual views from poses kept on the device (cameras.virtual_view + settings_from_pose: two launches per view, no "
+                         "host matrix work or uploads); a camera may differ from the host route's in the last float32 bit.  Default: the host route")
     ap.add_argument("--one-device", action="store_true", help="every rank on cuda:0 (with --backend gloo: the multi-process walk on a "
                                                               "one-GPU box; messages are staged through host memory)")
     ap.add_argument("--ranks", type=int, default=0, help="as a BARE command (WORLD_SIZE unset): start this many ranks of this very script "
@@ -531,7 +555,8 @@ def main():
         return launch_check(a)
     cfg = HTConfig(frames=a.frames, width=a.width, height=a.height, gt_gaussians=a.gt_gaussians, leaf_gaussians=a.leaf_gaussians,
                    leaf_iters_per_frame=a.leaf_iters, phase1_iters_per_frame=a.phase1_iters, phase2_iters_per_frame=[a.phase2_iters] * 3,
-                   importance_views=a.importance_views, densify=a.densify, fit_pose=a.fit_pose, stage_a_batch=a.stage_a_batch, stage_a_lambda_depth=a.stage_a_lambda_depth, stage_a_early_exit=a.stage_a_early_exit, stage_a_init=a.stage_a_init, sh_up_every=a.sh_up_every)
+                   importance_views=a.importance_views, densify=a.densify, fit_pose=a.fit_pose, stage_a_batch=a.stage_a_batch, stage_a_lambda_depth=a.stage_a_lambda_depth, stage_a_early_exit=a.stage_a_early_exit, stage_a_init=a.stage_a_init, sh_up_every=a.sh_up_every,
+                   device_cameras=a.device_cameras)
     if a.pose_lr is not None:
         cfg.pose_lr = a.pose_lr
     if not torch.cuda.is_available():

@@ -59,7 +59,19 @@ class FrameSequence:
     # ---- cameras ---------------------------------------------------------------------------------------------------
     def settings_for_pose(self, pose_w2c: torch.Tensor, bg=None) -> GaussianRasterizationSettings:
         """Raster settings of a camera whose world-to-camera transform is `pose_w2c` ([4,4], in whatever coordinate
-        system the model being rendered lives in)."""
+        system the model being rendered lives in).  A pose on the device stays there: its camera comes from one kernel launch
+        (cameras.settings_from_pose) and may differ from the host route's in the last float32 bit; a host pose takes the host route."""
+        if pose_w2c.is_cuda:
+            from . import cameras
+            tpl = self.__dict__.get("_device_template")
+            if tpl is None:      # size, field of view and a zero background: host numbers, made once
+                cam = syn.make_camera(self.W, self.H)
+                tpl = self._device_template = GaussianRasterizationSettings(
+                    image_height=self.H, image_width=self.W, tanfovx=cam["tanfovx"], tanfovy=cam["tanfovy"],
+                    bg=torch.zeros(3, device=self.device), scale_modifier=1.0, viewmatrix=None, projmatrix=None, sh_degree=self.sh_degree,
+                    campos=None, prefiltered=False, debug=False), (cam["fx"], cam["fy"], 0.5 * self.W, 0.5 * self.H)
+            st = cameras.settings_from_pose(tpl[0], pose_w2c, intrinsics=tpl[1])
+            return st if bg is None else st._replace(bg=bg.to(self.device))
         p = pose_w2c.detach().float().cpu()
         cam = syn.make_camera(self.W, self.H, R=p[:3, :3], t=p[:3, 3])
         d = self.device

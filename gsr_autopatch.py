@@ -55,6 +55,18 @@ Importing this module BEFORE the trainer swaps both for the HIP kernels of this 
     and reads neither).  `compute_cov3D_python`, an override colour, `convert_SHs_python` without `view_dependent`, an unknown pose
     object, CPU tensors or an unexpected layout run the ORIGINAL method; `GSR_AUTOPATCH_IMPORTANCE=0` leaves the method alone.
 
+  * `trainer.trainer.GaussianTrainer.load_viewpoint_cam` (patched when that module is imported, now or later): the frame loader the trainer
+    calls before EVERY iteration (/root/reference/trainer/trainer.py:989-1142) converts the frame's image again and builds a new `Camera`
+    (/root/reference/scene/cameras.py:17-101: an upload of the image, a multiply, three small uploads, a `bmm`, an `inverse()` that waits for
+    the device) on every call.  Patched, the FIRST call for a frame runs the original and keeps, per trainer and on the device, the
+    original's `original_image` tensor itself and the camera's pose-independent fields; later calls return a `Camera` assembled without
+    `Camera.__init__` -- identity cameras from cached tensors, posed ones from one launch of gsr_camera_from_pose.  Calls with work the
+    cache cannot know (`pose_to_train=True`, `load_depth` / `load_vfi` whose result is not in `mono_depth` / `vfi` yet), a frame whose
+    cached image somebody wrote into, and frames beyond `GSR_AUTOPATCH_FRAMES_MB` (default 16384) run the original.
+    `HTGaussianModel.get_RT` returns a `DevicePose`, a tensor subclass whose `.cpu()` is itself, so that the trainer's
+    `get_RT(fidx).detach().cpu()` no longer waits for the device; `.numpy()`, an operation with a genuine CPU tensor and the original
+    loader get the host values at the old cost.  `GSR_AUTOPATCH_FRAMES=0` leaves both methods alone.
+
 `apply()` / `remove()` switch the patches on and off (importing the module calls `apply()`); `GSR_AUTOPATCH=0` disables them.
 The rasterizer itself needs no patch: `diff_gaussian_rasterization` IS this library's drop-in package.
 """
@@ -62,6 +74,7 @@ import importlib
 import importlib.abc
 import importlib.machinery
 import math
+import numbers
 import os
 import sys
 
@@ -78,6 +91,8 @@ _patched_loss_classes = []          # [(class, original forward)]
 LOSS_MODULES = ("trainer.losses",)
 RENDER_MODULES = ("scene.gaussian_model_ht",)
 TRAINER_MODULES = ("trainer.ht3dgs_trainer",)
+FRAME_MODULES = ("trainer.trainer",)
+_patched_frame_classes = []         # [(class, attribute, original function)]: GaussianTrainer.load_viewpoint_cam, HTGaussianModel.get_RT
 _patched_trainer_classes = []       # [(class, attribute, original attribute as found in the class __dict__)]
 _patched_render_classes = []        # [(class, attribute, original function)]
 RAW_NAMES = ("_xyz", "_features_dc", "_features_rest", "_opacity", "_scaling", "_rotation")
@@ -600,6 +615,179 @@ def _patch_render_module(mod):
         setattr(cls, attr, fn)
 
 
+# ---- GaussianTrainer.load_viewpoint_cam: the frame cache; HTGaussianModel.get_RT: poses that stay on the device ---------------------------
+class DevicePose(torch.Tensor):
+    """What the patched `HTGaussianModel.get_RT` returns: the pose tensor itself (same storage, same autograd history) under a type whose
+    `.cpu()` returns the object unchanged -- the trainer's `get_RT(fidx).detach().cpu()` (ht3dgs_trainer.py:539, :559, :615, :897 ...) then
+    waits for nothing, and the patched `load_viewpoint_cam` takes the pose where it is.  `.detach()` and indexing keep the type; `.numpy()` /
+    `np.asarray` deliver the host values (one copy, the wait the reference had); any torch function that also takes a genuine CPU tensor
+    (`pose_dict[...].cpu() @ pose` with a `pose_dict` loaded from a file, ht3dgs_trainer.py:561) sees the pose as the CPU tensor the
+    reference would have had; a function of DevicePoses alone (the same statement with the `pose_dict` stage A filled from `get_RT()`)
+    returns a DevicePose; everything else -- a pose combined with a plain device tensor -- sees the plain tensor."""
+
+    @classmethod
+    def __torch_function__(cls, func, types, args=(), kwargs=None):
+        kwargs = kwargs or {}
+        me = args[0] if args else None
+        if isinstance(me, DevicePose):
+            if func is torch.Tensor.cpu:
+                return me
+            if func in (torch.Tensor.detach, torch.Tensor.__getitem__):
+                with torch._C.DisableTorchFunctionSubclass():
+                    out = func(*args, **kwargs)
+                    return out.as_subclass(DevicePose) if isinstance(out, torch.Tensor) else out
+            if func in (torch.Tensor.numpy, torch.Tensor.__array__):
+                with torch._C.DisableTorchFunctionSubclass():
+                    return func(me.as_subclass(torch.Tensor).detach().cpu(), *args[1:], **kwargs)
+        from torch.utils._pytree import tree_map
+        with torch._C.DisableTorchFunctionSubclass():
+            flat = []
+            tree_map(lambda a: flat.append(a) if isinstance(a, torch.Tensor) else None, (args, kwargs))
+            to_host = any(not isinstance(a, DevicePose) and a.device.type == "cpu" for a in flat)
+
+            def plain(a):
+                if isinstance(a, DevicePose):
+                    a = a.as_subclass(torch.Tensor)
+                    return a.cpu() if to_host else a
+                return a
+            only_poses = bool(flat) and all(isinstance(a, DevicePose) for a in flat)
+            args, kwargs = tree_map(plain, (args, kwargs))
+            out = func(*args, **kwargs)
+            # poses combined with poses alone stay poses: `pose_dict[...]` holds `get_RT().detach()` results (ht3dgs_trainer.py:379-380,
+            # :424-428), so `pose_dict[...].detach().cpu() @ pose_train` (:561) is such a product -- a CPU tensor in the reference; here a
+            # DevicePose, which `.numpy()`, the patched loader and the original loader's hand-over all take
+            return out.as_subclass(DevicePose) if only_poses and type(out) is torch.Tensor else out
+
+
+def get_RT_device(self, idx=None):
+    """Drop-in body of `HTGaussianModel.get_RT` (/root/reference/scene/gaussian_model_ht.py:150-166): the original's tensor as a
+    `DevicePose`."""
+    orig = next((f for c, a, f in _patched_frame_classes if a == "get_RT" and isinstance(self, c)), None)
+    if orig is None:
+        raise RuntimeError("gsr_autopatch.get_RT_device: needs the original HTGaussianModel.get_RT")
+    out = orig(self, idx)
+    return out.as_subclass(DevicePose) if type(out) is torch.Tensor else out
+
+
+def _plain_pose(pose):
+    with torch._C.DisableTorchFunctionSubclass():
+        return pose.as_subclass(torch.Tensor) if isinstance(pose, DevicePose) else pose
+
+
+def _frame_budget_bytes() -> int:
+    return int(float(os.environ.get("GSR_AUTOPATCH_FRAMES_MB", "16384")) * (1 << 20))
+
+
+_FRAME_FIELDS = ("uid", "colmap_id", "FoVx", "FoVy", "image_name", "intrinsics", "depth", "optical_flow", "mask_for_relative_pose", "mask",
+                 "data_device", "image_width", "image_height", "gt_alpha_mask", "zfar", "znear", "trans", "scale", "projection_matrix", "focal_x",
+                 "focal_y")
+
+
+def _frame_entry(cam):
+    """What is kept of a camera the original loader built, or None when it is not the camera the cache can hand out again (no device
+    image, fields missing, a projection the kernel does not restate)."""
+    image = getattr(cam, "original_image", None)
+    if not isinstance(cam, torch.nn.Module) or type(image) is not torch.Tensor or image.dim() != 3 or (_REQUIRE_CUDA and not image.is_cuda):
+        return None
+    if any(not hasattr(cam, k) for k in _FRAME_FIELDS) or getattr(cam, "gt_alpha_mask", None) is not None:
+        return None
+    K = cam.intrinsics
+    try:
+        fx, fy, cx, cy = float(K[0, 0]), float(K[1, 1]), float(K[0, 2]), float(K[1, 2])
+    except Exception:
+        return None
+    if not (fx > 0 and fy > 0) or tuple(cam.projection_matrix.shape) != (4, 4) or cam.projection_matrix.device != image.device:
+        return None
+    return {"cls": type(cam), "image": image, "version": image._version, "bytes": image.numel() * image.element_size(),
+            "fields": {k: getattr(cam, k) for k in _FRAME_FIELDS}, "K": (fx, fy, cx, cy), "identity": None}
+
+
+def _camera_from_entry(e, R, T, view, full, center, vfi):
+    """A `Camera` with the attributes `Camera.__init__` sets (cameras.py:35-103), without running it."""
+    cam = object.__new__(e["cls"])
+    torch.nn.Module.__init__(cam)
+    for k, v in e["fields"].items():
+        setattr(cam, k, v)
+    cam.R, cam.T, cam.vfi = R, T, vfi
+    cam.original_image = e["image"]
+    cam.world_view_transform, cam.full_proj_transform, cam.camera_center = view, full, center
+    return cam
+
+
+def load_viewpoint_cam_cached(self, idx, pose=None, load_depth=False, pose_to_train=False, load_vfi=False):
+    """Drop-in body of `GaussianTrainer.load_viewpoint_cam` (/root/reference/trainer/trainer.py:989-1142): same arguments, a camera with the
+    same attributes.  See the module docstring for what is cached and what runs the original."""
+    orig = next((f for c, a, f in _patched_frame_classes if a == "load_viewpoint_cam" and isinstance(self, c)), None)
+    if orig is None:
+        raise RuntimeError("gsr_autopatch.load_viewpoint_cam_cached: needs the original GaussianTrainer.load_viewpoint_cam")
+
+    def original():
+        # the reference's own statements, on the host pose they were written for (a DevicePose is copied down here: the old cost)
+        # and so is any other device tensor, unless the call asks for a camera that stays differentiable in the pose it was given
+        host = pose
+        if isinstance(pose, DevicePose):
+            host = _plain_pose(pose).cpu()
+        elif isinstance(pose, torch.Tensor) and pose.device.type != "cpu" and not pose_to_train:
+            host = pose.detach().cpu()
+        return orig(self, idx, pose=host, load_depth=load_depth, pose_to_train=pose_to_train, load_vfi=load_vfi)
+
+    # the trainable-pose camera, a pose or an index this loader does not recognise: the original, nothing kept
+    if pose_to_train or not isinstance(idx, numbers.Integral) or \
+            (pose is not None and not (isinstance(pose, torch.Tensor) and tuple(pose.shape) == (4, 4))):
+        return original()
+    # work the cache cannot know -- the original's side effects, `mono_depth[idx]` and `vfi[...]` not there yet: the original runs (and its
+    # frame is kept like any first call's)
+    side_effects = bool(load_depth) and idx not in getattr(self, "mono_depth", {})
+    vfi_key = f"{idx}_to_{idx + 1}"
+    if load_vfi and not (idx + 1 < len(self.data) and vfi_key in getattr(self, "vfi", {})):
+        side_effects = True
+    frames = self.__dict__.setdefault("_gsr_frames", {"entries": {}, "bytes": 0})
+    e = frames["entries"].get(idx)
+    if e is not None and e["image"]._version != e["version"]:        # somebody wrote into the cached plane: rebuild it from the original
+        frames["bytes"] -= e["bytes"]
+        del frames["entries"][idx]
+        e = None
+    if e is None or side_effects or (pose is None and e["identity"] is None):
+        cam = original()
+        if e is None:
+            e = _frame_entry(cam)
+            if e is None or frames["bytes"] + e["bytes"] > _frame_budget_bytes():
+                return cam                                           # not a frame the cache holds (or no room): the original path, every time
+            frames["entries"][idx] = e
+            frames["bytes"] += e["bytes"]
+        if pose is None:                                             # (the identity camera's tensors do not depend on the frame's image)
+            e["identity"] = (cam.R, cam.T, cam.world_view_transform, cam.full_proj_transform, cam.camera_center)
+        if cam.original_image is not e["image"]:                     # (a second original call made a second plane: hand out the kept one)
+            cam.original_image = e["image"]
+        return cam
+    vfi = self.vfi[vfi_key] if load_vfi else None                    # a vfi image that is there is attached as the original does
+    if pose is None:
+        R, T, view, full, center = e["identity"]
+        return _camera_from_entry(e, R, T, view, full, center, vfi)
+    p = _plain_pose(pose).detach()
+    dev = e["image"].device
+    if p.device != dev or p.dtype != torch.float32:                  # a host pose: one small upload, then the kernel as for a device pose
+        p = p.to(device=dev, dtype=torch.float32)
+    fx, fy, cx, cy = e["K"]
+    f = e["fields"]
+    view, full, center = _ops().camera_from_pose(p, fx, fy, cx, cy, int(f["image_width"]), int(f["image_height"]), float(f["znear"]), float(f["zfar"]))
+    # R, T: numpy blocks of a host pose, as the original keeps them; views of a device pose (a DevicePose's deliver numpy on `.numpy()`)
+    keep = pose.detach()
+    R, T = (keep[:3, :3].numpy(), keep[:3, 3].numpy()) if type(pose) is torch.Tensor and pose.device.type == "cpu" else (keep[:3, :3], keep[:3, 3])
+    return _camera_from_entry(e, R, T, view, full, center, vfi)
+
+
+def _patch_frames_module(mod):
+    if os.environ.get("GSR_AUTOPATCH_FRAMES", "1") == "0":
+        return
+    for cname, attr, fn in (("GaussianTrainer", "load_viewpoint_cam", load_viewpoint_cam_cached), ("HTGaussianModel", "get_RT", get_RT_device)):
+        cls = getattr(mod, cname, None)
+        if cls is None or not hasattr(cls, attr) or any(c is cls and a == attr for c, a, _ in _patched_frame_classes):
+            continue
+        _patched_frame_classes.append((cls, attr, getattr(cls, attr)))
+        setattr(cls, attr, fn)
+
+
 # ---- utils.image_utils.psnr: the training PSNR the trainer evaluates on every iteration (ht3dgs_trainer.py:138) ---------------------
 IMAGE_UTILS_MODULES = ("utils.image_utils",)
 _patched_psnr = []                  # [(module, attribute, original function)]
@@ -642,16 +830,23 @@ def _patch_loss_module(mod):
     cls.forward = loss_forward
 
 
+def _patch_render_and_pose_module(mod):
+    """`scene.gaussian_model_ht` holds both the render wrapper and `HTGaussianModel.get_RT`."""
+    _patch_render_module(mod)
+    _patch_frames_module(mod)
+
+
 class _PostImportFinder(importlib.abc.MetaPathFinder):
-    """Patches `trainer.losses` / `scene.gaussian_model_ht` / `utils.image_utils` / `trainer.ht3dgs_trainer` right after they have
+    """Patches `trainer.losses` / `scene.gaussian_model_ht` / `utils.image_utils` / `trainer.ht3dgs_trainer` / `trainer.trainer` right after they have
     been executed, whenever that import happens."""
 
     def find_spec(self, fullname, path, target=None):
         if (fullname not in LOSS_MODULES and fullname not in RENDER_MODULES and fullname not in IMAGE_UTILS_MODULES
-                and fullname not in TRAINER_MODULES) or not _applied:
+                and fullname not in TRAINER_MODULES and fullname not in FRAME_MODULES) or not _applied:
             return None
-        patch = _patch_loss_module if fullname in LOSS_MODULES else _patch_render_module if fullname in RENDER_MODULES \
-            else _patch_trainer_module if fullname in TRAINER_MODULES else _patch_image_utils_module
+        patch = _patch_loss_module if fullname in LOSS_MODULES else _patch_render_and_pose_module if fullname in RENDER_MODULES \
+            else _patch_trainer_module if fullname in TRAINER_MODULES else _patch_frames_module if fullname in FRAME_MODULES \
+            else _patch_image_utils_module
         for finder in sys.meta_path:
             if finder is self or not hasattr(finder, "find_spec"):
                 continue
@@ -689,7 +884,10 @@ def apply():
             _patch_loss_module(sys.modules[name])
     for name in RENDER_MODULES:
         if name in sys.modules:
-            _patch_render_module(sys.modules[name])
+            _patch_render_and_pose_module(sys.modules[name])
+    for name in FRAME_MODULES:
+        if name in sys.modules:
+            _patch_frames_module(sys.modules[name])
     for name in IMAGE_UTILS_MODULES:
         if name in sys.modules:
             _patch_image_utils_module(sys.modules[name])
@@ -718,6 +916,9 @@ def remove():
         setattr(mod, attr, fn)
     while _patched_trainer_classes:
         cls, attr, fn = _patched_trainer_classes.pop()
+        setattr(cls, attr, fn)
+    while _patched_frame_classes:
+        cls, attr, fn = _patched_frame_classes.pop()
         setattr(cls, attr, fn)
 
 

@@ -378,7 +378,8 @@ const char* gsr_last_error(void);
  * 115: the frozen call of gsr_backward (camera / transform gradients alone, see GsrBackwardArgs); no struct changed.
  * 116: GsrForwardArgs ends with render_only (the render-only call).
  * 117: the retire table: gsr_forward_retire, GsrBackwardArgs ends with retired_at, retire_step, gsr_batch_retire; GsrForwardArgs unchanged.
- * 118: gsr_depth_to_points, gsr_voxel_scratch_bytes, gsr_voxel_down_sample; no struct changes (gsr_struct_bytes as in 117). */
+ * 118: gsr_depth_to_points, gsr_voxel_scratch_bytes, gsr_voxel_down_sample; no struct changes (gsr_struct_bytes as in 117).
+ * 119: gsr_camera_from_pose, gsr_pose_virtual_view; no struct changes. */
 int gsr_version(void);
 size_t gsr_struct_bytes(int32_t which); /* 0 GsrForwardArgs, 1 GsrBackwardArgs, 2 GsrForwardOut; anything else 0 */
 
@@ -704,6 +705,38 @@ size_t gsr_voxel_scratch_bytes(int64_t N);
 int    gsr_voxel_down_sample(const float* points /*[N,3]*/, const float* colors /*[N,3] or NULL*/, int64_t N, double voxel_size,
                              float* out_points /*[N,3] capacity*/, float* out_colors /*[N,3] or NULL*/, int32_t* out_counts /*[N] or NULL*/,
                              int64_t* meta /*device, 4 x int64: M, dropped, status, 0*/, void* scratch, size_t scratch_bytes, void* stream);
+
+/* ---- cameras from device poses (version 119) ---------------------------------------------------------------------------------------------
+ * Both entries are one launch of one wave, fully asynchronous on `stream`, float64 inside with ONE rounding to float32 per output, and
+ * evaluated without multiply-add contraction in the operation order written here (csrc/camera_kernels.hip), so that the same statements in
+ * host float64 give the same bits wherever no sin / cos / acos is involved.  4x4 matrices are row-major float32.
+ *
+ * gsr_camera_from_pose -- replaces the matrices `Camera(is_co3d=True)` builds per call (/root/reference/scene/cameras.py:76-98: the
+ * transpose at :78-80, the projection at :83-91, the `bmm` at :97 and the `inverse()` at :98, which waits for the device) behind
+ * `load_viewpoint_cam(idx, pose)` (/root/reference/trainer/trainer.py:1098-1132).  pose[b] = world-to-camera, last row (0,0,0,1), b < B:
+ *   viewmatrix[b][i][j] = pose[b][j][i]                                  (world_view_transform; a copy)
+ *   P = [[2 fx / W, 0, -(W - 2 cx) / W, 0], [0, 2 fy / H, -(H - 2 cy) / H, 0], [0, 0, zfar / (zfar - znear), -(zfar znear) / (zfar - znear)],
+ *        [0, 0, 1, 0]]  in float64 from the arguments as given (the reference rounds these entries to float32 first: its full projection
+ *        may differ from this one in the last float32 bit)
+ *   projmatrix[b][i][j] = ((pose[0][i] P[j][0] + pose[1][i] P[j][1]) + pose[2][i] P[j][2]) + pose[3][i] P[j][3]     (full_proj_transform)
+ *   campos[b][i] = -(((adj[i][0] t0 + adj[i][1] t1) + adj[i][2] t2) / det),  A = pose[:3,:3], t = pose[:3,3], adj = the adjugate of A,
+ *        det = (A00 adj00 + A01 adj10) + A02 adj20                        (camera_center = -A^-1 t; A need not be orthonormal)
+ * GSR_ERR_ARG (before anything is enqueued): a NULL pointer, B < 1 or B > 16, W or H not positive, fx or fy not positive, a non-finite
+ * intrinsic or plane, zfar == znear.
+ *
+ * gsr_pose_virtual_view -- replaces `get_virtual_view` (/root/reference/trainer/ht3dgs_trainer.py:462-479) and, with `base`, the
+ * teacher-relative pose of :878.  Poses are taken as rigid 3x4 blocks (the last row of every output is written as (0,0,0,1)):
+ *   rel = pose0^-1 pose1 (inverse by the adjugate);  phi = Log of its rotation: theta = acos(clamp((trace - 1) / 2)), phi = k w with
+ *   w = the half antisymmetric part, k = theta / sin(theta), or 1 + theta^2 / 6 below theta = 1e-4;  tau = V(phi)^-1 t (adjugate);
+ *   out = pose0 Exp(alpha (tau, phi)), Exp = (R, V tau') with R = I + a K + b K^2, V = I + b K + c K^2, a = sin t / t, b = (1 - cos t) / t^2,
+ *   c = (t - sin t) / t^3, or their two-term series below t^2 = 1e-8 (the switches of pose.py);  out_rel = out base^-1.
+ * base and out_rel are given BOTH or NEITHER.  alpha = 0 returns pose0 bit for bit.
+ * GSR_ERR_ARG (before anything is enqueued): pose0, pose1 or out NULL, base without out_rel or the reverse, alpha outside [0, 1] or NaN. */
+int gsr_camera_from_pose(const float* pose /*[B,16]*/, int32_t B, double fx, double fy, double cx, double cy, int32_t W, int32_t H,
+                         double znear, double zfar, float* viewmatrix /*[B,16]*/, float* projmatrix /*[B,16]*/, float* campos /*[B,3]*/,
+                         void* stream);
+int gsr_pose_virtual_view(const float* pose0 /*[16]*/, const float* pose1 /*[16]*/, double alpha, const float* base /*[16] or NULL*/,
+                          float* out /*[16]*/, float* out_rel /*[16] or NULL*/, void* stream);
 
 /* Measurement hook (bench.py roofline.peak_measured): float4 streaming copy of `bytes` bytes (a multiple of 16, 16-byte aligned
  * pointers) with `blocks` workgroups of 256 threads.  variant 0 = plain loads / stores, 1 = nt bit, 2 = four loads in flight per

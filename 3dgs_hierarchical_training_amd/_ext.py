@@ -259,3 +259,12 @@ def _register_fakes():
     @torch.library.register_fake("gsr::pose_virtual_view")
     def _(pose0, pose1, alpha, base=None):
         return pose0.new_empty((4, 4), dtype=torch.float32), pose0.new_empty((4, 4) if base is not None else (0,), dtype=torch.float32)
+
+    @torch.library.register_fake("gsr::resize_plan")
+    def _(flags):
+        return (flags.new_empty((lib.gsr_resize_plan_bytes(int(flags.shape[0])) // 4,), dtype=torch.int32),
+                flags.new_empty((L.GSR_RESIZE_META_WORDS,), dtype=torch.int64))
+
+    @torch.library.register_fake("gsr::resize_apply")
+    def _(plan, meta, N, nA, nB, nC, nSplit, src, kinds, child, check=False):
+        return [t.new_empty((nA + nB + 2 * nC,) + tuple(t.shape[1:])) for t in src]

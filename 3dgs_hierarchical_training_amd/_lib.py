@@ -73,6 +73,17 @@ class GsrAdamTensor(C.Structure):
                 ("n", C.c_uint64), ("lr", C.c_float)]
 
 
+class GsrResizeTensor(C.Structure):
+    _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("child", C.c_void_p), ("row_bytes", C.c_int64), ("kind", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+# include/gsr.h, version 120: flag bits, tensor kinds, the words of `meta`, the segments of the plan
+GSR_RESIZE_KEEP, GSR_RESIZE_CLONE, GSR_RESIZE_SPLIT, GSR_RESIZE_CHILD = 1, 2, 4, 8
+GSR_RESIZE_PARAM, GSR_RESIZE_MOMENT, GSR_RESIZE_CHILD_SOURCED = 0, 1, 2
+GSR_RESIZE_MAX_TENSORS, GSR_RESIZE_META_WORDS, GSR_RESIZE_META_STATUS, GSR_RESIZE_PLAN_SEGMENTS = 18, 8, 4, 5
+GSR_RESIZE_PLAN_ROWS_A, GSR_RESIZE_PLAN_ROWS_B, GSR_RESIZE_PLAN_ROWS_C, GSR_RESIZE_PLAN_RANK_C, GSR_RESIZE_PLAN_SPLIT_ROWS = 0, 1, 2, 3, 4
+
 EXPORTS = [
     "gsr_geom_bytes", "gsr_image_bytes", "gsr_forward_scratch_bytes", "gsr_binning_bytes",
     "gsr_binning_scratch_bytes", "gsr_backward_scratch_bytes", "gsr_forward", "gsr_backward",
@@ -90,6 +101,7 @@ EXPORTS = [
     "gsr_batch_retire_scratch_bytes", "gsr_batch_retire", "gsr_forward_retire",
     "gsr_depth_to_points", "gsr_voxel_scratch_bytes", "gsr_voxel_down_sample",
     "gsr_camera_from_pose", "gsr_pose_virtual_view",
+    "gsr_resize_scratch_bytes", "gsr_resize_plan_bytes", "gsr_resize_plan", "gsr_resize_apply",
 ]
 GSR_DEPTH_LOSS_L1, GSR_DEPTH_LOSS_INVARIANT = 0, 1
 
@@ -174,6 +186,15 @@ def load():
     lib.gsr_pose_virtual_view.restype = C.c_int
     # (pose0, pose1, alpha, base, out, out_rel, stream)
     lib.gsr_pose_virtual_view.argtypes = [C.c_void_p, C.c_void_p, C.c_double] + [C.c_void_p] * 4
+    for fn in ("gsr_resize_scratch_bytes", "gsr_resize_plan_bytes"):
+        getattr(lib, fn).restype = C.c_size_t
+        getattr(lib, fn).argtypes = [C.c_int64]
+    lib.gsr_resize_plan.restype = C.c_int
+    # (flags, N, plan, plan_bytes, meta, scratch, scratch_bytes, stream)
+    lib.gsr_resize_plan.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+    lib.gsr_resize_apply.restype = C.c_int
+    # (plan, plan_bytes, N, nA, nB, nC, nSplit, tensors, count, meta, stream)
+    lib.gsr_resize_apply.argtypes = [C.c_void_p, C.c_size_t] + [C.c_int64] * 5 + [C.POINTER(GsrResizeTensor), C.c_int32, C.c_void_p, C.c_void_p]
     lib.gsr_adam_step.restype = C.c_int
     lib.gsr_adam_step.argtypes = [C.POINTER(GsrAdamTensor), C.c_int32, C.c_float, C.c_float, C.c_float, C.c_int64, C.c_void_p]
     lib.gsr_pose_step.restype = C.c_int

@@ -91,8 +91,11 @@ class BatchedGaussianParams(GaussianParams):
 
     # resizing one model of a batch would move every later model's blocks: stage A never densifies (densify=False at
     # /root/reference/trainer/ht3dgs_trainer.py:298)
-    def prune_points(self, mask):
+    def prune_points(self, mask, route="torch"):
         raise RuntimeError("BatchedGaussianParams: the models of a batch cannot be resized")
 
-    def densification_postfix(self, new):
+    def densification_postfix(self, new, route="torch"):
+        raise RuntimeError("BatchedGaussianParams: the models of a batch cannot be resized")
+
+    def resize_by_flags(self, flags, planned=None, children=None):
         raise RuntimeError("BatchedGaussianParams: the models of a batch cannot be resized")

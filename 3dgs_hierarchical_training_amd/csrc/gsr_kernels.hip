@@ -68,6 +68,9 @@ static int fail(int code, const char* fmt, const char* detail = "")
     return code;
 }
 
+// the same for the other translation units of the library (resize_kernels.hip): `text` is stored as it is
+int fail_text(int code, const char* text) { return fail(code, "%s", text); }
+
 #define GSR_HIP(expr)                                                         \
     do {                                                                      \
         hipError_t e_ = (expr);                                               \
@@ -4309,7 +4312,7 @@ size_t gsr_prepared_bytes(int32_t N) { return prep_layout(N).bytes; }
 size_t gsr_prepared_radii_offset(int32_t N) { return prep_layout(N).radii; }
 int gsr_prepare_supported(int32_t M, int32_t D, int32_t raw_params) { return (raw_params && M == 16 && D >= 0 && D <= 3) ? 1 : 0; }
 const char* gsr_last_error(void) { return g_err; }
-int gsr_version(void) { return 119; }
+int gsr_version(void) { return 120; }
 size_t gsr_struct_bytes(int32_t which)
 {
     return which == 0 ? sizeof(GsrForwardArgs) : which == 1 ? sizeof(GsrBackwardArgs) : which == 2 ? sizeof(GsrForwardOut) : 0;

@@ -1,0 +1,248 @@
+// resize_kernels.hip -- resizing the model on the device: prune, clone and split as one layout decision and one row move.
+//
+// Densification and pruning (densify.py, train_step.GaussianParams) replace the six parameter tensors and their Adam moments by tensors of
+// another length.  What the new tensors hold is decided by one flag byte per row; the kernels of this file turn the flag bytes into the
+// source-row lists of the new layout (the plan) and then move the rows.  They compute no float: every byte of the result is a copy of a byte
+// the caller supplied, or zero.  Semantics in include/gsr.h (version 120).
+//
+//   gsr_resize_plan    count     one workgroup per tile of kResizeTile rows: how many rows of the tile enter each of the four lists;
+//                      scan      four workgroups, one per list: exclusive scan of its tile counts in place, the list's length to meta;
+//                      write     the tile again: every row's position inside its lists = the tile's offset + its rank in the tile.
+//                      (the count -> scan -> write shape of voxel_kernels.hip's segment heads)
+//   gsr_resize_apply   one launch; blockIdx.y picks the tensor, the x dimension strides over the tensor's destination in 4-byte words, so a
+//                      wave stores 256 consecutive bytes.  Every row number read from the plan is compared against N before it is used as
+//                      an address: a row that fails is written as zeros and raises meta[4].
+// No workgroup of this file waits for another one inside a launch.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "../../include/gsr.h"
+
+namespace gsr {
+
+int fail_text(int code, const char* text);      // gsr_kernels.hip: sets gsr_last_error()
+
+constexpr int kResizeTile = 256;                // rows per workgroup of the plan: one per thread
+constexpr int kResizeApplyGridX = 2048;         // workgroups per tensor of the apply launch at most (they stride)
+
+struct ResizeTable {
+    GsrResizeTensor t[GSR_RESIZE_MAX_TENSORS];
+};
+
+// list membership of one flag byte, one 16-bit field per list (a tile holds at most 256 of each): A | B << 16 | C << 32 | S << 48
+__device__ __forceinline__ unsigned long long resize_fields(uint8_t f)
+{
+    const unsigned long long a = (f & GSR_RESIZE_KEEP) ? 1ull : 0ull;
+    const unsigned long long b = (f & GSR_RESIZE_CLONE) ? 1ull : 0ull;
+    const unsigned long long s = (f & GSR_RESIZE_SPLIT) ? 1ull : 0ull;
+    const unsigned long long c = ((f & GSR_RESIZE_SPLIT) && (f & GSR_RESIZE_CHILD)) ? 1ull : 0ull;
+    return a | (b << 16) | (c << 32) | (s << 48);
+}
+
+// inclusive scan of one value per thread over the 256 threads of a workgroup; returns the caller's exclusive prefix, *total the sum
+template <typename T>
+__device__ __forceinline__ T resize_block_scan(T v, T* __restrict__ s, T* total)
+{
+    s[threadIdx.x] = v;
+    __syncthreads();
+    for (unsigned int off = 1; off < 256; off <<= 1) {
+        const T add = threadIdx.x >= off ? s[threadIdx.x - off] : (T)0;
+        __syncthreads();
+        s[threadIdx.x] += add;
+        __syncthreads();
+    }
+    const T incl = s[threadIdx.x];
+    *total = s[255];
+    __syncthreads();
+    return incl - v;
+}
+
+// tile_count: [4][ntiles]
+__global__ __launch_bounds__(256) void k_resize_count(const uint8_t* __restrict__ flags, int64_t N, int64_t ntiles,
+                                                      unsigned int* __restrict__ tile_count)
+{
+    __shared__ unsigned long long s[256];
+    const int64_t i = (int64_t)blockIdx.x * kResizeTile + threadIdx.x;
+    const unsigned long long v = i < N ? resize_fields(flags[i]) : 0ull;
+    unsigned long long total;
+    resize_block_scan(v, s, &total);
+    if (threadIdx.x < 4) tile_count[(int64_t)threadIdx.x * ntiles + blockIdx.x] = (unsigned int)((total >> (16 * threadIdx.x)) & 0xffffull);
+}
+
+// workgroup b: exclusive scan of list b's tile counts in place, its length to meta[b]; workgroup 0 also clears the status words
+__global__ __launch_bounds__(256) void k_resize_scan_tiles(unsigned int* __restrict__ tile_count, int64_t ntiles, int64_t* __restrict__ meta)
+{
+    __shared__ unsigned int s[256];
+    unsigned int* tc = tile_count + (int64_t)blockIdx.x * ntiles;
+    unsigned int running = 0;
+    for (int64_t lo = 0; lo < ntiles; lo += 256) {
+        const int64_t t = lo + threadIdx.x;
+        const unsigned int v = t < ntiles ? tc[t] : 0u;
+        unsigned int total;
+        const unsigned int excl = resize_block_scan(v, s, &total);
+        if (t < ntiles) tc[t] = running + excl;
+        running += total;
+    }
+    if (threadIdx.x == 0) meta[blockIdx.x] = (int64_t)running;
+    if (blockIdx.x == 0 && threadIdx.x >= 4 && threadIdx.x < GSR_RESIZE_META_WORDS) meta[threadIdx.x] = 0;
+}
+
+__global__ __launch_bounds__(256) void k_resize_write(const uint8_t* __restrict__ flags, int64_t N, int64_t ntiles,
+                                                      const unsigned int* __restrict__ tile_offset, int32_t* __restrict__ plan, int64_t stride)
+{
+    __shared__ unsigned long long s[256];
+    const int64_t i = (int64_t)blockIdx.x * kResizeTile + threadIdx.x;
+    const unsigned long long v = i < N ? resize_fields(flags[i]) : 0ull;
+    unsigned long long total;
+    const unsigned long long excl = resize_block_scan(v, s, &total);
+    if (i >= N) return;
+    // positions are below N (a list holds each row at most once), so every store stays inside its N-entry segment
+    const unsigned int pa = tile_offset[blockIdx.x] + (unsigned int)(excl & 0xffffull);
+    const unsigned int pb = tile_offset[ntiles + blockIdx.x] + (unsigned int)((excl >> 16) & 0xffffull);
+    const unsigned int pc = tile_offset[2 * ntiles + blockIdx.x] + (unsigned int)((excl >> 32) & 0xffffull);
+    const unsigned int ps = tile_offset[3 * ntiles + blockIdx.x] + (unsigned int)((excl >> 48) & 0xffffull);
+    // (the comparisons with N hold whenever the flags are the bytes the count pass saw; they keep a caller's race inside the buffer)
+    const unsigned int n = (unsigned int)N;
+    if ((v & 0xffffull) && pa < n) plan[GSR_RESIZE_PLAN_ROWS_A * stride + pa] = (int32_t)i;
+    if (((v >> 16) & 0xffffull) && pb < n) plan[GSR_RESIZE_PLAN_ROWS_B * stride + pb] = (int32_t)i;
+    if (((v >> 32) & 0xffffull) && pc < n) {
+        plan[GSR_RESIZE_PLAN_ROWS_C * stride + pc] = (int32_t)i;
+        plan[GSR_RESIZE_PLAN_RANK_C * stride + pc] = (int32_t)ps;
+    }
+    if (((v >> 48) & 0xffffull) && ps < n) plan[GSR_RESIZE_PLAN_SPLIT_ROWS * stride + ps] = (int32_t)i;
+}
+
+__global__ void k_resize_meta_zero(int64_t* __restrict__ meta)
+{
+    if (threadIdx.x < GSR_RESIZE_META_WORDS) meta[threadIdx.x] = 0;
+}
+
+// grid (x, count): tensor blockIdx.y, destination words e = row * words + w
+__global__ __launch_bounds__(256) void k_resize_apply(const int32_t* __restrict__ plan, int64_t stride, int64_t N, int64_t nA, int64_t nB,
+                                                      int64_t nC, int64_t nSplit, ResizeTable table, int64_t* __restrict__ meta)
+{
+    const GsrResizeTensor T = table.t[blockIdx.y];
+    if (!T.src || !T.dst || T.row_bytes <= 0) return;
+    const uint32_t words = (uint32_t)(T.row_bytes >> 2);
+    const int64_t nout = nA + nB + 2 * nC;
+    const int64_t total = nout * (int64_t)words;
+    const uint32_t* __restrict__ src = static_cast<const uint32_t*>(T.src);
+    const uint32_t* __restrict__ child = static_cast<const uint32_t*>(T.child);
+    uint32_t* __restrict__ dst = static_cast<uint32_t*>(T.dst);
+    const bool small = total <= 0xffffffffll;      // (a 32-bit division serves every model that fits a device)
+    for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (int64_t)gridDim.x * 256) {
+        const int64_t r = small ? (int64_t)((uint32_t)e / words) : e / (int64_t)words;
+        const uint32_t w = (uint32_t)(e - r * words);
+        uint32_t value = 0;
+        bool bad = false;
+        if (r < nA) {
+            const int64_t srow = plan[GSR_RESIZE_PLAN_ROWS_A * stride + r];
+            if (srow >= 0 && srow < N) value = src[srow * words + w]; else bad = true;
+        } else if (T.kind == GSR_RESIZE_MOMENT) {
+            value = 0;                                  // a new Gaussian starts with zero moments: nothing is read
+        } else if (r < nA + nB) {
+            const int64_t srow = plan[GSR_RESIZE_PLAN_ROWS_B * stride + (r - nA)];
+            if (srow >= 0 && srow < N) value = src[srow * words + w]; else bad = true;
+        } else {
+            const int64_t q = r - nA - nB;
+            const int64_t copy = q >= nC ? 1 : 0, j = q - copy * nC;      // j < nC <= nSplit <= N: inside the segment
+            if (T.kind == GSR_RESIZE_CHILD_SOURCED) {
+                const int64_t rank = plan[GSR_RESIZE_PLAN_RANK_C * stride + j];
+                if (rank >= 0 && rank < nSplit) value = child[(copy * nSplit + rank) * words + w]; else bad = true;
+            } else {
+                const int64_t srow = plan[GSR_RESIZE_PLAN_ROWS_C * stride + j];
+                if (srow >= 0 && srow < N) value = src[srow * words + w]; else bad = true;
+            }
+        }
+        dst[e] = value;
+        if (bad && w == 0) atomicOr(reinterpret_cast<unsigned long long*>(meta + GSR_RESIZE_META_STATUS), 1ull);
+    }
+}
+
+static inline int64_t resize_stride(int64_t N) { return (N + 63) / 64 * 64; }      // entries per plan segment: 256-byte aligned segments
+static inline int64_t resize_tiles(int64_t N) { return (N + kResizeTile - 1) / kResizeTile; }
+
+}  // namespace gsr
+
+using namespace gsr;
+
+extern "C" {
+
+size_t gsr_resize_scratch_bytes(int64_t N)
+{
+    if (N <= 0) return 0;
+    if (N >= ((int64_t)1 << 31)) N = ((int64_t)1 << 31) - 1;      // (larger models are refused by the call itself)
+    return ((size_t)resize_tiles(N) * 4 * sizeof(unsigned int) + 255) & ~(size_t)255;
+}
+
+size_t gsr_resize_plan_bytes(int64_t N)
+{
+    if (N <= 0) return 0;
+    if (N >= ((int64_t)1 << 31)) N = ((int64_t)1 << 31) - 1;
+    return (size_t)resize_stride(N) * GSR_RESIZE_PLAN_SEGMENTS * sizeof(int32_t);
+}
+
+int gsr_resize_plan(const uint8_t* flags, int64_t N, void* plan, size_t plan_bytes, int64_t* meta, void* scratch, size_t scratch_bytes,
+                    void* stream)
+{
+    if (N < 0 || N >= ((int64_t)1 << 31)) return fail_text(GSR_ERR_ARG, "gsr_resize_plan: N must be in [0, 2^31)");
+    if (!meta || ((uintptr_t)meta & 7) != 0) return fail_text(GSR_ERR_ARG, "gsr_resize_plan: meta is NULL or not 8-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    if (N == 0) {
+        hipLaunchKernelGGL(k_resize_meta_zero, dim3(1), dim3(64), 0, st, meta);
+        return hipGetLastError() == hipSuccess ? GSR_OK : GSR_ERR_HIP;
+    }
+    if (!flags) return fail_text(GSR_ERR_ARG, "gsr_resize_plan: flags is NULL");
+    if (!plan || ((uintptr_t)plan & 3) != 0) return fail_text(GSR_ERR_ARG, "gsr_resize_plan: plan is NULL or not 4-byte aligned");
+    if (plan_bytes < gsr_resize_plan_bytes(N)) return fail_text(GSR_ERR_ARG, "gsr_resize_plan: plan is shorter than gsr_resize_plan_bytes(N)");
+    if (!scratch || ((uintptr_t)scratch & 3) != 0) return fail_text(GSR_ERR_ARG, "gsr_resize_plan: scratch is NULL or not 4-byte aligned");
+    if (scratch_bytes < gsr_resize_scratch_bytes(N))
+        return fail_text(GSR_ERR_ARG, "gsr_resize_plan: scratch is shorter than gsr_resize_scratch_bytes(N)");
+    const int64_t ntiles = resize_tiles(N), stride = resize_stride(N);
+    unsigned int* tiles = static_cast<unsigned int*>(scratch);
+    hipLaunchKernelGGL(k_resize_count, dim3((unsigned)ntiles), dim3(256), 0, st, flags, N, ntiles, tiles);
+    hipLaunchKernelGGL(k_resize_scan_tiles, dim3(4), dim3(256), 0, st, tiles, ntiles, meta);
+    hipLaunchKernelGGL(k_resize_write, dim3((unsigned)ntiles), dim3(256), 0, st, flags, N, ntiles, tiles, static_cast<int32_t*>(plan), stride);
+    return hipGetLastError() == hipSuccess ? GSR_OK : GSR_ERR_HIP;
+}
+
+int gsr_resize_apply(const void* plan, size_t plan_bytes, int64_t N, int64_t nA, int64_t nB, int64_t nC, int64_t nSplit,
+                     const GsrResizeTensor* tensors, int32_t count, int64_t* meta, void* stream)
+{
+    if (N < 0 || N >= ((int64_t)1 << 31)) return fail_text(GSR_ERR_ARG, "gsr_resize_apply: N must be in [0, 2^31)");
+    if (!meta || ((uintptr_t)meta & 7) != 0) return fail_text(GSR_ERR_ARG, "gsr_resize_apply: meta is NULL or not 8-byte aligned");
+    if (count < 0 || count > GSR_RESIZE_MAX_TENSORS) return fail_text(GSR_ERR_ARG, "gsr_resize_apply: at most GSR_RESIZE_MAX_TENSORS (18) tensors");
+    if (count > 0 && !tensors) return fail_text(GSR_ERR_ARG, "gsr_resize_apply: tensors is NULL");
+    if (nA < 0 || nB < 0 || nC < 0 || nSplit < 0 || nA > N || nB > N || nSplit > N || nC > nSplit)
+        return fail_text(GSR_ERR_ARG, "gsr_resize_apply: counts beyond the plan's capacity (0 <= nA, nB, nSplit <= N and nC <= nSplit)");
+    const int64_t nout = nA + nB + 2 * nC;
+    if (nout > 0 && (!plan || ((uintptr_t)plan & 3) != 0)) return fail_text(GSR_ERR_ARG, "gsr_resize_apply: plan is NULL or not 4-byte aligned");
+    if (nout > 0 && plan_bytes < gsr_resize_plan_bytes(N))
+        return fail_text(GSR_ERR_ARG, "gsr_resize_apply: plan is shorter than gsr_resize_plan_bytes(N)");
+    ResizeTable table{};
+    int64_t most = 0;
+    for (int k = 0; k < count; k++) {
+        const GsrResizeTensor& t = tensors[k];
+        if (t.row_bytes < 0 || (t.row_bytes & 3) != 0 || t.row_bytes >= ((int64_t)1 << 31))
+            return fail_text(GSR_ERR_ARG, "gsr_resize_apply: row_bytes must be a non-negative multiple of 4 below 2^31");
+        if (t.kind != GSR_RESIZE_PARAM && t.kind != GSR_RESIZE_MOMENT && t.kind != GSR_RESIZE_CHILD_SOURCED)
+            return fail_text(GSR_ERR_ARG, "gsr_resize_apply: kind is GSR_RESIZE_PARAM, GSR_RESIZE_MOMENT or GSR_RESIZE_CHILD_SOURCED");
+        table.t[k] = t;
+        if (t.row_bytes == 0 || (!t.src && !t.dst)) { table.t[k].src = nullptr; table.t[k].dst = nullptr; continue; }      // skipped
+        if (!t.src || !t.dst) return fail_text(GSR_ERR_ARG, "gsr_resize_apply: src and dst are given both or neither");
+        if ((((uintptr_t)t.src | (uintptr_t)t.dst | (uintptr_t)t.child) & 3) != 0)
+            return fail_text(GSR_ERR_ARG, "gsr_resize_apply: src, dst and child must be 4-byte aligned");
+        if (t.kind == GSR_RESIZE_CHILD_SOURCED && nC > 0 && !t.child)
+            return fail_text(GSR_ERR_ARG, "gsr_resize_apply: a GSR_RESIZE_CHILD_SOURCED tensor needs child rows when nC > 0");
+        const int64_t words = nout * (t.row_bytes >> 2);
+        if (words > most) most = words;
+    }
+    if (most == 0) return GSR_OK;      // nothing kept, or nothing to move: not an error
+    int64_t gx = (most + 255) / 256;
+    if (gx > kResizeApplyGridX) gx = kResizeApplyGridX;
+    hipLaunchKernelGGL(k_resize_apply, dim3((unsigned)gx, (unsigned)count), dim3(256), 0, (hipStream_t)stream,
+                       static_cast<const int32_t*>(plan), resize_stride(N), N, nA, nB, nC, nSplit, table, meta);
+    return hipGetLastError() == hipSuccess ? GSR_OK : GSR_ERR_HIP;
+}
+
+}  // extern "C"

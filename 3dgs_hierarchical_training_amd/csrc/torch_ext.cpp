@@ -27,6 +27,8 @@
 //   gsr::voxel_down_sample    -> gsr_voxel_down_sample (voxel-grid means; its read of `meta` is the one host synchronisation)
 //   gsr::camera_from_pose     -> gsr_camera_from_pose (view matrix, full projection and camera centre of up to 16 device poses, one launch)
 //   gsr::pose_virtual_view    -> gsr_pose_virtual_view (the interpolated pose between two device poses, and that pose relative to a base)
+//   gsr::resize_plan          -> gsr_resize_plan (flag bytes -> the source-row lists of the resized model; no host synchronisation)
+//   gsr::resize_apply         -> gsr_resize_apply (every row of every parameter and moment tensor moved in one launch)
 //
 // Registered with TORCH_LIBRARY so the ops are visible to the dispatcher (torch.ops.gsr.*, fake kernels in _ext.py for
 // torch.compile).  An empty tensor (numel 0) stands for "None".  Everything runs on the current HIP stream of the
@@ -1311,6 +1313,77 @@ std::tuple<Tensor, Tensor> pose_virtual_view(const Tensor& pose0_, const Tensor&
     return {out, out_rel};
 }
 
+// gsr::resize_plan -> gsr_resize_plan.  flags uint8 [N] -> (plan int32 [gsr_resize_plan_bytes(N) / 4], meta int64 [8], both on the device).
+// No host synchronisation: the caller reads meta (its one wait) and hands the four counts to gsr::resize_apply.  No autograd.
+std::tuple<Tensor, Tensor> resize_plan(const Tensor& flags_)
+{
+    TORCH_CHECK(flags_.is_cuda(), "resize_plan: flags must be on a ROCm/HIP device (no CPU fallback)");
+    TORCH_CHECK(flags_.dim() == 1 && flags_.scalar_type() == at::kByte, "resize_plan: flags is uint8 [N]");
+    const c10::hip::HIPGuardMasqueradingAsCUDA guard(flags_.device());
+    const Tensor flags = flags_.contiguous();
+    const int64_t N = flags.numel();
+    const size_t pb = gsr_resize_plan_bytes(N), sb = gsr_resize_scratch_bytes(N);
+    Tensor plan = at::empty({(int64_t)(pb / 4)}, flags.options().dtype(at::kInt));
+    Tensor meta = at::empty({GSR_RESIZE_META_WORDS}, flags.options().dtype(at::kLong));
+    Tensor scratch = at::empty({(int64_t)sb}, flags.options());
+    check(gsr_resize_plan(N ? flags.data_ptr<uint8_t>() : nullptr, N, N ? plan.data_ptr() : nullptr, pb, meta.data_ptr<int64_t>(),
+                          N ? scratch.data_ptr() : nullptr, sb, c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream()), "gsr_resize_plan");
+    return {plan, meta};
+}
+
+// gsr::resize_apply -> gsr_resize_apply.  src[k]: [N, ...] contiguous, kinds[k]: GSR_RESIZE_PARAM / MOMENT / CHILD_SOURCED, child[k]: [2 nSplit, ...]
+// for a CHILD_SOURCED tensor, an empty tensor otherwise.  Returns fresh tensors [nA + nB + 2 nC, ...].  check: read meta's status word back
+// afterwards (a host synchronisation) and raise on a plan entry out of range; without it the call is asynchronous.  No autograd: surgery on
+// detached storage.
+std::vector<Tensor> resize_apply(const Tensor& plan, Tensor meta, int64_t N, int64_t nA, int64_t nB, int64_t nC, int64_t nSplit,
+                                 at::TensorList src_, at::IntArrayRef kinds, at::TensorList child_, bool do_check)
+{
+    TORCH_CHECK(plan.is_cuda() && meta.is_cuda(), "resize_apply: plan and meta must be on a ROCm/HIP device (no CPU fallback)");
+    TORCH_CHECK(plan.scalar_type() == at::kInt && plan.is_contiguous() && plan.dim() == 1, "resize_apply: plan is the int32 tensor of resize_plan");
+    TORCH_CHECK(meta.scalar_type() == at::kLong && meta.is_contiguous() && meta.numel() == GSR_RESIZE_META_WORDS,
+                "resize_apply: meta is the int64 [8] tensor of resize_plan");
+    TORCH_CHECK(src_.size() == kinds.size() && src_.size() == child_.size(), "resize_apply: src, kinds and child have one entry per tensor");
+    TORCH_CHECK((int64_t)src_.size() <= GSR_RESIZE_MAX_TENSORS, "resize_apply: at most ", GSR_RESIZE_MAX_TENSORS, " tensors");
+    TORCH_CHECK(N >= 0 && nA >= 0 && nB >= 0 && nC >= 0 && nSplit >= 0, "resize_apply: negative count");
+    const c10::hip::HIPGuardMasqueradingAsCUDA guard(plan.device());
+    const int64_t nout = nA + nB + 2 * nC;
+    std::vector<Tensor> src, child, dst;
+    std::vector<GsrResizeTensor> table(src_.size());
+    for (size_t k = 0; k < src_.size(); k++) {
+        TORCH_CHECK(src_[k].is_cuda() && src_[k].device() == plan.device(), "resize_apply: src[", k, "] must be on the plan's device (no CPU fallback)");
+        TORCH_CHECK(src_[k].dim() >= 1 && src_[k].size(0) == N, "resize_apply: src[", k, "] has N rows");
+        src.push_back(src_[k].detach().contiguous());
+        std::vector<int64_t> shape = src[k].sizes().vec();
+        shape[0] = nout;
+        dst.push_back(at::empty(shape, src[k].options()));
+        int64_t row_bytes = (int64_t)src[k].element_size();
+        for (size_t d = 1; d < shape.size(); d++) row_bytes *= shape[d];
+        GsrResizeTensor& t = table[k];
+        t.kind = (int32_t)kinds[k];
+        t.row_bytes = row_bytes;
+        const bool moves = row_bytes > 0 && nout > 0;
+        t.src = (moves && N > 0) ? src[k].data_ptr() : nullptr;
+        t.dst = (moves && N > 0) ? dst[k].data_ptr() : nullptr;
+        t.child = nullptr;
+        if (kinds[k] == GSR_RESIZE_CHILD_SOURCED && has(child_[k])) {
+            TORCH_CHECK(child_[k].is_cuda() && child_[k].device() == plan.device(), "resize_apply: child[", k, "] must be on the plan's device (no CPU fallback)");
+            TORCH_CHECK(child_[k].scalar_type() == src[k].scalar_type() && child_[k].size(0) == 2 * nSplit &&
+                        child_[k].numel() * (int64_t)child_[k].element_size() == 2 * nSplit * row_bytes,
+                        "resize_apply: child[", k, "] is [2 nSplit, ...] rows of its tensor");
+            child.push_back(child_[k].detach().contiguous());
+            t.child = child.back().data_ptr();
+        }
+    }
+    check(gsr_resize_apply(plan.numel() ? plan.data_ptr() : nullptr, (size_t)plan.numel() * 4, N, nA, nB, nC, nSplit, table.data(), (int32_t)table.size(),
+                           meta.data_ptr<int64_t>(), c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream()), "gsr_resize_apply");
+    if (do_check) {
+        const Tensor host = meta.cpu();
+        TORCH_CHECK(host.data_ptr<int64_t>()[GSR_RESIZE_META_STATUS] == 0, "resize_apply: the plan holds a row number outside [0, N) (status ",
+                    host.data_ptr<int64_t>()[GSR_RESIZE_META_STATUS], "): the rows it names were written as zeros");
+    }
+    return dst;
+}
+
 }  // namespace
 
 // ---- the trainer's per-iteration bookkeeping (gsr_masked_max / gsr_densify_stats_add / gsr_psnr; include/gsr.h) ------------------
@@ -1448,6 +1521,9 @@ TORCH_LIBRARY(gsr, m)
     m.def("camera_from_pose(Tensor pose, float fx, float fy, float cx, float cy, int W, int H, float znear=0.01, float zfar=100.0) -> "
           "(Tensor viewmatrix, Tensor projmatrix, Tensor campos)");
     m.def("pose_virtual_view(Tensor pose0, Tensor pose1, float alpha, Tensor? base=None) -> (Tensor out, Tensor out_rel)");
+    m.def("resize_plan(Tensor flags) -> (Tensor plan, Tensor meta)");
+    m.def("resize_apply(Tensor plan, Tensor(a!) meta, int N, int nA, int nB, int nC, int nSplit, Tensor[] src, int[] kinds, Tensor[] child, "
+          "bool check=False) -> Tensor[]");
     m.def("masked_max_(Tensor(a!) dst, Tensor src, Tensor mask) -> ()");
     m.def("densify_stats_add_(Tensor(a!) accum, Tensor(b!) denom, Tensor grad, Tensor mask) -> ()");
     m.def("psnr(Tensor a, Tensor b) -> Tensor");
@@ -1479,6 +1555,8 @@ TORCH_LIBRARY_IMPL(gsr, CUDA, m)   // the dispatch key of HIP tensors on a ROCm 
     m.impl("voxel_down_sample", &voxel_down_sample);
     m.impl("camera_from_pose", &camera_from_pose);
     m.impl("pose_virtual_view", &pose_virtual_view);
+    m.impl("resize_plan", &resize_plan);
+    m.impl("resize_apply", &resize_apply);
     m.impl("masked_max_", &masked_max_);
     m.impl("densify_stats_add_", &densify_stats_add_);
     m.impl("psnr", &psnr);

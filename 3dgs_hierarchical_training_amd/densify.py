@@ -28,6 +28,8 @@ from typing import Optional
 import torch
 import torch.nn.functional as F
 
+from . import resize as R
+
 
 @dataclass
 class DensifyConfig:
@@ -55,7 +57,12 @@ def _quat_to_rotmat(q: torch.Tensor) -> torch.Tensor:
 class Densifier:
     """Per-model statistics + the clone / split / prune surgery, on a `GaussianParams`."""
 
-    def __init__(self, params, scene_extent: float = 1.0, cfg: Optional[DensifyConfig] = None, seed: int = 0):
+    def __init__(self, params, scene_extent: float = 1.0, cfg: Optional[DensifyConfig] = None, seed: int = 0, route: str = "torch"):
+        """route: how `densify_and_prune` resizes the model.  "torch" (the default): the statement sequence below it, boolean indexing and
+        torch.cat per tensor.  "kernel": the same selections, made with the same torch statements, turned into one flag byte per row and
+        handed to gsr_resize_plan / gsr_resize_apply (resize.py): one host wait and one launch that moves every row -- the same tensors,
+        moments, statistics and generator state to the bit."""
+        self.route = R.check_route(route, "Densifier")
         self.params = params
         self.extent = float(scene_extent)
         self.cfg = cfg or DensifyConfig()
@@ -114,6 +121,8 @@ class Densifier:
     # ---- gaussian_model_ht.py:632-691 --------------------------------------------------------------------------------
     @torch.no_grad()
     def densify_and_prune(self, max_grad: float, min_opacity: float, max_screen_size: Optional[float]):
+        if self.route == "kernel" and self._densify_and_prune_kernel(max_grad, min_opacity, max_screen_size):
+            return
         p = self.params
         grads = self.xyz_gradient_accum / self.denom
         grads[grads.isnan()] = 0.0
@@ -156,6 +165,71 @@ class Densifier:
             mask = mask | (self.max_radii2D > max_screen_size) | (p.get_scaling.detach().max(dim=1).values > 0.1 * self.extent)
         if bool(mask.any()):
             self._prune(mask)
+
+    @torch.no_grad()
+    def _resize_flags(self, max_grad: float, min_opacity: float, max_screen_size: Optional[float]):
+        """The flag byte per row that `densify_and_prune` amounts to (resize.KEEP | CLONE | SPLIT | CHILD), from the torch route's own
+        statements: elementwise over the N rows, no host wait, any device; max_grad > 0 is the caller's to check.  Returns (flags, the
+        clone selection, get_scaling)."""
+        p, c = self.params, self.cfg
+        grads = self.xyz_gradient_accum / self.denom
+        grads[grads.isnan()] = 0.0
+        scaling = p.get_scaling.detach()
+        smax = scaling.max(dim=1).values
+        big = smax > c.percent_dense * self.extent
+        clone = (grads.norm(dim=-1) >= max_grad) & ~big
+        split = (grads.squeeze(1) >= max_grad) & big
+        gone = (p.get_opacity.detach() < min_opacity).squeeze(1)            # the final prune's predicate on a row as it stands
+        child_gone = gone
+        if max_screen_size:
+            stats_term = bool(0.0 > max_screen_size)                         # max_radii2D is all zeros at the final prune
+            gone = gone | stats_term | (smax > 0.1 * self.extent)
+            child_scaling = torch.exp(torch.log(scaling / (0.8 * 2)))
+            child_gone = child_gone | stats_term | (child_scaling.max(dim=1).values > 0.1 * self.extent)
+        flags = ((~split & ~gone).to(torch.uint8) * R.KEEP + (clone & ~gone).to(torch.uint8) * R.CLONE
+                 + split.to(torch.uint8) * R.SPLIT + (split & ~child_gone).to(torch.uint8) * R.CHILD)
+        return flags, clone, scaling
+
+    def _densify_and_prune_kernel(self, max_grad: float, min_opacity: float, max_screen_size: Optional[float]):
+        """`densify_and_prune` on the resize kernels.  Every selection below is the torch route's own statement, evaluated on the N rows the
+        call starts with; what the torch route decides about an appended row follows from its source row, because an appended row is a copy:
+          * a clone carries its parent's parameters, so the final prune removes it iff it removes the parent;
+          * a cloned row is never split: its padded gradient is 0 and max_grad > 0 (hence the refusal of max_grad <= 0);
+          * a split parent is removed right after its children are appended, whatever the final prune thinks of it;
+          * a child has its parent's opacity and the scale exp(log(get_scaling / 1.6)), and the statistics were zeroed before the final
+            prune, so its screen-size term is false.
+        The kernels then only order rows and copy them; the children's positions and scales are the torch route's statements on
+        index_select(split rows), with the same shapes and the same draw from the generator.  Returns True when the call is done, False
+        when `cfg.max_points` cancels the clones or the splits: `meta` says so before anything has been changed or drawn, and the capped
+        call is left to the torch route."""
+        p, c = self.params, self.cfg
+        if not max_grad > 0:
+            raise ValueError("Densifier(route='kernel'): max_grad must be positive (a cloned row must not qualify for a split)")
+        R.need_device("Densifier(route='kernel')", params=p._xyz)
+        flags, clone, scaling = self._resize_flags(max_grad, min_opacity, max_screen_size)
+        n = p.num_points
+        plan, meta = R.resize_plan(flags)
+        counts = R.read_counts(meta, clone.sum() if c.max_points is not None else None)      # the call's one host wait
+        nA, nB, nC, nS = counts[:4]
+        if c.max_points is not None:
+            n_clone = counts[5]
+            clones_cancelled = n + n_clone > c.max_points
+            if clones_cancelled or n + n_clone + nS > c.max_points:
+                return False
+        children = None
+        if nS:
+            rows = R.plan_segment(plan, n, R.L.GSR_RESIZE_PLAN_SPLIT_ROWS, nS)
+            parent_scaling = scaling.index_select(0, rows)
+            parent_rotation = p._rotation.detach().index_select(0, rows)
+            stds = parent_scaling.repeat(2, 1)
+            samples = torch.randn(stds.shape, generator=self.gen, device=stds.device) * stds
+            rots = _quat_to_rotmat(parent_rotation).repeat(2, 1, 1)
+            children = {"xyz": torch.bmm(rots, samples.unsqueeze(-1)).squeeze(-1) + p._xyz.detach().index_select(0, rows).repeat(2, 1),
+                        "scaling": torch.log(parent_scaling.repeat(2, 1) / (0.8 * 2))}
+        if not (nA == n and nB == 0 and nS == 0):       # (nothing moves: no tensor is replaced, as the torch route replaces none)
+            p.resize_by_flags(flags, planned=(plan, meta, counts), children=children)
+        self.reset_stats()
+        return True
 
     # ---- ht3dgs_trainer.py:137-155 -------------------------------------------------------------------------------------
     @torch.no_grad()

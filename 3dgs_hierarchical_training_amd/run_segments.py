@@ -102,6 +102,8 @@ class HTConfig:
                                                 # batch waits for all its models); 'device' = each model retires at its own iteration, on the device
     stage_a_init: str = "pixels"                # a stage-A model's initialisation: 'pixels' = sequence.pixel_scene (a strided pixel grid, built on the
                                                 # host); 'voxels' = sequence.depth_scene (every pixel, voxel grid 0.01, create_from_pcd: the reference's, on the device)
+    densify_route: str = "torch"                # how a densification resizes the model: 'torch' = boolean indexing and torch.cat per tensor; 'kernel' =
+                                                # gsr_resize_plan / gsr_resize_apply (resize.py): the same result to the bit, one host wait, one row-moving launch
     device_cameras: bool = False                # phase 1's virtual views from poses kept on the device: cameras.virtual_view + settings_from_pose, two
                                                 # launches per view instead of host matrix work and eight uploads; a camera may differ from the host
                                                 # route's in the last float32 bit, so the default stays the host route
@@ -237,7 +239,7 @@ class RankRunner:
         if self.cfg.densify:
             seg.densifier = densify.Densifier(seg.params, scene_extent=5.0, cfg=densify.DensifyConfig(
                 densify_from_iter=50, densification_interval=100, opacity_reset_interval=3000,
-                max_points=4 * seg.params.num_points), seed=self.rank)
+                max_points=4 * seg.params.num_points), seed=self.rank, route=self.cfg.densify_route)
 
     # ---- leaf (:729-753) ---------------------------------------------------------------------------------------------
     def train_leaf(self):
@@ -538,6 +540,9 @@ def main():
     ap.add_argument("--stage-a-init", choices=("pixels", "voxels"), default="pixels",
                     help="a stage-A model's initialisation: pixels = one Gaussian per strided pixel, built on the host (default); voxels = every "
                          "pixel un-projected, voxel grid of 0.01, create_from_pcd -- the reference's initialisation, built on the device")
+    ap.add_argument("--densify-route", choices=("torch", "kernel"), default="torch",
+                    help="how a densification resizes the model: torch = boolean indexing and torch.cat per tensor (default); kernel = the "
+                         "resize kernels, the same result to the bit with one host wait and one launch that moves every row")
     ap.add_argument("--device-cameras", action="store_true",
                     help="phase 1's virtual views from poses kept on the device (cameras.virtual_view + settings_from_pose: two launches per view, no "
                          "host matrix work or uploads); a camera may differ from the host route's in the last float32 bit.  Default: the host route")
@@ -555,7 +560,7 @@ def main():
         return launch_check(a)
     cfg = HTConfig(frames=a.frames, width=a.width, height=a.height, gt_gaussians=a.gt_gaussians, leaf_gaussians=a.leaf_gaussians,
                    leaf_iters_per_frame=a.leaf_iters, phase1_iters_per_frame=a.phase1_iters, phase2_iters_per_frame=[a.phase2_iters] * 3,
-                   importance_views=a.importance_views, densify=a.densify, fit_pose=a.fit_pose, stage_a_batch=a.stage_a_batch, stage_a_lambda_depth=a.stage_a_lambda_depth, stage_a_early_exit=a.stage_a_early_exit, stage_a_init=a.stage_a_init, sh_up_every=a.sh_up_every,
+                   importance_views=a.importance_views, densify=a.densify, fit_pose=a.fit_pose, stage_a_batch=a.stage_a_batch, stage_a_lambda_depth=a.stage_a_lambda_depth, stage_a_early_exit=a.stage_a_early_exit, stage_a_init=a.stage_a_init, densify_route=a.densify_route, sh_up_every=a.sh_up_every,
                    device_cameras=a.device_cameras)
     if a.pose_lr is not None:
         cfg.pose_lr = a.pose_lr

@@ -16,6 +16,7 @@ import torch
 import torch.nn.functional as F
 
 from ._ext import use_ctypes as E_use_ctypes
+from . import resize as R
 from .loss import DEPTH_CLAMP, fused_depth_loss, fused_photometric_loss, fused_training_loss_report
 from .optim import FusedAdam
 from .rasterizer import GaussianRasterizationSettings, GaussianRasterizer, rasterize_gaussians_raw, render_gaussians
@@ -212,31 +213,74 @@ class GaussianParams:
 
     def _swap_group_tensor(self, group, new_tensor, moments):
         """moments: callable(old_state_tensor) -> new state tensor (shape of new_tensor)."""
+        st = self.optimizer.state.get(group["params"][0])
+        return self._install_group_tensor(group, new_tensor, None if st is None else (moments(st["exp_avg"]), moments(st["exp_avg_sq"])))
+
+    def _install_group_tensor(self, group, new_tensor, new_moments):
+        """The bookkeeping both resize routes share: `new_tensor` becomes the group's parameter as a fresh leaf that requires grad, the
+        group's optimizer state is re-keyed to it with its `step` kept and its moments replaced by `new_moments` (exp_avg, exp_avg_sq;
+        ignored for a group without state), and the hand-over buffer of "prepare in backward" is dropped."""
         old = group["params"][0]
         st = self.optimizer.state.pop(old, None)
         new = new_tensor.detach().contiguous().requires_grad_(True)
         if st is not None:
-            st["exp_avg"], st["exp_avg_sq"] = moments(st["exp_avg"]), moments(st["exp_avg_sq"])
+            st["exp_avg"], st["exp_avg_sq"] = new_moments
             self.optimizer.state[new] = st
         group["params"][0] = new
         setattr(self, self._GROUP_ATTR[group["name"]], new)
         self._prepared = None            # a hand-over buffer of "prepare in backward" describes the old tensors
         return new
 
-    def prune_points(self, mask: torch.Tensor):
-        """Remove the Gaussians where mask is True (gaussian_model_ht.py:568-582)."""
+    def prune_points(self, mask: torch.Tensor, route: str = "torch"):
+        """Remove the Gaussians where mask is True (gaussian_model_ht.py:568-582).  route="kernel": the same result through
+        gsr_resize_plan / gsr_resize_apply (resize.py) -- one host wait and one launch that moves all six groups and their moments."""
+        if R.check_route(route, "prune_points") == "kernel":
+            R.need_device("prune_points(route='kernel')", mask=mask, params=self._xyz)
+            self.resize_by_flags((~mask).to(torch.uint8))          # KEEP = 1
+            return
         keep = ~mask
         for g in self.optimizer.param_groups:
             self._swap_group_tensor(g, g["params"][0][keep], lambda m: m[keep].contiguous())
         self._screenspace_zero = None
 
-    def densification_postfix(self, new: Dict[str, torch.Tensor]):
-        """Append Gaussians; `new` maps group name -> tensor of new rows (gaussian_model_ht.py:584-629)."""
+    def densification_postfix(self, new: Dict[str, torch.Tensor], route: str = "torch"):
+        """Append Gaussians; `new` maps group name -> tensor of new rows (gaussian_model_ht.py:584-629).  `route` is accepted so that
+        callers need not care, and both values run the torch statements below: an append is one allocation and two copies per tensor
+        and has no layout to decide, so there is nothing for the resize kernels to do."""
+        R.check_route(route, "densification_postfix")
         for g in self.optimizer.param_groups:
             ext = new[g["name"]]
             self._swap_group_tensor(g, torch.cat((g["params"][0].detach(), ext), dim=0),
                                     lambda m, ext=ext: torch.cat((m, torch.zeros_like(ext)), dim=0))
         self._screenspace_zero = None
+
+    def resize_by_flags(self, flags: torch.Tensor, planned=None, children: Dict[str, torch.Tensor] = None):
+        """The kernel route of every resize: flags (uint8 [N], resize.KEEP | CLONE | SPLIT | CHILD per row) -> all six groups and the
+        moments that exist replaced by their resized tensors, through one gsr_resize_apply launch.  planned = (plan, meta, counts) when the
+        caller has run the plan and read `meta` already (Densifier does, to sample the split children in between); children = {"xyz",
+        "scaling"} -> [2 nSplit, 3] rows for the surviving split children.  Returns the counts (nA, nB, nC, nSplit).  The plan is the one
+        gsr_resize_plan has just written, so its status word is not read back (that would be a second host wait)."""
+        plan, meta, counts = planned if planned is not None else (None, None, None)
+        if plan is None:
+            plan, meta = R.resize_plan(flags)
+            counts = R.read_counts(meta)          # the one host wait
+        n = self.num_points
+        entries, src, kinds, child = [], [], [], []
+        for g in self.optimizer.param_groups:
+            p = g["params"][0]
+            st = self.optimizer.state.get(p)
+            sourced = children is not None and g["name"] in children
+            entries.append((g, st is not None))
+            src.append(p.detach()); kinds.append(R.CHILD_SOURCED if sourced else R.PARAM); child.append(children[g["name"]] if sourced else None)
+            if entries[-1][1]:        # (moments an optimizer has not created yet have nothing to move)
+                for k in ("exp_avg", "exp_avg_sq"):
+                    src.append(st[k]); kinds.append(R.MOMENT); child.append(None)
+        out = iter(R.resize_apply(plan, meta, n, counts, src, kinds, child))
+        for g, has_moments in entries:
+            new = next(out)
+            self._install_group_tensor(g, new, (next(out), next(out)) if has_moments else None)
+        self._screenspace_zero = None
+        return tuple(counts[:4])
 
     def reset_opacity(self, ceiling: float = 0.01):
         """opacity <- min(opacity, ceiling) with zeroed moments (gaussian_model_ht.py:468-474, 532-546)."""

@@ -379,7 +379,8 @@ const char* gsr_last_error(void);
  * 116: GsrForwardArgs ends with render_only (the render-only call).
  * 117: the retire table: gsr_forward_retire, GsrBackwardArgs ends with retired_at, retire_step, gsr_batch_retire; GsrForwardArgs unchanged.
  * 118: gsr_depth_to_points, gsr_voxel_scratch_bytes, gsr_voxel_down_sample; no struct changes (gsr_struct_bytes as in 117).
- * 119: gsr_camera_from_pose, gsr_pose_virtual_view; no struct changes. */
+ * 119: gsr_camera_from_pose, gsr_pose_virtual_view; no struct changes.
+ * 120: gsr_resize_plan, gsr_resize_apply, gsr_resize_scratch_bytes, gsr_resize_plan_bytes (GsrResizeTensor is new); no existing struct changes. */
 int gsr_version(void);
 size_t gsr_struct_bytes(int32_t which); /* 0 GsrForwardArgs, 1 GsrBackwardArgs, 2 GsrForwardOut; anything else 0 */
 
@@ -737,6 +738,83 @@ int gsr_camera_from_pose(const float* pose /*[B,16]*/, int32_t B, double fx, dou
                          void* stream);
 int gsr_pose_virtual_view(const float* pose0 /*[16]*/, const float* pose1 /*[16]*/, double alpha, const float* base /*[16] or NULL*/,
                           float* out /*[16]*/, float* out_rel /*[16] or NULL*/, void* stream);
+
+/* ---- resizing the model on the device (version 120) -------------------------------------------------------------------------------------
+ * Pruning and densification replace every per-Gaussian tensor (six parameter groups, twelve Adam moments) by a tensor of another length.
+ * The two entries decide the new layout from one flag byte per row and move the rows.  Neither computes a float: every byte they write is
+ * a copy of a byte the caller supplied, or zero.  Both are asynchronous on `stream`; no workgroup waits for another one.
+ *
+ * Flag bits of row i (flags: uint8 [N], device):
+ *   GSR_RESIZE_KEEP   the row survives as itself, parameters and moments;
+ *   GSR_RESIZE_CLONE  a copy of the row's parameters is appended with zero moments;
+ *   GSR_RESIZE_SPLIT  the row is a split parent: it takes a rank among the split parents, in ascending row order;
+ *   GSR_RESIZE_CHILD  (with SPLIT; ignored without it) the split parent's two children survive.
+ * The new layout, nA + nB + 2 nC rows, is: A = the KEEP rows ascending; B = the CLONE rows ascending; C = the SPLIT + CHILD rows
+ * ascending, copy 0; then the same rows again, copy 1 -- the order in which "append the clones, append both copies of the children, prune
+ * the parents, prune" leaves them.
+ *
+ * gsr_resize_plan writes the plan, the scratch and meta, nothing else.
+ *   plan: gsr_resize_plan_bytes(N) bytes, 4-byte aligned: GSR_RESIZE_PLAN_SEGMENTS segments of int32, each S = 64 * ceil(N / 64) entries
+ *         long (segment k starts at entry k * S):
+ *           GSR_RESIZE_PLAN_ROWS_A      [nA]      the KEEP rows
+ *           GSR_RESIZE_PLAN_ROWS_B      [nB]      the CLONE rows
+ *           GSR_RESIZE_PLAN_ROWS_C      [nC]      the SPLIT + CHILD rows
+ *           GSR_RESIZE_PLAN_RANK_C      [nC]      the split rank of each of them (its position in the next list)
+ *           GSR_RESIZE_PLAN_SPLIT_ROWS  [nSplit]  all SPLIT rows, with children or not (the caller gathers the parents with it)
+ *         entries beyond a list's length are not written.
+ *   meta: GSR_RESIZE_META_WORDS x int64 on the device, 8-byte aligned: {nA, nB, nC, nSplit, status, 0, 0, 0}.  The plan clears the status;
+ *         gsr_resize_apply raises it.  The caller reads meta (its one host wait) and passes the four counts to gsr_resize_apply.
+ *   scratch: gsr_resize_scratch_bytes(N) bytes, 4-byte aligned.  Both sizes are closed forms in N, monotone, 0 for N <= 0.
+ *   N == 0: meta is zeroed, nothing else is touched (flags, plan and scratch may be NULL).
+ *   GSR_ERR_ARG (before anything is enqueued; gsr_last_error() names the rule): N < 0 or N >= 2^31, meta NULL or misaligned, and for N > 0
+ *   flags, plan or scratch NULL, plan or scratch misaligned or shorter than its size function says.
+ *
+ * gsr_resize_apply writes every destination row of up to GSR_RESIZE_MAX_TENSORS tensors in one launch.  Tensor k has N source rows and
+ * nA + nB + 2 nC destination rows of row_bytes bytes each (a multiple of 4; rows are moved in 4-byte words); dst is a fresh buffer that
+ * overlaps nothing.  By kind:
+ *   GSR_RESIZE_PARAM          every destination row is the copy of its source row;
+ *   GSR_RESIZE_MOMENT         the rows of A are copies, the rows of B and C are zero (all bits);
+ *   GSR_RESIZE_CHILD_SOURCED  as PARAM, but copy c of the C entry with split rank r is row c * nSplit + r of `child`, a caller tensor of
+ *                             2 nSplit rows (the sampled positions and the shrunken scales of the children).
+ * A tensor with row_bytes == 0, or with src and dst both NULL, is skipped (a zero-width group; moments that do not exist yet).
+ * Every row number read from the plan is compared with N (a rank: with nSplit) before it is used as an address; an entry that fails writes
+ * its destination row as zeros and sets meta[GSR_RESIZE_META_STATUS] to 1.  A wrong plan is a status, never an access out of bounds.
+ * nA + nB + 2 nC == 0 (nothing kept) and N == 0 are not errors: nothing is launched.
+ * GSR_ERR_ARG (before anything is enqueued; gsr_last_error() names the rule): N < 0 or N >= 2^31, meta NULL or misaligned, count < 0 or
+ * beyond GSR_RESIZE_MAX_TENSORS, tensors NULL with count > 0, a count outside the plan's capacity (0 <= nA, nB, nSplit <= N, 0 <= nC <=
+ * nSplit), plan NULL, misaligned or shorter than gsr_resize_plan_bytes(N) when there are rows to write, a row_bytes that is negative, not a
+ * multiple of 4 or 2^31 and more, an unknown kind, src without dst or the reverse, a misaligned src / dst / child, a CHILD_SOURCED tensor
+ * without child when nC > 0. */
+#define GSR_RESIZE_KEEP 1
+#define GSR_RESIZE_CLONE 2
+#define GSR_RESIZE_SPLIT 4
+#define GSR_RESIZE_CHILD 8
+#define GSR_RESIZE_PARAM 0
+#define GSR_RESIZE_MOMENT 1
+#define GSR_RESIZE_CHILD_SOURCED 2
+#define GSR_RESIZE_MAX_TENSORS 18
+#define GSR_RESIZE_META_WORDS 8
+#define GSR_RESIZE_META_STATUS 4
+#define GSR_RESIZE_PLAN_SEGMENTS 5
+#define GSR_RESIZE_PLAN_ROWS_A 0
+#define GSR_RESIZE_PLAN_ROWS_B 1
+#define GSR_RESIZE_PLAN_ROWS_C 2
+#define GSR_RESIZE_PLAN_RANK_C 3
+#define GSR_RESIZE_PLAN_SPLIT_ROWS 4
+typedef struct GsrResizeTensor {
+    const void* src;      /* [N, row_bytes] */
+    void* dst;            /* [nA + nB + 2 nC, row_bytes] */
+    const void* child;    /* [2 nSplit, row_bytes]: GSR_RESIZE_CHILD_SOURCED only, NULL otherwise */
+    int64_t row_bytes;
+    int32_t kind;
+    int32_t reserved;
+} GsrResizeTensor;
+size_t gsr_resize_scratch_bytes(int64_t N);
+size_t gsr_resize_plan_bytes(int64_t N);
+int    gsr_resize_plan(const uint8_t* flags /*[N]*/, int64_t N, void* plan, size_t plan_bytes, int64_t* meta /*device, 8 x int64*/,
+                       void* scratch, size_t scratch_bytes, void* stream);
+int    gsr_resize_apply(const void* plan, size_t plan_bytes, int64_t N, int64_t nA, int64_t nB, int64_t nC, int64_t nSplit,
+                        const GsrResizeTensor* tensors, int32_t count, int64_t* meta, void* stream);
 
 /* Measurement hook (bench.py roofline.peak_measured): float4 streaming copy of `bytes` bytes (a multiple of 16, 16-byte aligned
  * pointers) with `blocks` workgroups of 256 threads.  variant 0 = plain loads / stores, 1 = nt bit, 2 = four loads in flight per

@@ -410,3 +410,182 @@ class StubTrainer:
         if load_depth:
             self._want_depth(idx, frame, floor=self.near)
         return cam
+
+
+# ---- the model's surgery: densify / prune as the unmodified trainer runs it -----------------------------------------------------------------
+# Written from what `HTGaussianModel`'s surgery methods DO (/root/reference/scene/gaussian_model_ht.py:468-474, :532-716), in this file's own
+# words: the method and attribute names are the interface (the trainer calls them, `gsr_autopatch` replaces two of them and reads the rest),
+# the statements are this file's.  Tensors are created on the model's own device, so the same class runs on the CPU for the dispatch tests.
+def build_rotation(q):
+    """Rotation matrices [n,3,3] of raw quaternions [n,4] in (w,x,y,z) order; each is divided by its length first (the length formed as the
+    root of the four squares added left to right, the arithmetic of the reference's helper of this name in utils/general_utils.py)."""
+    length = torch.sqrt(q[:, 0] * q[:, 0] + q[:, 1] * q[:, 1] + q[:, 2] * q[:, 2] + q[:, 3] * q[:, 3])
+    w, x, y, z = (q / length[:, None]).unbind(1)
+    rows = (1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y),
+            2 * (x * y + w * z), 1 - 2 * (x * x + z * z), 2 * (y * z - w * x),
+            2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y))
+    return torch.stack(rows, dim=1).reshape(-1, 3, 3)
+
+
+def logit(p):
+    return torch.log(p / (1 - p))
+
+
+SURGERY_GROUPS = (("xyz", "_xyz", 0.00016), ("f_dc", "_features_dc", 0.0025), ("f_rest", "_features_rest", 0.0025 / 20.0),
+                  ("opacity", "_opacity", 0.05), ("scaling", "_scaling", 0.005), ("rotation", "_rotation", 0.001))
+
+
+class StubSurgeryModel:
+    """Stand-in for `HTGaussianModel` as far as densification goes: the six raw tensors as `nn.Parameter` leaves, the optimizer over the six
+    named groups (optimizer="adam": the stock torch.optim.Adam, "fused": this library's FusedAdam, both `lr=0.0, eps=1e-15` with per-group
+    rates), the three statistics tensors, `percent_dense`, the activations, and the surgery methods with the reference's sequence of torch
+    operations: boolean indexing and `torch.cat` tensor by tensor, the optimizer's state re-keyed group by group, fresh parameters every
+    time.  It is the unpatched arm `gsr_autopatch`'s `densify_and_prune` / `prune_points` are compared with and timed against, and also
+    carries the attributes the patched render reads (`active_sh_degree`, the pose switches, `get_xyz`).
+
+    One deliberate difference: where the reference writes `.squeeze()` on an [N,1] tensor this class squeezes the last axis only, so that
+    a model of ONE row keeps a mask of shape [1] (the reference's 0-d mask would index a new axis into every tensor)."""
+
+    def __init__(self, raw, optimizer="adam", percent_dense=0.01, active_sh_degree=None):
+        self.scaling_activation, self.scaling_inverse_activation = torch.exp, torch.log
+        self.opacity_activation, self.inverse_opacity_activation = torch.sigmoid, logit
+        self.rotation_activation = torch.nn.functional.normalize
+        for _, attr, _ in SURGERY_GROUPS:
+            setattr(self, attr, torch.nn.Parameter(raw[attr].detach().clone().contiguous().requires_grad_(True)))
+        n, dev = self._xyz.shape[0], self._xyz.device
+        self.max_sh_degree = int(round(math.sqrt(self._features_rest.shape[1] + 1))) - 1
+        self.active_sh_degree = self.max_sh_degree if active_sh_degree is None else int(active_sh_degree)
+        self.percent_dense = percent_dense
+        self.empty_cache = True               # the reference ends densify_and_prune / prune with torch.cuda.empty_cache(); False: a timing arm without it
+        self.rotate_xyz = self.rotate_seq = False
+        self.seq_idx, self.P = 0, None
+        self.xyz_gradient_accum = torch.zeros((n, 1), device=dev)
+        self.denom = torch.zeros((n, 1), device=dev)
+        self.max_radii2D = torch.zeros((n,), device=dev)
+        groups = [{"params": [getattr(self, attr)], "lr": lr, "name": name} for name, attr, lr in SURGERY_GROUPS]
+        if optimizer == "fused":
+            from .optim import FusedAdam
+            self.optimizer = FusedAdam(groups, lr=0.0, eps=1e-15)
+        elif optimizer == "adam":
+            from torch.optim.adam import Adam          # (the stock class, also while gsr_autopatch has redirected `torch.optim.Adam`)
+            self.optimizer = Adam(groups, lr=0.0, eps=1e-15)
+        else:
+            raise ValueError("StubSurgeryModel: optimizer is 'adam' or 'fused'")
+
+    get_xyz = property(lambda s: s._xyz)
+    get_scaling = property(lambda s: s.scaling_activation(s._scaling))
+    get_rotation = property(lambda s: s.rotation_activation(s._rotation))
+    get_opacity = property(lambda s: s.opacity_activation(s._opacity))
+    get_features = property(lambda s: torch.cat((s._features_dc, s._features_rest), dim=1))
+
+    def get_RT(self, idx=None):
+        return torch.eye(4, device=self._xyz.device)
+
+    def add_densification_stats(self, viewspace_point_tensor, update_filter):
+        self.xyz_gradient_accum[update_filter] += torch.norm(viewspace_point_tensor.grad[update_filter, :2], dim=-1, keepdim=True)
+        self.denom[update_filter] += 1
+
+    # -- the optimizer's side of every resize: one group at a time ------------------------------------------------------------------------
+    def _regroup(self, group, new_tensor, moments):
+        """`new_tensor` becomes the group's parameter (a fresh `nn.Parameter`); a group that has optimizer state keeps the state's dict,
+        re-keyed, with both moments passed through `moments`; a group without state stays without."""
+        old = group["params"][0]
+        st = self.optimizer.state.get(old, None)
+        if st is not None:
+            st["exp_avg"], st["exp_avg_sq"] = moments(st["exp_avg"]), moments(st["exp_avg_sq"])
+            del self.optimizer.state[old]
+        group["params"][0] = torch.nn.Parameter(new_tensor.requires_grad_(True))
+        if st is not None:
+            self.optimizer.state[group["params"][0]] = st
+        return group["params"][0]
+
+    def _adopt(self, by_name):
+        for name, attr, _ in SURGERY_GROUPS:
+            if name in by_name:
+                setattr(self, attr, by_name[name])
+
+    def replace_tensor_to_optimizer(self, tensor, name):
+        return {g["name"]: self._regroup(g, tensor, lambda m: torch.zeros_like(tensor))
+                for g in self.optimizer.param_groups if g["name"] == name}
+
+    def _prune_optimizer(self, mask):
+        return {g["name"]: self._regroup(g, g["params"][0][mask], lambda m: m[mask]) for g in self.optimizer.param_groups}
+
+    def prune_points(self, mask):
+        keep = ~mask
+        self._adopt(self._prune_optimizer(keep))
+        self.xyz_gradient_accum = self.xyz_gradient_accum[keep]
+        self.denom = self.denom[keep]
+        self.max_radii2D = self.max_radii2D[keep]
+
+    def cat_tensors_to_optimizer(self, tensors_dict):
+        out = {}
+        for g in self.optimizer.param_groups:
+            assert len(g["params"]) == 1
+            ext = tensors_dict[g["name"]]
+            out[g["name"]] = self._regroup(g, torch.cat((g["params"][0], ext), dim=0), lambda m, ext=ext: torch.cat((m, torch.zeros_like(ext)), dim=0))
+        return out
+
+    def densification_postfix(self, new_xyz, new_features_dc, new_features_rest, new_opacities, new_scaling, new_rotation):
+        self._adopt(self.cat_tensors_to_optimizer({"xyz": new_xyz, "f_dc": new_features_dc, "f_rest": new_features_rest,
+                                                   "opacity": new_opacities, "scaling": new_scaling, "rotation": new_rotation}))
+        n, dev = self.get_xyz.shape[0], self._xyz.device
+        self.xyz_gradient_accum = torch.zeros((n, 1), device=dev)
+        self.denom = torch.zeros((n, 1), device=dev)
+        self.max_radii2D = torch.zeros((n,), device=dev)
+
+    # -- the selections ---------------------------------------------------------------------------------------------------------------------
+    def densify_and_clone(self, grads, grad_threshold, scene_extent):
+        sel = torch.where(torch.norm(grads, dim=-1) >= grad_threshold, True, False)
+        sel = torch.logical_and(sel, torch.max(self.get_scaling, dim=1).values <= self.percent_dense * scene_extent)
+        self.densification_postfix(self._xyz[sel], self._features_dc[sel], self._features_rest[sel], self._opacity[sel],
+                                   self._scaling[sel], self._rotation[sel])
+
+    def densify_and_split(self, grads, grad_threshold, scene_extent, N=2):
+        n, dev = self.get_xyz.shape[0], self._xyz.device
+        padded = torch.zeros((n,), device=dev)
+        padded[:grads.shape[0]] = grads.squeeze(-1)          # rows appended by the clone step count as zero
+        sel = torch.where(padded >= grad_threshold, True, False)
+        sel = torch.logical_and(sel, torch.max(self.get_scaling, dim=1).values > self.percent_dense * scene_extent)
+        stds = self.get_scaling[sel].repeat(N, 1)
+        means = torch.zeros((stds.size(0), 3), device=dev)
+        samples = torch.normal(mean=means, std=stds)
+        rots = build_rotation(self._rotation[sel]).repeat(N, 1, 1)
+        new_xyz = torch.bmm(rots, samples.unsqueeze(-1)).squeeze(-1) + self.get_xyz[sel].repeat(N, 1)
+        new_scaling = self.scaling_inverse_activation(self.get_scaling[sel].repeat(N, 1) / (0.8 * N))
+        self.densification_postfix(new_xyz, self._features_dc[sel].repeat(N, 1, 1), self._features_rest[sel].repeat(N, 1, 1),
+                                   self._opacity[sel].repeat(N, 1), new_scaling, self._rotation[sel].repeat(N, 1))
+        self.prune_points(torch.cat((sel, torch.zeros(N * sel.sum(), device=dev, dtype=torch.bool))))
+
+    def _mean_gradient(self):
+        grads = self.xyz_gradient_accum / self.denom
+        grads[grads.isnan()] = 0.0
+        return grads
+
+    def _removal_mask(self, min_opacity, extent, max_screen_size):
+        mask = (self.get_opacity < min_opacity).squeeze(-1)
+        if max_screen_size:
+            too_big_on_screen = self.max_radii2D > max_screen_size
+            too_big_in_world = self.get_scaling.max(dim=1).values > 0.1 * extent
+            mask = torch.logical_or(torch.logical_or(mask, too_big_on_screen), too_big_in_world)
+        return mask
+
+    def densify(self, max_grad, min_opacity, extent, max_screen_size):
+        grads = self._mean_gradient()
+        self.densify_and_clone(grads, max_grad, extent)
+        self.densify_and_split(grads, max_grad, extent)
+
+    def densify_and_prune(self, max_grad, min_opacity, extent, max_screen_size):
+        self.densify(max_grad, min_opacity, extent, max_screen_size)
+        self.prune_points(self._removal_mask(min_opacity, extent, max_screen_size))
+        if self._xyz.is_cuda and self.empty_cache:
+            torch.cuda.empty_cache()
+
+    def prune(self, max_grad, min_opacity, extent, max_screen_size):
+        self.prune_points(self._removal_mask(min_opacity, extent, max_screen_size))
+        if self._xyz.is_cuda and self.empty_cache:
+            torch.cuda.empty_cache()
+
+    def reset_opacity(self):
+        capped = torch.min(self.get_opacity, torch.ones_like(self.get_opacity) * 0.01)
+        self._adopt(self.replace_tensor_to_optimizer(self.inverse_opacity_activation(capped), "opacity"))

@@ -67,6 +67,21 @@ Importing this module BEFORE the trainer swaps both for the HIP kernels of this 
     `get_RT(fidx).detach().cpu()` no longer waits for the device; `.numpy()`, an operation with a genuine CPU tensor and the original
     loader get the host values at the old cost.  `GSR_AUTOPATCH_FRAMES=0` leaves both methods alone.
 
+  * `scene.gaussian_model_ht.HTGaussianModel.densify_and_prune` and `prune_points` (/root/reference/scene/gaussian_model_ht.py:548-695;
+    the trainer's call at ht3dgs_trainer.py:152-153, `merge_two_3DGS`'s at :241; patched when that module is imported, now or later):
+    the selections stay torch statements on the model's own properties (`get_scaling`, `get_opacity`, `scaling_inverse_activation`,
+    the module's `build_rotation`), become one flag byte per row, and gsr_resize_plan / gsr_resize_apply (resize.py) move every
+    parameter and moment in one launch after ONE host wait; the reference's boolean indexing and `torch.cat` per tensor wait 59 times
+    per `densify_and_prune` and 21 times per `prune_points`.  Same rows in the same order, fresh `nn.Parameter`s without .grad, state
+    dicts re-keyed with `step` kept, statistics zeroed, the same children from the same draw of the default CUDA generator,
+    `torch.cuda.empty_cache()` last (`GSR_AUTOPATCH_EMPTY_CACHE=0`: not called; default 1, the reference's behaviour).  A
+    `max_grad` that is not positive, an optimizer that is not exactly the six named groups of one parameter each, a CPU, non-float32,
+    non-contiguous or wrongly sized tensor, N = 0, moments unlike their parameter or a `mask` that is not a bool tensor [N] run the
+    ORIGINAL method.  Measured on one MI355X with `empty_cache()` in both arms (tools/trainer_resize_probe.py,
+    profiles/trainer_resize.txt): densify_and_prune 13.27 -> 2.89 ms at 1 M / degree 3, 7.93 -> 1.51 at 300 k / degree 3, 6.82 -> 1.08
+    at 130 k / degree 0, beyond the same-arm spread (<= 0.40 ms) at all three sizes -- GSR_AUTOPATCH_RESIZE: ships ON
+    (`GSR_AUTOPATCH_RESIZE=0` leaves both methods alone).
+
 `apply()` / `remove()` switch the patches on and off (importing the module calls `apply()`); `GSR_AUTOPATCH=0` disables them.
 The rasterizer itself needs no patch: `diff_gaussian_rasterization` IS this library's drop-in package.
 """
@@ -788,6 +803,186 @@ def _patch_frames_module(mod):
         setattr(cls, attr, fn)
 
 
+# ---- HTGaussianModel.densify_and_prune / prune_points: the model resized by the resize kernels ------------------------------------------
+# The reference's surgery (/root/reference/scene/gaussian_model_ht.py:548-695) is boolean indexing and `torch.cat` tensor by tensor -- an
+# append for the clones, an append for the split children, a prune of the split parents, a final prune -- every boolean index a `nonzero`
+# with a host wait.  The two methods below make the SAME selections with the model's own torch statements, turn them into one flag byte
+# per row and hand the rows to gsr_resize_plan / gsr_resize_apply (resize.py): one host wait, one launch per call that moves every
+# parameter and moment.  The kernels order rows and copy bytes; every float is computed by torch, from the model's own activations.
+_patched_resize_classes = []        # [(class, attribute, original function)]
+_GROUP_ATTR = dict(zip(FUSED_NAMES, RAW_NAMES))
+_STAT_NAMES = ("xyz_gradient_accum", "denom", "max_radii2D")
+_RESIZE_DEFAULT = "1"
+
+
+def _resize():
+    return importlib.import_module("3dgs_hierarchical_training_amd.resize")
+
+
+def _resize_original(self, attr):
+    orig = next((f for c, a, f in _patched_resize_classes if a == attr and isinstance(self, c)), None)
+    if orig is None:
+        raise RuntimeError(f"gsr_autopatch: this call needs the original HTGaussianModel.{attr}")
+    return orig
+
+
+def _resize_entries(self):
+    """[(group, attribute, parameter, state or None)] in the optimizer's group order when the model has the layout the resize kernels take,
+    else None: exactly the six named groups of one parameter each, which are the model's six raw tensors; those, the moments that exist and
+    the three statistics tensors float32, contiguous, N rows, on one device (the GPU); 0 < N < 2^31."""
+    if os.environ.get("GSR_AUTOPATCH_RESIZE", _RESIZE_DEFAULT) == "0":
+        return None
+    opt = getattr(self, "optimizer", None)
+    groups = getattr(opt, "param_groups", None)
+    if groups is None or not hasattr(opt, "state") or len(groups) != 6 or sorted(g.get("name", "") for g in groups) != sorted(FUSED_NAMES):
+        return None
+    x = getattr(self, "_xyz", None)
+    if not torch.is_tensor(x) or x.dim() != 2 or (_REQUIRE_CUDA and not x.is_cuda):
+        return None
+    n = x.shape[0]
+    if not 0 < n < 2 ** 31:
+        return None
+    ok = lambda t, shape=None: torch.is_tensor(t) and t.dtype == torch.float32 and t.device == x.device and t.is_contiguous() and \
+        t.dim() >= 1 and t.shape[0] == n and (shape is None or t.shape == shape)
+    entries = []
+    for g in groups:
+        ps = g["params"]
+        if torch.is_tensor(ps) or len(ps) != 1 or ps[0] is not getattr(self, _GROUP_ATTR[g["name"]], None) or not ok(ps[0]):
+            return None
+        st = opt.state.get(ps[0], None)
+        if st is not None and not (ok(st.get("exp_avg"), ps[0].shape) and ok(st.get("exp_avg_sq"), ps[0].shape)):
+            return None
+        entries.append((g, _GROUP_ATTR[g["name"]], ps[0], st))
+    if not all(ok(getattr(self, k, None)) for k in _STAT_NAMES):
+        return None
+    return entries
+
+
+def _install_resized(self, entries, out):
+    """What the reference's `_prune_optimizer` / `cat_tensors_to_optimizer` leave behind, from the tensors of one gsr_resize_apply: every
+    parameter a fresh `nn.Parameter` leaf (`.grad` None), the group's state dict re-keyed to it with `step` kept and the moments replaced."""
+    opt, out = self.optimizer, iter(out)
+    for g, attr, old, st in entries:
+        new = torch.nn.Parameter(next(out).requires_grad_(True))
+        if st is not None:
+            st["exp_avg"], st["exp_avg_sq"] = next(out), next(out)
+            del opt.state[old]
+            opt.state[new] = st
+        g["params"][0] = new
+        setattr(self, attr, new)
+
+
+def _resize_sources(entries, children=None):
+    """The table of one gsr_resize_apply over the parameters and the moments that exist: (src, kinds, child); `children` maps a group's name
+    to the [2 nSplit, ...] rows its surviving split children take."""
+    R = _resize()
+    src, kinds, child = [], [], []
+    for g, attr, p, st in entries:
+        rows = (children or {}).get(g["name"])
+        src.append(p.detach()); kinds.append(R.PARAM if rows is None else R.CHILD_SOURCED); child.append(rows)
+        if st is not None:
+            src += [st["exp_avg"], st["exp_avg_sq"]]; kinds += [R.MOMENT, R.MOMENT]; child += [None, None]
+    return src, kinds, child
+
+
+def _normal_draw(mean, std):
+    """The reference's draw `torch.normal(mean=mean, std=std)` on the default generator, taken apart: torch evaluates that call as a standard
+    normal fill of the output, times `std`, plus `mean` -- after a validity check of `std` (all >= 0) that reads the device back, twice in
+    this build, which would make three host waits of the call's one.  `std` here is the model's own scaling activation.  The same samples
+    and the same generator state to the bit: the tests hold this against the arm that calls `torch.normal` itself."""
+    return torch.empty_like(std).normal_(0.0, 1.0).mul_(std).add_(mean)
+
+
+def prune_points_fused(self, mask):
+    """Drop-in body of `HTGaussianModel.prune_points` (/root/reference/scene/gaussian_model_ht.py:548-582): the rows where `mask` is True
+    leave the six parameters, the moments that exist and the three statistics tensors.  One host wait (the row count) and two launches of
+    gsr_resize_apply -- the parameters with their moments, then the statistics -- instead of 21 boolean-index gathers."""
+    entries = _resize_entries(self)
+    if entries is None or not (isinstance(mask, torch.Tensor) and mask.dtype == torch.bool and mask.dim() == 1 and
+                               mask.shape[0] == self._xyz.shape[0] and mask.device == self._xyz.device):
+        return _resize_original(self, "prune_points")(self, mask)
+    R = _resize()
+    with torch.no_grad():
+        n = self._xyz.shape[0]
+        flags = ((~mask.as_subclass(torch.Tensor)).to(torch.uint8) * R.KEEP).contiguous()
+        plan, meta = R.resize_plan(flags)
+        counts = R.read_counts(meta)                                   # the call's one host wait
+        src, kinds, child = _resize_sources(entries)
+        _install_resized(self, entries, R.resize_apply(plan, meta, n, counts, src, kinds, child))
+        stats = R.resize_apply(plan, meta, n, counts, [getattr(self, k) for k in _STAT_NAMES], [R.PARAM] * 3)      # (21 tensors exceed one table)
+        for k, t in zip(_STAT_NAMES, stats):
+            setattr(self, k, t)
+
+
+def densify_and_prune_fused(self, max_grad, min_opacity, extent, max_screen_size):
+    """Drop-in body of `HTGaussianModel.densify_and_prune` (/root/reference/scene/gaussian_model_ht.py:631-695).  Every selection is the
+    reference's own statement evaluated on the N rows the call starts with; what the reference decides about a row it appended follows from
+    the row it was copied from:
+      * a clone carries its parent's parameters, so the final prune removes it iff it removes the parent;
+      * a cloned row is never split: its padded gradient is 0 and max_grad > 0 (anything else runs the original);
+      * a split parent is removed right after its children were appended, whatever the final prune thinks of it;
+      * a child has its parent's opacity and the scale get_scaling / (0.8 * 2) taken through the model's inverse activation and its
+        activation, and `max_radii2D` is all zeros at the final prune.
+    The rows come out as the reference's append / append / prune / prune leaves them: kept rows, clones, children copy 0, children copy 1.
+    The children's positions and scales are the reference's statements on index_select(split rows) -- the same shapes, also when nothing is
+    split, and the same draw on the default generator as the reference's `torch.normal(mean=zeros, std=stds)` (`_normal_draw`)."""
+    entries = _resize_entries(self)
+    helpers = sys.modules.get(type(self).__module__)
+    build_rotation = getattr(helpers, "build_rotation", None)
+    if entries is None or not max_grad > 0 or build_rotation is None or \
+            not all(hasattr(self, k) for k in ("get_scaling", "get_opacity", "scaling_activation", "scaling_inverse_activation", "percent_dense")):
+        return _resize_original(self, "densify_and_prune")(self, max_grad, min_opacity, extent, max_screen_size)
+    R = _resize()
+    with torch.no_grad():
+        n, dev = self._xyz.shape[0], self._xyz.device
+        grads = self.xyz_gradient_accum / self.denom
+        grads[grads.isnan()] = 0.0
+        scaling = self.get_scaling
+        smax = torch.max(scaling, dim=1).values
+        clone = torch.logical_and(torch.norm(grads, dim=-1) >= max_grad, smax <= self.percent_dense * extent)
+        split = torch.logical_and(grads.squeeze(-1) >= max_grad, smax > self.percent_dense * extent)
+        gone = (self.get_opacity < min_opacity).squeeze(-1)              # the final prune's predicate on a row as it stands
+        child_gone = gone
+        if max_screen_size:
+            on_screen = bool(0.0 > max_screen_size)                      # (max_radii2D is all zeros at the final prune)
+            gone = gone | on_screen | (smax > 0.1 * extent)
+            child_scaling = self.scaling_activation(self.scaling_inverse_activation(scaling / (0.8 * 2)))
+            child_gone = child_gone | on_screen | (child_scaling.max(dim=1).values > 0.1 * extent)
+        flags = ((~split & ~gone).to(torch.uint8) * R.KEEP + (clone & ~gone).to(torch.uint8) * R.CLONE
+                 + split.to(torch.uint8) * R.SPLIT + (split & ~child_gone).to(torch.uint8) * R.CHILD)
+        plan, meta = R.resize_plan(flags)
+        counts = R.read_counts(meta)                                     # the call's one host wait
+        nA, nB, nC, nS = counts[:4]
+        rows = R.plan_segment(plan, n, R.L.GSR_RESIZE_PLAN_SPLIT_ROWS, nS)
+        parent_scaling = scaling.index_select(0, rows)
+        stds = parent_scaling.repeat(2, 1)
+        means = torch.zeros((stds.size(0), 3), device=dev)
+        samples = _normal_draw(means, stds)
+        rots = build_rotation(self._rotation.index_select(0, rows)).repeat(2, 1, 1)
+        positions = getattr(self, "get_xyz", self._xyz)                  # (the posed means where the model poses them, as the reference reads them)
+        children = {"xyz": torch.bmm(rots, samples.unsqueeze(-1)).squeeze(-1) + positions.index_select(0, rows).repeat(2, 1),
+                    "scaling": self.scaling_inverse_activation(parent_scaling.repeat(2, 1) / (0.8 * 2))}
+        src, kinds, child = _resize_sources(entries, children if nS else None)
+        _install_resized(self, entries, R.resize_apply(plan, meta, n, counts, src, kinds, child))
+        nout = nA + nB + 2 * nC
+        self.xyz_gradient_accum = torch.zeros((nout, 1), device=dev)
+        self.denom = torch.zeros((nout, 1), device=dev)
+        self.max_radii2D = torch.zeros((nout,), device=dev)
+        if dev.type == "cuda" and os.environ.get("GSR_AUTOPATCH_EMPTY_CACHE", "1") != "0":
+            torch.cuda.empty_cache()
+
+
+def _patch_resize_module(mod):
+    if os.environ.get("GSR_AUTOPATCH_RESIZE", _RESIZE_DEFAULT) == "0":
+        return
+    cls = getattr(mod, "HTGaussianModel", None)
+    for attr, fn in (("densify_and_prune", densify_and_prune_fused), ("prune_points", prune_points_fused)):
+        if cls is None or not hasattr(cls, attr) or any(c is cls and a == attr for c, a, _ in _patched_resize_classes):
+            continue
+        _patched_resize_classes.append((cls, attr, getattr(cls, attr)))
+        setattr(cls, attr, fn)
+
+
 # ---- utils.image_utils.psnr: the training PSNR the trainer evaluates on every iteration (ht3dgs_trainer.py:138) ---------------------
 IMAGE_UTILS_MODULES = ("utils.image_utils",)
 _patched_psnr = []                  # [(module, attribute, original function)]
@@ -831,9 +1026,10 @@ def _patch_loss_module(mod):
 
 
 def _patch_render_and_pose_module(mod):
-    """`scene.gaussian_model_ht` holds both the render wrapper and `HTGaussianModel.get_RT`."""
+    """`scene.gaussian_model_ht` holds the render wrapper, `HTGaussianModel.get_RT` and the model's surgery."""
     _patch_render_module(mod)
     _patch_frames_module(mod)
+    _patch_resize_module(mod)
 
 
 class _PostImportFinder(importlib.abc.MetaPathFinder):
@@ -919,6 +1115,9 @@ def remove():
         setattr(cls, attr, fn)
     while _patched_frame_classes:
         cls, attr, fn = _patched_frame_classes.pop()
+        setattr(cls, attr, fn)
+    while _patched_resize_classes:
+        cls, attr, fn = _patched_resize_classes.pop()
         setattr(cls, attr, fn)
 
 

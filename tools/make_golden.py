@@ -17,6 +17,8 @@ What it pins, and with what:
     python_sh.npz      CF3DGS_Render.render(cam, convert_SHs_python=True) with view_dependent (gaussian_model_ht.py:845-865):
                        the colors_precomp and means3D it hands to the rasterizer, for degree-3 models under non-identity
                        frame poses (refstub's SE3 standing in for lietorch), rotate_seq on and off, uid != seq_idx
+    trainer_resize.npz HTGaussianModel.densify_and_prune / prune_points (gaussian_model_ht.py:548-695) run on the CPU: four small models
+                       before and after, optimizer moments and statistics included, and the samples torch.normal drew
   self-generated regression vectors (our oracle, NOT the reference -- parity unpinned, see oracle header):
     oracle_c1_deg0.npz, oracle_small_deg3.npz   full forward + backward of oracle/gsr_oracle.c
 
@@ -396,6 +398,131 @@ def gen_depth_loss(out):
     np.savez_compressed(os.path.join(out, "depth_loss.npz"), **res)
 
 
+TRAINER_RESIZE_GROUPS = (("xyz", "_xyz"), ("f_dc", "_features_dc"), ("f_rest", "_features_rest"), ("opacity", "_opacity"),
+                         ("scaling", "_scaling"), ("rotation", "_rotation"))
+
+
+def trainer_resize_inputs(case, seed):
+    """Inputs of one case of trainer_resize.npz, numpy float32: the six raw tensors, the three statistics tensors and the call's arguments.
+    Every quantity a selection compares is drawn from values well apart from its threshold (and `refuse_near_threshold` checks it)."""
+    rng = np.random.default_rng(seed)
+    n, coeffs = {"a": (96, 16), "b": (77, 1), "c": (128, 16), "d": (101, 16)}[case]
+    extent = {"a": 4.0, "b": 4.0, "c": 0.5, "d": 4.0}[case]
+    args = {"max_grad": 0.0002, "min_opacity": 0.005, "extent": extent, "max_screen_size": {"a": 20.0, "b": 0.0, "c": 20.0, "d": 0.0}[case],
+            "percent_dense": 0.01}
+    # the largest scale per row from five bands relative to the extent: small (cloned when hot), split with surviving children, split with
+    # children above the world-size ceiling (parent scale / 1.6 > 0.1 extent), and far above it
+    band = rng.integers(0, 5, n)
+    smax = extent * np.choose(band, [0.002, 0.006, 0.03, 0.13, 0.4]) * rng.uniform(0.88, 1.12, n)
+    scales = smax[:, None] * np.where(np.arange(3)[None] == rng.integers(0, 3, n)[:, None], 1.0, rng.uniform(0.2, 0.9, (n, 3)))
+    d = {"_xyz": rng.uniform(-2, 2, (n, 3)), "_features_dc": rng.normal(0, 0.5, (n, 1, 3)), "_features_rest": rng.normal(0, 0.1, (n, coeffs - 1, 3)),
+         "_opacity": np.where(rng.random(n) < 0.12, rng.uniform(-8.0, -6.5, n), rng.uniform(-2.0, 3.0, n))[:, None], "_scaling": np.log(scales),
+         "_rotation": rng.normal(0, 1, (n, 4))}
+    denom = rng.integers(0, 5, (n, 1)).astype(np.float64)
+    hot = rng.random((n, 1)) < 0.4
+    mean = np.where(hot, rng.uniform(0.0004, 0.002, (n, 1)), rng.uniform(0.0, 0.0001, (n, 1)))
+    d["xyz_gradient_accum"] = mean * denom                          # (denom 0: 0 / 0, the NaN the reference zeroes)
+    d["denom"] = denom
+    d["max_radii2D"] = np.where(rng.random(n) < 0.3, rng.uniform(25, 60, n), rng.uniform(0, 15, n))
+    d = {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in d.items()}
+    if case == "d":
+        d["mask"] = rng.random(n) < 0.5
+    return d, args
+
+
+def refuse_near_threshold(d, args, rel=1e-3):
+    """A last-bit difference of exp / sigmoid between machines must not flip a decision: every compared quantity, evaluated in float64,
+    lies further than `rel` (relative) from its threshold."""
+    def far(values, threshold, what):
+        values = np.asarray(values, dtype=np.float64)
+        values = values[np.isfinite(values)]
+        if np.any(np.abs(values - threshold) <= rel * abs(threshold)):
+            raise SystemExit(f"gen_trainer_resize: {what} within {rel} of its threshold {threshold}; choose another seed")
+    s = np.exp(d["_scaling"].astype(np.float64)).max(axis=1)
+    with np.errstate(all="ignore"):
+        far(d["xyz_gradient_accum"].astype(np.float64) / d["denom"].astype(np.float64), args["max_grad"], "mean gradient")
+    far(s, args["percent_dense"] * args["extent"], "scale against percent_dense * extent")
+    far(s, 0.1 * args["extent"], "scale against 0.1 * extent")
+    far(s / 1.6, 0.1 * args["extent"], "child scale against 0.1 * extent")
+    far(1.0 / (1.0 + np.exp(-d["_opacity"].astype(np.float64))), args["min_opacity"], "opacity")
+
+
+def gen_trainer_resize(out):
+    """trainer_resize.npz: the reference's own `HTGaussianModel.densify_and_prune` / `prune_points` (scene/gaussian_model_ht.py:548-695), run for
+    real on the CPU under the shim, four cases at N <= 128 -- inputs, outputs and the samples `torch.normal` drew:
+      a  degree 3, one Adam step behind it (moments, step 1), max_screen_size 20
+      b  max_sh_degree 0 (`_features_rest` [N,0,3]), an optimizer that has never stepped (no state), max_screen_size None
+      c  an extent so small that the children of surviving split parents fall to the world-size term
+      d  prune_points of a random mask, non-zero statistics"""
+    from scene.gaussian_model_ht import HTGaussianModel
+    opt_args = types.SimpleNamespace(percent_dense=0.01, position_lr_init=0.00016, position_lr_final=0.0000016, position_lr_delay_mult=0.01,
+                                     position_lr_max_steps=30000, feature_lr=0.0025, opacity_lr=0.05, scaling_lr=0.005, rotation_lr=0.001)
+    res = {"cases": np.array(["a", "b", "c", "d"])}
+    real_normal = torch.normal
+    for seed, case in enumerate(("a", "b", "c", "d"), start=41):
+        d, args = trainer_resize_inputs(case, seed)
+        refuse_near_threshold(d, args)
+        drawn = []
+
+        def recording_normal(*a, **k):
+            drawn.append(real_normal(*a, **k))
+            return drawn[-1]
+        torch.manual_seed(seed)
+        with _CudaToCpu():
+            m = HTGaussianModel(0 if case == "b" else 3)
+            m.spatial_lr_scale, m.P = 1.0, None
+            for _, attr in TRAINER_RESIZE_GROUPS:
+                setattr(m, attr, torch.nn.Parameter(torch.from_numpy(d[attr].copy()).requires_grad_(True)))
+            m.training_setup(opt_args)
+            if case != "b":                                   # one Adam step: moments and step 1
+                g = torch.Generator().manual_seed(seed)
+                for _, attr in TRAINER_RESIZE_GROUPS:
+                    p = getattr(m, attr)
+                    p.grad = torch.randn(p.shape, generator=g) * 0.01
+                m.optimizer.step()
+                m.optimizer.zero_grad(set_to_none=True)
+            for k in ("xyz_gradient_accum", "denom", "max_radii2D"):
+                setattr(m, k, torch.from_numpy(d[k].copy()))
+            pre = case + "_"
+            for name, attr in TRAINER_RESIZE_GROUPS:
+                res[pre + "in" + attr] = t2n(getattr(m, attr)).copy()
+                st = m.optimizer.state.get(getattr(m, attr))
+                res[pre + "in_state_" + name] = np.bool_(st is not None)
+                if st is not None:
+                    res[pre + "in_exp_avg_" + name], res[pre + "in_exp_avg_sq_" + name] = t2n(st["exp_avg"]).copy(), t2n(st["exp_avg_sq"]).copy()
+                    res[pre + "in_step_" + name] = np.float64(float(st["step"]))
+            for k in ("xyz_gradient_accum", "denom", "max_radii2D"):
+                res[pre + "in_" + k] = d[k]
+            for k, v in args.items():
+                res[pre + k] = np.float64(v)
+            torch.normal = recording_normal
+            try:
+                with torch.no_grad():
+                    if case == "d":
+                        res[pre + "mask"] = d["mask"]
+                        m.prune_points(torch.from_numpy(d["mask"].copy()))
+                    else:
+                        m.densify_and_prune(args["max_grad"], args["min_opacity"], args["extent"], args["max_screen_size"] or None)
+            finally:
+                torch.normal = real_normal
+        assert len(drawn) == (0 if case == "d" else 1)
+        if drawn:
+            res[pre + "samples"] = t2n(drawn[0])
+        for name, attr in TRAINER_RESIZE_GROUPS:
+            p = getattr(m, attr)
+            assert type(p) is torch.nn.Parameter and p.grad is None and p.is_leaf and m.optimizer.param_groups[[g["name"] for g in m.optimizer.param_groups].index(name)]["params"][0] is p
+            res[pre + "out" + attr] = t2n(p).copy()
+            st = m.optimizer.state.get(p)
+            assert (st is not None) == bool(res[pre + "in_state_" + name])
+            if st is not None:
+                res[pre + "out_exp_avg_" + name], res[pre + "out_exp_avg_sq_" + name] = t2n(st["exp_avg"]).copy(), t2n(st["exp_avg_sq"]).copy()
+                res[pre + "out_step_" + name] = np.float64(float(st["step"]))
+        for k in ("xyz_gradient_accum", "denom", "max_radii2D"):
+            res[pre + "out_" + k] = t2n(getattr(m, k)).copy()
+        print(f"gen_trainer_resize {case}: N {d['_xyz'].shape[0]} -> {getattr(m, '_xyz').shape[0]}" + (f", {drawn[0].shape[0] // 2} split" if drawn else ""))
+    np.savez_compressed(os.path.join(out, "trainer_resize.npz"), **res)
+
+
 def gen_oracle(out):
     sys.path.insert(0, REPO)
     syn = importlib.import_module("3dgs_hierarchical_training_amd.synthetic")
@@ -447,7 +574,8 @@ def main():
         gen_python_sh(OUT, captured)
         return
     if args.only:
-        {"gen_depth_loss": gen_depth_loss, "gen_loss": gen_loss, "gen_camera_general": gen_camera_general}[args.only](OUT)
+        {"gen_depth_loss": gen_depth_loss, "gen_loss": gen_loss, "gen_camera_general": gen_camera_general,
+         "gen_trainer_resize": gen_trainer_resize}[args.only](OUT)
         return
     gen_sh(OUT)
     gen_cov3d(OUT)
@@ -457,6 +585,7 @@ def main():
     gen_python_sh(OUT, captured)
     gen_loss(OUT)
     gen_depth_loss(OUT)
+    gen_trainer_resize(OUT)
     gen_oracle(OUT)
     for f in sorted(os.listdir(OUT)):
         print(f, os.path.getsize(os.path.join(OUT, f)))

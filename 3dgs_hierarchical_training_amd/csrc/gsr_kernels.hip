@@ -36,6 +36,7 @@
 #include "adam_math.h"
 #include "radix_sort.h"
 #include "blend_common.h"
+#include "options.h"
 
 #ifndef GSR_K9_UNROLL
 #define GSR_K9_UNROLL 2
@@ -51,16 +52,6 @@ namespace gsr {
 // small helpers
 // ------------------------------------------------------------------------------------------------
 static thread_local char g_err[512] = "";
-// prepare in backward: up to this many Gaussians the per-Gaussian backward kernel also counts the digits of the next depth sort
-// (saves that sort's histogram launch: ~7 us + a launch gap on small models); above, its ~2 global adds per key cost more inside
-// the HBM-bound kernel than the histogram kernel does on its own (1 M: +20 us against -8 us).  Both sides of the hand-over
-// evaluate the same predicate on N.
-static int g_prep_hist_max_n = 262144;
-static int g_small_sort9 = 1;   // smallest N for which a forward with its own preprocess sorts depths in three 9-bit passes (0 = only above prep_hist_max_n).
-                                // Measured (same-box A/B, tools/ab_130k.sh): depth sort 53 -> 45 us at 130 k, 44 -> 37 us at 20 k
-static inline bool prep_counts_digits(int N) { return N <= g_prep_hist_max_n; }
-static int g_poll_iters = 400000;   // bound of gsr_forward's busy-wait for R in units of ~50 ns (20 ms); 0 = no polling: hipStreamSynchronize at once
-static int g_emit_hist = 1;   // 1: k_emit counts the tile sort's digits (no histogram launch); 0: k_radix_ghist
 
 static int fail(int code, const char* fmt, const char* detail = "")
 {
@@ -91,7 +82,7 @@ enum ProfId { P_PRE_FWD, P_SORT_DEPTH, P_SCAN, P_EMIT, P_SORT_TILE, P_RANGES, P_
               P_IMP_BLEND, P_IMP_FINISH, P_COUNT };
 static const char* kProfNames[P_COUNT] = {"preprocess_fwd", "sort_depth", "scan", "emit", "sort_tile", "ranges",
                                           "blend_fwd", "blend_bwd", "preprocess_bwd", "cut_repair", "importance_blend", "importance_finish"};
-static int g_profile = 0;
+static std::atomic<int> g_profile{0};   // "profile": not in Options, every stage's ProfScope reads it as it is at that moment
 static std::atomic<unsigned> g_profile_tick{0};   // mode 3: every third launch of the forward blend is timed
 struct ProfPair { hipEvent_t a, b; };
 static std::mutex g_prof_mutex;
@@ -100,7 +91,8 @@ struct ProfScope {
     int id; hipStream_t st; hipEvent_t a = nullptr, b = nullptr;
     ProfScope(int id_, hipStream_t st_) : id(id_), st(st_)
     {
-        if (!g_profile || id >= P_COUNT || (g_profile >= 2 && id != P_BLEND_FWD)) return;
+        const int mode = g_profile.load(std::memory_order_relaxed);
+        if (!mode || id >= P_COUNT || (mode >= 2 && id != P_BLEND_FWD)) return;
         if (hipEventCreate(&a) != hipSuccess || hipEventCreate(&b) != hipSuccess) { a = b = nullptr; return; }
         (void)hipEventRecord(a, st);
     }
@@ -4125,28 +4117,7 @@ static std::mutex g_state_mutex;
 static std::map<int, std::vector<PinSlot*>> g_pin_slots;                     // device -> slots
 static std::map<std::tuple<int, int, int, int>, uint64_t> g_hints;         // (device, W, H, bucket of N) -> capacity
 static long long g_hint_override = -1;                                      // tests: capacity of the NEXT forward (one shot)
-static int g_speculate = 1;
-static int g_deterministic = 0;   // 1: the blend backward accumulates per Gaussian in a fixed order (debug; slower)
-static int g_bwd_split = 0;  // workgroups a long tile's backward is split over (checkpoints from the forward); 1 = off; 0 = auto: 16 on a
-                             // 980x545 frame, fewer the more tiles there are (the parts that find nothing to do still cost a launch slot:
-                             // 16 x 17 408 workgroups for eight batched images spent 170 of 860 us on them) -- about 35 000 workgroups
-static int g_ckpt_first = 1;  // 128-instance batches of a tile before the forward starts leaving checkpoints
-static int g_depth_sort9 = 1;     // depth sort of large models in three 9-bit passes over (key - near-plane bits) (radix_sort.h); 0 = four 8-bit passes
-static int g_tile_sort = 1;       // round 5: no global depth sort in front of the direct binning -- every tile's pairs are sorted by depth where they lie (k_tile_sort).
-                                  // 0 = off (depth sort + direct binning), 1 = where it wins: tile lists of up to g_tile_sort_max_avg pairs on average (by the caller's
-                                  // last R, or 4 N before there is one), 2 = wherever the direct binning runs
-static int g_tile_sort_emit_max_n = 400000;   // behind the emit path (batched renders, frames above 4 096 tiles): models of up to this many Gaussians
-static int g_tile_sort_max_avg = 700;   // measured (tools/ab_tile_sort*.sh, 980x545): 20 k ... 300 k Gaussians (50 ... 620 pairs per tile) -3 ... -6 % of the step,
-                                        // 1 M (2 070 per tile) +6 %: the per-tile sorts move R pairs where the depth sort moves N keys
-static int g_direct_bin = 1;      // tile lists by direct placement (k_chunk_counts / k_chunk_scatter) instead of emit + tile sort + ranges; 0 = the sort route
-static int g_view_pose_tol_e6 = 2000;   // balanced placement without a view id: a render belongs to the cached view whose pose is within this (x 1e-6) in every matrix entry
-static int g_list_cut = 1;        // round 6: tile lists written only up to where the tiles stopped at the frame's previous render (ListCut); 0 = full lists,
-                                  // 1 = for models of at least g_list_cut_min_n Gaussians (where it was measured to pay), 2 = wherever the route allows
-static int g_list_cut_min_n = 2000000;
-static int g_list_cut_margin_e3 = 50;   // ... x (1 + this / 1000) of the depth its waves reached
-static int g_list_cut_deep = 8;        // tiles whose own cut may lie behind the frame's (served by cut_chunk_tiles)
-static int g_early_r = 1;         // the host learns R from the preprocess's per-block shares (published by the depth sort's histogram kernel) instead of from the scan
-static int g_blend_balance = 1;   // forward blend: place the waves by the visits each took at the previous render of the same view (balance_build)
+static long long g_late_bias = 0;   // "debug_late_bias" (tests): added ONCE to the early count a forward remembers for its late check (one shot)
 static std::atomic<long long> g_spec_overflows{0}, g_spec_forwards{0}, g_exact_forwards{0}, g_depth_window_resorts{0};
 // host-side time accounting of the two entry points (gsr_get_counter): wall time inside the call, and the part of the forward
 // spent waiting for the instance count -- their difference is what the launching thread really works per call
@@ -4176,7 +4147,6 @@ static PinSlot* acquire_pin_slot(int dev)
     return s;
 }
 static std::atomic<long long> g_late_checks{0}, g_late_mismatches{0};
-static int g_debug_late_bias = 0;
 // The scan's late report of a forward that took its count early (scan_report_late).  wait: poll for it (the slot is about to be
 // reused -- in a training loop the report arrived a backward ago; a back-to-back forward waits for its predecessor's scan, which runs
 // long before that forward's blend ends, so the device stays fed).  Returns 0 = nothing pending / not there yet / consistent; 1 = the
@@ -4356,17 +4326,13 @@ int gsr_debug_k8_timing(unsigned long long* host_dst, int blocks)
 int gsr_set_option(const char* name, int value)
 {
     if (!name) return GSR_ERR_ARG;
-    // 0 / 7 = one wave per 8x8 sub-tile with reach bits, the only forward blend (6, the same without the bits, and the tile-per-workgroup
-    // A/B kernels of rounds 1-4, values 1-5, have left the tree: DESIGN_HISTORY.md)
-    if (!strcmp(name, "blend_fwd_ppt")) return (value == 0 || value == 7) ? GSR_OK : GSR_ERR_ARG;
-    if (!strcmp(name, "ab_variants")) return 0;   // query kept for callers of the round-4 ABI: no A/B kernels in the library
-    if (!strcmp(name, "bwd_split")) { if (value < 0 || value > 64) return GSR_ERR_ARG; g_bwd_split = value; return GSR_OK; }
-    if (!strcmp(name, "ckpt_first")) { if (value < 1 || value > 64) return GSR_ERR_ARG; g_ckpt_first = value; return GSR_OK; }
-    if (!strcmp(name, "tile_map")) return value == 2 ? GSR_OK : GSR_ERR_ARG;   // 2x2 tile blocks dealt to the XCDs: the only map (blend_common.h)
-    if (!strcmp(name, "blend_balance")) { g_blend_balance = value ? 1 : 0; return GSR_OK; }
-    if (!strcmp(name, "early_r")) { g_early_r = value ? 1 : 0; return GSR_OK; }
-    if (!strcmp(name, "list_cut")) { g_list_cut = value < 0 || value > 2 ? 1 : value; return GSR_OK; }
-    if (!strcmp(name, "list_cut_min_n")) { g_list_cut_min_n = value < 0 ? 2000000 : value; return GSR_OK; }
+    // the options that are plain values, and the retired names: csrc/options.h
+    switch (options_set(name, value)) {
+        case SetResult::Stored: return GSR_OK;
+        case SetResult::Refused: return GSR_ERR_ARG;
+        case SetResult::Unknown: break;
+    }
+    // the actions
     if (!strcmp(name, "view_cache_reset")) {   // tests: every per-frame cache of the current device forgets its frames (placement costs, list cuts, counters)
         int dev_id = 0;
         if (hipGetDevice(&dev_id) != hipSuccess || hipDeviceSynchronize() != hipSuccess) return GSR_ERR_HIP;
@@ -4375,16 +4341,11 @@ int gsr_set_option(const char* name, int value)
             if (c.dev == dev_id && hipMemset(c.mem, 0, c.bytes) != hipSuccess) return GSR_ERR_HIP;
         return GSR_OK;
     }
-    if (!strcmp(name, "list_cut_margin_e3")) { g_list_cut_margin_e3 = value < 0 ? 50 : value; return GSR_OK; }
-    if (!strcmp(name, "list_cut_deep")) { g_list_cut_deep = value < 0 ? 8 : value; return GSR_OK; }
-    if (!strcmp(name, "debug_late_bias")) { g_debug_late_bias = value; return GSR_OK; }   // tests: added ONCE to the early count a forward remembers for its late check
-    if (!strcmp(name, "tile_sort")) { if (value < 0 || value > 2) return GSR_ERR_ARG; g_tile_sort = value; return GSR_OK; }
-    if (!strcmp(name, "tile_sort_max_avg")) { if (value < 0) return GSR_ERR_ARG; g_tile_sort_max_avg = value; return GSR_OK; }
-    if (!strcmp(name, "view_pose_tol_e6")) { if (value < 0) return GSR_ERR_ARG; g_view_pose_tol_e6 = value; return GSR_OK; }
-    if (!strcmp(name, "depth_sort9")) { g_depth_sort9 = value ? 1 : 0; return GSR_OK; }
-    if (!strcmp(name, "direct_binning")) { g_direct_bin = value ? 1 : 0; return GSR_OK; }
-    if (!strcmp(name, "speculative_binning")) { g_speculate = value ? 1 : 0; return GSR_OK; }
-    if (!strcmp(name, "deterministic_backward")) { g_deterministic = value ? 1 : 0; return GSR_OK; }
+    if (!strcmp(name, "debug_late_bias")) {   // tests: falsifies the next count a forward remembers for its late check (one shot)
+        std::lock_guard<std::mutex> lk(g_state_mutex);
+        g_late_bias = value;
+        return GSR_OK;
+    }
     if (!strcmp(name, "binning_capacity_hint")) {   // tests: capacity of the next forward (one shot; forces an overflow re-run)
         std::lock_guard<std::mutex> lk(g_state_mutex);
         g_hint_override = value > 0 ? value : -1;
@@ -4398,14 +4359,6 @@ int gsr_set_option(const char* name, int value)
         return GSR_OK;
     }
     if (!strcmp(name, "profile")) { g_profile = (value == 2 || value == 3) ? value : (value ? 1 : 0); g_profile_tick = 0; return GSR_OK; }
-    if (!strcmp(name, "prep_hist_max_n")) { g_prep_hist_max_n = value; return GSR_OK; }
-    if (!strcmp(name, "small_sort9")) { if (value < 0) return GSR_ERR_ARG; g_small_sort9 = value; return GSR_OK; }
-    if (!strcmp(name, "poll_iters")) { g_poll_iters = value < 0 ? 0 : value; return GSR_OK; }
-    if (!strcmp(name, "emit_hist")) { g_emit_hist = value ? 1 : 0; return GSR_OK; }
-    // 2 = onesweep, the only sort: nothing to set (the name stays for callers that pass it through)
-    if (!strcmp(name, "sort_algo")) return value == 2 ? GSR_OK : GSR_ERR_ARG;
-    // 0 or 2 = the packed two-pixel kernel, the only backward blend: nothing to set (the name stays for callers that pass it through)
-    if (!strcmp(name, "blend_bwd_ppt")) return (value == 0 || value == 2) ? GSR_OK : GSR_ERR_ARG;
     return GSR_ERR_ARG;
 }
 
@@ -4457,6 +4410,8 @@ static int forward_impl(const GsrForwardArgs* a, const int32_t* retired_at, int6
     CallTimer call_timer(g_fwd_calls, g_fwd_ns);
     hipStream_t st = (hipStream_t)stream_;
     if (!a || !out) return fail(GSR_ERR_ARG, "null args%s");
+    // the process-wide options as they are NOW: one forward uses one consistent set and hands what its backward needs to it (forward_flags)
+    const Options opt = options_snapshot();
     int rc = check_common(a->N, a->M, a->D, a->W, a->H);
     if (rc) return rc;
     // the render-only call (GsrForwardArgs::render_only): its own rules come first; its workspace is asked for behind the last argument
@@ -4480,13 +4435,11 @@ static int forward_impl(const GsrForwardArgs* a, const int32_t* retired_at, int6
     rc = batch_dev(a->batch, N, H, bt);
     if (rc) return rc;
     const int NB = bt.B;   // images rendered by this call (batched render: a tall grid of NB * tiles_y tile rows)
-    // the process-wide options as they are NOW: one forward uses one consistent set and hands it to its backward
-    const int opt_ckpt = g_ckpt_first;
     const int tiles_x = (W + kTile - 1) / kTile, tiles_y = (H + kTile - 1) / kTile, T = tiles_x * tiles_y * NB;
     if (a->sh_origin && (!a->shs || NB > 1 || a->prepared))
         return fail(GSR_ERR_ARG, "sh_origin needs shs and is not served with a batch of B > 1 or a prepared buffer%s");
     out->num_rendered = 0; out->binning = nullptr; out->binning_bytes = 0; out->binning_capacity = 0;
-    out->forward_flags = pack_fwd_flags(opt_ckpt) | (ro ? GSR_FWD_FLAG_RENDER_ONLY : 0);
+    out->forward_flags = pack_fwd_flags(opt.ckpt_first) | (ro ? GSR_FWD_FLAG_RENDER_ONLY : 0);
     uint64_t R = 0;
     BlendBalance bb = {};   // filled in front of k_tile_counts (whose extra workgroups build the placement the blend reads)
     ListCut lc = {};        // filled with it: the list cut lives in the same per-frame cache
@@ -4532,7 +4485,7 @@ static int forward_impl(const GsrForwardArgs* a, const int32_t* retired_at, int6
     // direct binning (k_chunk_counts ... k_chunk_scatter) where the frame's tile tables fit a wave's LDS; else emit + tile sort
     DirectBin db = {};
     DirectBinScratch dbs = {};
-    const bool direct = g_direct_bin && !wide_keys && direct_bin_geometry(N, T, db, dbs);
+    const bool direct = opt.direct_binning && !wide_keys && direct_bin_geometry(N, T, db, dbs);
     // tile-sort route (round 5): the binning runs over the Gaussians in index order and k_tile_sort orders every tile's pairs by depth:
     // single renders whose tile tables fit one wave
     bool tsort = false;   // (decided below, once the caller's capacity hint is known)
@@ -4576,7 +4529,7 @@ static int forward_impl(const GsrForwardArgs* a, const int32_t* retired_at, int6
         uint32_t* v0 = (tile_passes & 1) ? gid_alt2 : list;
         uint32_t* v1 = (tile_passes & 1) ? list : gid_alt2;
         // the emission counts the tile sort's digits itself when that sort's head is known to be zero (cleared by k_block_scan)
-        const bool emit_hist = prezeroed && g_emit_hist;
+        const bool emit_hist = prezeroed && opt.emit_hist;
         EmitHist eh = {};
         if (emit_hist) {
             eh.ghist = reinterpret_cast<uint32_t*>(bs + S.sort);
@@ -4644,21 +4597,22 @@ static int forward_impl(const GsrForwardArgs* a, const int32_t* retired_at, int6
         // the forward blend (one wave per 8x8 sub-tile, sign-encoded done + sub-tile reach bits), or the render-only one with or without
         // depth / alpha: one parameter list
         auto k7 = ro ? (a->out_depth ? k_blend_fwd_render<true> : k_blend_fwd_render<false>) : k_blend_fwd_w6;
-        if (g_profile && (g_profile != 3 || g_profile_tick.fetch_add(1u) % 3u == 0u)) {
+        const int prof = g_profile.load(std::memory_order_relaxed);
+        if (prof && (prof != 3 || g_profile_tick.fetch_add(1u) % 3u == 0u)) {
             // timed launch (bench.py's in-run roofline timing): the dispatch's OWN start / stop timestamps
             // (hipExtLaunchKernelGGL) instead of an event record in front of and behind it -- each of those is a barrier packet that
             // idles the queue for ~6 us (tools/api_timeline.sh: 12 us per step of the timed region went to the measurement)
             hipEvent_t ea = nullptr, eb = nullptr;
             if (hipEventCreate(&ea) != hipSuccess || hipEventCreate(&eb) != hipSuccess) return fail(GSR_ERR_HIP, "hipEventCreate failed%s");
             hipExtLaunchKernelGGL(k7, dim3(8 * 4 * slots_per_xcd(T, tiles_x)), dim3(64), 0, st, ea, eb, 0, W, H, tiles_x, T, ranges, list,
-                                  splat, a->bg, a->out_color, a->out_depth, a->out_alpha, img, staged, ckpt, opt_ckpt, tiles_y, bb, a->out_color_clamped,
+                                  splat, a->bg, a->out_color, a->out_depth, a->out_alpha, img, staged, ckpt, opt.ckpt_first, tiles_y, bb, a->out_color_clamped,
                                   lc, lc.key ? 1 : 0);
             std::lock_guard<std::mutex> lk(g_prof_mutex);
             g_prof_events[P_BLEND_FWD].push_back({ea, eb});
         } else {
-            ProfScope ps(g_profile == 3 ? P_COUNT : P_BLEND_FWD, st);   // (mode 3, an untimed launch: no events)
+            ProfScope ps(prof == 3 ? P_COUNT : P_BLEND_FWD, st);   // (mode 3, an untimed launch: no events)
             hipLaunchKernelGGL(k7, dim3(8 * 4 * slots_per_xcd(T, tiles_x)), dim3(64), 0, st, W, H, tiles_x, T, ranges, list, splat, a->bg,
-                               a->out_color, a->out_depth, a->out_alpha, img, staged, ckpt, opt_ckpt, tiles_y, bb, a->out_color_clamped,
+                               a->out_color, a->out_depth, a->out_alpha, img, staged, ckpt, opt.ckpt_first, tiles_y, bb, a->out_color_clamped,
                                lc, lc.key ? 1 : 0);
         }
         if (lc.key && lc_capacity > 0) {
@@ -4670,7 +4624,7 @@ static int forward_impl(const GsrForwardArgs* a, const int32_t* retired_at, int6
                                tiles_x, tiles_y, sorted_gid, reinterpret_cast<const TileRec*>(fs + L.srec), splat, list, ranges,
                                (uint32_t)std::min<uint64_t>(lc_capacity, 0xffffffffull), (const uint32_t*)nullptr, (uint2*)nullptr, lc);
             hipLaunchKernelGGL(k_blend_fwd_w6, dim3(8 * 4 * slots_per_xcd(T, tiles_x)), dim3(64), 0, st, W, H, tiles_x, T, ranges, list, splat, a->bg,
-                               a->out_color, a->out_depth, a->out_alpha, img, staged, ckpt, opt_ckpt, tiles_y, bb, a->out_color_clamped, lc, 2);
+                               a->out_color, a->out_depth, a->out_alpha, img, staged, ckpt, opt.ckpt_first, tiles_y, bb, a->out_color_clamped, lc, 2);
         }
         GSR_HIP(hipGetLastError());
         return GSR_OK;
@@ -4714,16 +4668,16 @@ static int forward_impl(const GsrForwardArgs* a, const int32_t* retired_at, int6
         if (g_hint_override > 0) { hint = (uint64_t)g_hint_override; g_hint_override = -1; }
         else { auto it = g_hints.find(hint_key); if (it != g_hints.end()) hint = it->second; }
     }
-    const bool speculative = g_speculate && hint > 0;
+    const bool speculative = opt.speculative_binning && hint > 0;
     const uint64_t cap = speculative ? hint : 0;
     {
-        const int ts_mode = g_tile_sort;
+        const int ts_mode = opt.tile_sort;
         const uint64_t avg = (hint > 0 ? hint : (uint64_t)N * 4u) / (uint64_t)T;
         // (behind the direct binning: single renders whose tile tables fit one wave; behind the emit path: batched renders, frames above
         //  4 096 tiles)
         // (on the emit path the keys are gathered per pair and the lists of a large model spread widely: measured at 1920x1080, 300 k
         //  Gaussians -1.7 % of the step, 1 M +1 ... +12 %; eight stage-A models in one launch chain -2.5 %: small models only)
-        const bool auto_ok = ts_mode == 1 && avg <= (uint64_t)g_tile_sort_max_avg && (direct || N / std::max(1, NB) <= g_tile_sort_emit_max_n);
+        const bool auto_ok = ts_mode == 1 && avg <= (uint64_t)opt.tile_sort_max_avg && (direct || N / std::max(1, NB) <= opt.tile_sort_emit_max_n);
         tsort = (ts_mode == 2 || auto_ok) && (direct ? NB == 1 : true);
     }
 
@@ -4753,10 +4707,10 @@ static int forward_impl(const GsrForwardArgs* a, const int32_t* retired_at, int6
     // ends ~10 us into the forward instead of behind sort + counts + scan, and the caller can enqueue its loss and its backward while
     // the forward is still running.  (A forward that takes a prepared buffer finds the shares in it: the backward that ran its
     // preprocess left them there, k_preprocess_bwd's next-view tail.)
-    const bool early_r = g_early_r && speculative;
+    const bool early_r = opt.early_r && speculative;
     uint2* early_parts = early_r ? reinterpret_cast<uint2*>(a->prepared ? static_cast<uint8_t*>(a->prepared) + prep_layout(N).early : fs + L.early) : nullptr;
     // visible depth keys beyond the 27-bit window of the three-pass sort are counted whenever this forward MAY sort on it
-    const uint32_t early_window = (N > g_prep_hist_max_n || (g_small_sort9 && !a->prepared && N >= g_small_sort9)) ? (1u << 27) - 1u : 0xffffffffu;
+    const uint32_t early_window = (N > opt.prep_hist_max_n || (opt.small_sort9 && !a->prepared && N >= opt.small_sort9)) ? (1u << 27) - 1u : 0xffffffffu;
     if (a->prepared) {
         // "prepare in backward": the preceding gsr_backward already ran the preprocess of this render on the updated
         // parameters (k_preprocess_bwd<..., PREP>); its records, sort keys and tile records are taken from the hand-over buffer
@@ -4771,7 +4725,7 @@ static int forward_impl(const GsrForwardArgs* a, const int32_t* retired_at, int6
         // models the backward also counted the digits and cleared the status words, so the sort starts with its first pass
         // (onesweep_sort_pairs hist_done)
         depth_scratch = pb + PL.sort;
-        depth_hist_done = prep_counts_digits(N);
+        depth_hist_done = opt.prep_counts_digits(N);
         // radii: a caller that takes them straight from the buffer (gsr_prepared_radii_offset) passes its own pointer into it
         // and nothing at all runs in front of the sort; otherwise a 4 N-byte copy kernel
         if (a->radii != reinterpret_cast<const int32_t*>(pb + PL.radii))
@@ -4813,7 +4767,7 @@ static int forward_impl(const GsrForwardArgs* a, const int32_t* retired_at, int6
     // the full sort.
     // (round 5: a forward that runs its own preprocess launches a digit histogram anyway, so below the threshold too three 9-bit passes
     //  behind it beat four 8-bit ones -- one latency-bound pass less; "small_sort9" = the smallest model that takes them, 0 = off)
-    bool wide_depth = g_depth_sort9 && !depth_hist_done && (N > g_prep_hist_max_n || (g_small_sort9 && N >= g_small_sort9));
+    bool wide_depth = opt.depth_sort9 && !depth_hist_done && (N > opt.prep_hist_max_n || (opt.small_sort9 && N >= opt.small_sort9));
     if (wide_depth) {
         std::lock_guard<std::mutex> lk(g_state_mutex);
         auto it = g_full_depth_sort.find(hint_key);
@@ -4873,7 +4827,7 @@ static int forward_impl(const GsrForwardArgs* a, const int32_t* retired_at, int6
         // 65 535 sub-tile waves; the per-view cost cache is a lazily allocated device buffer per (device, frame geometry)
         {
             const int nslots4 = 4 * slots_per_xcd(T, tiles_x), items = 8 * nslots4;
-            if (g_blend_balance && NB == 1 && items <= 65535 && nslots4 <= 20 * kEmitThreads && a->viewmatrix) {
+            if (opt.blend_balance && NB == 1 && items <= 65535 && nslots4 <= 20 * kEmitThreads && a->viewmatrix) {
                 const size_t hdr_bytes = align256(sizeof(ViewCostHdr));
                 // header | visit counts [entries][items] | list cut: depth keys [entries][T], the model size they belong to [entries]
                 const size_t vc_cut = align256(hdr_bytes + (size_t)kVcEntries * items * sizeof(uint16_t));
@@ -4909,11 +4863,11 @@ static int forward_impl(const GsrForwardArgs* a, const int32_t* retired_at, int6
                     bb.cur = reinterpret_cast<uint32_t*>(ib);
                     bb.perm = reinterpret_cast<uint16_t*>(ib + 256);
                     bb.vm = a->viewmatrix; bb.pt = a->points_transform; bb.view_id = (long long)a->view_id;
-                    bb.tol = 1e-6f * (float)g_view_pose_tol_e6;
+                    bb.tol = 1e-6f * (float)opt.view_pose_tol_e6;
                     bb.items = items; bb.nslots4 = nslots4; bb.W = W; bb.H = H;
                     // the list cut: the plain direct binning behind a global depth sort, one model, the default blend
                     // (not under a render-only call: the cut's repair pass reads state that call does not keep)
-                    if (!ro && direct && !tsort && db.NC <= 16000 && T == db.T && (g_list_cut == 2 || (g_list_cut == 1 && N >= g_list_cut_min_n))) {
+                    if (!ro && direct && !tsort && db.NC <= 16000 && T == db.T && (opt.list_cut == 2 || (opt.list_cut == 1 && N >= opt.list_cut_min_n))) {
                         uint8_t* dm = fs + align256(L.bytes);
                         lc.key = reinterpret_cast<uint32_t*>(mem + vc_cut);
                         lc.owner_n = reinterpret_cast<uint32_t*>(mem + vc_own);
@@ -4927,8 +4881,8 @@ static int forward_impl(const GsrForwardArgs* a, const int32_t* retired_at, int6
                         lc.hist = reinterpret_cast<uint32_t*>(dm + dbs.cut_hist);
                         lc.skey = in_alt ? dkey_alt : dkey;
                         lc.tbase = reinterpret_cast<uint32_t*>(dm + dbs.tbase);
-                        lc.margin = 1e-3f * (float)g_list_cut_margin_e3;
-                        lc.dmax = std::max(0, g_list_cut_deep);
+                        lc.margin = 1e-3f * (float)opt.list_cut_margin_e3;
+                        lc.dmax = std::max(0, opt.list_cut_deep);
                     }
                 }
             }
@@ -4960,8 +4914,8 @@ static int forward_impl(const GsrForwardArgs* a, const int32_t* retired_at, int6
             volatile unsigned long long* hp = pin.s->host;
             const unsigned long long want = pin.s->seq;
             bool seen = false;
-            if (g_poll_iters > 0) {
-                const auto limit = w0 + std::chrono::nanoseconds((long long)g_poll_iters * 50);
+            if (opt.poll_iters > 0) {
+                const auto limit = w0 + std::chrono::nanoseconds((long long)opt.poll_iters * 50);
                 while (!(seen = (hp[1] == want))) {
                     for (int it = 0; it < 64 && !(seen = (hp[1] == want)); it++) cpu_relax();
                     if (seen || std::chrono::steady_clock::now() > limit) break;
@@ -4983,17 +4937,18 @@ static int forward_impl(const GsrForwardArgs* a, const int32_t* retired_at, int6
         static std::map<int, unsigned long long> seen_giveups;   // per device; guarded by g_state_mutex
         const unsigned long long gv = static_cast<volatile unsigned long long*>(pin.s->host)[2];
         bool fresh;
+        long long late_bias = 0;
         {
             std::lock_guard<std::mutex> lk(g_state_mutex);
             unsigned long long& seen = seen_giveups[dev_id];
             fresh = gv != seen;
             seen = gv;
+            if (early_r && !fresh) { late_bias = g_late_bias; g_late_bias = 0; }   // ("debug_late_bias": consumed by the forward it falsifies)
         }
         if (fresh)
             return fail(GSR_ERR_HIP, "a radix-sort look-back gave up (status words overwritten?): the binning of this or the previous forward is invalid%s");
         if (early_r) {   // R and the give-up counter came from the rider, in front of this forward's own sorts: checked again behind them
-            pin.s->pending = true; pin.s->pending_seq = rider.seq; pin.s->pending_R = R + (unsigned long long)g_debug_late_bias; pin.s->pending_giveups = gv;
-            g_debug_late_bias = 0;
+            pin.s->pending = true; pin.s->pending_seq = rider.seq; pin.s->pending_R = R + (unsigned long long)late_bias; pin.s->pending_giveups = gv;
         }
     }
     bool resorted = false;
@@ -5066,6 +5021,7 @@ int gsr_backward(const GsrBackwardArgs* a, void* stream_)
     CallTimer call_timer(g_bwd_calls, g_bwd_ns);
     hipStream_t st = (hipStream_t)stream_;
     if (!a) return fail(GSR_ERR_ARG, "null args%s");
+    const Options opt = options_snapshot();
     if (a->forward_flags & GSR_FWD_FLAG_RENDER_ONLY)
         return fail(GSR_ERR_ARG, "gsr_backward: forward_flags come from a render-only forward, which keeps nothing a backward could read%s");
     int rc = check_common(a->N, a->M, a->D, a->W, a->H);
@@ -5123,7 +5079,7 @@ int gsr_backward(const GsrBackwardArgs* a, void* stream_)
     }
     // the forward's checkpoint layout travels with its output (forward_flags); a caller of the round-1 ABI (flags 0) gets the
     // process-wide option as before
-    int f_ckpt = g_ckpt_first;
+    int f_ckpt = opt.ckpt_first;
     if (a->forward_flags & 1) {
         f_ckpt = (int)((a->forward_flags >> 6) & 127);
         if (!flags_from_forward(a->forward_flags) || f_ckpt < 1) return fail(GSR_ERR_ARG, "forward_flags do not come from gsr_forward%s");
@@ -5160,7 +5116,7 @@ int gsr_backward(const GsrBackwardArgs* a, void* stream_)
     {
         const uint32_t* staged4 = reinterpret_cast<const uint32_t*>(static_cast<const uint8_t*>(a->image) + image_staged_offset(W, H, NB));
         const int tpad = 8 * slots_per_xcd(T, tiles_x);
-        const int want_split = g_bwd_split ? g_bwd_split : 16;
+        const int want_split = opt.bwd_split ? opt.bwd_split : 16;
         const int split_ok = want_split > 1 ? 1 : 0;
         const size_t n4 = (size_t)N * kGG * sizeof(double) / sizeof(float4);
         int fill_blocks = (int)std::min<size_t>(4096, (n4 + 255) / 256);
@@ -5191,7 +5147,7 @@ int gsr_backward(const GsrBackwardArgs* a, void* stream_)
         uint8_t* det_mem = nullptr;
         const uint32_t Rn = (uint32_t)a->num_rendered;
         size_t o_part = 0, o_k0 = 0, o_k1 = 0, o_v0 = 0, o_v1 = 0, o_sort = 0, det_bytes = 0;
-        if (g_deterministic) {
+        if (opt.deterministic_backward) {
             size_t o = 0;
             o_part = o; o += align256((size_t)Rn * kDetStride * 4);
             o_k0 = o; o += align256((size_t)Rn * 4); o_k1 = o; o += align256((size_t)Rn * 4);
@@ -5206,7 +5162,7 @@ int gsr_backward(const GsrBackwardArgs* a, void* stream_)
                            a->grad_alpha, gg, ckpt, det_part, item_hdr, items};
         if (a->grad_depth || a->grad_alpha) hipLaunchKernelGGL(k_blend_bwd2<true>, dim3(bwd_grid), dim3(128), 0, st, ba);
         else hipLaunchKernelGGL(k_blend_bwd2<false>, dim3(bwd_grid), dim3(128), 0, st, ba);
-        if (g_deterministic) {
+        if (opt.deterministic_backward) {
             uint32_t* k0 = reinterpret_cast<uint32_t*>(det_mem + o_k0); uint32_t* k1 = reinterpret_cast<uint32_t*>(det_mem + o_k1);
             uint32_t* v0 = reinterpret_cast<uint32_t*>(det_mem + o_v0); uint32_t* v1 = reinterpret_cast<uint32_t*>(det_mem + o_v1);
             hipLaunchKernelGGL(k_det_iota, dim3((Rn + 255) / 256), dim3(256), 0, st, Rn, v0, list, k0, (uint32_t)N);
@@ -5283,9 +5239,9 @@ int gsr_backward(const GsrBackwardArgs* a, void* stream_)
         po.gid = reinterpret_cast<uint32_t*>(pb + PL.gid);
         po.rec = reinterpret_cast<TileRec*>(pb + PL.rec);
         po.early_parts = reinterpret_cast<uint2*>(pb + PL.early);
-        po.early_window = N > g_prep_hist_max_n ? (1u << 27) - 1u : 0xffffffffu;   // (counted whenever the next forward MAY sort on the 27-bit window)
+        po.early_window = N > opt.prep_hist_max_n ? (1u << 27) - 1u : 0xffffffffu;   // (counted whenever the next forward MAY sort on the 27-bit window)
         if (!prep_head_cleared) GSR_HIP(hipMemsetAsync(prep_head, 0, kOnesweepHeadWordsMax * sizeof(uint32_t), st));   // (no blend launch: empty frame / other variant)
-        if (prep_counts_digits(N)) {
+        if (opt.prep_counts_digits(N)) {
             po.dh.ghist = prep_head;
             po.dh.status = onesweep_status(pb + PL.sort);
             po.dh.status_words = onesweep_status_words<uint32_t>((uint32_t)N, 32);

@@ -384,7 +384,8 @@ const char* gsr_last_error(void);
 int gsr_version(void);
 size_t gsr_struct_bytes(int32_t which); /* 0 GsrForwardArgs, 1 GsrBackwardArgs, 2 GsrForwardOut; anything else 0 */
 
-/* Process-wide knobs (value 0 = default unless stated):
+/* Process-wide knobs (value 0 = default unless stated; the defaults and accepted ranges are those of csrc/options.h, which a call
+ * into the library reads once, on entry: setting an option from another thread never changes a call that is under way):
  *   "blend_fwd_ppt"        forward blend kernel: 0 or 7 = one wave per 8x8 sub-tile, finished pixels encoded in the sign of T,
  *                          instances the sub-tile cannot see skipped by reach bits -- the only forward blend, so setting it changes
  *                          nothing.  Any other value is refused (the A/B kernels rounds 1-4 selected with 1-5 left the tree in

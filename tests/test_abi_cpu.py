@@ -135,6 +135,73 @@ def test_tile_sort_option_values():
         lib.gsr_set_option(b"tile_sort_max_avg", 700)
 
 
+INT_MIN, INT_MAX = -2**31, 2**31 - 1
+# name: (default, lowest accepted, highest accepted, refused outside).  Outside the range a name that is not refused stores a
+# value of its own choice and returns GSR_OK (tests/options_check/options_check.cpp looks at what is stored).
+OPTION_TABLE = {
+    "bwd_split": (0, 0, 64, True),
+    "ckpt_first": (1, 1, 64, True),
+    "tile_sort": (1, 0, 2, True),
+    "tile_sort_max_avg": (700, 0, INT_MAX, True),
+    "view_pose_tol_e6": (2000, 0, INT_MAX, True),
+    "small_sort9": (1, 0, INT_MAX, True),
+    "list_cut": (1, 0, 2, False),
+    "list_cut_min_n": (2000000, 0, INT_MAX, False),
+    "list_cut_margin_e3": (50, 0, INT_MAX, False),
+    "list_cut_deep": (8, 0, INT_MAX, False),
+    "poll_iters": (400000, 0, INT_MAX, False),
+    "prep_hist_max_n": (262144, INT_MIN, INT_MAX, False),
+    "blend_balance": (1, 0, 1, False),
+    "early_r": (1, 0, 1, False),
+    "depth_sort9": (1, 0, 1, False),
+    "direct_binning": (1, 0, 1, False),
+    "speculative_binning": (1, 0, 1, False),
+    "emit_hist": (1, 0, 1, False),
+    "deterministic_backward": (0, 0, 1, False),
+}
+RETIRED_OPTIONS = {"blend_fwd_ppt": (0, 7), "tile_map": (2,), "sort_algo": (2,), "blend_bwd_ppt": (0, 2)}
+
+
+def test_option_table_accepts_and_refuses_as_documented():
+    """gsr_set_option over every value option: the boundary values of the accepted range are taken, one value beyond each end is
+    refused (GSR_ERR_ARG, -1) or taken, as the table says; the retired names take the values that selected what is now the only
+    code path and refuse their neighbours; "ab_variants" returns 0 whatever it is given; an unknown or a null name is refused.
+    No GPU needed: options are host state."""
+    L = importlib.import_module("3dgs_hierarchical_training_amd._lib")
+    lib = L.load()
+    try:
+        for name, (_, lo, hi, refused_outside) in OPTION_TABLE.items():
+            n = name.encode()
+            assert lib.gsr_set_option(n, lo) == 0 and lib.gsr_set_option(n, hi) == 0, name
+            for beyond in ([lo - 1] if lo > INT_MIN else []) + ([hi + 1] if hi < INT_MAX else []):
+                assert lib.gsr_set_option(n, beyond) == (-1 if refused_outside else 0), (name, beyond)
+        for name, accepted in RETIRED_OPTIONS.items():
+            n = name.encode()
+            for v in accepted:
+                assert lib.gsr_set_option(n, v) == 0, (name, v)
+            for v in sorted({min(accepted) - 1, max(accepted) + 1} | set(range(min(accepted), max(accepted))) - set(accepted)):
+                assert lib.gsr_set_option(n, v) == -1, (name, v)
+        for v in (INT_MIN, -1, 0, 1, 5, INT_MAX):
+            assert lib.gsr_set_option(b"ab_variants", v) == 0
+        assert lib.gsr_set_option(b"no_such_option", 1) == -1 and lib.gsr_set_option(b"", 0) == -1
+        assert lib.gsr_set_option(b"tile_sort_emit_max_n", 400000) == -1     # (a threshold of the library that no name sets)
+        assert lib.gsr_set_option(None, 1) == -1
+    finally:
+        for name, (default, _, _, _) in OPTION_TABLE.items():
+            assert lib.gsr_set_option(name.encode(), default) == 0
+
+
+def test_options_header_stores_what_the_table_says(tmp_path):
+    """csrc/options.h on its own (plain C++17): tests/options_check/options_check.cpp asserts the defaults of Options{}, the value every
+    "store the default" / "store 0" / "store value != 0" rule leaves in the snapshot, and that a refused call leaves it unchanged."""
+    import subprocess
+    exe = str(tmp_path / "options_check")
+    subprocess.check_call(["g++", "-O1", "-std=c++17", "-pthread",
+                           os.path.join(REPO, "tests", "options_check", "options_check.cpp"), "-o", exe])
+    r = subprocess.run([exe], capture_output=True, text=True)
+    assert r.returncode == 0 and "options_check: ok" in r.stdout, r.stderr[-600:]
+
+
 def test_options_from_the_environment_at_load():
     """`GSR_OPTS=name=value,...` is applied by _lib.load() (a whole test run or bench under a non-default route of the library); a name or
     value the library refuses is an error at load, not a silently ignored word.  Own processes: the options are process state."""

@@ -7,11 +7,8 @@ bt = importlib.import_module("3dgs_hierarchical_training_amd.batched")
 L = importlib.import_module("3dgs_hierarchical_training_amd._lib")
 raster = importlib.import_module("3dgs_hierarchical_training_amd.rasterizer")
 host = importlib.import_module("3dgs_hierarchical_training_amd.host"); host.cap_host_threads()
-lib = L.load()
+lib = L.load()     # (applies GSR_OPTS="name=value,...")
 import os
-for kv in os.environ.get("GSR_OPTS", "").split(","):
-    if "=" in kv:
-        k, v = kv.split("="); print("option", k, v, lib.gsr_set_option(k.encode(), int(v)))
 BS = [int(x) for x in os.environ.get("GSR_BS", "1,2,4,8").split(",")]
 dev = torch.device("cuda:0")
 STAGES = ["preprocess_fwd", "sort_depth", "scan", "emit", "sort_tile", "ranges", "blend_fwd", "blend_bwd", "preprocess_bwd"]

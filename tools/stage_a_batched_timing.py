@@ -8,10 +8,7 @@ rs = importlib.import_module("3dgs_hierarchical_training_amd.run_segments")
 host = importlib.import_module("3dgs_hierarchical_training_amd.host"); host.cap_host_threads()
 dev = torch.device("cuda:0")
 import os
-_L = importlib.import_module("3dgs_hierarchical_training_amd._lib")
-for _kv in os.environ.get("GSR_OPTS", "").split(","):     # A/B runs: GSR_OPTS="tile_sort=0"
-    if "=" in _kv:
-        _k, _v = _kv.split("="); assert _L.load().gsr_set_option(_k.encode(), int(_v)) == 0
+# (A/B runs: GSR_OPTS="tile_sort=0" is applied by the library's loader, _lib.load())
 ONLY_DEFAULT = os.environ.get("STAGE_A_ONLY_DEFAULT") == "1"
 frames = int(sys.argv[1]) if len(sys.argv) > 1 else 40
 img_it, pose_it = (int(sys.argv[2]), int(sys.argv[3])) if len(sys.argv) > 3 else (1000, 300)

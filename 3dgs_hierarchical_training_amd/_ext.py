@@ -268,3 +268,13 @@ def _register_fakes():
     @torch.library.register_fake("gsr::resize_apply")
     def _(plan, meta, N, nA, nB, nC, nSplit, src, kinds, child, check=False):
         return [t.new_empty((nA + nB + 2 * nC,) + tuple(t.shape[1:])) for t in src]
+
+    @torch.library.register_fake("gsr::select_smallest")
+    def _(values, k):
+        n = values.shape[0]
+        return (values.new_empty((n,), dtype=torch.uint8), values.new_empty((n,), dtype=torch.uint8),
+                values.new_empty((L.GSR_SELECT_META_WORDS,), dtype=torch.int64))
+
+    @torch.library.register_fake("gsr::merge_apply")
+    def _(plan_a, plan_b, meta, Na, nA, Nb, nB, src_a, src_b, kinds, check=False):
+        return [t.new_empty((nA + nB,) + tuple(t.shape[1:])) for t in src_a]

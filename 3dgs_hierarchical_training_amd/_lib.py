@@ -78,11 +78,19 @@ class GsrResizeTensor(C.Structure):
                 ("reserved", C.c_int32)]
 
 
+class GsrMergeTensor(C.Structure):
+    _fields_ = [("src_a", C.c_void_p), ("src_b", C.c_void_p), ("dst", C.c_void_p), ("row_bytes", C.c_int64), ("kind", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
 # include/gsr.h, version 120: flag bits, tensor kinds, the words of `meta`, the segments of the plan
 GSR_RESIZE_KEEP, GSR_RESIZE_CLONE, GSR_RESIZE_SPLIT, GSR_RESIZE_CHILD = 1, 2, 4, 8
 GSR_RESIZE_PARAM, GSR_RESIZE_MOMENT, GSR_RESIZE_CHILD_SOURCED = 0, 1, 2
 GSR_RESIZE_MAX_TENSORS, GSR_RESIZE_META_WORDS, GSR_RESIZE_META_STATUS, GSR_RESIZE_PLAN_SEGMENTS = 18, 8, 4, 5
 GSR_RESIZE_PLAN_ROWS_A, GSR_RESIZE_PLAN_ROWS_B, GSR_RESIZE_PLAN_ROWS_C, GSR_RESIZE_PLAN_RANK_C, GSR_RESIZE_PLAN_SPLIT_ROWS = 0, 1, 2, 3, 4
+# version 121: the selection (meta = {k, below, equal, threshold key, NaN rows, status, 0, 0})
+GSR_SELECT_MAX_COLUMNS, GSR_SELECT_META_WORDS = 64, 8
+GSR_SELECT_META_K, GSR_SELECT_META_BELOW, GSR_SELECT_META_EQUAL, GSR_SELECT_META_KEY, GSR_SELECT_META_NAN, GSR_SELECT_META_STATUS = 0, 1, 2, 3, 4, 5
 
 EXPORTS = [
     "gsr_geom_bytes", "gsr_image_bytes", "gsr_forward_scratch_bytes", "gsr_binning_bytes",
@@ -102,6 +110,7 @@ EXPORTS = [
     "gsr_depth_to_points", "gsr_voxel_scratch_bytes", "gsr_voxel_down_sample",
     "gsr_camera_from_pose", "gsr_pose_virtual_view",
     "gsr_resize_scratch_bytes", "gsr_resize_plan_bytes", "gsr_resize_plan", "gsr_resize_apply",
+    "gsr_select_scratch_bytes", "gsr_select_smallest", "gsr_merge_apply",
 ]
 GSR_DEPTH_LOSS_L1, GSR_DEPTH_LOSS_INVARIANT = 0, 1
 
@@ -195,6 +204,15 @@ def load():
     lib.gsr_resize_apply.restype = C.c_int
     # (plan, plan_bytes, N, nA, nB, nC, nSplit, tensors, count, meta, stream)
     lib.gsr_resize_apply.argtypes = [C.c_void_p, C.c_size_t] + [C.c_int64] * 5 + [C.POINTER(GsrResizeTensor), C.c_int32, C.c_void_p, C.c_void_p]
+    lib.gsr_select_scratch_bytes.restype = C.c_size_t
+    lib.gsr_select_scratch_bytes.argtypes = [C.c_int64]
+    lib.gsr_select_smallest.restype = C.c_int
+    # (values, N, C, k, drop, keep_flags, meta, scratch, scratch_bytes, stream)
+    lib.gsr_select_smallest.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                        C.c_void_p]
+    lib.gsr_merge_apply.restype = C.c_int
+    # (plan_a, plan_a_bytes, Na, nA, plan_b, plan_b_bytes, Nb, nB, tensors, count, meta, stream)
+    lib.gsr_merge_apply.argtypes = [C.c_void_p, C.c_size_t, C.c_int64, C.c_int64] * 2 + [C.POINTER(GsrMergeTensor), C.c_int32, C.c_void_p, C.c_void_p]
     lib.gsr_adam_step.restype = C.c_int
     lib.gsr_adam_step.argtypes = [C.POINTER(GsrAdamTensor), C.c_int32, C.c_float, C.c_float, C.c_float, C.c_int64, C.c_void_p]
     lib.gsr_pose_step.restype = C.c_int

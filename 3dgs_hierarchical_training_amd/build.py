@@ -6,7 +6,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(CSRC, "libgsr_hip.so")
 SOURCES = ["gsr_kernels.hip", "loss_kernels.hip", "optim_kernels.hip", "knn_kernels.hip", "voxel_kernels.hip", "camera_kernels.hip",
-           "resize_kernels.hip"]
+           "resize_kernels.hip", "select_kernels.hip"]
 HEADERS = ["gsr_math.h", "adam_math.h", "radix_sort.h", "blend_common.h", "options.h", os.path.join("..", "..", "include", "gsr.h")]
 
 

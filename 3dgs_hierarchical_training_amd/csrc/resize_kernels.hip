@@ -12,6 +12,7 @@
 //   gsr_resize_apply   one launch; blockIdx.y picks the tensor, the x dimension strides over the tensor's destination in 4-byte words, so a
 //                      wave stores 256 consecutive bytes.  Every row number read from the plan is compared against N before it is used as
 //                      an address: a row that fails is written as zeros and raises meta[4].
+//   gsr_merge_apply    (version 121) the same launch over two models: the A lists of two plans name the rows of the appended result.
 // No workgroup of this file waits for another one inside a launch.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -159,6 +160,40 @@ __global__ __launch_bounds__(256) void k_resize_apply(const int32_t* __restrict_
     }
 }
 
+struct MergeTable {
+    GsrMergeTensor t[GSR_RESIZE_MAX_TENSORS];
+};
+
+// gsr_merge_apply: grid (x, count) as k_resize_apply.  Destination rows [0, nA) are the rows of model a that its plan's A list names, rows
+// [nA, nA + nB) those of model b; a MOMENT tensor's b rows are zero and nothing of b is read for them.
+__global__ __launch_bounds__(256) void k_merge_apply(const int32_t* __restrict__ rows_a, int64_t Na, int64_t nA, const int32_t* __restrict__ rows_b,
+                                                     int64_t Nb, int64_t nB, MergeTable table, int64_t* __restrict__ meta)
+{
+    const GsrMergeTensor T = table.t[blockIdx.y];
+    if (!T.dst || T.row_bytes <= 0) return;
+    const uint32_t words = (uint32_t)(T.row_bytes >> 2);
+    const int64_t total = (nA + nB) * (int64_t)words;
+    const uint32_t* __restrict__ src_a = static_cast<const uint32_t*>(T.src_a);
+    const uint32_t* __restrict__ src_b = static_cast<const uint32_t*>(T.src_b);
+    uint32_t* __restrict__ dst = static_cast<uint32_t*>(T.dst);
+    const bool small = total <= 0xffffffffll;
+    for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (int64_t)gridDim.x * 256) {
+        const int64_t r = small ? (int64_t)((uint32_t)e / words) : e / (int64_t)words;
+        const uint32_t w = (uint32_t)(e - r * words);
+        uint32_t value = 0;
+        bool bad = false;
+        if (r < nA) {
+            const int64_t srow = rows_a[r];                     // r < nA <= Na: inside the segment
+            if (srow >= 0 && srow < Na) value = src_a[srow * words + w]; else bad = true;
+        } else if (T.kind != GSR_RESIZE_MOMENT) {
+            const int64_t srow = rows_b[r - nA];                // r - nA < nB <= Nb
+            if (srow >= 0 && srow < Nb) value = src_b[srow * words + w]; else bad = true;
+        }
+        dst[e] = value;
+        if (bad && w == 0) atomicOr(reinterpret_cast<unsigned long long*>(meta + GSR_RESIZE_META_STATUS), 1ull);
+    }
+}
+
 static inline int64_t resize_stride(int64_t N) { return (N + 63) / 64 * 64; }      // entries per plan segment: 256-byte aligned segments
 static inline int64_t resize_tiles(int64_t N) { return (N + kResizeTile - 1) / kResizeTile; }
 
@@ -242,6 +277,47 @@ int gsr_resize_apply(const void* plan, size_t plan_bytes, int64_t N, int64_t nA,
     if (gx > kResizeApplyGridX) gx = kResizeApplyGridX;
     hipLaunchKernelGGL(k_resize_apply, dim3((unsigned)gx, (unsigned)count), dim3(256), 0, (hipStream_t)stream,
                        static_cast<const int32_t*>(plan), resize_stride(N), N, nA, nB, nC, nSplit, table, meta);
+    return hipGetLastError() == hipSuccess ? GSR_OK : GSR_ERR_HIP;
+}
+
+int gsr_merge_apply(const void* plan_a, size_t plan_a_bytes, int64_t Na, int64_t nA, const void* plan_b, size_t plan_b_bytes, int64_t Nb, int64_t nB,
+                    const GsrMergeTensor* tensors, int32_t count, int64_t* meta, void* stream)
+{
+    if (Na < 0 || Na >= ((int64_t)1 << 31) || Nb < 0 || Nb >= ((int64_t)1 << 31))
+        return fail_text(GSR_ERR_ARG, "gsr_merge_apply: Na and Nb must be in [0, 2^31)");
+    if (!meta || ((uintptr_t)meta & 7) != 0) return fail_text(GSR_ERR_ARG, "gsr_merge_apply: meta is NULL or not 8-byte aligned");
+    if (count < 0 || count > GSR_RESIZE_MAX_TENSORS) return fail_text(GSR_ERR_ARG, "gsr_merge_apply: at most GSR_RESIZE_MAX_TENSORS (18) tensors");
+    if (count > 0 && !tensors) return fail_text(GSR_ERR_ARG, "gsr_merge_apply: tensors is NULL");
+    if (nA < 0 || nB < 0 || nA > Na || nB > Nb)
+        return fail_text(GSR_ERR_ARG, "gsr_merge_apply: counts beyond the plans' capacity (0 <= nA <= Na and 0 <= nB <= Nb)");
+    if (nA > 0 && (!plan_a || ((uintptr_t)plan_a & 3) != 0)) return fail_text(GSR_ERR_ARG, "gsr_merge_apply: plan_a is NULL or not 4-byte aligned");
+    if (nA > 0 && plan_a_bytes < gsr_resize_plan_bytes(Na)) return fail_text(GSR_ERR_ARG, "gsr_merge_apply: plan_a is shorter than gsr_resize_plan_bytes(Na)");
+    if (nB > 0 && (!plan_b || ((uintptr_t)plan_b & 3) != 0)) return fail_text(GSR_ERR_ARG, "gsr_merge_apply: plan_b is NULL or not 4-byte aligned");
+    if (nB > 0 && plan_b_bytes < gsr_resize_plan_bytes(Nb)) return fail_text(GSR_ERR_ARG, "gsr_merge_apply: plan_b is shorter than gsr_resize_plan_bytes(Nb)");
+    MergeTable table{};
+    int64_t most = 0;
+    for (int k = 0; k < count; k++) {
+        const GsrMergeTensor& t = tensors[k];
+        if (t.row_bytes < 0 || (t.row_bytes & 3) != 0 || t.row_bytes >= ((int64_t)1 << 31))
+            return fail_text(GSR_ERR_ARG, "gsr_merge_apply: row_bytes must be a non-negative multiple of 4 below 2^31");
+        if (t.kind != GSR_RESIZE_PARAM && t.kind != GSR_RESIZE_MOMENT)
+            return fail_text(GSR_ERR_ARG, "gsr_merge_apply: kind is GSR_RESIZE_PARAM or GSR_RESIZE_MOMENT");
+        table.t[k] = t;
+        if (t.row_bytes == 0 || (!t.src_a && !t.src_b && !t.dst)) { table.t[k].dst = nullptr; continue; }      // skipped
+        if (!t.dst) return fail_text(GSR_ERR_ARG, "gsr_merge_apply: dst is NULL for a tensor with sources");
+        if (nA > 0 && !t.src_a) return fail_text(GSR_ERR_ARG, "gsr_merge_apply: src_a is NULL when nA > 0");
+        if (nB > 0 && t.kind == GSR_RESIZE_PARAM && !t.src_b) return fail_text(GSR_ERR_ARG, "gsr_merge_apply: src_b is NULL for a GSR_RESIZE_PARAM tensor when nB > 0");
+        if ((((uintptr_t)t.src_a | (uintptr_t)t.src_b | (uintptr_t)t.dst) & 3) != 0)
+            return fail_text(GSR_ERR_ARG, "gsr_merge_apply: src_a, src_b and dst must be 4-byte aligned");
+        const int64_t words = (nA + nB) * (t.row_bytes >> 2);
+        if (words > most) most = words;
+    }
+    if (most == 0) return GSR_OK;      // nothing kept, or nothing to move: not an error
+    int64_t gx = (most + 255) / 256;
+    if (gx > kResizeApplyGridX) gx = kResizeApplyGridX;
+    const int32_t* rows_a = plan_a ? static_cast<const int32_t*>(plan_a) + GSR_RESIZE_PLAN_ROWS_A * resize_stride(Na) : nullptr;
+    const int32_t* rows_b = plan_b ? static_cast<const int32_t*>(plan_b) + GSR_RESIZE_PLAN_ROWS_A * resize_stride(Nb) : nullptr;
+    hipLaunchKernelGGL(k_merge_apply, dim3((unsigned)gx, (unsigned)count), dim3(256), 0, (hipStream_t)stream, rows_a, Na, nA, rows_b, Nb, nB, table, meta);
     return hipGetLastError() == hipSuccess ? GSR_OK : GSR_ERR_HIP;
 }
 

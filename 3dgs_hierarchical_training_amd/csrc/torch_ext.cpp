@@ -29,6 +29,8 @@
 //   gsr::pose_virtual_view    -> gsr_pose_virtual_view (the interpolated pose between two device poses, and that pose relative to a base)
 //   gsr::resize_plan          -> gsr_resize_plan (flag bytes -> the source-row lists of the resized model; no host synchronisation)
 //   gsr::resize_apply         -> gsr_resize_apply (every row of every parameter and moment tensor moved in one launch)
+//   gsr::select_smallest      -> gsr_select_smallest (the k rows with the smallest row maximum, as flag bytes; no host synchronisation)
+//   gsr::merge_apply          -> gsr_merge_apply (the kept rows of two models appended in one launch)
 //
 // Registered with TORCH_LIBRARY so the ops are visible to the dispatcher (torch.ops.gsr.*, fake kernels in _ext.py for
 // torch.compile).  An empty tensor (numel 0) stands for "None".  Everything runs on the current HIP stream of the
@@ -1384,6 +1386,80 @@ std::vector<Tensor> resize_apply(const Tensor& plan, Tensor meta, int64_t N, int
     return dst;
 }
 
+// gsr::select_smallest -> gsr_select_smallest.  values float32 [N, C] (or [N]: C = 1) -> (drop bool-as-uint8 [N], keep_flags uint8 [N],
+// meta int64 [8]), all on the device.  No host synchronisation, no autograd.
+std::tuple<Tensor, Tensor, Tensor> select_smallest(const Tensor& values_, int64_t k)
+{
+    TORCH_CHECK(values_.is_cuda(), "select_smallest: values must be on a ROCm/HIP device (no CPU fallback)");
+    TORCH_CHECK((values_.dim() == 1 || values_.dim() == 2) && values_.scalar_type() == at::kFloat, "select_smallest: values is float32 [N, C] or [N]");
+    const c10::hip::HIPGuardMasqueradingAsCUDA guard(values_.device());
+    const Tensor values = values_.detach().contiguous();
+    const int64_t N = values.size(0), C = values.dim() == 2 ? values.size(1) : 1;
+    TORCH_CHECK(C >= 1 && C <= GSR_SELECT_MAX_COLUMNS, "select_smallest: C must be in [1, ", GSR_SELECT_MAX_COLUMNS, "]");
+    const size_t sb = gsr_select_scratch_bytes(N);
+    const auto bytes = values.options().dtype(at::kByte);
+    Tensor drop = at::empty({N}, bytes), keep = at::empty({N}, bytes), scratch = at::empty({(int64_t)sb}, bytes);
+    Tensor meta = at::empty({GSR_SELECT_META_WORDS}, values.options().dtype(at::kLong));
+    check(gsr_select_smallest(N ? values.data_ptr<float>() : nullptr, N, (int32_t)C, k, drop.data_ptr<uint8_t>(), keep.data_ptr<uint8_t>(),
+                              meta.data_ptr<int64_t>(), N ? scratch.data_ptr() : nullptr, sb,
+                              c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream()), "gsr_select_smallest");
+    return {drop, keep, meta};
+}
+
+// gsr::merge_apply -> gsr_merge_apply.  src_a[k]: [Na, ...], src_b[k]: [Nb, ...] with the same trailing shape (an empty tensor for a MOMENT
+// whose b rows do not exist), kinds[k]: GSR_RESIZE_PARAM / MOMENT.  Returns fresh tensors [nA + nB, ...].  check as in resize_apply.
+std::vector<Tensor> merge_apply(const Tensor& plan_a, const Tensor& plan_b, Tensor meta, int64_t Na, int64_t nA, int64_t Nb, int64_t nB,
+                                at::TensorList src_a_, at::TensorList src_b_, at::IntArrayRef kinds, bool do_check)
+{
+    TORCH_CHECK(plan_a.is_cuda() && plan_b.is_cuda() && meta.is_cuda(), "merge_apply: the plans and meta must be on a ROCm/HIP device (no CPU fallback)");
+    TORCH_CHECK(plan_a.scalar_type() == at::kInt && plan_a.is_contiguous() && plan_a.dim() == 1 && plan_b.scalar_type() == at::kInt &&
+                plan_b.is_contiguous() && plan_b.dim() == 1, "merge_apply: plan_a and plan_b are int32 tensors of resize_plan");
+    TORCH_CHECK(meta.scalar_type() == at::kLong && meta.is_contiguous() && meta.numel() == GSR_RESIZE_META_WORDS,
+                "merge_apply: meta is the int64 [8] tensor of resize_plan");
+    TORCH_CHECK(src_a_.size() == kinds.size() && src_a_.size() == src_b_.size(), "merge_apply: src_a, src_b and kinds have one entry per tensor");
+    TORCH_CHECK((int64_t)src_a_.size() <= GSR_RESIZE_MAX_TENSORS, "merge_apply: at most ", GSR_RESIZE_MAX_TENSORS, " tensors");
+    TORCH_CHECK(Na >= 0 && nA >= 0 && Nb >= 0 && nB >= 0, "merge_apply: negative count");
+    const c10::hip::HIPGuardMasqueradingAsCUDA guard(plan_a.device());
+    const int64_t nout = nA + nB;
+    std::vector<Tensor> src_a, src_b, dst;
+    std::vector<GsrMergeTensor> table(src_a_.size());
+    for (size_t k = 0; k < src_a_.size(); k++) {
+        TORCH_CHECK(src_a_[k].is_cuda() && src_a_[k].device() == plan_a.device() && src_b_[k].is_cuda() && src_b_[k].device() == plan_a.device(),
+                    "merge_apply: src_a[", k, "] and src_b[", k, "] must be on the plans' device (no CPU fallback)");
+        TORCH_CHECK(src_a_[k].dim() >= 1 && src_a_[k].size(0) == Na, "merge_apply: src_a[", k, "] has Na rows");
+        src_a.push_back(src_a_[k].detach().contiguous());
+        std::vector<int64_t> shape = src_a[k].sizes().vec();
+        int64_t row_bytes = (int64_t)src_a[k].element_size();
+        for (size_t d = 1; d < shape.size(); d++) row_bytes *= shape[d];
+        const bool absent_b = kinds[k] == GSR_RESIZE_MOMENT && src_b_[k].dim() == 1 && src_b_[k].numel() == 0;
+        if (!absent_b) {
+            shape[0] = Nb;
+            TORCH_CHECK(src_b_[k].sizes().vec() == shape && src_b_[k].scalar_type() == src_a[k].scalar_type(),
+                        "merge_apply: src_b[", k, "] is [Nb, ...] with src_a's trailing shape and dtype");
+        }
+        src_b.push_back(src_b_[k].detach().contiguous());
+        shape[0] = nout;
+        dst.push_back(at::empty(shape, src_a[k].options()));
+        GsrMergeTensor& t = table[k];
+        t.kind = (int32_t)kinds[k];
+        t.row_bytes = row_bytes;
+        t.reserved = 0;
+        const bool moves = row_bytes > 0 && nout > 0;
+        t.src_a = (moves && Na > 0) ? src_a[k].data_ptr() : nullptr;
+        t.src_b = (moves && !absent_b && Nb > 0) ? src_b[k].data_ptr() : nullptr;
+        t.dst = moves ? dst[k].data_ptr() : nullptr;
+    }
+    check(gsr_merge_apply(plan_a.numel() ? plan_a.data_ptr() : nullptr, (size_t)plan_a.numel() * 4, Na, nA, plan_b.numel() ? plan_b.data_ptr() : nullptr,
+                          (size_t)plan_b.numel() * 4, Nb, nB, table.data(), (int32_t)table.size(), meta.data_ptr<int64_t>(),
+                          c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream()), "gsr_merge_apply");
+    if (do_check) {
+        const Tensor host = meta.cpu();
+        TORCH_CHECK(host.data_ptr<int64_t>()[GSR_RESIZE_META_STATUS] == 0, "merge_apply: a plan holds a row number outside its model (status ",
+                    host.data_ptr<int64_t>()[GSR_RESIZE_META_STATUS], "): the rows it names were written as zeros");
+    }
+    return dst;
+}
+
 }  // namespace
 
 // ---- the trainer's per-iteration bookkeeping (gsr_masked_max / gsr_densify_stats_add / gsr_psnr; include/gsr.h) ------------------
@@ -1524,6 +1600,9 @@ TORCH_LIBRARY(gsr, m)
     m.def("resize_plan(Tensor flags) -> (Tensor plan, Tensor meta)");
     m.def("resize_apply(Tensor plan, Tensor(a!) meta, int N, int nA, int nB, int nC, int nSplit, Tensor[] src, int[] kinds, Tensor[] child, "
           "bool check=False) -> Tensor[]");
+    m.def("select_smallest(Tensor values, int k) -> (Tensor drop, Tensor keep_flags, Tensor meta)");
+    m.def("merge_apply(Tensor plan_a, Tensor plan_b, Tensor(a!) meta, int Na, int nA, int Nb, int nB, Tensor[] src_a, Tensor[] src_b, int[] kinds, "
+          "bool check=False) -> Tensor[]");
     m.def("masked_max_(Tensor(a!) dst, Tensor src, Tensor mask) -> ()");
     m.def("densify_stats_add_(Tensor(a!) accum, Tensor(b!) denom, Tensor grad, Tensor mask) -> ()");
     m.def("psnr(Tensor a, Tensor b) -> Tensor");
@@ -1557,6 +1636,8 @@ TORCH_LIBRARY_IMPL(gsr, CUDA, m)   // the dispatch key of HIP tensors on a ROCm 
     m.impl("pose_virtual_view", &pose_virtual_view);
     m.impl("resize_plan", &resize_plan);
     m.impl("resize_apply", &resize_apply);
+    m.impl("select_smallest", &select_smallest);
+    m.impl("merge_apply", &merge_apply);
     m.impl("masked_max_", &masked_max_);
     m.impl("densify_stats_add_", &densify_stats_add_);
     m.impl("psnr", &psnr);

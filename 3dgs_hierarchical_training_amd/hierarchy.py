@@ -127,9 +127,18 @@ def calc_importance(seg: Dict[str, torch.Tensor], views: List[GaussianRasterizat
     return _calc_importance_kernel(seg, views) if route == "kernel" else _calc_importance_autograd(seg, views)
 
 
-def prune_mask(importance: torch.Tensor, prune_ratio: float) -> torch.Tensor:
+def prune_mask(importance: torch.Tensor, prune_ratio: float, route: str = "torch") -> torch.Tensor:
     """True = dropped: the `prune_ratio * N` Gaussians with the smallest max-over-coefficients importance
-    (ht3dgs_trainer.py:234-239)."""
+    (ht3dgs_trainer.py:234-239).
+
+    route: "torch" = amax, topk, a zero fill and an indexed store; "kernel" = gsr_select_smallest on the [N, 3 M] tensor as it is (merge.py;
+    no amax launch, no host wait).  With distinct scores both give the same mask; among rows tied at the threshold the kernel route drops
+    those with the lowest row numbers, where topk promises no rule.  The kernel route has no CPU fallback."""
+    from . import merge
+    if merge.check_route(route, "prune_mask") == "kernel":
+        merge.need_device("prune_mask", importance=importance)
+        values = importance.reshape(importance.shape[0], -1) if importance.dim() > 1 else importance
+        return merge.select_smallest(values, int(values.shape[0] * prune_ratio))[0]
     score = importance.amax(-1).reshape(-1)
     k = int(score.shape[0] * prune_ratio)
     mask = torch.zeros_like(score, dtype=torch.bool)
@@ -139,12 +148,13 @@ def prune_mask(importance: torch.Tensor, prune_ratio: float) -> torch.Tensor:
 
 
 def merge_send(tr, dst: int, seg: Dict[str, torch.Tensor], views, prune_ratio: float, frames=None, poses=None,
-               start_fidx: int = 0, global_iteration: int = 0, importance_fn=calc_importance, drop=None, sh_degree: int = -1) -> Dict:
+               start_fidx: int = 0, global_iteration: int = 0, importance_fn=calc_importance, drop=None, sh_degree: int = -1,
+               route: str = "torch") -> Dict:
     """Source side of one pair: own importance -> drop mask; ship the UN-PRUNED child + mask + frames / poses.
-    `drop`: a mask computed beforehand (then `views` is not used)."""
+    `drop`: a mask computed beforehand (then `views` is not used).  route: prune_mask's."""
     t0 = time.perf_counter()
     if drop is None:
-        drop = prune_mask(importance_fn(seg, views), prune_ratio)
+        drop = prune_mask(importance_fn(seg, views), prune_ratio, route=route)
     imp_ms = _elapsed_ms(t0, seg["_xyz"])
     st = segments.send_child(tr, dst, seg, drop=drop, frames=frames, poses=poses, start_fidx=start_fidx,
                              global_iteration=global_iteration, sh_degree=sh_degree)
@@ -153,13 +163,14 @@ def merge_send(tr, dst: int, seg: Dict[str, torch.Tensor], views, prune_ratio: f
 
 
 def merge_recv(tr, src: int, seg: Dict[str, torch.Tensor], views, prune_ratio: float, src_to_dst=None,
-               importance_fn=calc_importance, drop=None) -> Dict:
+               importance_fn=calc_importance, drop=None, route: str = "torch") -> Dict:
     """Destination side: own importance (in parallel with the source's), receive the un-pruned child, apply both masks,
     move the child's points by `src_to_dst` (a [4,4] or a callable(child_message) -> [4,4]) and append.
+    route: prune_mask's and segments.merge_segments'.
 
     Returns {'merged', 'teachers': [own un-pruned, child un-pruned], 'child': message, stats...}."""
     t0 = time.perf_counter()
-    drop_dst = drop if drop is not None else prune_mask(importance_fn(seg, views), prune_ratio)
+    drop_dst = drop if drop is not None else prune_mask(importance_fn(seg, views), prune_ratio, route=route)
     imp_ms = _elapsed_ms(t0, seg["_xyz"])
     msg = segments.recv_child(tr, src, seg["_xyz"].device)
     child = msg["seg"]
@@ -167,7 +178,7 @@ def merge_recv(tr, src: int, seg: Dict[str, torch.Tensor], views, prune_ratio: f
                                                                          device=child["_xyz"].device)
     T = src_to_dst(msg) if callable(src_to_dst) else src_to_dst
     t1 = time.perf_counter()
-    merged = segments.merge_segments(seg, child, ~drop_dst, ~drop_src, T)
+    merged = segments.merge_segments(seg, child, ~drop_dst, ~drop_src, T, route=route)
     own = {k: seg[k].detach() for k in segments.SEGMENT_KEYS}
     return {"role": "dst", "peer": src, "merged": merged, "teachers": [own, child], "child": msg,
             "importance_ms": imp_ms, "recv_ms": msg["ms"], "bytes": msg["bytes"],
@@ -176,14 +187,18 @@ def merge_recv(tr, src: int, seg: Dict[str, torch.Tensor], views, prune_ratio: f
 
 
 def merge_level(seg: Dict[str, torch.Tensor], views: List[GaussianRasterizationSettings], level_pairs, prune_ratio: float,
-                src_to_dst: Optional[torch.Tensor] = None, importance_fn=calc_importance, group=None, transport=None):
+                src_to_dst: Optional[torch.Tensor] = None, importance_fn=calc_importance, group=None, transport=None,
+                route: str = "torch"):
     """One level of the merge tree for this rank.  Returns the merged segment on destination ranks, None on
-    source ranks (their GPU is free after the send), and the unchanged segment on ranks idle at this level."""
+    source ranks (their GPU is free after the send), and the unchanged segment on ranks idle at this level.
+    route: merge_send's and merge_recv's."""
+    from . import merge
+    merge.check_route(route, "merge_level")
     tr = transport if transport is not None else segments.DistTransport(group)
     role = segments.partner(tr.rank, level_pairs)
     if role is None:
         return seg
     if role[0] == "send":
-        merge_send(tr, role[1], seg, views, prune_ratio, importance_fn=importance_fn)
+        merge_send(tr, role[1], seg, views, prune_ratio, importance_fn=importance_fn, route=route)
         return None
-    return merge_recv(tr, role[1], seg, views, prune_ratio, src_to_dst, importance_fn=importance_fn)["merged"]
+    return merge_recv(tr, role[1], seg, views, prune_ratio, src_to_dst, importance_fn=importance_fn, route=route)["merged"]

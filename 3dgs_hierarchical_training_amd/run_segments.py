@@ -104,6 +104,8 @@ class HTConfig:
                                                 # host); 'voxels' = sequence.depth_scene (every pixel, voxel grid 0.01, create_from_pcd: the reference's, on the device)
     densify_route: str = "torch"                # how a densification resizes the model: 'torch' = boolean indexing and torch.cat per tensor; 'kernel' =
                                                 # gsr_resize_plan / gsr_resize_apply (resize.py): the same result to the bit, one host wait, one row-moving launch
+    merge_route: str = "torch"                  # how a merge picks and moves its rows: 'torch' = amax, topk, boolean gathers and torch.cat; 'kernel' =
+                                                # gsr_select_smallest and gsr_merge_apply (merge.py): one host wait; ties at the threshold go by row number
     device_cameras: bool = False                # phase 1's virtual views from poses kept on the device: cameras.virtual_view + settings_from_pose, two
                                                 # launches per view instead of host matrix work and eight uploads; a camera may differ from the host
                                                 # route's in the last float32 bit, so the default stays the host route
@@ -274,7 +276,7 @@ class RankRunner:
         st = hierarchy.merge_send(self.tr, self.role(k)[1], seg.params.raw(), self._importance_views(seg), self.cfg.prune_ratio,
                                   frames=seg.frames, poses=seg.pose_tensor(), start_fidx=seg.start_fidx,
                                   global_iteration=seg.global_iteration, importance_fn=self.importance_fn,
-                                  sh_degree=seg.params.active_sh_degree)
+                                  sh_degree=seg.params.active_sh_degree, route=self.cfg.merge_route)
         self.seg = None          # this GPU is free from here on
         self._emit({"phase": "merge", "level": k, **st})
 
@@ -284,7 +286,7 @@ class RankRunner:
         # start frame is one of this model's own frames (the partitions overlap by two frames).
         src_to_dst = lambda msg: torch.linalg.inv(seg.poses[msg["start_fidx"]])
         out = hierarchy.merge_recv(self.tr, self.role(k)[1], seg.params.raw(), self._importance_views(seg),
-                                   self.cfg.prune_ratio, src_to_dst, importance_fn=self.importance_fn)
+                                   self.cfg.prune_ratio, src_to_dst, importance_fn=self.importance_fn, route=self.cfg.merge_route)
         child = out["child"]
         # teachers render at the active degree their model was trained at: the destination's own, and the child's as its message
         # states it (uneven frame splits or iteration counts can leave the two on different sides of an oneupSHdegree boundary)
@@ -543,6 +545,9 @@ def main():
     ap.add_argument("--densify-route", choices=("torch", "kernel"), default="torch",
                     help="how a densification resizes the model: torch = boolean indexing and torch.cat per tensor (default); kernel = the "
                          "resize kernels, the same result to the bit with one host wait and one launch that moves every row")
+    ap.add_argument("--merge-route", choices=("torch", "kernel"), default="torch",
+                    help="how a merge picks the Gaussians it drops and appends the rest: torch = amax, topk, boolean gathers and torch.cat "
+                         "(default); kernel = the selection and row-move kernels, one host wait; rows tied at the threshold are dropped by row number")
     ap.add_argument("--device-cameras", action="store_true",
                     help="phase 1's virtual views from poses kept on the device (cameras.virtual_view + settings_from_pose: two launches per view, no "
                          "host matrix work or uploads); a camera may differ from the host route's in the last float32 bit.  Default: the host route")
@@ -560,7 +565,7 @@ def main():
         return launch_check(a)
     cfg = HTConfig(frames=a.frames, width=a.width, height=a.height, gt_gaussians=a.gt_gaussians, leaf_gaussians=a.leaf_gaussians,
                    leaf_iters_per_frame=a.leaf_iters, phase1_iters_per_frame=a.phase1_iters, phase2_iters_per_frame=[a.phase2_iters] * 3,
-                   importance_views=a.importance_views, densify=a.densify, fit_pose=a.fit_pose, stage_a_batch=a.stage_a_batch, stage_a_lambda_depth=a.stage_a_lambda_depth, stage_a_early_exit=a.stage_a_early_exit, stage_a_init=a.stage_a_init, densify_route=a.densify_route, sh_up_every=a.sh_up_every,
+                   importance_views=a.importance_views, densify=a.densify, fit_pose=a.fit_pose, stage_a_batch=a.stage_a_batch, stage_a_lambda_depth=a.stage_a_lambda_depth, stage_a_early_exit=a.stage_a_early_exit, stage_a_init=a.stage_a_init, densify_route=a.densify_route, merge_route=a.merge_route, sh_up_every=a.sh_up_every,
                    device_cameras=a.device_cameras)
     if a.pose_lr is not None:
         cfg.pose_lr = a.pose_lr

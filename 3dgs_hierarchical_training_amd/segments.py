@@ -269,9 +269,15 @@ def recv_segment(src: int, device, group=None) -> Tuple[Dict[str, torch.Tensor],
 
 
 def merge_segments(dst_seg: Dict[str, torch.Tensor], src_seg: Dict[str, torch.Tensor], dst_keep: torch.Tensor,
-                   src_keep: torch.Tensor, src_to_dst: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+                   src_keep: torch.Tensor, src_to_dst: Optional[torch.Tensor] = None, route: str = "torch") -> Dict[str, torch.Tensor]:
     """merge_two_3DGS (:233-271): prune both by their importance masks, move the source points by the 4x4
-    relative transform (homogeneous, with the divide of :252-254), append."""
+    relative transform (homogeneous, with the divide of :252-254), append.
+
+    route: "torch" = a boolean gather per tensor and side, then torch.cat; "kernel" = the moved points by the same three statements on all
+    source rows, the keep masks as flag bytes into two gsr_resize_plan calls, ONE host read of both metas, one gsr_merge_apply over the
+    six tensors (merge.py) -- the same tensors to the bit.  The kernel route has no CPU fallback."""
+    from . import merge, resize
+    merge.check_route(route, "merge_segments")
     out = {}
     xyz = src_seg["_xyz"]
     if src_to_dst is not None:
@@ -279,6 +285,19 @@ def merge_segments(dst_seg: Dict[str, torch.Tensor], src_seg: Dict[str, torch.Te
         h = xyz @ T[:3, :3].t() + T[:3, 3]
         w = xyz @ T[3, :3] + T[3, 3]
         xyz = h / w.unsqueeze(1)
+    if route == "kernel":
+        merge.need_device("merge_segments", dst_keep=dst_keep, src_keep=src_keep, **{"dst" + k: dst_seg[k] for k in SEGMENT_KEYS},
+                          **{"src" + k: src_seg[k] for k in SEGMENT_KEYS})
+        if dst_keep.dtype != torch.bool or src_keep.dtype != torch.bool:
+            raise ValueError("merge_segments: the keep masks are bool tensors")
+        n_dst, n_src = int(dst_seg["_xyz"].shape[0]), int(xyz.shape[0])
+        # a bool True is the byte 1 = GSR_RESIZE_KEEP: the masks are the flag bytes as they stand
+        plan_a, meta_a = resize.resize_plan(dst_keep.reshape(-1).contiguous().view(torch.uint8))
+        plan_b, meta_b = resize.resize_plan(src_keep.reshape(-1).contiguous().view(torch.uint8))
+        kept_dst, _, kept_src, _ = merge.read_counts_pair(meta_a, meta_b)          # the one host wait
+        moved = merge.merge_apply(plan_a, meta_a, n_dst, kept_dst, plan_b, n_src, kept_src, [dst_seg[k] for k in SEGMENT_KEYS],
+                                  [xyz if k == "_xyz" else src_seg[k] for k in SEGMENT_KEYS])
+        return dict(zip(SEGMENT_KEYS, moved))
     xyz = xyz[src_keep]
     for key in SEGMENT_KEYS:
         s = xyz if key == "_xyz" else src_seg[key][src_keep]

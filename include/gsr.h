@@ -380,7 +380,8 @@ const char* gsr_last_error(void);
  * 117: the retire table: gsr_forward_retire, GsrBackwardArgs ends with retired_at, retire_step, gsr_batch_retire; GsrForwardArgs unchanged.
  * 118: gsr_depth_to_points, gsr_voxel_scratch_bytes, gsr_voxel_down_sample; no struct changes (gsr_struct_bytes as in 117).
  * 119: gsr_camera_from_pose, gsr_pose_virtual_view; no struct changes.
- * 120: gsr_resize_plan, gsr_resize_apply, gsr_resize_scratch_bytes, gsr_resize_plan_bytes (GsrResizeTensor is new); no existing struct changes. */
+ * 120: gsr_resize_plan, gsr_resize_apply, gsr_resize_scratch_bytes, gsr_resize_plan_bytes (GsrResizeTensor is new); no existing struct changes.
+ * 121: gsr_select_scratch_bytes, gsr_select_smallest, gsr_merge_apply (GsrMergeTensor is new); no existing struct changes. */
 int gsr_version(void);
 size_t gsr_struct_bytes(int32_t which); /* 0 GsrForwardArgs, 1 GsrBackwardArgs, 2 GsrForwardOut; anything else 0 */
 
@@ -816,6 +817,68 @@ int    gsr_resize_plan(const uint8_t* flags /*[N]*/, int64_t N, void* plan, size
                        void* scratch, size_t scratch_bytes, void* stream);
 int    gsr_resize_apply(const void* plan, size_t plan_bytes, int64_t N, int64_t nA, int64_t nB, int64_t nC, int64_t nSplit,
                         const GsrResizeTensor* tensors, int32_t count, int64_t* meta, void* stream);
+
+/* ---- the merge on the device (version 121) -----------------------------------------------------------------------------------------------
+ * merge_two_3DGS drops the prune_ratio * N Gaussians of least importance on both sides and appends what is left of the source to what is
+ * left of the destination.  Two entries: which rows go (gsr_select_smallest), and the move of two models' kept rows into one (gsr_merge_apply,
+ * after one gsr_resize_plan per model).  Like the resize they decide with integers and copy bytes; both are asynchronous on `stream`, wait
+ * for nothing on the host, and no workgroup waits for another one.
+ *
+ * gsr_select_smallest: the k rows of values [N, C] (float32, row-major, device) with the smallest row maximum.
+ *   score  the maximum of the row's C values; a NaN anywhere in the row makes the score NaN (torch.amax).
+ *   key    the score as an unsigned 32-bit integer that orders like the float: -0 counts as +0; a non-negative float is its bits with the
+ *          sign bit set, a negative one the complement of its bits (so negatives order below positives and -inf is lowest); every NaN is
+ *          0xffffffff, the largest key of all -- the order of torch.topk(largest=False).
+ *   The k rows with the smallest keys are selected.  AMONG ROWS WHOSE KEY EQUALS THE k-TH SMALLEST KEY (the threshold key), THOSE WITH THE
+ *   LOWEST ROW NUMBERS ARE TAKEN: the selection is np.argsort(key, kind="stable")[:k], where torch.topk promises no rule.
+ *   drop        [N] or NULL: 1 for a selected row, 0 otherwise (a torch bool mask, byte for byte).
+ *   keep_flags  [N] or NULL: GSR_RESIZE_KEEP for a row that is not selected, 0 for a selected one: the flag bytes gsr_resize_plan takes.
+ *   meta        GSR_SELECT_META_WORDS x int64 on the device, 8-byte aligned: {k, rows with a key below the threshold key, rows with the
+ *               threshold key, the threshold key, NaN rows, status = 0, 0, 0}.  With k == 0 nothing is selected and the threshold key and
+ *               the two counts beside it are 0 (the NaN rows are still counted); with N == 0 all eight words are 0.
+ *   scratch     gsr_select_scratch_bytes(N) bytes, 4-byte aligned (the keys, four histograms of 256 bins, one counter per 256 rows): a
+ *               closed form in N, monotone, 0 for N <= 0.
+ *   The only float operations are comparisons.  Histograms are summed with integer atomics, whose result does not depend on their order: a
+ *   repeat of the call is bit-identical.  Addresses are formed from row numbers below N, tile numbers below ceil(N / 256) and digits below
+ *   256 only; the positions counted by the histograms are compared with k and with each other, never added to a pointer.
+ *   GSR_SELECT_MAX_COLUMNS is 64: with C a multiple of 4 a workgroup stages 256 rows x C / 4 partial keys in LDS, 16 KiB at the cap; 48
+ *   (SH degree 3, three channels) and 64 (the same with a fourth channel) pass.  Wider inputs are reduced by the caller first.
+ *   GSR_ERR_ARG (before a device is touched; gsr_last_error() names the rule): N < 0 or N >= 2^31 (a plan's row numbers are int32), C < 1
+ *   or C > GSR_SELECT_MAX_COLUMNS, k < 0 or k > N, meta NULL or misaligned, and for N > 0 drop and keep_flags both NULL, values or scratch
+ *   NULL or not 4-byte aligned, scratch shorter than gsr_select_scratch_bytes(N).  N == 0 (only meta is written; the other pointers
+ *   may be NULL, as an empty allocation's are), k == 0 and k == N are served.
+ *
+ * gsr_merge_apply: plan_a / plan_b are the plans gsr_resize_plan wrote for the flag bytes of model a (Na rows) and model b (Nb rows); only
+ * their GSR_RESIZE_PLAN_ROWS_A segments are read, nA / nB are the lengths the caller read from the two metas.  Destination rows [0, nA) are
+ * model a's kept rows ascending, rows [nA, nA + nB) model b's: prune_points on both, then densification_postfix.  One launch over up to
+ * GSR_RESIZE_MAX_TENSORS tensors, rows moved in 4-byte words; dst [nA + nB, row_bytes] is a fresh buffer that overlaps nothing.  By kind:
+ *   GSR_RESIZE_PARAM   both parts are copies of their source rows;
+ *   GSR_RESIZE_MOMENT  the rows of a are copies, the rows of b are zero (all bits) and src_b is not read (it may be NULL): what
+ *                      cat_tensors_to_optimizer leaves of the destination's optimizer state.
+ * A tensor with row_bytes == 0, or with src_a, src_b and dst all NULL, is skipped.  A plan entry outside [0, Na) (for b: [0, Nb)) is never
+ * used as an address: its destination row is written as zeros and meta[GSR_RESIZE_META_STATUS] is set to 1 (meta: 8 x int64 on the
+ * device, either plan's meta -- gsr_resize_plan cleared its status word).  nA + nB == 0 is not an error: nothing is launched.
+ * GSR_ERR_ARG (before anything is enqueued): Na or Nb outside [0, 2^31), meta NULL or misaligned, count < 0 or beyond
+ * GSR_RESIZE_MAX_TENSORS, tensors NULL with count > 0, nA outside [0, Na] or nB outside [0, Nb], plan_a (plan_b) NULL, misaligned or
+ * shorter than gsr_resize_plan_bytes(Na) (Nb) when nA > 0 (nB > 0), a row_bytes that is negative, not a multiple of 4 or 2^31 and more, a
+ * kind other than PARAM and MOMENT, sources without dst, src_a NULL with nA > 0, src_b NULL on a PARAM tensor with nB > 0, a misaligned
+ * src_a / src_b / dst. */
+#define GSR_SELECT_MAX_COLUMNS 64
+#define GSR_SELECT_META_WORDS 8
+typedef struct GsrMergeTensor {
+    const void* src_a;    /* [Na, row_bytes] */
+    const void* src_b;    /* [Nb, row_bytes]; may be NULL for GSR_RESIZE_MOMENT */
+    void* dst;            /* [nA + nB, row_bytes] */
+    int64_t row_bytes;
+    int32_t kind;
+    int32_t reserved;
+} GsrMergeTensor;
+size_t gsr_select_scratch_bytes(int64_t N);
+int    gsr_select_smallest(const float* values /*[N,C] row-major*/, int64_t N, int32_t C, int64_t k, uint8_t* drop /*[N] or NULL*/,
+                           uint8_t* keep_flags /*[N] or NULL*/, int64_t* meta /*device, 8 x int64*/, void* scratch, size_t scratch_bytes,
+                           void* stream);
+int    gsr_merge_apply(const void* plan_a, size_t plan_a_bytes, int64_t Na, int64_t nA, const void* plan_b, size_t plan_b_bytes, int64_t Nb,
+                       int64_t nB, const GsrMergeTensor* tensors, int32_t count, int64_t* meta, void* stream);
 
 /* Measurement hook (bench.py roofline.peak_measured): float4 streaming copy of `bytes` bytes (a multiple of 16, 16-byte aligned
  * pointers) with `blocks` workgroups of 256 threads.  variant 0 = plain loads / stores, 1 = nt bit, 2 = four loads in flight per

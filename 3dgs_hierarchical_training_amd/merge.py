@@ -5,7 +5,7 @@
   merge_apply       gsr_merge_apply       (csrc/resize_kernels.hip)
 
 The kernels decide with integers and copy bytes; they compute no float.  `hierarchy.prune_mask(route="kernel")` and
-`segments.merge_segments(route="kernel")` are the callers.  Both bindings serve it: `torch.ops.gsr.select_smallest` / `merge_apply`, and the
+`segments.merge_segments(route="kernel")` are the callers, and `gsr_autopatch.merge_two_3DGS_fused` under the unmodified trainer.  Both bindings serve it: `torch.ops.gsr.select_smallest` / `merge_apply`, and the
 ctypes view of the same C ABI under GSR_BINDING=ctypes.  No CPU fallback: a CPU tensor raises RuntimeError before a device is touched.
 """
 import ctypes as C

@@ -589,3 +589,96 @@ class StubSurgeryModel:
     def reset_opacity(self):
         capped = torch.min(self.get_opacity, torch.ones_like(self.get_opacity) * 0.01)
         self._adopt(self.replace_tensor_to_optimizer(self.inverse_opacity_activation(capped), "opacity"))
+
+
+# ---- the merge: `HTGaussianTrainer.merge_two_3DGS` as the unmodified trainer runs it ----------------------------------------------------------
+# Written from what the reference's method DOES (trainer/ht3dgs_trainer.py:226-272, `calc_importance` :1427-1462), in this
+# file's own words over `StubSurgeryModel`: the method and attribute names are the interface (`gsr_autopatch` replaces `merge_two_3DGS` and
+# calls the rest), the statements are this file's.
+class StubModelRender(StubRender):
+    """`StubRender` around a model that exists already (a `StubSurgeryModel`): `.gaussians`, `.bg_color`, the original wrapper's `render`."""
+
+    def __init__(self, gaussians, bg=(0.0, 0.0, 0.0)):
+        self.gaussians = gaussians
+        self.bg_color = torch.tensor(bg, dtype=torch.float32, device=gaussians._xyz.device)
+
+
+class _ListLogger:
+    """`logger.info` that keeps its lines."""
+
+    def __init__(self):
+        self.lines = []
+
+    def info(self, text):
+        self.lines.append(str(text))
+
+
+class StubMergeTrainer:
+    """Stand-in for `HTGaussianTrainer` as far as a merge goes: `logger`, `pipe_cfg.prune_ratio`, a counting `load_viewpoint_cam` that hands
+    out prepared cameras, `calc_importance` (a staticmethod, looked up on the class at the call -- replace it on a subclass to inject
+    prepared scores) and `merge_two_3DGS` with the reference's sequence of torch operations: per model the row maximum of the score, `topk` of
+    the lowest, a zero fill and an indexed store for the mask; `prune_points` on the destination between the two scores; the source's points
+    through the homogeneous transform on all rows; six boolean gathers; `densification_postfix`.  It is the unpatched arm
+    `gsr_autopatch.merge_two_3DGS_fused` is compared with and timed against.  Tensors are created on the model's own device, so the same
+    class runs on the CPU for the dispatch tests."""
+
+    def __init__(self, prune_ratio=0.5, cameras=None):
+        import types
+        self.pipe_cfg = types.SimpleNamespace(prune_ratio=prune_ratio, compute_cov3D_python=False, convert_SHs_python=False)
+        self.logger = _ListLogger()
+        self.cameras = {} if cameras is None else cameras            # frame index -> camera
+        self.cam_calls = []                                          # (frame index, pose, load_depth) per call, in order
+
+    def load_viewpoint_cam(self, idx, pose=None, load_depth=False, pose_to_train=False, load_vfi=False):
+        self.cam_calls.append((idx, pose, load_depth))
+        return self.cameras.get(idx)
+
+    @staticmethod
+    def calc_importance(gs_render, cameras, pipe):
+        """Sum over the cameras of |d sum(render) / d SH coefficient|, over the pixel count: [N, 3 M]."""
+        g = gs_render.gaussians
+        hooks = [t.register_hook(lambda grad: grad.abs()) for t in (g._features_dc, g._features_rest)]
+        g._features_dc.grad = None
+        g._features_rest.grad = None
+        num_pixels = 0
+        for cam in cameras:
+            image = gs_render.render(cam, compute_cov3D_python=pipe.compute_cov3D_python, convert_SHs_python=pipe.convert_SHs_python,
+                                     override_color=None)["image"]
+            image.sum().backward()
+            num_pixels += image.shape[1] * image.shape[2]
+        importance = torch.cat([g._features_dc.grad, g._features_rest.grad], 1).flatten(-2) / num_pixels
+        for h in hooks:
+            h.remove()
+        if g._xyz.is_cuda:
+            torch.cuda.empty_cache()
+        return importance.detach()
+
+    def _cameras_of(self, gaussians, frames):
+        cams = []
+        for fidx in frames:
+            pose = gaussians.get_RT(fidx).detach().cpu() if not gaussians.rotate_seq else None
+            cams.append(self.load_viewpoint_cam(fidx, pose=pose, load_depth=True))
+        return cams
+
+    def _lowest_mask(self, gaussians, importance):
+        score = importance.amax(-1).squeeze()
+        _, lowest = torch.topk(score, int(score.shape[0] * self.pipe_cfg.prune_ratio), largest=False)
+        mask = torch.zeros((gaussians._xyz.shape[0], 1), device=gaussians._xyz.device)
+        mask[lowest, :] = 1
+        return mask.bool()
+
+    def merge_two_3DGS(self, gs_render_dst, gs_render_src, transform_matrix, to_visit_frames_dst=None, to_visit_frames_src=None):
+        dst, src = gs_render_dst.gaussians, gs_render_src.gaussians
+        self.logger.info(f"The number of 3D Gaussians in the first 3DGS before merging: {dst.get_xyz.shape[0]}")
+        self.logger.info(f"The number of 3D Gaussians in the second 3DGS before merging: {src.get_xyz.shape[0]}")
+        importance = type(self).calc_importance(gs_render_dst, self._cameras_of(dst, to_visit_frames_dst), self.pipe_cfg)
+        dst.prune_points(self._lowest_mask(dst, importance).squeeze())
+        importance = type(self).calc_importance(gs_render_src, self._cameras_of(src, to_visit_frames_src), self.pipe_cfg)
+        keep = ~(self._lowest_mask(src, importance).squeeze())
+        n = len(src._xyz)
+        homogeneous = torch.cat([src._xyz, torch.ones((n, 1), device=src._xyz.device)], dim=1)
+        moved = homogeneous @ transform_matrix.T
+        moved = moved[:, :3] / moved[:, 3].unsqueeze(1)
+        dst.densification_postfix(moved[keep], src._features_dc[keep], src._features_rest[keep], src._opacity[keep], src._scaling[keep],
+                                  src._rotation[keep])
+        self.logger.info(f"The number of 3D Gaussians in the merged 3DGS: {dst.get_xyz.shape[0]}")

@@ -82,6 +82,29 @@ Importing this module BEFORE the trainer swaps both for the HIP kernels of this 
     at 130 k / degree 0, beyond the same-arm spread (<= 0.40 ms) at all three sizes -- GSR_AUTOPATCH_RESIZE: ships ON
     (`GSR_AUTOPATCH_RESIZE=0` leaves both methods alone).
 
+  * `trainer.ht3dgs_trainer.HTGaussianTrainer.merge_two_3DGS` (trainer/ht3dgs_trainer.py:214-272; patched where
+    `calc_importance` is, through the same hook): the same log lines, the same `load_viewpoint_cam` calls in the same order, both scores
+    through `HTGaussianTrainer.calc_importance` as the class holds it at the call (the patched one above, or a user's own); then
+    gsr_select_smallest per model on the [N, C] score as it stands instead of `amax`, `topk`, a zero fill and an indexed store; the
+    reference's own three torch statements for the moved points on all source rows (the floats are the unpatched trainer's to the bit);
+    two gsr_resize_plan and ONE gsr_merge_apply over the destination's six parameters and twelve moments (kept rows copied, appended rows
+    zero) instead of `prune_points`, twelve boolean gathers and `densification_postfix`; installed as the resize patch installs, statistics
+    zeroed.  The kept counts are N - int(N * prune_ratio) by construction, so from the scores on the call does not wait for the device
+    (the stand-in's statements: 29 synchronisation warnings).  Nothing of the source model is written.  THE TIE RULE is the patch's own:
+    among rows whose score equals the k-th smallest, the rows with the lowest row numbers go, where `torch.topk` promises nothing; with
+    distinct scores at the threshold the result is the unpatched trainer's to the bit; where they tie (unseen Gaussians, score exactly
+    0) as many rows go, every row strictly below the threshold goes, and the tied rows that go are the lowest-numbered.  A model outside
+    the resize patch's layout (the source: its six tensors), two models of unlike trailing shapes / dtype / device, a `transform_matrix`
+    that is not a float32 [4,4] tensor on that device, a `prune_ratio` that is not a number in [0, 1] or a model of fewer than 2 rows
+    run the ORIGINAL method, decided before a camera is loaded; an importance of another shape, dtype or device, or wider than
+    GSR_SELECT_MAX_COLUMNS, finishes the call with the reference's own statements on that importance.  Measured on one MI355X against
+    the stand-in of the same process, every other patch installed in both arms (tools/trainer_merge_probe.py,
+    profiles/trainer_merge.txt; two models of N rows, ratio 0.5, 30 % zero scores): 2.42 -> 1.03 ms at 1 M / degree 3, 1.54 -> 0.65 at
+    300 k / degree 3, 1.27 -> 0.55 at 130 k / degree 0 with prepared scores, 3.91 -> 2.59, 2.53 -> 1.60, 2.16 -> 1.33 with
+    `calc_importance` over two views per model, beyond the same-arm spread (<= 0.02 ms) at all three sizes; the peak allocation of the
+    call is higher (767 against 463 MiB at 1 M: all 18 destinations exist before the old tensors are released) --
+    GSR_AUTOPATCH_MERGE: ships ON (`GSR_AUTOPATCH_MERGE=0` leaves the method alone).
+
 `apply()` / `remove()` switch the patches on and off (importing the module calls `apply()`); `GSR_AUTOPATCH=0` disables them.
 The rasterizer itself needs no patch: `diff_gaussian_rasterization` IS this library's drop-in package.
 """
@@ -586,6 +609,12 @@ def calc_importance_fused(gs_render, cameras, pipe, override_color=None):
 
 
 def _patch_trainer_module(mod):
+    """`trainer.ht3dgs_trainer` holds `HTGaussianTrainer`: its `calc_importance` and its `merge_two_3DGS`, each behind its own switch."""
+    _patch_importance_module(mod)
+    _patch_merge_module(mod)
+
+
+def _patch_importance_module(mod):
     # (on since the kernel route was measured faster than a render and a full backward per view at both sizes:
     #  profiles/importance_probe.txt, DESIGN.md section 6)
     if os.environ.get("GSR_AUTOPATCH_IMPORTANCE", "1") == "0":
@@ -827,11 +856,16 @@ def _resize_original(self, attr):
 
 
 def _resize_entries(self):
+    """`_resize_layout` behind the switch of the resize patch."""
+    if os.environ.get("GSR_AUTOPATCH_RESIZE", _RESIZE_DEFAULT) == "0":
+        return None
+    return _resize_layout(self)
+
+
+def _resize_layout(self):
     """[(group, attribute, parameter, state or None)] in the optimizer's group order when the model has the layout the resize kernels take,
     else None: exactly the six named groups of one parameter each, which are the model's six raw tensors; those, the moments that exist and
     the three statistics tensors float32, contiguous, N rows, on one device (the GPU); 0 < N < 2^31."""
-    if os.environ.get("GSR_AUTOPATCH_RESIZE", _RESIZE_DEFAULT) == "0":
-        return None
     opt = getattr(self, "optimizer", None)
     groups = getattr(opt, "param_groups", None)
     if groups is None or not hasattr(opt, "state") or len(groups) != 6 or sorted(g.get("name", "") for g in groups) != sorted(FUSED_NAMES):
@@ -983,6 +1017,162 @@ def _patch_resize_module(mod):
         setattr(cls, attr, fn)
 
 
+# ---- HTGaussianTrainer.merge_two_3DGS: the selection and the row move of a merge on the merge kernels ----------------------------------------
+# The reference's merge (trainer/ht3dgs_trainer.py:214-272) scores both models, drops the `prune_ratio` lowest-scoring rows of
+# each (`amax`, `topk`, a zero fill and an indexed store per mask), prunes the destination tensor by tensor, gathers the kept source rows
+# tensor by tensor and appends them with six `torch.cat` and twelve moment `cat`s.  The body below keeps the reference's order of calls and
+# its torch statements wherever a float is computed (the importance through the class's own `calc_importance`, the moved points), and hands
+# the decisions and the bytes to the kernels: gsr_select_smallest per model, gsr_resize_plan per model, ONE gsr_merge_apply over the
+# destination's six parameters and the moments that exist.
+#
+# THE TIE RULE is this patch's own: among rows whose score equals the k-th smallest, the rows with the LOWEST ROW NUMBERS go
+# (gsr_select_smallest, `np.argsort(key, kind="stable")[:k]`); `torch.topk` promises nothing there.  Where the scores at the threshold are
+# distinct the result is the unpatched trainer's to the bit.  Where they tie -- typically unseen Gaussians with a score of exactly 0 -- the
+# number of rows dropped is the same, every row strictly below the threshold is dropped, and the tied rows that go are the lowest-numbered.
+_patched_merge_classes = []         # [(class, attribute, original function)]
+_MERGE_DEFAULT = "1"
+
+
+def _merge():
+    return importlib.import_module("3dgs_hierarchical_training_amd.merge")
+
+
+def _merge_original(self):
+    orig = next((f for c, a, f in _patched_merge_classes if a == "merge_two_3DGS" and isinstance(self, c)), None)
+    if orig is None:
+        raise RuntimeError("gsr_autopatch: this call needs the original HTGaussianTrainer.merge_two_3DGS")
+    return orig
+
+
+def _merge_source_tensors(g):
+    """The six raw tensors of a merge's source model under the tensor checks of `_resize_layout` (its optimizer is not needed), else None."""
+    ts = [getattr(g, k, None) for k in RAW_NAMES]
+    x = ts[0]
+    if not torch.is_tensor(x) or x.dim() != 2 or (_REQUIRE_CUDA and not x.is_cuda) or not 0 < x.shape[0] < 2 ** 31:
+        return None
+    if not all(torch.is_tensor(t) and t.dtype == torch.float32 and t.device == x.device and t.is_contiguous() and t.dim() >= 1 and
+               t.shape[0] == x.shape[0] for t in ts):
+        return None
+    return ts
+
+
+def _merge_setup(self, gs_render_dst, gs_render_src, transform_matrix):
+    """(destination entries, source tensors, prune_ratio) when the patched merge serves this call, else None.  Reads attributes only: no
+    camera is loaded, nothing is rendered or written."""
+    if os.environ.get("GSR_AUTOPATCH_MERGE", _MERGE_DEFAULT) == "0":
+        return None
+    g_dst, g_src = getattr(gs_render_dst, "gaussians", None), getattr(gs_render_src, "gaussians", None)
+    if g_dst is None or g_src is None or g_dst is g_src:
+        return None
+    entries, src = _resize_layout(g_dst), _merge_source_tensors(g_src)
+    if entries is None or src is None:
+        return None
+    dst = [getattr(g_dst, k) for k in RAW_NAMES]
+    if any(a.shape[1:] != b.shape[1:] or a.dtype != b.dtype or a.device != b.device for a, b in zip(dst, src)):
+        return None
+    if tuple(dst[0].shape[1:]) != (3,) or dst[0].shape[0] < 2 or src[0].shape[0] < 2:      # (`amax(-1).squeeze()` loses its dimension at N = 1)
+        return None
+    T = transform_matrix
+    if not (type(T) is torch.Tensor and tuple(T.shape) == (4, 4) and T.dtype == torch.float32 and T.device == dst[0].device):
+        return None
+    ratio = getattr(getattr(self, "pipe_cfg", None), "prune_ratio", None)
+    if not isinstance(ratio, numbers.Real) or not 0 <= ratio <= 1:
+        return None
+    return entries, src, ratio
+
+
+def _merge_importance_ok(imp, like) -> bool:
+    return type(imp) is torch.Tensor and imp.dtype == torch.float32 and imp.device == like.device and imp.dim() == 2 and \
+        imp.shape[0] == like.shape[0] and 1 <= imp.shape[1] <= _merge().L.GSR_SELECT_MAX_COLUMNS
+
+
+def _merge_reference_tail(g_dst, g_src, importance_dst, importance_src, transform_matrix, ratio):
+    """The reference's own statements from the importance on (ht3dgs_trainer.py:234-271), through the model's methods."""
+    dev = g_dst._xyz.device
+    masks = []
+    for g, importance in ((g_dst, importance_dst), (g_src, importance_src)):
+        score = importance.amax(-1).squeeze()
+        _, lowest = torch.topk(score, int(score.shape[0] * ratio), largest=False)
+        mask = torch.zeros((g._xyz.shape[0], 1), device=dev)
+        mask[lowest, :] = 1
+        masks.append(mask.bool())
+    g_dst.prune_points(masks[0].squeeze())
+    n = len(g_src._xyz)
+    points_homogeneous = torch.cat([g_src._xyz, torch.ones((n, 1), device=dev)], dim=1)
+    aligned_xyz_homogeneous = points_homogeneous @ transform_matrix.T
+    aligned_xyz = aligned_xyz_homogeneous[:, :3] / aligned_xyz_homogeneous[:, 3].unsqueeze(1)
+    valid = ~(masks[1].squeeze())
+    g_dst.densification_postfix(aligned_xyz[valid], g_src._features_dc[valid], g_src._features_rest[valid], g_src._opacity[valid],
+                                g_src._scaling[valid], g_src._rotation[valid])
+
+
+def merge_two_3DGS_fused(self, gs_render_dst, gs_render_src, transform_matrix, to_visit_frames_dst=None, to_visit_frames_src=None):
+    """Drop-in body of `HTGaussianTrainer.merge_two_3DGS` (trainer/ht3dgs_trainer.py:214-272): same arguments, the same log
+    lines, the same `load_viewpoint_cam` calls in the same order, both scores through `HTGaussianTrainer.calc_importance` as the class holds
+    it at the call.  Then gsr_select_smallest per model on the [N, C] importance as it stands (no `amax`, `topk` or indexed store), the
+    reference's three statements for the moved points on all source rows, two gsr_resize_plan and one gsr_merge_apply over the destination's
+    six parameters and the moments that exist (kept rows copied, appended rows zero: what `_prune_optimizer` and `cat_tensors_to_optimizer`
+    leave), installed as the resize patch installs (fresh `nn.Parameter` leaves, `.grad` None, state re-keyed with `step` kept; a deferred
+    Adam update that was planned on the replaced tensors is dropped by `step()`, as after `prune_points`), statistics zeroed.  The kept
+    counts are N - int(N * prune_ratio) by construction, so the call does not wait for the device at all.  Nothing of the source model is
+    written.  Ties at the threshold: see THE TIE RULE above.  The switch off, a model outside the resize patch's layout, two models of unlike
+    trailing shapes / dtype / device, a `transform_matrix` that is not a float32 [4,4] tensor on that device, a `prune_ratio` outside [0, 1]
+    or a model of fewer than 2 rows run the ORIGINAL method, decided before anything is loaded or rendered; an importance of another shape,
+    dtype or device (or wider than GSR_SELECT_MAX_COLUMNS) finishes the call with the reference's own statements on that importance."""
+    setup = _merge_setup(self, gs_render_dst, gs_render_src, transform_matrix)
+    if setup is None:
+        return _merge_original(self)(self, gs_render_dst, gs_render_src, transform_matrix, to_visit_frames_dst, to_visit_frames_src)
+    entries, src, ratio = setup
+    trainer_cls = next((c for c, a, _ in _patched_merge_classes if a == "merge_two_3DGS" and isinstance(self, c)), type(self))
+    g_dst, g_src = gs_render_dst.gaussians, gs_render_src.gaussians
+    n_dst, n_src, dev = g_dst._xyz.shape[0], g_src._xyz.shape[0], g_dst._xyz.device
+    self.logger.info(f"The number of 3D Gaussians in the first 3DGS before merging: {n_dst}")
+    self.logger.info(f"The number of 3D Gaussians in the second 3DGS before merging: {n_src}")
+    importance = []
+    for g, render, frames in ((g_dst, gs_render_dst, to_visit_frames_dst), (g_src, gs_render_src, to_visit_frames_src)):
+        cameras = []
+        for fidx in frames:
+            pose = g.get_RT(fidx).detach().cpu() if not g.rotate_seq else None
+            cameras.append(self.load_viewpoint_cam(fidx, pose=pose, load_depth=True))
+        importance.append(trainer_cls.calc_importance(render, cameras, self.pipe_cfg))
+    with torch.no_grad():
+        if not (_merge_importance_ok(importance[0], g_dst._xyz) and _merge_importance_ok(importance[1], g_src._xyz)):
+            _merge_reference_tail(g_dst, g_src, importance[0], importance[1], transform_matrix, ratio)
+        else:
+            M, R = _merge(), _resize()
+            k_dst, k_src = int(n_dst * ratio), int(n_src * ratio)
+            keep_dst = M.select_smallest(importance[0].contiguous(), k_dst)[1]
+            keep_src = M.select_smallest(importance[1].contiguous(), k_src)[1]
+            points_homogeneous = torch.cat([src[0], torch.ones((n_src, 1), device=dev)], dim=1)
+            aligned_xyz_homogeneous = points_homogeneous @ transform_matrix.T
+            aligned_xyz = aligned_xyz_homogeneous[:, :3] / aligned_xyz_homogeneous[:, 3].unsqueeze(1)
+            plan_dst, meta = R.resize_plan(keep_dst)
+            plan_src, _ = R.resize_plan(keep_src)
+            kept_dst, kept_src = n_dst - k_dst, n_src - k_src          # (what the two metas hold; reading them would be the call's one wait)
+            by_attr = dict(zip(RAW_NAMES, [aligned_xyz] + [t.detach() for t in src[1:]]))
+            src_a, src_b, kinds = [], [], []
+            for _, attr, p, st in entries:
+                src_a.append(p.detach()); src_b.append(by_attr[attr]); kinds.append(M.PARAM)
+                if st is not None:
+                    src_a += [st["exp_avg"], st["exp_avg_sq"]]; src_b += [None, None]; kinds += [M.MOMENT, M.MOMENT]
+            _install_resized(g_dst, entries, M.merge_apply(plan_dst, meta, n_dst, kept_dst, plan_src, n_src, kept_src, src_a, src_b, kinds))
+            n = kept_dst + kept_src
+            g_dst.xyz_gradient_accum = torch.zeros((n, 1), device=dev)
+            g_dst.denom = torch.zeros((n, 1), device=dev)
+            g_dst.max_radii2D = torch.zeros((n,), device=dev)
+    self.logger.info(f"The number of 3D Gaussians in the merged 3DGS: {g_dst._xyz.shape[0]}")
+
+
+def _patch_merge_module(mod):
+    if os.environ.get("GSR_AUTOPATCH_MERGE", _MERGE_DEFAULT) == "0":
+        return
+    cls = getattr(mod, "HTGaussianTrainer", None)
+    if cls is None or not hasattr(cls, "merge_two_3DGS") or any(c is cls for c, _, _ in _patched_merge_classes):
+        return
+    _patched_merge_classes.append((cls, "merge_two_3DGS", cls.merge_two_3DGS))
+    cls.merge_two_3DGS = merge_two_3DGS_fused
+
+
 # ---- utils.image_utils.psnr: the training PSNR the trainer evaluates on every iteration (ht3dgs_trainer.py:138) ---------------------
 IMAGE_UTILS_MODULES = ("utils.image_utils",)
 _patched_psnr = []                  # [(module, attribute, original function)]
@@ -1115,6 +1305,9 @@ def remove():
         setattr(cls, attr, fn)
     while _patched_frame_classes:
         cls, attr, fn = _patched_frame_classes.pop()
+        setattr(cls, attr, fn)
+    while _patched_merge_classes:
+        cls, attr, fn = _patched_merge_classes.pop()
         setattr(cls, attr, fn)
     while _patched_resize_classes:
         cls, attr, fn = _patched_resize_classes.pop()

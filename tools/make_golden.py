@@ -19,6 +19,10 @@ What it pins, and with what:
                        frame poses (refstub's SE3 standing in for lietorch), rotate_seq on and off, uid != seq_idx
     trainer_resize.npz HTGaussianModel.densify_and_prune / prune_points (gaussian_model_ht.py:548-695) run on the CPU: four small models
                        before and after, optimizer moments and statistics included, and the samples torch.normal drew
+    trainer_merge.npz  HTGaussianTrainer.merge_two_3DGS (trainer/ht3dgs_trainer.py:214-272), the one function compiled out of the file's
+                       text (the module is never imported) and run on the CPU over two HTGaussianModel objects with prepared distinct
+                       scores: four cases (257 + 300 and 1000 + 64 rows, 16 and 1 stored coefficients, with and without optimizer state,
+                       ratios 0.5 and 0.25, a rigid and a projective transform), both models before, the destination after
   self-generated regression vectors (our oracle, NOT the reference -- parity unpinned, see oracle header):
     oracle_c1_deg0.npz, oracle_small_deg3.npz   full forward + backward of oracle/gsr_oracle.c
 
@@ -523,6 +527,139 @@ def gen_trainer_resize(out):
     np.savez_compressed(os.path.join(out, "trainer_resize.npz"), **res)
 
 
+TRAINER_MERGE_CASES = {
+    # case: (N destination, N source, stored SH coefficients, optimizer state, prune_ratio, transform)
+    "a": (257, 300, 16, True, 0.5, "rigid"),
+    "b": (1000, 64, 1, False, 0.25, "projective"),
+    "c": (1000, 64, 16, False, 0.5, "projective"),
+    "d": (257, 300, 1, True, 0.25, "rigid"),
+}
+TRAINER_MERGE_STATS = ("xyz_gradient_accum", "denom", "max_radii2D")
+
+
+def trainer_merge_inputs(case, seed):
+    """Inputs of one case of trainer_merge.npz, numpy float32: per model the six raw tensors, twelve moments, the three statistics tensors
+    and the [N, 3 M] scores (every row's maximum distinct, or the seed is refused); the transform; the ratio.  The colour tensors and the
+    moments are multiples of 1/64 (the merge copies them; the file stays small).  The one thing the merge COMPUTES is the moved points, a
+    [n,4] x [4,4] product whose last bits depend on the machine's GEMM (order of the four terms, fused multiply-adds); the points are
+    therefore multiples of 1/256 and the transform's entries multiples of 1/64 with few bits, so that every product and every partial sum
+    is exact in float32 in any order and the one rounding left, the division by w, is the same on every machine: a test may hold the
+    recorded points with `torch.equal` wherever it runs.  The rigid transform is a quarter-turn rotation (a signed permutation matrix of
+    determinant +1) and a translation; the projective one a scaled, sheared matrix whose fourth row is (1/64, -1/32, 1/64, 1.125)."""
+    n_dst, n_src, coeffs, _, ratio, kind = TRAINER_MERGE_CASES[case]
+    rng = np.random.default_rng(seed)
+    grid = lambda scale, shape: np.round(rng.normal(0, scale, shape) * 64) / 64
+    models = []
+    for n in (n_dst, n_src):
+        d = {"_xyz": np.round(rng.uniform(-2, 2, (n, 3)) * 256) / 256, "_features_dc": grid(0.5, (n, 1, 3)), "_features_rest": grid(0.25, (n, coeffs - 1, 3)),
+             "_opacity": rng.uniform(-2.0, 3.0, (n, 1)), "_scaling": rng.uniform(-5.0, -2.0, (n, 3)), "_rotation": rng.normal(0, 1, (n, 4))}
+        d.update({"exp_avg" + k: grid(0.25, d[k].shape) for k in list(d)})
+        d.update({"exp_avg_sq" + k: np.abs(grid(0.25, d[k].shape)) for k in ("_xyz", "_features_dc", "_features_rest", "_opacity", "_scaling", "_rotation")})
+        d["xyz_gradient_accum"], d["denom"] = rng.uniform(0, 0.01, (n, 1)), rng.integers(0, 5, (n, 1))
+        d["max_radii2D"] = rng.uniform(0, 40, n)
+        top = ((rng.permutation(n) + 1) / (n + 1)).astype(np.float32)                    # the row maxima: distinct by construction ...
+        score = (np.floor(top[:, None] * rng.uniform(0.0, 0.9, (n, 3 * coeffs)) * 64) / 64).astype(np.float32)      # (below the maximum, on the grid)
+        score[np.arange(n), rng.integers(0, 3 * coeffs, n)] = top
+        if np.unique(score.max(axis=1)).size != n:                                       # ... and checked on what the file holds
+            raise SystemExit(f"gen_trainer_merge: case {case}, seed {seed}: two rows share a score; choose another seed")
+        d["score"] = score
+        models.append({k: np.ascontiguousarray(v, dtype=np.float32) for k, v in d.items()})
+    Q = np.zeros((3, 3))
+    Q[np.arange(3), rng.permutation(3)] = rng.choice([-1.0, 1.0], 3)
+    if np.linalg.det(Q) < 0:
+        Q[:, 0] = -Q[:, 0]
+    T = np.eye(4)
+    T[:3, :3], T[:3, 3] = Q, rng.integers(-64, 65, 3) / 64
+    if kind == "projective":
+        T[:3, :3] = 1.25 * Q + rng.integers(-8, 9, (3, 3)) / 16
+        T[3] = [1 / 64, -1 / 32, 1 / 64, 1.125]                                          # w between 1 and 1.25 on these points
+    exact = np.concatenate([models[1]["_xyz"].astype(np.float64), np.ones((models[1]["_xyz"].shape[0], 1))], axis=1) @ T.T
+    assert np.array_equal(exact.astype(np.float32).astype(np.float64), exact) and exact[:, 3].min() >= 1.0       # the product is exact in float32
+    return models, T.astype(np.float32), ratio
+
+
+def gen_trainer_merge(out, ref):
+    """trainer_merge.npz: the reference's own `HTGaussianTrainer.merge_two_3DGS` (trainer/ht3dgs_trainer.py:214-272) run on the CPU under the
+    shim over two real `HTGaussianModel` objects per case.  `trainer.ht3dgs_trainer` is NOT imported (its imports reach `trainer/trainer.py`,
+    which calls `torch.hub` at import): the file is read as text, the one function node is taken out with `ast` and compiled into a namespace
+    that holds `torch` and a stand-in `HTGaussianTrainer` whose static `calc_importance` returns the case's prepared scores.  Arrays only."""
+    import ast
+    from scene.gaussian_model_ht import HTGaussianModel
+    path = os.path.join(ref, "trainer", "ht3dgs_trainer.py")
+    with open(path) as f:
+        tree = ast.parse(f.read())
+    cls = next(n for n in tree.body if isinstance(n, ast.ClassDef) and n.name == "HTGaussianTrainer")
+    fn = next(n for n in cls.body if isinstance(n, ast.FunctionDef) and n.name == "merge_two_3DGS")
+    opt_args = types.SimpleNamespace(percent_dense=0.01, position_lr_init=0.00016, position_lr_final=0.0000016, position_lr_delay_mult=0.01,
+                                     position_lr_max_steps=30000, feature_lr=0.0025, opacity_lr=0.05, scaling_lr=0.005, rotation_lr=0.001)
+    res = {"cases": np.array(list(TRAINER_MERGE_CASES))}
+    for seed, case in enumerate(TRAINER_MERGE_CASES, start=61):
+        n_dst, n_src, coeffs, with_state, _, kind = TRAINER_MERGE_CASES[case]
+        inputs, T, ratio = trainer_merge_inputs(case, seed)
+        pre = case + "_"
+        res[pre + "transform"], res[pre + "prune_ratio"], res[pre + "state"] = T, np.float64(ratio), np.bool_(with_state)
+        scores, lines, loads = {}, [], []
+
+        class StandInTrainer:
+            @staticmethod
+            def calc_importance(gs_render, cameras, pipe):
+                return scores[id(gs_render)].clone()
+        namespace = {"torch": torch, "HTGaussianTrainer": StandInTrainer}
+        exec(compile(ast.Module(body=[fn], type_ignores=[]), path, "exec"), namespace)
+        trainer = types.SimpleNamespace(logger=types.SimpleNamespace(info=lines.append), pipe_cfg=types.SimpleNamespace(prune_ratio=ratio),
+                                        load_viewpoint_cam=lambda fidx, pose=None, load_depth=False: loads.append((fidx, load_depth)))
+        with _CudaToCpu():
+            renders = []
+            for side, d in zip(("dst", "src"), inputs):
+                m = HTGaussianModel(3 if coeffs == 16 else 0)
+                m.spatial_lr_scale, m.P = 1.0, None
+                for _, attr in TRAINER_RESIZE_GROUPS:
+                    setattr(m, attr, torch.nn.Parameter(torch.from_numpy(d[attr].copy()).requires_grad_(True)))
+                m.training_setup(opt_args)
+                if with_state:                                # one Adam step for the state's own layout, then the case's moments in its place
+                    for _, attr in TRAINER_RESIZE_GROUPS:
+                        getattr(m, attr).grad = torch.zeros_like(getattr(m, attr))
+                    m.optimizer.step()
+                    m.optimizer.zero_grad(set_to_none=True)
+                    for _, attr in TRAINER_RESIZE_GROUPS:
+                        st = m.optimizer.state[getattr(m, attr)]
+                        st["exp_avg"], st["exp_avg_sq"] = torch.from_numpy(d["exp_avg" + attr].copy()), torch.from_numpy(d["exp_avg_sq" + attr].copy())
+                for k in TRAINER_MERGE_STATS:
+                    setattr(m, k, torch.from_numpy(d[k].copy()))
+                r = types.SimpleNamespace(gaussians=m)
+                scores[id(r)] = torch.from_numpy(d["score"].copy())
+                renders.append(r)
+                for _, attr in TRAINER_RESIZE_GROUPS:
+                    res[f"{pre}{side}_in{attr}"] = t2n(getattr(m, attr)).copy()
+                    if with_state:
+                        st = m.optimizer.state[getattr(m, attr)]
+                        res[f"{pre}{side}_in_exp_avg{attr}"], res[f"{pre}{side}_in_exp_avg_sq{attr}"] = t2n(st["exp_avg"]).copy(), t2n(st["exp_avg_sq"]).copy()
+                        res[f"{pre}{side}_in_step{attr}"] = np.float64(float(st["step"]))
+                for k in TRAINER_MERGE_STATS:
+                    res[f"{pre}{side}_in_{k}"] = d[k]
+                res[f"{pre}{side}_score"] = d["score"]
+            namespace["merge_two_3DGS"](trainer, renders[0], renders[1], torch.from_numpy(T.copy()), [0, 1], [2, 3])
+        assert loads == [(0, True), (1, True), (2, True), (3, True)] and len(lines) == 3, (loads, lines)
+        m, src = renders[0].gaussians, renders[1].gaussians
+        for _, attr in TRAINER_RESIZE_GROUPS:                 # the source model is as it was
+            assert np.array_equal(t2n(getattr(src, attr)), res[f"{pre}src_in{attr}"])
+        for name, attr in TRAINER_RESIZE_GROUPS:
+            p = getattr(m, attr)
+            assert type(p) is torch.nn.Parameter and p.grad is None and p.is_leaf
+            res[pre + "out" + attr] = t2n(p).copy()
+            st = m.optimizer.state.get(p)
+            assert (st is not None) == with_state
+            if st is not None:
+                res[pre + "out_exp_avg" + attr], res[pre + "out_exp_avg_sq" + attr] = t2n(st["exp_avg"]).copy(), t2n(st["exp_avg_sq"]).copy()
+                res[pre + "out_step" + attr] = np.float64(float(st["step"]))
+        for k in TRAINER_MERGE_STATS:
+            res[pre + "out_" + k] = t2n(getattr(m, k)).copy()
+        res[pre + "log"] = np.array(lines)
+        print(f"gen_trainer_merge {case}: {n_dst} + {n_src} -> {m._xyz.shape[0]} ({kind}, ratio {ratio}, {'state' if with_state else 'no state'})")
+    np.savez_compressed(os.path.join(out, "trainer_merge.npz"), **res)
+    print("trainer_merge.npz", os.path.getsize(os.path.join(out, "trainer_merge.npz")), "bytes")
+
+
 def gen_oracle(out):
     sys.path.insert(0, REPO)
     syn = importlib.import_module("3dgs_hierarchical_training_amd.synthetic")
@@ -575,7 +712,7 @@ def main():
         return
     if args.only:
         {"gen_depth_loss": gen_depth_loss, "gen_loss": gen_loss, "gen_camera_general": gen_camera_general,
-         "gen_trainer_resize": gen_trainer_resize}[args.only](OUT)
+         "gen_trainer_resize": gen_trainer_resize, "gen_trainer_merge": lambda out: gen_trainer_merge(out, args.ref)}[args.only](OUT)
         return
     gen_sh(OUT)
     gen_cov3d(OUT)
@@ -586,6 +723,7 @@ def main():
     gen_loss(OUT)
     gen_depth_loss(OUT)
     gen_trainer_resize(OUT)
+    gen_trainer_merge(OUT, args.ref)
     gen_oracle(OUT)
     for f in sorted(os.listdir(OUT)):
         print(f, os.path.getsize(os.path.join(OUT, f)))

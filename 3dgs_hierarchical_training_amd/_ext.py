@@ -269,6 +269,15 @@ def _register_fakes():
     def _(plan, meta, N, nA, nB, nC, nSplit, src, kinds, child, check=False):
         return [t.new_empty((nA + nB + 2 * nC,) + tuple(t.shape[1:])) for t in src]
 
+    @torch.library.register_fake("gsr::resize_plan_batched")
+    def _(flags, first_block, counts):
+        return (flags.new_empty((lib.gsr_resize_plan_bytes(int(flags.shape[0])) // 4,), dtype=torch.int32),
+                flags.new_empty((len(counts), L.GSR_RESIZE_META_WORDS), dtype=torch.int64))
+
+    @torch.library.register_fake("gsr::resize_apply_batched")
+    def _(plan, meta, first_block, counts, counts4, new_first_block, src, kinds, child, pad, check=False):
+        return [t.new_empty((L.GSR_RESIZE_BLOCK * new_first_block[-1],) + tuple(t.shape[1:])) for t in src]
+
     @torch.library.register_fake("gsr::select_smallest")
     def _(values, k):
         n = values.shape[0]

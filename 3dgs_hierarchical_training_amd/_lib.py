@@ -78,6 +78,19 @@ class GsrResizeTensor(C.Structure):
                 ("reserved", C.c_int32)]
 
 
+GSR_RESIZE_MAX_MODELS, GSR_RESIZE_BLOCK = 16, 128      # version 122: the models of a batch
+
+
+class GsrResizeBatch(C.Structure):
+    _fields_ = [("B", C.c_int32), ("reserved", C.c_int32), ("first_block", C.c_int64 * (GSR_RESIZE_MAX_MODELS + 1)),
+                ("counts", C.c_int64 * GSR_RESIZE_MAX_MODELS)]
+
+
+class GsrResizeBatchTensor(C.Structure):
+    _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("child", C.c_void_p), ("pad", C.c_void_p), ("row_bytes", C.c_int64),
+                ("kind", C.c_int32), ("reserved", C.c_int32)]
+
+
 class GsrMergeTensor(C.Structure):
     _fields_ = [("src_a", C.c_void_p), ("src_b", C.c_void_p), ("dst", C.c_void_p), ("row_bytes", C.c_int64), ("kind", C.c_int32),
                 ("reserved", C.c_int32)]
@@ -111,6 +124,7 @@ EXPORTS = [
     "gsr_camera_from_pose", "gsr_pose_virtual_view",
     "gsr_resize_scratch_bytes", "gsr_resize_plan_bytes", "gsr_resize_plan", "gsr_resize_apply",
     "gsr_select_scratch_bytes", "gsr_select_smallest", "gsr_merge_apply",
+    "gsr_resize_scratch_bytes_batched", "gsr_resize_plan_batched", "gsr_resize_apply_batched",
 ]
 GSR_DEPTH_LOSS_L1, GSR_DEPTH_LOSS_INVARIANT = 0, 1
 
@@ -204,6 +218,16 @@ def load():
     lib.gsr_resize_apply.restype = C.c_int
     # (plan, plan_bytes, N, nA, nB, nC, nSplit, tensors, count, meta, stream)
     lib.gsr_resize_apply.argtypes = [C.c_void_p, C.c_size_t] + [C.c_int64] * 5 + [C.POINTER(GsrResizeTensor), C.c_int32, C.c_void_p, C.c_void_p]
+    lib.gsr_resize_scratch_bytes_batched.restype = C.c_size_t
+    lib.gsr_resize_scratch_bytes_batched.argtypes = [C.c_int64]
+    lib.gsr_resize_plan_batched.restype = C.c_int
+    # (flags, batch, plan, plan_bytes, meta, scratch, scratch_bytes, stream)
+    lib.gsr_resize_plan_batched.argtypes = [C.c_void_p, C.POINTER(GsrResizeBatch), C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t,
+                                            C.c_void_p]
+    lib.gsr_resize_apply_batched.restype = C.c_int
+    # (plan, plan_bytes, old_batch, counts4, new_first_block, tensors, count, meta, stream)
+    lib.gsr_resize_apply_batched.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(GsrResizeBatch), C.POINTER(C.c_int64), C.POINTER(C.c_int64),
+                                             C.POINTER(GsrResizeBatchTensor), C.c_int32, C.c_void_p, C.c_void_p]
     lib.gsr_select_scratch_bytes.restype = C.c_size_t
     lib.gsr_select_scratch_bytes.argtypes = [C.c_int64]
     lib.gsr_select_smallest.restype = C.c_int

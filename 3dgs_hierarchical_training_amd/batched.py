@@ -13,6 +13,7 @@ from typing import Dict, List, Sequence
 
 import torch
 
+from . import resize as R
 from .rasterizer import GaussianRasterizationSettings
 from .train_step import GaussianParams
 
@@ -25,6 +26,18 @@ def _pad_rows(t: torch.Tensor, n_pad: int, fill: torch.Tensor) -> torch.Tensor:
     return torch.cat((t, fill.to(device=t.device, dtype=t.dtype).expand((n_pad,) + tuple(t.shape[1:]))), dim=0)     # (scenes built on the device stay there)
 
 
+def pad_scene_rows(sh_coeffs: int) -> Dict[str, torch.Tensor]:
+    """One padding Gaussian as a scene holds it (activated values): far behind every camera, opacity below the 1/255 threshold."""
+    return {"means3D": torch.tensor([[0.0, 0.0, -1.0e3]]), "shs": torch.zeros(1, sh_coeffs, 3), "scales": torch.full((1, 3), 1e-3),
+            "rotations": torch.tensor([[1.0, 0.0, 0.0, 0.0]]), "opacities": torch.full((1, 1), 1e-4)}
+
+
+def raw_pad_rows(sh_coeffs: int, device) -> Dict[str, torch.Tensor]:
+    """The padding row of each of the six raw tensors on `device`: `pad_scene_rows` through `GaussianParams.raw_from_scene`, the statements a
+    freshly built batch's padding rows went through on the same device -- so a padding row written by a resize equals one bit for bit."""
+    return GaussianParams.raw_from_scene(pad_scene_rows(sh_coeffs), device)
+
+
 def concat_scenes(scenes: Sequence[Dict]) -> Dict:
     """One scene dict holding the models back to back, each padded to a multiple of 128 Gaussians.  Padding rows sit far behind
     every camera with an opacity below the 1/255 threshold: culled by the near plane and by the exact tile test alike, they get no
@@ -34,11 +47,9 @@ def concat_scenes(scenes: Sequence[Dict]) -> Dict:
     for sc in scenes:
         n = sc["means3D"].shape[0]
         n_pad = (-n) % BLOCK
-        parts["means3D"].append(_pad_rows(sc["means3D"], n_pad, torch.tensor([[0.0, 0.0, -1.0e3]])))
-        parts["shs"].append(_pad_rows(sc["shs"], n_pad, torch.zeros(1, sc["shs"].shape[1], 3)))
-        parts["scales"].append(_pad_rows(sc["scales"], n_pad, torch.full((1, 3), 1e-3)))
-        parts["rotations"].append(_pad_rows(sc["rotations"], n_pad, torch.tensor([[1.0, 0.0, 0.0, 0.0]])))
-        parts["opacities"].append(_pad_rows(sc["opacities"], n_pad, torch.full((1, 1), 1e-4)))
+        pad = pad_scene_rows(sc["shs"].shape[1])
+        for k in parts:
+            parts[k].append(_pad_rows(sc[k], n_pad, pad[k]))
         counts.append(n)
         first_block.append(first_block[-1] + (n + n_pad) // BLOCK)
     out = dict(scenes[0])
@@ -71,6 +82,15 @@ class BatchedGaussianParams(GaussianParams):
         super().__init__(sc, device, spatial_lr_scale=spatial_lr_scale, optimizer=optimizer)
         self.first_block: List[int] = list(sc["first_block"])
         self.counts: List[int] = list(sc["counts"])
+        self._raw_pad_rows()
+
+    def _raw_pad_rows(self) -> Dict[str, torch.Tensor]:
+        """The six raw padding rows on the store's device, made once (the host-to-device copies behind them are waits a resize need not
+        repeat)."""
+        pads = getattr(self, "_pad_rows", None)
+        if pads is None or pads["_xyz"].device != self._xyz.device:
+            pads = self._pad_rows = raw_pad_rows(self._features_rest.shape[1] + 1, self._xyz.device)
+        return pads
 
     @property
     def num_models(self) -> int:
@@ -89,13 +109,58 @@ class BatchedGaussianParams(GaussianParams):
         r = self.model_rows(b)
         return {k: getattr(self, k).detach()[r] for k in ("_xyz", "_features_dc", "_features_rest", "_opacity", "_scaling", "_rotation")}
 
-    # resizing one model of a batch would move every later model's blocks: stage A never densifies (densify=False at
-    # /root/reference/trainer/ht3dgs_trainer.py:298)
+    # Resizing one model of a batch moves every later model's blocks, so the single-model calls stay refused: the whole store is resized
+    # at once, by the batched resize kernels (resize_models / prune_models; densify.BatchedDensifier is the caller that densifies).
+    _REFUSAL = ("BatchedGaussianParams: the models of a batch cannot be resized by the single-model calls "
+                "(resize_models / prune_models resize them all at once)")
+
     def prune_points(self, mask, route="torch"):
-        raise RuntimeError("BatchedGaussianParams: the models of a batch cannot be resized")
+        raise RuntimeError(BatchedGaussianParams._REFUSAL)
 
     def densification_postfix(self, new, route="torch"):
-        raise RuntimeError("BatchedGaussianParams: the models of a batch cannot be resized")
+        raise RuntimeError(BatchedGaussianParams._REFUSAL)
 
     def resize_by_flags(self, flags, planned=None, children=None):
-        raise RuntimeError("BatchedGaussianParams: the models of a batch cannot be resized")
+        raise RuntimeError(BatchedGaussianParams._REFUSAL)
+
+    def resize_models(self, flags: torch.Tensor, planned=None, children: Dict[str, torch.Tensor] = None):
+        """Every model of the batch resized at once: flags (uint8 over the rows of the store, resize.KEEP | CLONE | SPLIT | CHILD; the bytes
+        of padding rows are ignored) -> all six groups and the moments that exist replaced by the tensors of the new store, through one
+        gsr_resize_apply_batched launch, padding rows included; `first_block` and `counts` follow.  Model b comes out as
+        `GaussianParams.resize_by_flags` leaves it alone, bit for bit, and a padding row as a freshly built batch has it.  planned = (plan,
+        meta, rows) when the caller has run `resize.resize_plan_batched` and read meta already; children = {"xyz", "scaling"} -> the
+        models' surviving split children back to back ([2 sum nSplit_b, 3]).  One host wait (none with `planned`).  Returns the per-model
+        counts [(nA, nB, nC, nSplit)]."""
+        R.need_device("BatchedGaussianParams.resize_models", flags=flags, params=self._xyz)
+        plan, meta, rows = planned if planned is not None else (None, None, None)
+        if plan is None:
+            plan, meta = R.resize_plan_batched(flags, self.first_block, self.counts)
+            rows = R.read_counts_batched(meta)          # the one host wait
+        counts4 = [tuple(int(v) for v in r[:4]) for r in rows]
+        pads = self._raw_pad_rows()
+        entries, src, kinds, child, pad = [], [], [], [], []
+        for g in self.optimizer.param_groups:
+            p = g["params"][0]
+            st = self.optimizer.state.get(p)
+            sourced = children is not None and g["name"] in children
+            entries.append((g, st is not None))
+            src.append(p.detach()); kinds.append(R.CHILD_SOURCED if sourced else R.PARAM)
+            child.append(children[g["name"]] if sourced else None); pad.append(pads[self._GROUP_ATTR[g["name"]]])
+            if entries[-1][1]:        # (moments an optimizer has not created yet have nothing to move)
+                for k in ("exp_avg", "exp_avg_sq"):
+                    src.append(st[k]); kinds.append(R.MOMENT); child.append(None); pad.append(None)
+        tensors, new_first_block = R.resize_apply_batched(plan, meta, self.first_block, self.counts, counts4, src, kinds, child, pad)
+        out = iter(tensors)
+        for g, has_moments in entries:
+            new = next(out)
+            self._install_group_tensor(g, new, (next(out), next(out)) if has_moments else None)
+        self._screenspace_zero = None
+        self.first_block = list(new_first_block)
+        self.counts = [nA + nB + 2 * nC for nA, nB, nC, _ in counts4]
+        return counts4
+
+    def prune_models(self, mask: torch.Tensor):
+        """Remove the Gaussians where mask (bool over the rows of the store) is True, in every model at once.  A model that loses every
+        row keeps one block of padding."""
+        R.need_device("BatchedGaussianParams.prune_models", mask=mask, params=self._xyz)
+        return self.resize_models((~mask).to(torch.uint8))          # KEEP = 1

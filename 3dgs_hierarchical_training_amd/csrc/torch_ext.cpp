@@ -29,6 +29,8 @@
 //   gsr::pose_virtual_view    -> gsr_pose_virtual_view (the interpolated pose between two device poses, and that pose relative to a base)
 //   gsr::resize_plan          -> gsr_resize_plan (flag bytes -> the source-row lists of the resized model; no host synchronisation)
 //   gsr::resize_apply         -> gsr_resize_apply (every row of every parameter and moment tensor moved in one launch)
+//   gsr::resize_plan_batched  -> gsr_resize_plan_batched (the same lists for every model of a batch; the launches do not depend on B)
+//   gsr::resize_apply_batched -> gsr_resize_apply_batched (every row of the new store, padding included, in one launch)
 //   gsr::select_smallest      -> gsr_select_smallest (the k rows with the smallest row maximum, as flag bytes; no host synchronisation)
 //   gsr::merge_apply          -> gsr_merge_apply (the kept rows of two models appended in one launch)
 //
@@ -1386,6 +1388,111 @@ std::vector<Tensor> resize_apply(const Tensor& plan, Tensor meta, int64_t N, int
     return dst;
 }
 
+static GsrResizeBatch resize_batch_of(const char* who, at::IntArrayRef first_block, at::IntArrayRef counts)
+{
+    TORCH_CHECK(counts.size() >= 1 && counts.size() <= GSR_RESIZE_MAX_MODELS, who, ": B must be in [1, ", GSR_RESIZE_MAX_MODELS, "]");
+    TORCH_CHECK(first_block.size() == counts.size() + 1, who, ": first_block has B + 1 entries");
+    GsrResizeBatch batch{};
+    batch.B = (int32_t)counts.size();
+    for (size_t b = 0; b < first_block.size(); b++) batch.first_block[b] = first_block[b];
+    for (size_t b = 0; b < counts.size(); b++) batch.counts[b] = counts[b];
+    return batch;
+}
+
+// gsr::resize_plan_batched -> gsr_resize_plan_batched.  flags uint8 [128 * first_block[B]] -> (plan int32, meta int64 [B, 8]); no host
+// synchronisation, no autograd.
+std::tuple<Tensor, Tensor> resize_plan_batched(const Tensor& flags_, at::IntArrayRef first_block, at::IntArrayRef counts)
+{
+    TORCH_CHECK(flags_.is_cuda(), "resize_plan_batched: flags must be on a ROCm/HIP device (no CPU fallback)");
+    TORCH_CHECK(flags_.dim() == 1 && flags_.scalar_type() == at::kByte, "resize_plan_batched: flags is uint8 [N]");
+    const GsrResizeBatch batch = resize_batch_of("resize_plan_batched", first_block, counts);
+    const c10::hip::HIPGuardMasqueradingAsCUDA guard(flags_.device());
+    const Tensor flags = flags_.contiguous();
+    const int64_t N = flags.numel();
+    TORCH_CHECK(N == GSR_RESIZE_BLOCK * first_block.back(), "resize_plan_batched: flags has 128 * first_block[B] entries");
+    const size_t pb = gsr_resize_plan_bytes(N), sb = gsr_resize_scratch_bytes_batched(N);
+    Tensor plan = at::empty({(int64_t)(pb / 4)}, flags.options().dtype(at::kInt));
+    Tensor meta = at::empty({(int64_t)batch.B, GSR_RESIZE_META_WORDS}, flags.options().dtype(at::kLong));
+    Tensor scratch = at::empty({(int64_t)sb}, flags.options());
+    check(gsr_resize_plan_batched(N ? flags.data_ptr<uint8_t>() : nullptr, &batch, N ? plan.data_ptr() : nullptr, pb, meta.data_ptr<int64_t>(),
+                                  N ? scratch.data_ptr() : nullptr, sb, c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream()),
+          "gsr_resize_plan_batched");
+    return {plan, meta};
+}
+
+// gsr::resize_apply_batched -> gsr_resize_apply_batched.  src[k]: [N, ...]; counts4: B x {nA, nB, nC, nSplit} flattened; child[k]: the models'
+// children back to back ([2 sum nSplit_b, ...]) for a CHILD_SOURCED tensor, an empty tensor otherwise; pad[k]: one row of the tensor ([1, ...]
+// or [...]) for the padding rows, an empty tensor for zeros.  Returns fresh tensors [128 * new_first_block[B], ...].  check as in resize_apply.
+std::vector<Tensor> resize_apply_batched(const Tensor& plan, Tensor meta, at::IntArrayRef first_block, at::IntArrayRef counts, at::IntArrayRef counts4,
+                                         at::IntArrayRef new_first_block, at::TensorList src_, at::IntArrayRef kinds, at::TensorList child_,
+                                         at::TensorList pad_, bool do_check)
+{
+    TORCH_CHECK(plan.is_cuda() && meta.is_cuda(), "resize_apply_batched: plan and meta must be on a ROCm/HIP device (no CPU fallback)");
+    TORCH_CHECK(plan.scalar_type() == at::kInt && plan.is_contiguous() && plan.dim() == 1, "resize_apply_batched: plan is the int32 tensor of resize_plan_batched");
+    const GsrResizeBatch batch = resize_batch_of("resize_apply_batched", first_block, counts);
+    const int64_t B = batch.B, N = GSR_RESIZE_BLOCK * first_block.back();
+    TORCH_CHECK(meta.scalar_type() == at::kLong && meta.is_contiguous() && meta.numel() == B * GSR_RESIZE_META_WORDS,
+                "resize_apply_batched: meta is the int64 [B, 8] tensor of resize_plan_batched");
+    TORCH_CHECK((int64_t)counts4.size() == 4 * B && (int64_t)new_first_block.size() == B + 1,
+                "resize_apply_batched: counts4 has 4 B entries and new_first_block B + 1");
+    TORCH_CHECK(src_.size() == kinds.size() && src_.size() == child_.size() && src_.size() == pad_.size(),
+                "resize_apply_batched: src, kinds, child and pad have one entry per tensor");
+    TORCH_CHECK((int64_t)src_.size() <= GSR_RESIZE_MAX_TENSORS, "resize_apply_batched: at most ", GSR_RESIZE_MAX_TENSORS, " tensors");
+    int64_t n_split = 0;
+    for (int64_t b = 0; b < B; b++) {
+        TORCH_CHECK(counts4[4 * b + 3] >= 0, "resize_apply_batched: negative count");
+        n_split += counts4[4 * b + 3];
+    }
+    const int64_t nout = GSR_RESIZE_BLOCK * new_first_block.back();
+    TORCH_CHECK(nout >= 0, "resize_apply_batched: negative new_first_block");
+    const c10::hip::HIPGuardMasqueradingAsCUDA guard(plan.device());
+    std::vector<Tensor> src, keep, dst;
+    std::vector<GsrResizeBatchTensor> table(src_.size());
+    for (size_t k = 0; k < src_.size(); k++) {
+        TORCH_CHECK(src_[k].is_cuda() && src_[k].device() == plan.device(), "resize_apply_batched: src[", k, "] must be on the plan's device (no CPU fallback)");
+        TORCH_CHECK(src_[k].dim() >= 1 && src_[k].size(0) == N, "resize_apply_batched: src[", k, "] has 128 * first_block[B] rows");
+        src.push_back(src_[k].detach().contiguous());
+        std::vector<int64_t> shape = src[k].sizes().vec();
+        shape[0] = nout;
+        dst.push_back(at::empty(shape, src[k].options()));
+        int64_t row_bytes = (int64_t)src[k].element_size();
+        for (size_t d = 1; d < shape.size(); d++) row_bytes *= shape[d];
+        GsrResizeBatchTensor& t = table[k];
+        t.kind = (int32_t)kinds[k];
+        t.row_bytes = row_bytes;
+        const bool moves = row_bytes > 0 && nout > 0 && N > 0;
+        t.src = moves ? src[k].data_ptr() : nullptr;
+        t.dst = moves ? dst[k].data_ptr() : nullptr;
+        t.child = nullptr;
+        t.pad = nullptr;
+        if (kinds[k] == GSR_RESIZE_CHILD_SOURCED && has(child_[k])) {
+            TORCH_CHECK(child_[k].is_cuda() && child_[k].device() == plan.device(), "resize_apply_batched: child[", k, "] must be on the plan's device (no CPU fallback)");
+            TORCH_CHECK(child_[k].scalar_type() == src[k].scalar_type() && child_[k].size(0) == 2 * n_split &&
+                        child_[k].numel() * (int64_t)child_[k].element_size() == 2 * n_split * row_bytes,
+                        "resize_apply_batched: child[", k, "] is [2 sum nSplit_b, ...] rows of its tensor");
+            keep.push_back(child_[k].detach().contiguous());
+            t.child = keep.back().data_ptr();
+        }
+        if (has(pad_[k])) {
+            TORCH_CHECK(pad_[k].is_cuda() && pad_[k].device() == plan.device(), "resize_apply_batched: pad[", k, "] must be on the plan's device (no CPU fallback)");
+            TORCH_CHECK(pad_[k].scalar_type() == src[k].scalar_type() && pad_[k].numel() * (int64_t)pad_[k].element_size() == row_bytes,
+                        "resize_apply_batched: pad[", k, "] is one row of its tensor");
+            keep.push_back(pad_[k].detach().contiguous());
+            t.pad = keep.back().data_ptr();
+        }
+    }
+    check(gsr_resize_apply_batched(plan.numel() ? plan.data_ptr() : nullptr, (size_t)plan.numel() * 4, &batch, counts4.data(), new_first_block.data(),
+                                   table.data(), (int32_t)table.size(), meta.data_ptr<int64_t>(),
+                                   c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream()), "gsr_resize_apply_batched");
+    if (do_check) {
+        const Tensor host = meta.cpu();
+        for (int64_t b = 0; b < B; b++)
+            TORCH_CHECK(host.data_ptr<int64_t>()[b * GSR_RESIZE_META_WORDS + GSR_RESIZE_META_STATUS] == 0, "resize_apply_batched: the plan holds a row "
+                        "number outside model ", b, ": the rows it names were written as zeros");
+    }
+    return dst;
+}
+
 // gsr::select_smallest -> gsr_select_smallest.  values float32 [N, C] (or [N]: C = 1) -> (drop bool-as-uint8 [N], keep_flags uint8 [N],
 // meta int64 [8]), all on the device.  No host synchronisation, no autograd.
 std::tuple<Tensor, Tensor, Tensor> select_smallest(const Tensor& values_, int64_t k)
@@ -1600,6 +1707,9 @@ TORCH_LIBRARY(gsr, m)
     m.def("resize_plan(Tensor flags) -> (Tensor plan, Tensor meta)");
     m.def("resize_apply(Tensor plan, Tensor(a!) meta, int N, int nA, int nB, int nC, int nSplit, Tensor[] src, int[] kinds, Tensor[] child, "
           "bool check=False) -> Tensor[]");
+    m.def("resize_plan_batched(Tensor flags, int[] first_block, int[] counts) -> (Tensor plan, Tensor meta)");
+    m.def("resize_apply_batched(Tensor plan, Tensor(a!) meta, int[] first_block, int[] counts, int[] counts4, int[] new_first_block, Tensor[] src, "
+          "int[] kinds, Tensor[] child, Tensor[] pad, bool check=False) -> Tensor[]");
     m.def("select_smallest(Tensor values, int k) -> (Tensor drop, Tensor keep_flags, Tensor meta)");
     m.def("merge_apply(Tensor plan_a, Tensor plan_b, Tensor(a!) meta, int Na, int nA, int Nb, int nB, Tensor[] src_a, Tensor[] src_b, int[] kinds, "
           "bool check=False) -> Tensor[]");
@@ -1636,6 +1746,8 @@ TORCH_LIBRARY_IMPL(gsr, CUDA, m)   // the dispatch key of HIP tensors on a ROCm 
     m.impl("pose_virtual_view", &pose_virtual_view);
     m.impl("resize_plan", &resize_plan);
     m.impl("resize_apply", &resize_apply);
+    m.impl("resize_plan_batched", &resize_plan_batched);
+    m.impl("resize_apply_batched", &resize_apply_batched);
     m.impl("select_smallest", &select_smallest);
     m.impl("merge_apply", &merge_apply);
     m.impl("masked_max_", &masked_max_);

@@ -171,6 +171,12 @@ class Densifier:
         """The flag byte per row that `densify_and_prune` amounts to (resize.KEEP | CLONE | SPLIT | CHILD), from the torch route's own
         statements: elementwise over the N rows, no host wait, any device; max_grad > 0 is the caller's to check.  Returns (flags, the
         clone selection, get_scaling)."""
+        clone, split, gone, child_gone, scaling = self._resize_terms(max_grad, min_opacity, max_screen_size)
+        return self._flags_of(clone, split, gone, child_gone), clone, scaling
+
+    @torch.no_grad()
+    def _resize_terms(self, max_grad: float, min_opacity: float, max_screen_size: Optional[float]):
+        """(clone, split, gone, child_gone, get_scaling): the selections of `_resize_flags`, row by row."""
         p, c = self.params, self.cfg
         grads = self.xyz_gradient_accum / self.denom
         grads[grads.isnan()] = 0.0
@@ -186,9 +192,12 @@ class Densifier:
             gone = gone | stats_term | (smax > 0.1 * self.extent)
             child_scaling = torch.exp(torch.log(scaling / (0.8 * 2)))
             child_gone = child_gone | stats_term | (child_scaling.max(dim=1).values > 0.1 * self.extent)
-        flags = ((~split & ~gone).to(torch.uint8) * R.KEEP + (clone & ~gone).to(torch.uint8) * R.CLONE
-                 + split.to(torch.uint8) * R.SPLIT + (split & ~child_gone).to(torch.uint8) * R.CHILD)
-        return flags, clone, scaling
+        return clone, split, gone, child_gone, scaling
+
+    @staticmethod
+    def _flags_of(clone, split, gone, child_gone):
+        return ((~split & ~gone).to(torch.uint8) * R.KEEP + (clone & ~gone).to(torch.uint8) * R.CLONE
+                + split.to(torch.uint8) * R.SPLIT + (split & ~child_gone).to(torch.uint8) * R.CHILD)
 
     def _densify_and_prune_kernel(self, max_grad: float, min_opacity: float, max_screen_size: Optional[float]):
         """`densify_and_prune` on the resize kernels.  Every selection below is the torch route's own statement, evaluated on the N rows the
@@ -253,3 +262,96 @@ class Densifier:
         if iteration % c.opacity_reset_interval == 0 and iteration < reset_until:
             self.params.reset_opacity()
         return resized
+
+
+class BatchedDensifier(Densifier):
+    """`Densifier` over the B models of a `batched.BatchedGaussianParams`: the same interface (`fused_stats`, `touches_parameters_at`,
+    `after_backward`, `add_stats`, `reset_stats`), so `train_step(..., densifier=)` takes it unchanged; the statistics run over the rows of
+    the store.  `densify_and_prune` resizes every model at once on the batched resize kernels: the flag bytes are `_resize_flags`'
+    statements over the whole store, one `resize_plan_batched`, one host read, the children of model b drawn with the model's own
+    generator (seeds[b]) at the model's own shape -- the draw `Densifier(seed=seeds[b])` makes for it alone, whatever else is in the batch
+    -- and one `resize_models`.  `cfg.max_points` caps each model on its own (max_points=[...]: one cap per model instead)."""
+
+    def __init__(self, params, scene_extent: float = 1.0, cfg: Optional[DensifyConfig] = None, seeds=None, max_points=None):
+        if not hasattr(params, "first_block"):
+            raise ValueError("BatchedDensifier: params is a batched.BatchedGaussianParams")
+        seeds = list(range(params.num_models)) if seeds is None else [int(s) for s in seeds]
+        if len(seeds) != params.num_models:
+            raise ValueError("BatchedDensifier: one seed per model of the batch")
+        super().__init__(params, scene_extent, cfg, seed=seeds[0], route="kernel")
+        self.gens = [torch.Generator(device=params._xyz.device).manual_seed(s) for s in seeds]
+        self.gen = None          # (every draw is a model's own)
+        if max_points is not None and len(max_points) != params.num_models:
+            raise ValueError("BatchedDensifier: max_points has one cap per model of the batch")
+        self.max_points = None if max_points is None else [int(m) for m in max_points]
+
+    def _caps(self):
+        """The cap of every model, or None when nothing is capped."""
+        if self.max_points is not None:
+            return self.max_points
+        return None if self.cfg.max_points is None else [self.cfg.max_points] * self.params.num_models
+
+    @staticmethod
+    def cap_decisions(caps, counts, n_clone, n_split):
+        """Per model (clones cancelled, splits cancelled) under its cap: the torch route's rule on the model's own numbers."""
+        out = []
+        for cap, n, nc, ns in zip(caps, counts, n_clone, n_split):
+            clones_cancelled = n + nc > cap
+            out.append((clones_cancelled, n + (0 if clones_cancelled else nc) + ns > cap))
+        return out
+
+    @staticmethod
+    def capped_flags(terms, decisions, row_slices):
+        """The flag bytes with the capped models' selections cancelled on their rows: cancelled clones clear CLONE; a cancelled split row
+        is no split parent any more, so it is KEEP iff the final prune keeps it."""
+        clone, split, gone, child_gone = (t.clone() if k < 2 else t for k, t in enumerate(terms[:4]))
+        for (clones_cancelled, splits_cancelled), rows in zip(decisions, row_slices):
+            if clones_cancelled:
+                clone[rows] = False
+            if splits_cancelled:
+                split[rows] = False
+        return Densifier._flags_of(clone, split, gone, child_gone)
+
+    @torch.no_grad()
+    def densify_and_prune(self, max_grad: float, min_opacity: float, max_screen_size: Optional[float]):
+        p, c = self.params, self.cfg
+        if not max_grad > 0:
+            raise ValueError("BatchedDensifier: max_grad must be positive (a cloned row must not qualify for a split)")
+        R.need_device("BatchedDensifier", params=p._xyz)
+        terms = self._resize_terms(max_grad, min_opacity, max_screen_size)
+        clone, scaling = terms[0], terms[4]
+        flags = self._flags_of(*terms[:4])
+        nb = p.num_models
+        slices = [p.model_rows(b) for b in range(nb)]
+        plan, meta = R.resize_plan_batched(flags, p.first_block, p.counts)
+        caps = self._caps()
+        if caps is None:
+            rows = R.read_counts_batched(meta)                        # the call's one host wait
+        else:                                                         # (a padding row is never selected: its gradient is 0 < max_grad)
+            rows, n_clone = R.read_counts_batched(meta, torch.stack([clone[s].sum() for s in slices]))
+            decisions = self.cap_decisions(caps, p.counts, n_clone, [r[3] for r in rows])
+            if any(a or b for a, b in decisions):                     # a capped call: the plan again, and a second wait
+                flags = self.capped_flags(terms, decisions, slices)
+                plan, meta = R.resize_plan_batched(flags, p.first_block, p.counts)
+                rows = R.read_counts_batched(meta)
+        children = None
+        if any(r[3] for r in rows):
+            stride = R.plan_stride(p.num_points)
+            xyz, child_scaling = [], []
+            for b in range(nb):
+                nS = rows[b][3]
+                if not nS:
+                    continue
+                at = R.L.GSR_RESIZE_PLAN_SPLIT_ROWS * stride + R.BLOCK * p.first_block[b]
+                parents = plan[at: at + nS]                            # store rows
+                parent_scaling = scaling.index_select(0, parents)
+                parent_rotation = p._rotation.detach().index_select(0, parents)
+                stds = parent_scaling.repeat(2, 1)
+                samples = torch.randn(stds.shape, generator=self.gens[b], device=stds.device) * stds
+                rots = _quat_to_rotmat(parent_rotation).repeat(2, 1, 1)
+                xyz.append(torch.bmm(rots, samples.unsqueeze(-1)).squeeze(-1) + p._xyz.detach().index_select(0, parents).repeat(2, 1))
+                child_scaling.append(torch.log(parent_scaling.repeat(2, 1) / (0.8 * 2)))
+            children = {"xyz": torch.cat(xyz, dim=0), "scaling": torch.cat(child_scaling, dim=0)}
+        if not all(r[0] == n and r[1] == 0 and r[3] == 0 for r, n in zip(rows, p.counts)):      # (nothing moves: no tensor is replaced)
+            p.resize_models(flags, planned=(plan, meta, rows), children=children)
+        self.reset_stats()

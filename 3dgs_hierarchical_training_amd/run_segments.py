@@ -109,6 +109,9 @@ class HTConfig:
     device_cameras: bool = False                # phase 1's virtual views from poses kept on the device: cameras.virtual_view + settings_from_pose, two
                                                 # launches per view instead of host matrix work and eight uploads; a camera may differ from the host
                                                 # route's in the last float32 bit, so the default stays the host route
+    leaf_batch: int = 0                         # --local: leaves with the same number of frames trained up to this many at a time in ONE launch chain
+                                                # (batched.BatchedGaussianParams; with densify: densify.BatchedDensifier on the batched resize kernels);
+                                                # 0 and 1 = one leaf after the other
     fit_pose: bool = False                      # refine each frame's pose while training on it (training_setup(fit_pose=True), :733)
     pose_lr: float = 1e-5                       # Adam with eps 1e-15 moves a pose by ~lr per step whatever the gradient: on these
                                                 # frames (1-2 px of motion per frame) 5e-6..2e-5 gains 0.4-0.6 dB over fixed stage-A
@@ -398,12 +401,106 @@ class RankRunner:
         return self.seg
 
 
+LEAF_BATCH_MAX = 16      # models of one batched store (include/gsr.h GSR_RESIZE_MAX_MODELS)
+
+
+def check_leaf_batch(cfg: HTConfig, local: bool):
+    """The combinations `leaf_batch` >= 2 serves, refused before a device is touched: the local walk, without pose refinement."""
+    n = int(cfg.leaf_batch)
+    if n < 0:
+        raise ValueError("leaf_batch must not be negative")
+    if n < 2:
+        return
+    if n > LEAF_BATCH_MAX:
+        raise ValueError(f"leaf_batch: at most {LEAF_BATCH_MAX} leaves share a batch")
+    if not local:
+        raise ValueError("leaf_batch >= 2 needs --local: with one leaf per rank there is nothing to batch")
+    if cfg.fit_pose:
+        raise ValueError("leaf_batch >= 2 does not refine poses (--fit-pose trains one camera per step)")
+
+
+def leaf_groups(leaf_parts: List[List[int]], leaf_batch: int) -> List[List[int]]:
+    """The leaves (their ranks) that train together: leaves with the same number of frames advance in lockstep, so they are grouped by it,
+    in rank order, and cut into batches of `leaf_batch` at most.  partition(40, 3) gives leaves of 6, 7, 7, 7, 6, 7, 7, 7 frames: ranks
+    [0, 4] and [1, 2, 3, 5, 6, 7]."""
+    by_len: Dict[int, List[int]] = {}
+    for r, frames in enumerate(leaf_parts):
+        by_len.setdefault(len(frames), []).append(r)
+    n = max(1, int(leaf_batch))
+    return [ranks[i: i + n] for ranks in by_len.values() for i in range(0, len(ranks), n)]
+
+
+def train_leaves_batched(group: List["RankRunner"]):
+    """`RankRunner.train_leaf` for several leaves with the same number of frames, as one batch: one parameter store, one launch chain per
+    step.  Every runner's own `rng` draws its frames in the order the leaf alone would draw them; the cameras of a step go through
+    `batch_settings`; with cfg.densify one `BatchedDensifier` resizes all models at once (seeds[b] = the rank, the cap of model b four
+    times its first size, as `_new_densifier` gives a leaf alone).  At the end every runner receives its model as a `GaussianParams` of
+    its own (fresh optimizer: `merge_recv` builds a new one anyway), its Segment and its "leaf" report line."""
+    batched = importlib.import_module("3dgs_hierarchical_training_amd.batched")
+    r0 = group[0]
+    cfg, seq, dev = r0.cfg, r0.seq, r0.dev
+    frames = [rr.parts[rr.level][rr.rank] for rr in group]
+    assert len({len(f) for f in frames}) == 1, "the leaves of a batch have the same number of frames"
+    scenes = [seq.leaf_scene(f[0], cfg.leaf_gaussians, seed=cfg.seed + 17 * rr.rank) for rr, f in zip(group, frames)]
+    batch = batched.BatchedGaussianParams(scenes, dev, optimizer=cfg.optimizer)
+    batch.active_sh_degree = min(cfg.start_sh_degree, batch.max_sh_degree)
+    segs = [Segment(None, f, f[0], {f[0]: torch.eye(4)}) for f in frames]
+    densifier = None
+    if cfg.densify:
+        densifier = densify.BatchedDensifier(batch, scene_extent=5.0, cfg=densify.DensifyConfig(
+            densify_from_iter=50, densification_interval=100, opacity_reset_interval=3000), seeds=[rr.rank for rr in group],
+            max_points=[4 * n for n in batch.counts])
+    t0 = time.perf_counter()
+    visited, steps, iteration = [[f[0]] for f in frames], 0, 0
+    for j in range(1, len(frames[0])):
+        drawn = []
+        for rr, seg, fr, vis in zip(group, segs, frames, visited):
+            f = fr[j]
+            seg.poses[f] = seq.rel_pose(f - 1, f) @ seg.poses[f - 1]
+            vis.append(f)
+            drawn.append([rr.rng.choice(vis) for _ in range(cfg.leaf_iters_per_frame)])
+        views = [batched.batch_settings([rr._settings(seg, d[k]) for rr, seg, d in zip(group, segs, drawn)], dev)
+                 for k in range(cfg.leaf_iters_per_frame)]
+        for k, view in enumerate(views):
+            iteration += 1
+            up = cfg.sh_up_every > 0 and iteration % cfg.sh_up_every == 0
+            ts.train_step(batch, view, torch.stack([seq.target(d[k]) for d in drawn]), fused_optimizer=cfg.fused, densifier=densifier,
+                          iteration=iteration, next_settings=views[k + 1] if k + 1 < len(views) else None,
+                          next_sh_degree=min(batch.active_sh_degree + 1, batch.max_sh_degree) if up else None)
+            if up:
+                batch.oneup_sh_degree()
+        steps += len(views)
+    if dev.type == "cuda":
+        torch.cuda.synchronize(dev)
+    ms = 1e3 * (time.perf_counter() - t0)
+    for b, (rr, seg, fr) in enumerate(zip(group, segs, frames)):
+        seg.params = ts.GaussianParams.from_raw({k: v.clone() for k, v in batch.model_raw(b).items()}, dev, sh_degree=batch.active_sh_degree,
+                                                optimizer=cfg.optimizer)
+        seg.global_iteration = iteration
+        rr.seg = seg
+        rr._emit({"phase": "leaf", "frames": [fr[0], fr[-1]], "steps": steps, "gaussians": seg.params.num_points, "ms": ms / len(group),
+                  "leaf_batch": len(group), "batch_ms": ms})
+
+
+def train_leaves_local(runners: List["RankRunner"], cfg: HTConfig):
+    """The leaf phase of the local walk: one leaf after the other, or with cfg.leaf_batch >= 2 the groups of `leaf_groups` as batches."""
+    if cfg.leaf_batch >= 2:
+        for ranks in leaf_groups(runners[0].parts[runners[0].level], cfg.leaf_batch):
+            if len(ranks) == 1:
+                runners[ranks[0]].train_leaf()
+            else:
+                train_leaves_batched([runners[r] for r in ranks])
+    else:
+        for rr in runners:
+            rr.train_leaf()
+
+
 def run_local(world: int, seq, cfg: HTConfig, device, log=None):
     """All ranks in turn on one device (the reference's execution order).  Returns (root RankRunner, report)."""
+    check_leaf_batch(cfg, local=True)
     tr = segments.LocalTransport(world)
     runners = [RankRunner(r, world, tr, seq, cfg, device, log=log) for r in range(world)]
-    for rr in runners:
-        rr.train_leaf()
+    train_leaves_local(runners, cfg)
     for k in range(len(runners[0].schedule)):
         pairs = runners[0].schedule[k]
         for dst, src in pairs:
@@ -545,6 +642,9 @@ def main():
     ap.add_argument("--densify-route", choices=("torch", "kernel"), default="torch",
                     help="how a densification resizes the model: torch = boolean indexing and torch.cat per tensor (default); kernel = the "
                          "resize kernels, the same result to the bit with one host wait and one launch that moves every row")
+    ap.add_argument("--leaf-batch", type=int, default=0,
+                    help="--local: train up to this many leaves with the same number of frames in one launch chain (one batched store; with "
+                         "--densify the batched resize kernels resize all its models at once); 0 or 1 = one leaf after the other (default)")
     ap.add_argument("--merge-route", choices=("torch", "kernel"), default="torch",
                     help="how a merge picks the Gaussians it drops and appends the rest: torch = amax, topk, boolean gathers and torch.cat "
                          "(default); kernel = the selection and row-move kernels, one host wait; rows tied at the threshold are dropped by row number")
@@ -566,7 +666,8 @@ def main():
     cfg = HTConfig(frames=a.frames, width=a.width, height=a.height, gt_gaussians=a.gt_gaussians, leaf_gaussians=a.leaf_gaussians,
                    leaf_iters_per_frame=a.leaf_iters, phase1_iters_per_frame=a.phase1_iters, phase2_iters_per_frame=[a.phase2_iters] * 3,
                    importance_views=a.importance_views, densify=a.densify, fit_pose=a.fit_pose, stage_a_batch=a.stage_a_batch, stage_a_lambda_depth=a.stage_a_lambda_depth, stage_a_early_exit=a.stage_a_early_exit, stage_a_init=a.stage_a_init, densify_route=a.densify_route, merge_route=a.merge_route, sh_up_every=a.sh_up_every,
-                   device_cameras=a.device_cameras)
+                   device_cameras=a.device_cameras, leaf_batch=a.leaf_batch)
+    check_leaf_batch(cfg, local=a.local)
     if a.pose_lr is not None:
         cfg.pose_lr = a.pose_lr
     if not torch.cuda.is_available():

@@ -148,13 +148,20 @@ class GaussianParams:
         d = device
         self.max_sh_degree = int(round(math.sqrt(scene["shs"].shape[1]))) - 1
         self.active_sh_degree = int(scene["sh_degree"])
-        self._xyz = scene["means3D"].to(d).clone().requires_grad_(True)
-        self._features_dc = scene["shs"][:, :1].to(d).clone().contiguous().requires_grad_(True)
-        self._features_rest = scene["shs"][:, 1:].to(d).clone().contiguous().requires_grad_(True)
-        self._scaling = torch.log(scene["scales"].to(d)).requires_grad_(True)
-        self._rotation = scene["rotations"].to(d).clone().requires_grad_(True)
-        self._opacity = inverse_sigmoid(scene["opacities"].to(d).clamp(1e-4, 1 - 1e-4)).requires_grad_(True)
+        for k, t in self.raw_from_scene(scene, d).items():
+            setattr(self, k, t.requires_grad_(True))
         self._build_optimizer(spatial_lr_scale, optimizer)
+
+    @staticmethod
+    def raw_from_scene(scene: Dict, d) -> Dict[str, torch.Tensor]:
+        """The six raw tensors of a scene's activated ones, on device d: the one place that maps one to the other (the padding row of a
+        batched store goes through it as well, batched.raw_pad_rows)."""
+        return {"_xyz": scene["means3D"].to(d).clone(),
+                "_features_dc": scene["shs"][:, :1].to(d).clone().contiguous(),
+                "_features_rest": scene["shs"][:, 1:].to(d).clone().contiguous(),
+                "_scaling": torch.log(scene["scales"].to(d)),
+                "_rotation": scene["rotations"].to(d).clone(),
+                "_opacity": inverse_sigmoid(scene["opacities"].to(d).clamp(1e-4, 1 - 1e-4))}
 
     def _build_optimizer(self, spatial_lr_scale: float, optimizer: str):
         groups = [

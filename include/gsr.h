@@ -381,7 +381,9 @@ const char* gsr_last_error(void);
  * 118: gsr_depth_to_points, gsr_voxel_scratch_bytes, gsr_voxel_down_sample; no struct changes (gsr_struct_bytes as in 117).
  * 119: gsr_camera_from_pose, gsr_pose_virtual_view; no struct changes.
  * 120: gsr_resize_plan, gsr_resize_apply, gsr_resize_scratch_bytes, gsr_resize_plan_bytes (GsrResizeTensor is new); no existing struct changes.
- * 121: gsr_select_scratch_bytes, gsr_select_smallest, gsr_merge_apply (GsrMergeTensor is new); no existing struct changes. */
+ * 121: gsr_select_scratch_bytes, gsr_select_smallest, gsr_merge_apply (GsrMergeTensor is new); no existing struct changes.
+ * 122: gsr_resize_plan_batched, gsr_resize_apply_batched, gsr_resize_scratch_bytes_batched (GsrResizeBatch and GsrResizeBatchTensor are
+ *      new); no existing struct or entry changes. */
 int gsr_version(void);
 size_t gsr_struct_bytes(int32_t which); /* 0 GsrForwardArgs, 1 GsrBackwardArgs, 2 GsrForwardOut; anything else 0 */
 
@@ -817,6 +819,71 @@ int    gsr_resize_plan(const uint8_t* flags /*[N]*/, int64_t N, void* plan, size
                        void* scratch, size_t scratch_bytes, void* stream);
 int    gsr_resize_apply(const void* plan, size_t plan_bytes, int64_t N, int64_t nA, int64_t nB, int64_t nC, int64_t nSplit,
                         const GsrResizeTensor* tensors, int32_t count, int64_t* meta, void* stream);
+
+/* ---- resizing the models of a batch (version 122) ----------------------------------------------------------------------------------------
+ * The same two steps over B models that share one store (GsrBatch: model b owns the 128-row blocks [first_block[b], first_block[b + 1]);
+ * its own rows are the first counts[b] of them, the rest of its last block is padding).  Integers decide and bytes are copied, as above;
+ * the number of launches does not depend on B, and no workgroup waits for another one.
+ *
+ * GsrResizeBatch (host memory): B in [1, GSR_RESIZE_MAX_MODELS], first_block[0 .. B] starting at 0 and not decreasing, counts[b] in
+ * [0, 128 * (first_block[b + 1] - first_block[b])].  The store has N = 128 * first_block[B] rows, N < 2^31.
+ *
+ * gsr_resize_plan_batched: flags uint8 [N] as above.  Row i of model b is store row 128 * first_block[b] + i for i < counts[b]; the flag
+ * byte of any other row (padding) is ignored, whatever it holds.
+ *   plan: gsr_resize_plan_bytes(N) bytes: the five segments of gsr_resize_plan, S = N entries each.  Model b's four lists and its split
+ *         ranks are those gsr_resize_plan gives the model alone, each ascending, and start at entry 128 * first_block[b] of their segment
+ *         (a list is never longer than its model).  ROW NUMBERS ARE STORE ROWS (an index_select of the store with a SPLIT_ROWS list gathers
+ *         the model's split parents); SPLIT RANKS ARE MODEL-LOCAL.  Entries beyond a list's length are not written.
+ *   meta: [B][GSR_RESIZE_META_WORDS] int64 on the device, 8-byte aligned; row b = {nA_b, nB_b, nC_b, nSplit_b, status_b = 0, 0, 0, 0}.
+ *   scratch: gsr_resize_scratch_bytes_batched(N) bytes, 4-byte aligned (four counters per 128-row block: a block belongs to one model,
+ *         where a 256-row tile could hold the end of one and the start of the next); a closed form in N, monotone, 0 for N <= 0.
+ *   N == 0 (models without blocks only): meta is zeroed, nothing else is touched.
+ *   A repeat of the call is bit-identical: integer sums in a fixed order, no atomics.
+ *   GSR_ERR_ARG (before anything is enqueued; gsr_last_error() names the rule): batch NULL, B outside [1, 16], a first_block that does not
+ *   start at 0 or decreases, a counts[b] that is negative or beyond its model's blocks, N >= 2^31, meta NULL or misaligned, and for N > 0
+ *   flags, plan or scratch NULL, plan or scratch misaligned or shorter than its size function says.
+ *
+ * gsr_resize_apply_batched writes every row of the new store, padding included, for up to GSR_RESIZE_MAX_TENSORS tensors in one launch.
+ *   old_batch        the batch the plan was made for;  counts4 (host, [B][4]) = {nA_b, nB_b, nC_b, nSplit_b} as read from meta.
+ *   new_first_block  (host, [B + 1]) starts at 0 with new_first_block[b + 1] - new_first_block[b] = max(1, ceil(n'_b / 128)), n'_b = nA_b +
+ *                    nB_b + 2 nC_b: a model that loses every row keeps one block of padding, so model numbers stay what they were.  Any
+ *                    other new_first_block is refused.  The new store has N' = 128 * new_first_block[B] rows; dst is [N', row_bytes].
+ *   Model b's rows start at row 128 * new_first_block[b] in the single-model order (A, B, C copy 0, C copy 1); from there to the end of its
+ *   last block the rows are padding.  A padding row of a PARAM or CHILD_SOURCED tensor is the tensor's `pad` row (row_bytes bytes on the
+ *   device; NULL: zeros), a padding row of a MOMENT tensor is zero.  MOMENT keeps its meaning per model (A copied, B and C zero).  The
+ *   `child` tensor of a CHILD_SOURCED tensor holds the models' children back to back: model b's part starts at row 2 * sum_{j<b} nSplit_j,
+ *   and inside it copy c of rank r is row c * nSplit_b + r.
+ *   Every row number read from the plan is compared with its model's rows [128 * first_block[b], 128 * first_block[b] + counts[b]) before
+ *   it is used as an address, a rank with nSplit_b; an entry that fails writes its destination row as zeros and sets
+ *   meta[b][GSR_RESIZE_META_STATUS] to 1.  A wrong plan is a status in its model's row, never an access out of bounds.
+ *   GSR_ERR_ARG (before anything is enqueued): the rules of old_batch above, counts4 or new_first_block NULL, a count beyond its model's
+ *   capacity (0 <= nA_b, nB_b, nSplit_b <= counts[b], 0 <= nC_b <= nSplit_b), a new_first_block that is not exactly the one above, N' >=
+ *   2^31, meta NULL or misaligned, plan NULL, misaligned or shorter than gsr_resize_plan_bytes(N) when a model keeps a row, and per tensor
+ *   the row_bytes, kind, src / dst and alignment rules of gsr_resize_apply (pad is 4-byte aligned too; a CHILD_SOURCED tensor needs child
+ *   when any nC_b > 0). */
+#define GSR_RESIZE_MAX_MODELS 16
+#define GSR_RESIZE_BLOCK 128
+typedef struct GsrResizeBatch {
+    int32_t B;
+    int32_t reserved;
+    int64_t first_block[GSR_RESIZE_MAX_MODELS + 1];
+    int64_t counts[GSR_RESIZE_MAX_MODELS];
+} GsrResizeBatch;
+typedef struct GsrResizeBatchTensor {
+    const void* src;      /* [N, row_bytes] */
+    void* dst;            /* [N', row_bytes] */
+    const void* child;    /* [2 sum nSplit_b, row_bytes]: GSR_RESIZE_CHILD_SOURCED only, NULL otherwise */
+    const void* pad;      /* [row_bytes]: the padding row of a PARAM / CHILD_SOURCED tensor; NULL = zeros */
+    int64_t row_bytes;
+    int32_t kind;
+    int32_t reserved;
+} GsrResizeBatchTensor;
+size_t gsr_resize_scratch_bytes_batched(int64_t N);
+int    gsr_resize_plan_batched(const uint8_t* flags /*[N]*/, const GsrResizeBatch* batch, void* plan, size_t plan_bytes,
+                               int64_t* meta /*device, [B][8] int64*/, void* scratch, size_t scratch_bytes, void* stream);
+int    gsr_resize_apply_batched(const void* plan, size_t plan_bytes, const GsrResizeBatch* old_batch, const int64_t* counts4 /*host [B][4]*/,
+                                const int64_t* new_first_block /*host [B+1]*/, const GsrResizeBatchTensor* tensors, int32_t count,
+                                int64_t* meta /*device, [B][8] int64*/, void* stream);
 
 /* ---- the merge on the device (version 121) -----------------------------------------------------------------------------------------------
  * merge_two_3DGS drops the prune_ratio * N Gaussians of least importance on both sides and appends what is left of the source to what is

@@ -76,6 +76,26 @@ def _register_fakes():
         return [f(3, H, W), means3D.new_empty((N,), dtype=torch.int32), f(1, H, W), f(1, H, W), b(lib.gsr_geom_bytes(int(N))),
                 b(lib.gsr_image_bytes_batched(int(W), int(H), 1)), b(nbin), torch.empty((3,), dtype=torch.int64)]
 
+    def _views_outputs(means3D, viewmatrix, H, W, extras):
+        N, V = means3D.shape[0], viewmatrix.shape[0]
+        Npad = (N + 127) // 128 * 128
+        f = lambda *s: means3D.new_empty(s, dtype=torch.float32)
+        b = lambda n: means3D.new_empty((n,), dtype=torch.uint8)
+        nbin = torch.library.get_ctx().new_dynamic_size()
+        return [f(V, 3, H, W), means3D.new_empty((V * Npad,), dtype=torch.int32), f(V, 1, H, W), f(V, 1, H, W),
+                b(lib.gsr_geom_bytes_views(int(N), int(V))), b(lib.gsr_image_bytes_batched(int(W), int(H), int(V))), b(nbin),
+                torch.empty((3,), dtype=torch.int64), f(V, 3, H, W) if (extras & 1) else f(0), b(V * Npad if (extras & 2) else 0)]
+
+    @torch.library.register_fake("gsr::rasterize_forward_views")
+    def _(means3D, sh, colors_precomp, opacities, scales, rotations, cov3D_precomp, sh_rest, viewmatrix, projmatrix, campos, bg,
+          points_transform, image_height, image_width, tanfovx, tanfovy, scale_modifier, sh_degree, raw_params, extras=0, sh_origin=None):
+        return tuple(_views_outputs(means3D, viewmatrix, image_height, image_width, extras))
+
+    @torch.library.register_fake("gsr::importance_accumulate_views")
+    def _(acc, means3D, sh, colors_precomp, opacities, scales, rotations, cov3D_precomp, sh_rest, viewmatrix, projmatrix, campos, bg,
+          points_transform, image_height, image_width, tanfovx, tanfovy, scale_modifier, sh_degree, raw_params, sh_origin=None):
+        return _views_outputs(means3D, viewmatrix, image_height, image_width, 0)[:8]
+
     @torch.library.register_fake("gsr::importance_pass")
     def _(acc, means3D, sh, sh_rest, campos, points_transform, color, geom, image, binning, meta, image_height, image_width, sh_degree,
           sh_origin=None):

@@ -125,7 +125,9 @@ EXPORTS = [
     "gsr_resize_scratch_bytes", "gsr_resize_plan_bytes", "gsr_resize_plan", "gsr_resize_apply",
     "gsr_select_scratch_bytes", "gsr_select_smallest", "gsr_merge_apply",
     "gsr_resize_scratch_bytes_batched", "gsr_resize_plan_batched", "gsr_resize_apply_batched",
+    "gsr_geom_bytes_views", "gsr_forward_views", "gsr_importance_scratch_bytes_views", "gsr_importance_accumulate_views",
 ]
+GSR_FWD_FLAG_VIEWS, GSR_MAX_VIEWS = 1 << 15, 16     # version 123: V views of one model
 GSR_DEPTH_LOSS_L1, GSR_DEPTH_LOSS_INVARIANT = 0, 1
 
 _lib = None
@@ -257,6 +259,15 @@ def load():
     lib.gsr_backward.argtypes = [C.POINTER(GsrBackwardArgs), C.c_void_p]
     lib.gsr_importance_accumulate.restype = C.c_int
     lib.gsr_importance_accumulate.argtypes = [C.POINTER(GsrForwardArgs), C.POINTER(GsrForwardOut), C.c_void_p, C.c_void_p, C.c_void_p]
+    # version 123: V views of one model -- (args, V, out, stream) / (args, V, out, acc, scratch, stream)
+    for fn in ("gsr_geom_bytes_views", "gsr_importance_scratch_bytes_views"):
+        getattr(lib, fn).restype = C.c_size_t
+        getattr(lib, fn).argtypes = [C.c_int32, C.c_int32]
+    lib.gsr_forward_views.restype = C.c_int
+    lib.gsr_forward_views.argtypes = [C.POINTER(GsrForwardArgs), C.c_int32, C.POINTER(GsrForwardOut), C.c_void_p]
+    lib.gsr_importance_accumulate_views.restype = C.c_int
+    lib.gsr_importance_accumulate_views.argtypes = [C.POINTER(GsrForwardArgs), C.c_int32, C.POINTER(GsrForwardOut), C.c_void_p, C.c_void_p,
+                                                    C.c_void_p]
     lib.gsr_mark_visible.restype = C.c_int
     lib.gsr_mark_visible.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.gsr_last_error.restype = C.c_char_p

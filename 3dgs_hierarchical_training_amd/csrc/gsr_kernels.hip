@@ -462,6 +462,20 @@ __device__ __forceinline__ void count_large_rects(bool act, Splat& s, TileRec& r
     }
 }
 
+// V views of ONE model (gsr_forward_views, include/gsr.h): record v * Npad + n is Gaussian n under camera v, Npad = 128 view_nb.  The view of
+// a block is block / view_nb; the camera pointers of `p` move to that view's entries (the SH origin, a kernel argument of its own, is
+// moved by the caller); `row_ofs` = v * Npad is what the kernel subtracts from a record's index to find the model's parameter row.
+// Block-uniform: scalar arithmetic on kernel arguments.
+__device__ __forceinline__ int select_view_of_model(CamParams& p, int block, int view_nb, int& row_ofs)
+{
+    const int v = block / view_nb;
+    p.vm += 16 * v; p.pm += 16 * v;
+    if (p.campos) p.campos += 3 * v;
+    if (p.xf) p.xf += 12 * v;
+    row_ofs = v * view_nb * kPreThreads;
+    return v;
+}
+
 // The producer of the depth keys can count the depth sort's digits (4 x 8 bits, per run: radix_sort.h onesweep_run_len) and
 // clear that sort's status words, so the sort needs no histogram launch (onesweep_sort_pairs hist_done).  ghist == nullptr: off.
 // The counters must be zero before the kernel starts.
@@ -486,15 +500,20 @@ __global__ __launch_bounds__(kPreThreads) void k_preprocess(CamParams cp, int N,
                                                             TileRec* __restrict__ tilerec, uint32_t* __restrict__ zero_words,
                                                             int zero_count, int block0, DepthHist dh, uint2* __restrict__ early_parts = nullptr,
                                                             uint32_t window_max = 0xffffffffu, uint8_t* __restrict__ visible = nullptr,
-                                                            const float* __restrict__ sh_origin = nullptr, RetireDev rt = {})
+                                                            const float* __restrict__ sh_origin = nullptr, RetireDev rt = {}, int view_nb = 0)
 {
     constexpr int NC3 = 3 * (DEG + 1) * (DEG + 1);
     __shared__ float s_sh[kPreThreads * kShStride];
     __shared__ uint32_t s_early[2][kPreThreads / 64];
     const int tid = threadIdx.x;
-    const int base = ((int)blockIdx.x + block0) * kPreThreads;   // block0: first block of a partial launch (0 = the whole cloud)
+    // view_nb > 0 (gsr_forward_views): V views of one model.  `i` stays the model's row (parameters, N, the SH staging); records, keys,
+    // tile records, radii and visibility bytes go to io = i + v Npad.  view_nb == 0: row_ofs = 0, io = i, the kernel as it was.
+    int row_ofs = 0;
+    const int model = view_nb > 0 ? select_view_of_model(cp, (int)blockIdx.x + block0, view_nb, row_ofs)
+                                  : select_view(cp, (int)blockIdx.x + block0);   // batched render: this block's model and its camera
+    const int base = ((int)blockIdx.x + block0) * kPreThreads - row_ofs;   // block0: first block of a partial launch (0 = the whole cloud)
     const int i = base + tid;
-    const int model = select_view(cp, (int)blockIdx.x + block0);   // batched render: this block's model and its camera
+    const int io = i + row_ofs;
     if (blockIdx.x == 0)   // rides along: clear the head of the depth sort's scratch (saves a fill launch)
         for (int q = tid; q < zero_count; q += kPreThreads) zero_words[q] = 0u;
     if (rt.table) {   // the retire table: a model retired BEFORE this step is culled whole -- records and radii, no per-Gaussian arithmetic
@@ -625,7 +644,7 @@ __global__ __launch_bounds__(kPreThreads) void k_preprocess(CamParams cp, int N,
             float col[3];
             if constexpr (SHO) {   // (the geometry is done with both: the colour sees the origin and the raw mean from here on)
 #pragma unroll
-                for (int k = 0; k < 3; k++) { cam.cam[k] = sh_origin[k]; mean[k] = mraw[k]; }
+                for (int k = 0; k < 3; k++) { cam.cam[k] = sh_origin[(view_nb > 0 ? 3 * model : 0) + k]; mean[k] = mraw[k]; }
             }
             if (lin) splat_sh_color(cam, mean, s_rest + tid * NR - 3, 3, 1, col, s_dc + tid * 3);
             else splat_sh_color(cam, mean, &s_sh[tid * kShStride], 3, 1, col);
@@ -634,18 +653,24 @@ __global__ __launch_bounds__(kPreThreads) void k_preprocess(CamParams cp, int N,
     }
     if (dh.ghist && dh.clear_threads == 0u)   // fewer than 128 Gaussians, ragged: no block of k_preprocess_bwd ran the next-view tail
         for (uint32_t q = tid; q < dh.status_words / 4; q += kPreThreads) reinterpret_cast<uint4*>(dh.status)[q] = make_uint4(0u, 0u, 0u, 0u);
-    if (!act) return;
+    if (!act) {
+        if (view_nb > 0) {   // rows N .. Npad of a view: culled records (the chain behind reads every record of the V Npad)
+            culled_records(io, model, cam.tiles_y, splat, tilerec, radii, dkey, gid);
+            if (visible) visible[io] = 0;
+        }
+        return;
+    }
     {   // the stored record carries the remainders where the tile count sat (nobody reads the count back; it lives on in registers below)
         Splat st = s;
         st.tiles = lo_pack;
-        splat[i] = st;
+        splat[io] = st;
     }
-    tilerec[i] = rec;   // compact emission record: k_tile_counts / k_emit never touch the 48 B splats
-    radii[i] = s.radius;
-    if (visible) visible[i] = s.radius > 0 ? 1 : 0;   // `visibility_filter = radii > 0` (gaussian_model_ht.py:905), written here instead of by a torch launch
+    tilerec[io] = rec;   // compact emission record: k_tile_counts / k_emit never touch the 48 B splats
+    radii[io] = s.radius;
+    if (visible) visible[io] = s.radius > 0 ? 1 : 0;   // `visibility_filter = radii > 0` (gaussian_model_ht.py:905), written here instead of by a torch launch
     const uint32_t key = s.tiles > 0 ? __float_as_uint(s.depth) : 0xffffffffu;
-    dkey[i] = key;
-    gid[i] = (uint32_t)i;
+    dkey[io] = key;
+    gid[io] = (uint32_t)io;
     if (dh.ghist) {   // (only the single ragged block behind k_preprocess_bwd's next-view tail comes here: plain global adds)
         const uint32_t x = (uint32_t)i / onesweep_run_len<uint32_t>((uint32_t)N);
 #pragma unroll
@@ -2584,6 +2609,45 @@ __global__ __launch_bounds__(256) void k_importance_finish(int N, int M, int D, 
     if (sp.b > 0.f) a[2] += b * s.z;
 }
 
+// The finish over V views of one model (gsr_importance_accumulate_views): S holds V runs of Npad rows, record v Npad + n = Gaussian n
+// under camera v.  Thread (n, k) walks v = 0 .. V-1 IN THAT ORDER and adds each view's term to its three accumulator words -- the
+// order in which V single-view passes add into acc, with the same expression per term.  A view whose three sums are zero is skipped;
+// a row whose sums are zero in every view is neither read nor written.  campos / xf / sh_origin are arrays of V entries.
+__global__ __launch_bounds__(256) void k_importance_finish_views(int N, int Npad, int V, int M, int D, const float* __restrict__ means,
+                                                                 const float* __restrict__ xf, const float* __restrict__ campos,
+                                                                 const float* __restrict__ sh_origin, const Splat* __restrict__ splat,
+                                                                 const float* __restrict__ S, float* __restrict__ acc)
+{
+    const int n = (int)blockIdx.x * 16 + (int)(threadIdx.x >> 4), k = (int)(threadIdx.x & 15);
+    if (n >= N || k >= (D + 1) * (D + 1)) return;
+    float* a = acc + ((size_t)n * M + k) * 3;
+    float a0 = 0.f, a1 = 0.f, a2 = 0.f;
+    bool loaded = false;
+    float m0[3] = {0.f, 0.f, 0.f};
+    for (int v = 0; v < V; v++) {
+        const size_t rec = (size_t)v * Npad + n;
+        const float4 s = reinterpret_cast<const float4*>(S)[rec];
+        if (s.x == 0.f && s.y == 0.f && s.z == 0.f) continue;
+        if (!loaded) {
+            m0[0] = means[3 * (size_t)n]; m0[1] = means[3 * (size_t)n + 1]; m0[2] = means[3 * (size_t)n + 2];
+            a0 = a[0]; a1 = a[1]; a2 = a[2];
+            loaded = true;
+        }
+        float mean[3] = {m0[0], m0[1], m0[2]};
+        float o[3];
+        if (sh_origin) { o[0] = sh_origin[3 * v]; o[1] = sh_origin[3 * v + 1]; o[2] = sh_origin[3 * v + 2]; }
+        else { apply_points_transform(xf ? xf + 12 * v : nullptr, mean); o[0] = campos[3 * v]; o[1] = campos[3 * v + 1]; o[2] = campos[3 * v + 2]; }
+        float basis[16];
+        sh_basis_dir(D, mean, o, basis);
+        const Splat sp = splat[rec];
+        const float b = fabsf(basis[k]);
+        if (sp.r > 0.f) a0 += b * s.x;
+        if (sp.g > 0.f) a1 += b * s.y;
+        if (sp.b > 0.f) a2 += b * s.z;
+    }
+    if (loaded) { a[0] = a0; a[1] = a1; a[2] = a2; }
+}
+
 // (round 3, measured with tools/k6_wave_timing.py on the 1 M / 980x545 frame: the 8.6 k waves are all resident at once, eight to
 //  a SIMD; they start within 2 us, last 57 us on average (p90 76, max 104), half are gone after 58 us and the SIMDs finish between
 //  75 and 106 us -- a SIMD is done when the sum of ITS eight random lists is done, and what is left at the end cannot fill the
@@ -4282,7 +4346,7 @@ size_t gsr_prepared_bytes(int32_t N) { return prep_layout(N).bytes; }
 size_t gsr_prepared_radii_offset(int32_t N) { return prep_layout(N).radii; }
 int gsr_prepare_supported(int32_t M, int32_t D, int32_t raw_params) { return (raw_params && M == 16 && D >= 0 && D <= 3) ? 1 : 0; }
 const char* gsr_last_error(void) { return g_err; }
-int gsr_version(void) { return 122; }
+int gsr_version(void) { return 123; }
 size_t gsr_struct_bytes(int32_t which)
 {
     return which == 0 ? sizeof(GsrForwardArgs) : which == 1 ? sizeof(GsrBackwardArgs) : which == 2 ? sizeof(GsrForwardOut) : 0;
@@ -4405,7 +4469,24 @@ static bool direct_bin_geometry(int N, int T, DirectBin& db, DirectBinScratch& d
     return true;
 }
 
-static int forward_impl(const GsrForwardArgs* a, const int32_t* retired_at, int64_t retire_step, GsrForwardOut* out, void* stream_)
+// Npad of gsr_forward_views: a view's records, the model's rows rounded up to whole 128-Gaussian blocks
+static inline int64_t views_npad(int32_t N) { return ((int64_t)(N > 0 ? N : 0) + kPreThreads - 1) / kPreThreads * kPreThreads; }
+static_assert(GSR_MAX_VIEWS == kMaxBatch, "the views of one call ride the batched chain: one image of the tall grid per view");
+// the V rules of gsr_forward_views / gsr_importance_accumulate_views, checked before a device is touched
+static int check_views(const GsrForwardArgs* a, int32_t V)
+{
+    if (V < 1 || V > GSR_MAX_VIEWS) return fail(GSR_ERR_ARG, "views: 1..16 views expected%s");
+    if (a->batch) return fail(GSR_ERR_ARG, "views: not served with a batch (views of a GsrBatch are out of scope)%s");
+    if (a->prepared) return fail(GSR_ERR_ARG, "views: not served with a prepared buffer%s");
+    if (a->render_only) return fail(GSR_ERR_ARG, "views: not served with render_only%s");
+    if (a->N < 1) return fail(GSR_ERR_ARG, "views: at least one Gaussian expected%s");
+    if ((int64_t)V * views_npad(a->N) >= ((int64_t)1 << 31)) return fail(GSR_ERR_RANGE, "views: V * Npad must stay below 2^31 records%s");
+    return GSR_OK;
+}
+
+// views > 0: gsr_forward_views -- a->N is the MODEL's size, the chain runs over N = views * Npad records as a batch of `views` images whose
+// models start at the blocks {0, nb, 2 nb, ...}; only k_preprocess knows that the V "models" share one set of parameter rows.
+static int forward_impl(const GsrForwardArgs* a, const int32_t* retired_at, int64_t retire_step, GsrForwardOut* out, void* stream_, int views = 0)
 {
     CallTimer call_timer(g_fwd_calls, g_fwd_ns);
     hipStream_t st = (hipStream_t)stream_;
@@ -4430,16 +4511,24 @@ static int forward_impl(const GsrForwardArgs* a, const int32_t* retired_at, int6
         if (!a->out_color || !a->bg || !a->alloc) return fail(GSR_ERR_ARG, "missing output / workspace pointer%s");
     } else if (!a->out_color || !a->out_depth || !a->out_alpha || !a->image || !a->bg || !a->alloc)
         return fail(GSR_ERR_ARG, "missing output / workspace pointer%s");
-    const int N = a->N, W = a->W, H = a->H;
+    const int view_nb = views > 0 ? (int)(views_npad(a->N) / kPreThreads) : 0;
+    const int N = views > 0 ? views * view_nb * kPreThreads : a->N, W = a->W, H = a->H;
     BatchDev bt;
-    rc = batch_dev(a->batch, N, H, bt);
-    if (rc) return rc;
+    if (views > 0) {
+        if ((long long)views * ((H + kTile - 1) / kTile) > 4095) return fail(GSR_ERR_RANGE, "views: more than 4095 tile rows in total%s");
+        bt = BatchDev{};
+        bt.B = views;
+        for (int q = 0; q <= kMaxBatch; q++) bt.first_block[q] = std::min(q, views) * view_nb;
+    } else {
+        rc = batch_dev(a->batch, N, H, bt);
+        if (rc) return rc;
+    }
     const int NB = bt.B;   // images rendered by this call (batched render: a tall grid of NB * tiles_y tile rows)
     const int tiles_x = (W + kTile - 1) / kTile, tiles_y = (H + kTile - 1) / kTile, T = tiles_x * tiles_y * NB;
-    if (a->sh_origin && (!a->shs || NB > 1 || a->prepared))
+    if (a->sh_origin && (!a->shs || (NB > 1 && views == 0) || a->prepared))
         return fail(GSR_ERR_ARG, "sh_origin needs shs and is not served with a batch of B > 1 or a prepared buffer%s");
     out->num_rendered = 0; out->binning = nullptr; out->binning_bytes = 0; out->binning_capacity = 0;
-    out->forward_flags = pack_fwd_flags(opt.ckpt_first) | (ro ? GSR_FWD_FLAG_RENDER_ONLY : 0);
+    out->forward_flags = pack_fwd_flags(opt.ckpt_first) | (ro ? GSR_FWD_FLAG_RENDER_ONLY : 0) | (views > 0 ? GSR_FWD_FLAG_VIEWS : 0);
     uint64_t R = 0;
     BlendBalance bb = {};   // filled in front of k_tile_counts (whose extra workgroups build the placement the blend reads)
     ListCut lc = {};        // filled with it: the list cut lives in the same per-frame cache
@@ -4733,9 +4822,9 @@ static int forward_impl(const GsrForwardArgs* a, const int32_t* retired_at, int6
                                a->radii, (uint32_t*)nullptr, 0);
     } else {
 #define GSR_PRE_(DEG, RAW, SHO)                                                                                                     \
-    hipLaunchKernelGGL((k_preprocess<DEG, RAW, SHO>), dim3(grid), dim3(kPreThreads), 0, st, cp, N, a->means3D, a->scales,           \
+    hipLaunchKernelGGL((k_preprocess<DEG, RAW, SHO>), dim3(grid), dim3(kPreThreads), 0, st, cp, a->N, a->means3D, a->scales,        \
                        a->rotations, a->cov3D_precomp, a->opacities, a->shs, a->shs_rest, a->colors_precomp, splat, a->radii, dkey, gid, \
-                       ntiles, zero_words, zero_count, 0, DepthHist{}, early_parts, early_window, a->visible, a->sh_origin, rt)
+                       ntiles, zero_words, zero_count, 0, DepthHist{}, early_parts, early_window, a->visible, a->sh_origin, rt, view_nb)
 #define GSR_PRE(DEG) do { if (a->raw_params) GSR_PRE_(DEG, true, false); else GSR_PRE_(DEG, false, false); } while (0)
     // sh_origin: degree 0 takes the default kernel (the colour does not depend on the direction)
 #define GSR_PRE_SHO(DEG) do { if (a->raw_params) GSR_PRE_(DEG, true, true); else GSR_PRE_(DEG, false, true); } while (0)
@@ -4997,6 +5086,18 @@ static int forward_impl(const GsrForwardArgs* a, const int32_t* retired_at, int6
 }
 
 int gsr_forward(const GsrForwardArgs* a, GsrForwardOut* out, void* stream_) { return forward_impl(a, nullptr, 0, out, stream_); }
+size_t gsr_geom_bytes_views(int32_t N, int32_t V)
+{
+    const int64_t rec = (int64_t)(V > 0 ? V : 1) * views_npad(N);
+    return rec < ((int64_t)1 << 31) ? geom_layout((int32_t)rec).total : 0;
+}
+int gsr_forward_views(const GsrForwardArgs* a, int32_t V, GsrForwardOut* out, void* stream_)
+{
+    if (!a || !out) return fail(GSR_ERR_ARG, "null args%s");
+    const int rc = check_views(a, V);
+    if (rc) return rc;
+    return forward_impl(a, nullptr, 0, out, stream_, V);
+}
 int gsr_forward_retire(const GsrForwardArgs* a, const int32_t* retired_at, int64_t retire_step, GsrForwardOut* out, void* stream_)
 {
     return forward_impl(a, retired_at, retire_step, out, stream_);
@@ -5024,6 +5125,8 @@ int gsr_backward(const GsrBackwardArgs* a, void* stream_)
     const Options opt = options_snapshot();
     if (a->forward_flags & GSR_FWD_FLAG_RENDER_ONLY)
         return fail(GSR_ERR_ARG, "gsr_backward: forward_flags come from a render-only forward, which keeps nothing a backward could read%s");
+    if (a->forward_flags & GSR_FWD_FLAG_VIEWS)
+        return fail(GSR_ERR_ARG, "gsr_backward: forward_flags come from a views forward (gsr_forward_views): a backward over views is not served%s");
     int rc = check_common(a->N, a->M, a->D, a->W, a->H);
     if (rc) return rc;
     const int N = a->N, W = a->W, H = a->H;
@@ -5344,6 +5447,8 @@ int gsr_importance_accumulate(const GsrForwardArgs* a, const GsrForwardOut* out,
     if (!a || !out) return fail(GSR_ERR_ARG, "null args%s");
     if (out->forward_flags & GSR_FWD_FLAG_RENDER_ONLY)
         return fail(GSR_ERR_ARG, "importance: forward_flags come from a render-only forward, which keeps no image state or lists for the pass%s");
+    if (out->forward_flags & GSR_FWD_FLAG_VIEWS)
+        return fail(GSR_ERR_ARG, "importance: forward_flags come from a views forward: use gsr_importance_accumulate_views%s");
     int rc = check_common(a->N, a->M, a->D, a->W, a->H);
     if (rc) return rc;
     if (a->colors_precomp || !a->shs) return fail(GSR_ERR_ARG, "importance: the model must carry SH coefficients (colors_precomp has none)%s");
@@ -5373,6 +5478,56 @@ int gsr_importance_accumulate(const GsrForwardArgs* a, const GsrForwardOut* out,
         ProfScope ps(P_IMP_FINISH, st);
         hipLaunchKernelGGL(k_importance_finish, dim3((N + 15) / 16), dim3(256), 0, st, N, a->M, a->D, a->means3D, a->points_transform, a->campos,
                            a->sh_origin, splat, (const float*)S, acc);
+    }
+    GSR_HIP(hipGetLastError());
+    return GSR_OK;
+}
+
+// ---- the same over V views of one model, behind gsr_forward_views (include/gsr.h): one walk over the V T tiles, one finish ----------
+size_t gsr_importance_scratch_bytes_views(int32_t N, int32_t V)
+{
+    const int64_t rec = (int64_t)(V > 0 ? V : 1) * views_npad(N > 0 ? N : 1);
+    return align256((size_t)rec * kImpStride * sizeof(float));
+}
+
+int gsr_importance_accumulate_views(const GsrForwardArgs* a, int32_t V, const GsrForwardOut* out, float* acc, void* scratch, void* stream_)
+{
+    hipStream_t st = (hipStream_t)stream_;
+    if (!a || !out) return fail(GSR_ERR_ARG, "null args%s");
+    if (out->forward_flags & GSR_FWD_FLAG_RENDER_ONLY)
+        return fail(GSR_ERR_ARG, "importance: forward_flags come from a render-only forward, which keeps no image state or lists for the pass%s");
+    if (!(out->forward_flags & GSR_FWD_FLAG_VIEWS))
+        return fail(GSR_ERR_ARG, "importance over views: forward_flags do not come from gsr_forward_views%s");
+    int rc = check_views(a, V);
+    if (rc) return rc;
+    rc = check_common(a->N, a->M, a->D, a->W, a->H);
+    if (rc) return rc;
+    if (a->colors_precomp || !a->shs) return fail(GSR_ERR_ARG, "importance: the model must carry SH coefficients (colors_precomp has none)%s");
+    if (a->M < (a->D + 1) * (a->D + 1) || !a->campos) return fail(GSR_ERR_ARG, "shs needs campos and M >= (D+1)^2%s");
+    const int N = a->N, W = a->W, H = a->H;
+    if (!acc || !scratch || !a->geom || !a->image || !a->out_color || !a->means3D) return fail(GSR_ERR_ARG, "missing workspace / accumulator pointer%s");
+    if (out->num_rendered <= 0 || !out->binning) return GSR_OK;   // nothing was blended: every sum is zero, the accumulator keeps its bits
+    if (!flags_from_forward(out->forward_flags)) return fail(GSR_ERR_ARG, "forward_flags do not come from gsr_forward%s");
+    const int Npad = (int)views_npad(N);
+    const int tiles_x = (W + kTile - 1) / kTile, tiles_y = (H + kTile - 1) / kTile, T = tiles_x * tiles_y * V;
+    const Splat* splat = static_cast<const Splat*>(a->geom);
+    const BinLayout B = bin_layout(out->binning_capacity > 0 ? out->binning_capacity : out->num_rendered, W, H, V);
+    const uint8_t* bin = static_cast<const uint8_t*>(out->binning);
+    const uint2* ranges = reinterpret_cast<const uint2*>(bin + B.ranges);
+    const uint32_t* list = reinterpret_cast<const uint32_t*>(bin + B.list);
+    float* img = static_cast<float*>(a->image);
+    uint32_t* staged = reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(a->image) + image_staged_offset(W, H, V));
+    float* S = static_cast<float*>(scratch);
+    GSR_HIP(hipMemsetAsync(S, 0, (size_t)V * Npad * kImpStride * sizeof(float), st));
+    {
+        ProfScope ps(P_IMP_BLEND, st);
+        hipLaunchKernelGGL(k_blend_importance, dim3(8 * 4 * slots_per_xcd(T, tiles_x)), dim3(64), 0, st, W, H, tiles_x, T, ranges, list, splat,
+                           img, staged, tiles_y, (const float*)a->out_color, S);
+    }
+    {
+        ProfScope ps(P_IMP_FINISH, st);
+        hipLaunchKernelGGL(k_importance_finish_views, dim3((N + 15) / 16), dim3(256), 0, st, N, Npad, V, a->M, a->D, a->means3D,
+                           a->points_transform, a->campos, a->sh_origin, splat, (const float*)S, acc);
     }
     GSR_HIP(hipGetLastError());
     return GSR_OK;

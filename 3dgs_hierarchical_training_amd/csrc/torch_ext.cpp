@@ -292,6 +292,107 @@ std::vector<Tensor> importance_accumulate(
     return {color, std::get<1>(f), std::get<2>(f), std::get<3>(f), geom, image, binning, meta};
 }
 
+// gsr::rasterize_forward_views -> gsr_forward_views (include/gsr.h, version 123): ONE model under V cameras in one launch chain.
+// viewmatrix / projmatrix are [V,4,4], campos [V,3], points_transform [V,3,4] and sh_origin [V,3] when given; V = viewmatrix.size(0).
+// Returns {color [V,3,H,W], radii [V Npad], depth, alpha [V,1,H,W], geom, image, binning, meta, clamped, visible [V Npad]}; extras as in
+// rasterize_forward.  No autograd: there is no backward over a views forward.
+std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> rasterize_forward_views(
+    const Tensor& means3D_, const Tensor& sh_, const Tensor& colors_, const Tensor& opacities_, const Tensor& scales_,
+    const Tensor& rotations_, const Tensor& cov3D_, const Tensor& sh_rest_, const Tensor& viewmatrix_, const Tensor& projmatrix_,
+    const Tensor& campos_, const Tensor& bg_, const Tensor& xf_, int64_t H, int64_t W, double tanfovx, double tanfovy,
+    double scale_modifier, int64_t sh_degree, bool raw_params, int64_t extras, const c10::optional<Tensor>& sh_origin_)
+{
+    TORCH_CHECK(means3D_.is_cuda(), "rasterize_forward_views: tensors must be on a ROCm/HIP device (no CPU fallback)");
+    TORCH_CHECK(!take_retire().table.defined(), "rasterize_forward_views: a retire table (retired_at) is not served with views");
+    TORCH_CHECK(viewmatrix_.dim() == 3 && viewmatrix_.size(1) == 4 && viewmatrix_.size(2) == 4, "views: viewmatrix must be [V,4,4]");
+    const int64_t V = viewmatrix_.size(0);
+    TORCH_CHECK(V >= 1 && V <= GSR_MAX_VIEWS, "views: 1..16 views expected");
+    const c10::hip::HIPGuardMasqueradingAsCUDA guard(means3D_.device());
+    const Tensor means3D = f32c(means3D_), sh = f32c(sh_), colors = f32c(colors_), opac = f32c(opacities_), scales = f32c(scales_),
+                 rots = f32c(rotations_), cov = f32c(cov3D_), rest = f32c(sh_rest_), vm = f32c(viewmatrix_), pm = f32c(projmatrix_),
+                 campos = f32c(campos_), bg = f32c(bg_), xf = f32c(xf_);
+    Tensor sh_origin;
+    if (sh_origin_.has_value() && sh_origin_->defined()) {
+        TORCH_CHECK(sh_origin_->numel() == 3 * V && sh_origin_->is_cuda(), "views: sh_origin must be [V,3] on the device of the model");
+        sh_origin = f32c(sh_origin_->reshape({V, 3}));
+    }
+    TORCH_CHECK(pm.numel() == 16 * V && (!has(campos) || campos.numel() == 3 * V) && (!has(xf) || xf.numel() == 12 * V),
+                "views: projmatrix must be [V,4,4], campos [V,3], points_transform [V,3,4]");
+    const int64_t N = means3D.size(0);
+    TORCH_CHECK(N >= 1, "views: at least one Gaussian expected");
+    const int64_t M = has(sh) ? sh.size(1) + (has(rest) ? rest.size(1) : 0) : 0;
+    const int64_t Npad = (N + 127) / 128 * 128;
+    TORCH_CHECK(V * Npad < ((int64_t)1 << 31), "views: V * Npad must stay below 2^31 records");
+    const auto fo = means3D.options().dtype(at::kFloat);
+    const auto bo = means3D.options().dtype(at::kByte);
+    Tensor color = at::empty({V, 3, H, W}, fo), depth = at::empty({V, 1, H, W}, fo), alpha = at::empty({V, 1, H, W}, fo);
+    Tensor radii = at::empty({V * Npad}, means3D.options().dtype(at::kInt));
+    Tensor geom = at::empty({(int64_t)gsr_geom_bytes_views((int32_t)N, (int32_t)V)}, bo);
+    Tensor image = at::empty({(int64_t)gsr_image_bytes_batched((int32_t)W, (int32_t)H, (int32_t)V)}, bo);
+    AllocCtx actx{bo, Tensor(), {}};
+    GsrForwardArgs a{};
+    a.N = (int32_t)N; a.M = (int32_t)M; a.D = (int32_t)sh_degree; a.W = (int32_t)W; a.H = (int32_t)H;
+    a.scale_modifier = (float)scale_modifier; a.tanfovx = (float)tanfovx; a.tanfovy = (float)tanfovy;
+    a.means3D = fp(means3D); a.scales = fp(scales); a.rotations = fp(rots); a.cov3D_precomp = fp(cov);
+    a.opacities = fp(opac); a.shs = fp(sh); a.colors_precomp = fp(colors);
+    a.viewmatrix = fp(vm); a.projmatrix = fp(pm); a.campos = fp(campos); a.bg = fp(bg);
+    a.out_color = color.data_ptr<float>(); a.out_depth = depth.data_ptr<float>(); a.out_alpha = alpha.data_ptr<float>();
+    a.radii = radii.data_ptr<int32_t>();
+    a.geom = geom.data_ptr(); a.image = image.data_ptr();
+    a.alloc = alloc_cb; a.alloc_user = &actx;
+    a.shs_rest = fp(rest); a.raw_params = raw_params;
+    a.points_transform = fp(xf);
+    a.sh_origin = fp(sh_origin);
+    Tensor clamped = (extras & 1) ? at::empty_like(color) : at::empty({0}, fo);
+    Tensor visible = (extras & 2) ? at::empty({V * Npad}, bo) : at::empty({0}, bo);
+    a.out_color_clamped = has(clamped) ? clamped.data_ptr<float>() : nullptr;
+    a.visible = has(visible) ? visible.data_ptr<uint8_t>() : nullptr;
+    GsrForwardOut out{};
+    check(gsr_forward_views(&a, (int32_t)V, &out, c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream()), "gsr_forward_views");
+    Tensor meta = at::empty({3}, at::TensorOptions().dtype(at::kLong));   // CPU: R, capacity, flags
+    int64_t* mp = meta.data_ptr<int64_t>();
+    mp[0] = out.num_rendered; mp[1] = out.binning_capacity; mp[2] = out.forward_flags;
+    Tensor binning = actx.binning.defined() ? actx.binning : at::empty({0}, bo);
+    return {color, radii, depth, alpha, geom, image, binning, meta, clamped, visible};
+}
+
+// gsr::importance_accumulate_views -> gsr_forward_views + gsr_importance_accumulate_views: the colour importance of V views of one model
+// added to `acc` [N,M,3] in place, view by view in the order given (what hierarchy.calc_importance runs per group of views).  Returns the
+// forward's {color, radii, depth, alpha, geom, image, binning, meta}.
+std::vector<Tensor> importance_accumulate_views(
+    Tensor& acc, const Tensor& means3D_, const Tensor& sh_, const Tensor& colors_, const Tensor& opacities_, const Tensor& scales_,
+    const Tensor& rotations_, const Tensor& cov3D_, const Tensor& sh_rest_, const Tensor& viewmatrix_, const Tensor& projmatrix_,
+    const Tensor& campos_, const Tensor& bg_, const Tensor& xf_, int64_t H, int64_t W, double tanfovx, double tanfovy,
+    double scale_modifier, int64_t sh_degree, bool raw_params, const c10::optional<Tensor>& sh_origin_)
+{
+    TORCH_CHECK(means3D_.is_cuda(), "importance_accumulate_views: tensors must be on a ROCm/HIP device (no CPU fallback)");
+    TORCH_CHECK(has(sh_) && !has(colors_), "importance_accumulate_views: the model must carry SH coefficients (colors_precomp has none)");
+    const c10::hip::HIPGuardMasqueradingAsCUDA guard(means3D_.device());
+    const Tensor means3D = f32c(means3D_), sh = f32c(sh_), rest = f32c(sh_rest_), campos = f32c(campos_), xf = f32c(xf_);
+    const int64_t N = means3D.size(0), M = sh.size(1) + (has(rest) ? rest.size(1) : 0);
+    TORCH_CHECK(acc.is_cuda() && acc.scalar_type() == at::kFloat && acc.is_contiguous() && acc.dim() == 3 && acc.size(0) == N && acc.size(1) == M &&
+                    acc.size(2) == 3, "importance_accumulate_views: acc must be a contiguous float32 [N, M, 3] tensor (M = stored SH coefficients)");
+    auto f = rasterize_forward_views(means3D, sh, colors_, opacities_, scales_, rotations_, cov3D_, rest, viewmatrix_, projmatrix_, campos, bg_, xf, H, W,
+                                     tanfovx, tanfovy, scale_modifier, sh_degree, raw_params, 0, sh_origin_);
+    const Tensor &color = std::get<0>(f), &geom = std::get<4>(f), &image = std::get<5>(f), &binning = std::get<6>(f), &meta = std::get<7>(f);
+    const int64_t V = color.size(0);
+    Tensor sh_origin;
+    if (sh_origin_.has_value() && sh_origin_->defined()) sh_origin = f32c(sh_origin_->reshape({V, 3}));
+    GsrForwardArgs a{};
+    a.N = (int32_t)N; a.M = (int32_t)M; a.D = (int32_t)sh_degree; a.W = (int32_t)W; a.H = (int32_t)H;
+    a.means3D = fp(means3D); a.shs = fp(sh); a.shs_rest = fp(rest); a.campos = fp(campos); a.points_transform = fp(xf);
+    a.sh_origin = fp(sh_origin);
+    a.out_color = color.data_ptr<float>(); a.geom = geom.data_ptr(); a.image = image.data_ptr();
+    GsrForwardOut out{};
+    const int64_t* mp = meta.data_ptr<int64_t>();
+    out.num_rendered = mp[0]; out.binning_capacity = mp[1]; out.forward_flags = mp[2];
+    out.binning = has(binning) ? binning.data_ptr() : nullptr;
+    Tensor scratch = at::empty({(int64_t)gsr_importance_scratch_bytes_views((int32_t)N, (int32_t)V)}, means3D.options().dtype(at::kByte));
+    check(gsr_importance_accumulate_views(&a, (int32_t)V, &out, acc.data_ptr<float>(), scratch.data_ptr(),
+                                          c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream()), "gsr_importance_accumulate_views");
+    return {color, std::get<1>(f), std::get<2>(f), std::get<3>(f), geom, image, binning, meta};
+}
+
 struct BwdCommon {
     Tensor means3D, sh, colors, opac, scales, rots, cov, rest, vm, pm, campos, bg, xf, gc, gd, ga;
 };
@@ -1676,6 +1777,14 @@ TORCH_LIBRARY(gsr, m)
           "bool raw_params, int[] batch_first_block, int view_id=0, Tensor? sh_origin=None) -> Tensor[]");
     m.def("importance_pass(Tensor(a!) acc, Tensor means3D, Tensor sh, Tensor sh_rest, Tensor campos, Tensor points_transform, Tensor color, "
           "Tensor geom, Tensor image, Tensor binning, Tensor meta, int image_height, int image_width, int sh_degree, Tensor? sh_origin=None) -> ()");
+    m.def("rasterize_forward_views(Tensor means3D, Tensor sh, Tensor colors_precomp, Tensor opacities, Tensor scales, Tensor rotations, "
+          "Tensor cov3D_precomp, Tensor sh_rest, Tensor viewmatrix, Tensor projmatrix, Tensor campos, Tensor bg, Tensor points_transform, "
+          "int image_height, int image_width, float tanfovx, float tanfovy, float scale_modifier, int sh_degree, bool raw_params, "
+          "int extras=0, Tensor? sh_origin=None) -> (Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)");
+    m.def("importance_accumulate_views(Tensor(a!) acc, Tensor means3D, Tensor sh, Tensor colors_precomp, Tensor opacities, Tensor scales, "
+          "Tensor rotations, Tensor cov3D_precomp, Tensor sh_rest, Tensor viewmatrix, Tensor projmatrix, Tensor campos, Tensor bg, "
+          "Tensor points_transform, int image_height, int image_width, float tanfovx, float tanfovy, float scale_modifier, int sh_degree, "
+          "bool raw_params, Tensor? sh_origin=None) -> Tensor[]");
     m.def("mark_visible(Tensor means3D, Tensor viewmatrix, Tensor projmatrix) -> Tensor");
     m.def("photometric_loss_forward(Tensor render, Tensor target, float lambda_dssim, bool clamp) -> (Tensor, Tensor)");
     m.def("photometric_loss_backward(Tensor render, Tensor target, Tensor workspace, Tensor grad_loss, float lambda_dssim, bool clamp) -> Tensor");
@@ -1730,6 +1839,8 @@ TORCH_LIBRARY_IMPL(gsr, CUDA, m)   // the dispatch key of HIP tensors on a ROCm 
     m.impl("render", &render);
     m.impl("importance_accumulate", &importance_accumulate);
     m.impl("importance_pass", &importance_pass);
+    m.impl("rasterize_forward_views", &rasterize_forward_views);
+    m.impl("importance_accumulate_views", &importance_accumulate_views);
     m.impl("mark_visible", &mark_visible);
     m.impl("photometric_loss_forward", &photometric_loss_forward);
     m.impl("photometric_loss_backward", &photometric_loss_backward);

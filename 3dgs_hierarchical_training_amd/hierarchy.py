@@ -18,7 +18,8 @@ from typing import Dict, List, Optional
 import torch
 
 from . import segments
-from .rasterizer import GaussianRasterizationSettings, importance_accumulate, rasterize_gaussians_raw, render_gaussians_raw
+from .rasterizer import (GaussianRasterizationSettings, importance_accumulate, importance_accumulate_views, rasterize_gaussians_raw,
+                         render_gaussians_raw)
 
 
 def _elapsed_ms(t0: float, ref: torch.Tensor) -> float:
@@ -44,6 +45,17 @@ DEFAULT_IMPORTANCE_ROUTE = os.environ.get("GSR_IMPORTANCE_ROUTE", "kernel")
 IMPORTANCE_ROUTES = ("kernel", "autograd")
 if DEFAULT_IMPORTANCE_ROUTE not in IMPORTANCE_ROUTES:
     raise ValueError(f"GSR_IMPORTANCE_ROUTE={DEFAULT_IMPORTANCE_ROUTE!r}: one of {IMPORTANCE_ROUTES}")
+
+# How many views of a model one call of the kernel route takes (include/gsr.h gsr_importance_accumulate_views): 1 = a forward and a pass
+# per view, the route as it was; 2..16 = runs of views that share their frame go through ONE launch chain and one host wait.  The
+# default stays 1 whatever tools/importance_views_probe.py measures (profiles/importance_views.txt): changing it is
+# a decision of its own that cites that file.  VIEWS_MAX_RECORDS bounds what one call keeps alive -- V images of pixel state and V * Npad
+# splat records: at most 8 Mi records, 8 views at 1 M Gaussians.
+DEFAULT_IMPORTANCE_VIEWS = int(os.environ.get("GSR_IMPORTANCE_VIEWS", "1"))
+MAX_VIEWS_PER_CALL = 16
+VIEWS_MAX_RECORDS = 8 * 2 ** 20
+if not 1 <= DEFAULT_IMPORTANCE_VIEWS <= MAX_VIEWS_PER_CALL:
+    raise ValueError(f"GSR_IMPORTANCE_VIEWS={DEFAULT_IMPORTANCE_VIEWS}: 1..{MAX_VIEWS_PER_CALL}")
 
 _SH_C0 = 0.28209479177387814
 _SH_C1 = 0.4886025119029199
@@ -117,14 +129,75 @@ def _calc_importance_kernel(seg, views, points_transform=None, sh_origin=None, v
     return acc.flatten(-2) / max(num_pixels, 1)
 
 
-def calc_importance(seg: Dict[str, torch.Tensor], views: List[GaussianRasterizationSettings], route: Optional[str] = None) -> torch.Tensor:
+def _same_frame(a: GaussianRasterizationSettings, b: GaussianRasterizationSettings) -> bool:
+    """Do two views share what gsr_forward_views shares: image size, field of view, SH degree, scale modifier and background?"""
+    if (int(a.image_height), int(a.image_width), float(a.tanfovx), float(a.tanfovy), int(a.sh_degree), float(a.scale_modifier)) != \
+            (int(b.image_height), int(b.image_width), float(b.tanfovx), float(b.tanfovy), int(b.sh_degree), float(b.scale_modifier)):
+        return False
+    return a.bg is b.bg or (a.bg.shape == b.bg.shape and a.bg.device == b.bg.device and bool(torch.equal(a.bg, b.bg)))
+
+
+def group_views(views, per_call: int, N: int) -> List[List[int]]:
+    """The call plan of the kernel route: the indices of `views`, in order, cut into the groups one call each takes.  Consecutive views that
+    agree in image_height, image_width, tanfovx, tanfovy, sh_degree, scale_modifier and bg (the same tensor, or equal values) form a
+    run; a run is cut into groups of at most min(per_call, 16, max(1, VIEWS_MAX_RECORDS // Npad)) views, Npad = 128 ceil(N / 128).  A
+    group of one view goes through the single-view call.  Pure: nothing is rendered."""
+    if per_call < 1:
+        raise ValueError(f"group_views: per_call must be at least 1, got {per_call}")
+    npad = max(128, (int(N) + 127) // 128 * 128)
+    cap = min(int(per_call), MAX_VIEWS_PER_CALL, max(1, VIEWS_MAX_RECORDS // npad))
+    plan: List[List[int]] = []
+    for i, rs in enumerate(views):
+        if plan and len(plan[-1]) < cap and _same_frame(views[plan[-1][0]], rs):
+            plan[-1].append(i)
+        else:
+            plan.append([i])
+    return plan
+
+
+def stack_views(views, device) -> GaussianRasterizationSettings:
+    """One settings tuple for the views of a group (what batched.batch_settings returns): cameras [V,4,4], [V,4,4], [V,3]."""
+    v0 = views[0]
+    return v0._replace(viewmatrix=torch.stack([v.viewmatrix.to(device).float() for v in views]).contiguous(),
+                       projmatrix=torch.stack([v.projmatrix.to(device).float() for v in views]).contiguous(),
+                       campos=torch.stack([v.campos.to(device).float() for v in views]).contiguous())
+
+
+def _calc_importance_views(seg, views, per_call):
+    """The kernel route with up to `per_call` views per launch chain (group_views): ONE [N, M, 3] accumulator that the groups add into in
+    view order, the single division by the pixel count at the end."""
+    dc, rest = seg["_features_dc"].detach(), seg["_features_rest"].detach()
+    acc = torch.zeros((dc.shape[0], dc.shape[1] + rest.shape[1], 3), dtype=torch.float32, device=dc.device)
+    num_pixels = 0
+    for group in group_views(views, per_call, dc.shape[0]):
+        if len(group) == 1:
+            importance_accumulate(acc, seg["_xyz"], dc, seg["_opacity"], seg["_scaling"], seg["_rotation"], views[group[0]], sh_rest=rest,
+                                  raw_params=True)
+        else:
+            importance_accumulate_views(acc, seg["_xyz"], dc, seg["_opacity"], seg["_scaling"], seg["_rotation"],
+                                        stack_views([views[i] for i in group], dc.device), sh_rest=rest, raw_params=True)
+        num_pixels += sum(int(views[i].image_height) * int(views[i].image_width) for i in group)
+    return acc.flatten(-2) / max(num_pixels, 1)
+
+
+def calc_importance(seg: Dict[str, torch.Tensor], views: List[GaussianRasterizationSettings], route: Optional[str] = None,
+                    views_per_call: Optional[int] = None) -> torch.Tensor:
     """[N, 48] colour importance of a segment over `views` (each a full raster-settings tuple), entry k * 3 + c.
     route: "autograd" = per view a render and a full backward, |grad| of the SH tensors; "kernel" = per view a forward and the
-    importance pass (no backward, no autograd, no .grad left anywhere); None = DEFAULT_IMPORTANCE_ROUTE."""
+    importance pass (no backward, no autograd, no .grad left anywhere); None = DEFAULT_IMPORTANCE_ROUTE.
+    views_per_call: how many views one launch chain of the kernel route takes (group_views); 1 = the per-view route, 2..16 = the views
+    entry (gsr_importance_accumulate_views); None = DEFAULT_IMPORTANCE_VIEWS (GSR_IMPORTANCE_VIEWS, 1).  The autograd route takes 1 only."""
     route = DEFAULT_IMPORTANCE_ROUTE if route is None else route
     if route not in IMPORTANCE_ROUTES:
         raise ValueError(f"calc_importance: unknown route {route!r} (one of {IMPORTANCE_ROUTES})")
-    return _calc_importance_kernel(seg, views) if route == "kernel" else _calc_importance_autograd(seg, views)
+    per_call = DEFAULT_IMPORTANCE_VIEWS if views_per_call is None else int(views_per_call)
+    if not 1 <= per_call <= MAX_VIEWS_PER_CALL:
+        raise ValueError(f"calc_importance: views_per_call must be 1..{MAX_VIEWS_PER_CALL}, got {per_call}")
+    if route == "autograd":
+        if per_call > 1:
+            raise ValueError("calc_importance: views_per_call > 1 is served by the kernel route only (route='autograd' renders view by view)")
+        return _calc_importance_autograd(seg, views)
+    return _calc_importance_kernel(seg, views) if per_call == 1 else _calc_importance_views(seg, views, per_call)
 
 
 def prune_mask(importance: torch.Tensor, prune_ratio: float, route: str = "torch") -> torch.Tensor:

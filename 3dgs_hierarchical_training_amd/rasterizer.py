@@ -746,6 +746,147 @@ def importance_accumulate(acc, means3D, sh, opacities, scales, rotations, raster
         return f.color, f.radii, f.depth, f.alpha
 
 
+def _views_inputs(fn, means3D, view_settings, points_transform, sh_origin, sh):
+    """Checks and device copies shared by forward_views / importance_accumulate_views: (V, vm, pm, campos, xf | None, sh_origin | None)."""
+    dev = means3D.device
+    if dev.type != "cuda":
+        raise RuntimeError(f"{fn}: tensors must be on a ROCm/HIP device (no CPU fallback)")
+    rs = view_settings
+    if rs.viewmatrix.dim() != 3 or tuple(rs.viewmatrix.shape[1:]) != (4, 4):
+        raise RuntimeError(f"{fn}: view_settings must carry stacked cameras ([V,4,4], [V,4,4], [V,3]: batched.batch_settings)")
+    V = int(rs.viewmatrix.shape[0])
+    if not 1 <= V <= L.GSR_MAX_VIEWS:
+        raise RuntimeError(f"{fn}: 1..{L.GSR_MAX_VIEWS} views expected, got {V}")
+    if tuple(rs.projmatrix.shape) != (V, 4, 4) or tuple(rs.campos.shape) != (V, 3):
+        raise RuntimeError(f"{fn}: view_settings must carry stacked cameras ([V,4,4], [V,4,4], [V,3]: batched.batch_settings)")
+    f32 = lambda t: t.detach().to(device=dev, dtype=torch.float32).contiguous()
+    xf = None
+    if points_transform is not None:       # one [3,4] / [4,4] transform per view
+        if points_transform.dim() != 3 or tuple(points_transform.shape) not in ((V, 3, 4), (V, 4, 4)):
+            raise RuntimeError(f"{fn}: points_transform must be [V,3,4] or [V,4,4] (one transform per view)")
+        xf = f32(points_transform[:, :3])
+    if sh_origin is not None:
+        if sh_origin.numel() != 3 * V or _empty_to_none(sh) is None:
+            raise RuntimeError(f"{fn}: sh_origin must be [V,3] (one origin of the SH view direction per view) and needs SH coefficients")
+        sh_origin = f32(sh_origin.reshape(V, 3))
+    return V, f32(rs.viewmatrix), f32(rs.projmatrix), f32(rs.campos), xf, sh_origin
+
+
+class _CtypesViews:
+    """What one gsr_forward_views over ctypes leaves behind (forward_views and importance_accumulate_views share it)."""
+    __slots__ = ("a", "out", "keep", "color", "radii", "depth", "alpha", "clamped", "visible", "N", "M", "V", "Npad")
+
+
+def _ctypes_forward_views(means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, rs, sh_rest, raw_params, V, vm, pm, campos,
+                          xf, sh_origin, extras) -> _CtypesViews:
+    lib = L.load()
+    dev = means3D.device
+    prep = lambda t: _f32c(_empty_to_none(None if t is None else t.detach()))
+    means3D, opacities = _f32c(means3D.detach()), _f32c(opacities.detach())
+    sh, colors_precomp, scales, rotations = prep(sh), prep(colors_precomp), prep(scales), prep(rotations)
+    cov3Ds_precomp, sh_rest = prep(cov3Ds_precomp), prep(sh_rest)
+    bg = _f32c(rs.bg.detach().to(dev))
+    N = int(means3D.shape[0])
+    Npad = (N + 127) // 128 * 128
+    H, W = int(rs.image_height), int(rs.image_width)
+    M = (int(sh.shape[1]) + (int(sh_rest.shape[1]) if sh_rest is not None else 0)) if sh is not None else 0
+    new = lambda shape, dtype=torch.float32: torch.empty(shape, dtype=dtype, device=dev)
+    f = _CtypesViews()
+    f.N, f.M, f.V, f.Npad = N, M, V, Npad
+    f.color, f.depth, f.alpha, f.radii = new((V, 3, H, W)), new((V, 1, H, W)), new((V, 1, H, W)), new((V * Npad,), torch.int32)
+    f.clamped = new((V, 3, H, W)) if (extras & 1) else None
+    f.visible = new((V * Npad,), torch.uint8) if (extras & 2) else None
+    geom = new((lib.gsr_geom_bytes_views(N, V),), torch.uint8)
+    image = new((lib.gsr_image_bytes_batched(W, H, V),), torch.uint8)
+    ws = _Workspace(dev)
+    a = L.GsrForwardArgs()
+    a.N, a.M, a.D, a.W, a.H = N, M, int(rs.sh_degree), W, H
+    a.scale_modifier, a.tanfovx, a.tanfovy = float(rs.scale_modifier), float(rs.tanfovx), float(rs.tanfovy)
+    a.means3D, a.scales, a.rotations, a.cov3D_precomp = _ptr(means3D), _ptr(scales), _ptr(rotations), _ptr(cov3Ds_precomp)
+    a.opacities, a.shs, a.colors_precomp = _ptr(opacities), _ptr(sh), _ptr(colors_precomp)
+    a.viewmatrix, a.projmatrix, a.campos, a.bg = _ptr(vm), _ptr(pm), _ptr(campos), _ptr(bg)
+    a.out_color, a.out_depth, a.out_alpha, a.radii = f.color.data_ptr(), f.depth.data_ptr(), f.alpha.data_ptr(), f.radii.data_ptr()
+    a.geom, a.image = geom.data_ptr(), image.data_ptr()
+    a.alloc, a.alloc_user = ws.cb, None
+    a.shs_rest, a.raw_params = _ptr(sh_rest), int(bool(raw_params))
+    a.points_transform, a.sh_origin = _ptr(xf), _ptr(sh_origin)
+    a.out_color_clamped, a.visible = _ptr(f.clamped), _ptr(f.visible)
+    out = L.GsrForwardOut()
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        L.check(lib.gsr_forward_views(C.byref(a), V, C.byref(out), C.c_void_p(stream)), "gsr_forward_views")
+    ws.scratch.clear()  # stream-ordered reuse by the caching allocator is safe: same stream
+    f.a, f.out = a, out
+    f.keep = (means3D, opacities, sh, colors_precomp, scales, rotations, cov3Ds_precomp, sh_rest, bg, vm, pm, campos, xf, sh_origin, geom, image,
+              ws.binning)
+    return f
+
+
+def forward_views(means3D, sh, opacities, scales, rotations, view_settings, sh_rest=None, raw_params=False, cov3Ds_precomp=None,
+                  colors_precomp=None, points_transform=None, sh_origin=None, extras=0):
+    """ONE model under V cameras in one launch chain (include/gsr.h gsr_forward_views, torch.ops.gsr.rasterize_forward_views): the
+    preprocess reads the model's one set of parameter rows for every view, behind it the chain is a batched forward's.
+    view_settings: what batched.batch_settings returns for the V settings (cameras [V,4,4], [V,4,4], [V,3]; image size, field of view,
+    background, degree and scale modifier shared); points_transform [V,3,4] / [V,4,4] and sh_origin [V,3] are per view.  No autograd --
+    there is no backward over a views forward -- and inputs are detached.  extras: bit 0 = the clamped colour, bit 1 = the visibility
+    bytes.  Returns (color [V,3,H,W], radii [V,N], depth [V,1,H,W], alpha [V,1,H,W], clamped [V,3,H,W] | None, visible [V,N] | None);
+    every view's outputs are bit-identical with rendering that view alone."""
+    V, vm, pm, cp, xf, sh_origin = _views_inputs("forward_views", means3D, view_settings, points_transform, sh_origin, sh)
+    rs = view_settings
+    dev = means3D.device
+    N = int(means3D.shape[0])
+    Npad = (N + 127) // 128 * 128
+    rows = lambda t: t.view(V, Npad)[:, :N]
+    with torch.no_grad():
+        if not E.use_ctypes():
+            ops = E.load()
+            e = _e(dev)
+            pick = lambda t: e if (t is None or t.numel() == 0) else t.detach()
+            color, radii, depth, alpha, _geom, _image, _binning, _meta, cl, vis = ops.rasterize_forward_views(
+                means3D.detach(), pick(sh), pick(colors_precomp), opacities.detach(), pick(scales), pick(rotations), pick(cov3Ds_precomp),
+                pick(sh_rest), vm, pm, cp, rs.bg.detach().to(dev), e if xf is None else xf, int(rs.image_height), int(rs.image_width),
+                float(rs.tanfovx), float(rs.tanfovy), float(rs.scale_modifier), int(rs.sh_degree), bool(raw_params), int(extras), sh_origin)
+            return color, rows(radii), depth, alpha, cl if (extras & 1) else None, rows(vis) if (extras & 2) else None
+        f = _ctypes_forward_views(means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, rs, sh_rest, raw_params, V, vm, pm,
+                                  cp, xf, sh_origin, int(extras))
+        return f.color, rows(f.radii), f.depth, f.alpha, f.clamped, rows(f.visible) if f.visible is not None else None
+
+
+def importance_accumulate_views(acc, means3D, sh, opacities, scales, rotations, view_settings, sh_rest=None, raw_params=False,
+                                cov3Ds_precomp=None, colors_precomp=None, points_transform=None, sh_origin=None):
+    """importance_accumulate for V views of one model in one launch chain (include/gsr.h gsr_importance_accumulate_views): one
+    forward_views, one walk over the V images' tile lists, one finishing launch that adds the views' terms to `acc` [N, M, 3] in the
+    order the views are given -- the order V single-view calls would add them in.  One host wait for the instance count instead of V.
+    view_settings, points_transform, sh_origin: as in forward_views.  Returns the forward's (color [V,3,H,W], radii [V,N], depth, alpha)."""
+    V, vm, pm, cp, xf, sh_origin = _views_inputs("importance_accumulate_views", means3D, view_settings, points_transform, sh_origin, sh)
+    rs = view_settings
+    dev = means3D.device
+    N = int(means3D.shape[0])
+    Npad = (N + 127) // 128 * 128
+    rows = lambda t: t.view(V, Npad)[:, :N]
+    with torch.no_grad():
+        if not E.use_ctypes():
+            ops = E.load()
+            e = _e(dev)
+            pick = lambda t: e if (t is None or t.numel() == 0) else t.detach()
+            r = ops.importance_accumulate_views(
+                acc, means3D.detach(), pick(sh), pick(colors_precomp), opacities.detach(), pick(scales), pick(rotations), pick(cov3Ds_precomp),
+                pick(sh_rest), vm, pm, cp, rs.bg.detach().to(dev), e if xf is None else xf, int(rs.image_height), int(rs.image_width),
+                float(rs.tanfovx), float(rs.tanfovy), float(rs.scale_modifier), int(rs.sh_degree), bool(raw_params), sh_origin)
+            return r[0], rows(r[1]), r[2], r[3]
+        lib = L.load()
+        f = _ctypes_forward_views(means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, rs, sh_rest, raw_params, V, vm, pm,
+                                  cp, xf, sh_origin, 0)
+        if tuple(acc.shape) != (f.N, f.M, 3) or acc.dtype != torch.float32 or not acc.is_contiguous():
+            raise RuntimeError("importance_accumulate_views: acc must be a contiguous float32 [N, M, 3] tensor (M = stored SH coefficients)")
+        scratch = torch.empty(lib.gsr_importance_scratch_bytes_views(f.N, V), dtype=torch.uint8, device=dev)
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            L.check(lib.gsr_importance_accumulate_views(C.byref(f.a), V, C.byref(f.out), acc.data_ptr(), scratch.data_ptr(), C.c_void_p(stream)),
+                    "gsr_importance_accumulate_views")
+        return f.color, rows(f.radii), f.depth, f.alpha
+
+
 class GaussianRasterizer(nn.Module):
     """Callable exactly as at gaussian_model_ht.py:824,871-880 and gaussian_renderer/__init__.py:53,88-96."""
 

@@ -30,6 +30,7 @@ poses are synthetic (sequence.py); the relative-pose table stands for stage A's 
 Every rank prints one JSON line per phase: leaf, and per level {importance_ms, send_ms | recv_ms, bytes, ...}.
 """
 import argparse
+import functools
 import importlib
 import json
 import os
@@ -88,6 +89,8 @@ class HTConfig:
     phase2_iters_per_frame: List[int] = field(default_factory=lambda: [10, 10, 10])   # num_iterations_per_frame_each_level
     prune_ratio: float = 0.5                    # Ballroom.yml:44
     importance_views: int = 0                   # 0 = all of the child's frames (the reference), k = every (len/k)-th
+    importance_views_per_call: int = 1          # views of a model one launch chain of the merge's importance takes (hierarchy.group_views):
+                                                # 1 = a forward and a pass per view (default), 2..16 = gsr_importance_accumulate_views
     densify: bool = False
     seed: int = 0
     optimizer: str = "hip"
@@ -154,7 +157,10 @@ class RankRunner:
         """importance_fn / step_fn / teacher_render_fn replace the three places that reach the HIP rasterizer; the
         GPU-less gloo tests pass stand-ins so that the tree walk, the messages and the bookkeeping run on CPU."""
         self.rank, self.world, self.tr, self.seq, self.cfg, self.dev = rank, world, transport, seq, cfg, device
+        check_importance_views_per_call(cfg)
         self.importance_fn = importance_fn or hierarchy.calc_importance
+        if importance_fn is None and cfg.importance_views_per_call > 1:
+            self.importance_fn = functools.partial(hierarchy.calc_importance, views_per_call=int(cfg.importance_views_per_call))
         self.step_fn = step_fn
         self.teacher_render_fn = teacher_render_fn or hierarchy.render_raw
         self.level = world.bit_length() - 1
@@ -404,6 +410,13 @@ class RankRunner:
 LEAF_BATCH_MAX = 16      # models of one batched store (include/gsr.h GSR_RESIZE_MAX_MODELS)
 
 
+def check_importance_views_per_call(cfg: HTConfig):
+    """`importance_views_per_call` is 1 .. hierarchy.MAX_VIEWS_PER_CALL, refused before a device is touched."""
+    n = int(cfg.importance_views_per_call)
+    if not 1 <= n <= hierarchy.MAX_VIEWS_PER_CALL:
+        raise ValueError(f"importance_views_per_call: 1..{hierarchy.MAX_VIEWS_PER_CALL} views share a launch chain, got {n}")
+
+
 def check_leaf_batch(cfg: HTConfig, local: bool):
     """The combinations `leaf_batch` >= 2 serves, refused before a device is touched: the local walk, without pose refinement."""
     n = int(cfg.leaf_batch)
@@ -603,7 +616,7 @@ def launch_check(a):
     dist.destroy_process_group()
 
 
-def main():
+def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser()
     ap.add_argument("--local", action="store_true", help="walk the whole tree on one GPU (no process group)")
     ap.add_argument("--segments", type=int, default=8, help="leaf segments for --local (otherwise WORLD_SIZE)")
@@ -616,6 +629,9 @@ def main():
     ap.add_argument("--phase1-iters", type=int, default=5)
     ap.add_argument("--phase2-iters", type=int, default=10)
     ap.add_argument("--importance-views", type=int, default=0)
+    ap.add_argument("--importance-views-per-call", type=int, default=1,
+                    help="views of a model that one launch chain of the merge's importance takes: 1 = a forward and a pass per view "
+                         "(default); 2..16 = runs of views go through the views entry, one host wait per run")
     ap.add_argument("--densify", action="store_true")
     ap.add_argument("--pose-lr", type=float, default=None)
     ap.add_argument("--fit-pose", action="store_true", help="refine every frame's pose while training on it (the reference's "
@@ -658,14 +674,27 @@ def main():
                                                          "fewer visible devices than ranks: a JSON error line and exit code 3")
     ap.add_argument("--launch-check", action="store_true", help="launcher plumbing only (needs no GPU with --backend gloo): form the process "
                                                                 "group, run the link self-test along every edge of the merge tree, report, leave")
-    a = ap.parse_args()
+    return ap
+
+
+def parse_args(argv=None):
+    """The command line, with what can be refused without a device refused here."""
+    ap = build_parser()
+    a = ap.parse_args(argv)
+    if not 1 <= a.importance_views_per_call <= hierarchy.MAX_VIEWS_PER_CALL:
+        ap.error(f"--importance-views-per-call: 1..{hierarchy.MAX_VIEWS_PER_CALL} expected, got {a.importance_views_per_call}")
+    return a
+
+
+def main():
+    a = parse_args()
     if a.ranks > 1 and "WORLD_SIZE" not in os.environ:
         self_launch(a)
     if a.launch_check:
         return launch_check(a)
     cfg = HTConfig(frames=a.frames, width=a.width, height=a.height, gt_gaussians=a.gt_gaussians, leaf_gaussians=a.leaf_gaussians,
                    leaf_iters_per_frame=a.leaf_iters, phase1_iters_per_frame=a.phase1_iters, phase2_iters_per_frame=[a.phase2_iters] * 3,
-                   importance_views=a.importance_views, densify=a.densify, fit_pose=a.fit_pose, stage_a_batch=a.stage_a_batch, stage_a_lambda_depth=a.stage_a_lambda_depth, stage_a_early_exit=a.stage_a_early_exit, stage_a_init=a.stage_a_init, densify_route=a.densify_route, merge_route=a.merge_route, sh_up_every=a.sh_up_every,
+                   importance_views=a.importance_views, importance_views_per_call=a.importance_views_per_call, densify=a.densify, fit_pose=a.fit_pose, stage_a_batch=a.stage_a_batch, stage_a_lambda_depth=a.stage_a_lambda_depth, stage_a_early_exit=a.stage_a_early_exit, stage_a_init=a.stage_a_init, densify_route=a.densify_route, merge_route=a.merge_route, sh_up_every=a.sh_up_every,
                    device_cameras=a.device_cameras, leaf_batch=a.leaf_batch)
     check_leaf_batch(cfg, local=a.local)
     if a.pose_lr is not None:

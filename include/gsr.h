@@ -148,6 +148,9 @@ typedef struct GsrForwardArgs {
 
 #define GSR_FWD_FLAG_RENDER_ONLY ((int64_t)1 << 14) /* GsrForwardOut::forward_flags of a render-only forward */
 
+#define GSR_FWD_FLAG_VIEWS ((int64_t)1 << 15)       /* GsrForwardOut::forward_flags of gsr_forward_views */
+#define GSR_MAX_VIEWS 16                            /* views of one gsr_forward_views call (= the models of a GsrBatch) */
+
 typedef struct GsrForwardOut {
     int64_t num_rendered; /* R: (tile, Gaussian) instances */
     void* binning;        /* pointer returned by alloc(GSR_ALLOC_BINNING); pass to gsr_backward */
@@ -367,6 +370,36 @@ size_t gsr_importance_scratch_bytes(int32_t N);
 int gsr_importance_accumulate(const GsrForwardArgs* fwd, const GsrForwardOut* out, float* acc /* [N,M,3], += */, void* scratch,
                               void* stream);
 
+/* ---- version 123: V VIEWS OF ONE MODEL in one launch chain, and the colour importance over them.
+ * gsr_forward_views is the full forward of ONE model under V cameras, 1 <= V <= GSR_MAX_VIEWS.  GsrForwardArgs is unchanged (the count
+ * travels beside it, as the retire table of gsr_forward_retire does); with Npad = 128 ceil(N / 128) -- the caller does not pad, any N >= 1:
+ *   viewmatrix / projmatrix / campos are arrays of V entries (16 / 16 / 3 floats); points_transform and sh_origin, when given, are arrays
+ *     of V entries (12 / 3 floats); W, H, tanfov*, bg, D and scale_modifier are shared;
+ *   record v Npad + n is Gaussian n under camera v; the records n >= N of each view are culled records (radius 0, no tile);
+ *   geom holds gsr_geom_bytes_views(N, V) bytes, image gsr_image_bytes_batched(W, H, V) bytes; radii and visible are [V Npad];
+ *   out_color and out_color_clamped are [V,3,H,W], out_depth and out_alpha [V,1,H,W].
+ * The preprocess reads the model's ONE set of parameter rows for every view (a GsrBatch would need V copies of them); behind it the chain
+ * is the one a GsrBatch with first_block = {0, nb, 2 nb, ...} takes: every view's image, radii and visibility bytes are bit-identical with
+ * rendering that view alone, and the list-building routes, the early instance count, capacity hints, speculative binning and the balanced
+ * placement behave as a batched forward of V images treats them.  V = 1 is served: one view through the same front.
+ * forward_flags carries GSR_FWD_FLAG_VIEWS: gsr_backward and the single-view gsr_importance_accumulate refuse such flags (GSR_ERR_ARG)
+ * before anything is enqueued -- there is no backward over a views forward.
+ * Refused before a device is touched, the rule in gsr_last_error(): V outside [1, 16]; a->batch set; `prepared`; `render_only`;
+ * V Npad >= 2^31 (GSR_ERR_RANGE).  colors_precomp IS served by the forward.
+ *
+ * gsr_importance_accumulate_views is gsr_importance_accumulate over such a forward: ONE walk of the V T tiles into S[V Npad] (float
+ * atomics, as in the single-view pass) and ONE finishing launch that, per Gaussian n, adds |basis_k(dir_{n,v})| gate S[v Npad + n] to
+ * acc[n,k,:] for v = 0 .. V-1 IN THAT ORDER -- the order in which V single-view calls add into acc -- with view v's campos,
+ * points_transform and sh_origin and the colour gates of record v Npad + n.  A view whose three sums are zero is skipped; a row whose sums
+ * are zero in every view is neither read nor written.  acc is [N,M,3] (the MODEL's rows); scratch holds
+ * gsr_importance_scratch_bytes_views(N, V) bytes.  Refused as by the single-view entry (colors_precomp, render-only flags), plus flags
+ * without GSR_FWD_FLAG_VIEWS and the V rules above. */
+size_t gsr_geom_bytes_views(int32_t N, int32_t V);
+int gsr_forward_views(const GsrForwardArgs* args, int32_t V, GsrForwardOut* out, void* stream);
+size_t gsr_importance_scratch_bytes_views(int32_t N, int32_t V);
+int gsr_importance_accumulate_views(const GsrForwardArgs* fwd, int32_t V, const GsrForwardOut* out, float* acc /* [N,M,3], += */,
+                                    void* scratch, void* stream);
+
 const char* gsr_last_error(void);
 /* 100 * major + minor.  110 (round 6): GsrForwardArgs ends with view_id, out_color_clamped, visible (appended in round 5 under
  * version 100: a caller compiled against a shorter struct must be rebuilt -- check gsr_version() >= 110 AND
@@ -383,7 +416,9 @@ const char* gsr_last_error(void);
  * 120: gsr_resize_plan, gsr_resize_apply, gsr_resize_scratch_bytes, gsr_resize_plan_bytes (GsrResizeTensor is new); no existing struct changes.
  * 121: gsr_select_scratch_bytes, gsr_select_smallest, gsr_merge_apply (GsrMergeTensor is new); no existing struct changes.
  * 122: gsr_resize_plan_batched, gsr_resize_apply_batched, gsr_resize_scratch_bytes_batched (GsrResizeBatch and GsrResizeBatchTensor are
- *      new); no existing struct or entry changes. */
+ *      new); no existing struct or entry changes.
+ * 123: gsr_forward_views, gsr_geom_bytes_views, gsr_importance_accumulate_views, gsr_importance_scratch_bytes_views
+ *      (GSR_FWD_FLAG_VIEWS); no struct changes. */
 int gsr_version(void);
 size_t gsr_struct_bytes(int32_t which); /* 0 GsrForwardArgs, 1 GsrBackwardArgs, 2 GsrForwardOut; anything else 0 */
 

@@ -147,6 +147,19 @@ def _register_fakes():
                 f(*lead, 4, 4) if need_projmatrix else none, f(*lead, 3) if need_campos else none,
                 f(*lead, 3, 4) if (need_points_transform and points_transform.numel() > 0) else none]
 
+    @torch.library.register_fake("gsr::rasterize_backward_views")
+    def _(means3D, sh, colors_precomp, opacities, scales, rotations, cov3D_precomp, sh_rest, viewmatrix, projmatrix, campos, bg,
+          points_transform, geom, image, binning, meta, grad_color, grad_depth, grad_alpha, image_height, image_width, tanfovx, tanfovy,
+          scale_modifier, sh_degree, raw_params, need_means2D, need_viewmatrix, need_projmatrix, need_campos, need_points_transform,
+          sh_origin=None):
+        # {d_means2D [V Npad,3], d_viewmatrix [V,4,4], d_projmatrix [V,4,4], d_campos [V,3], d_points_transform [V,3,4]}; empty = not wanted
+        f = lambda *s: means3D.new_empty(s, dtype=torch.float32)
+        none = f(0)
+        N, V = means3D.shape[0], viewmatrix.shape[0]
+        Npad = (N + 127) // 128 * 128
+        return [f(V * Npad, 3) if need_means2D else none, f(V, 4, 4) if need_viewmatrix else none, f(V, 4, 4) if need_projmatrix else none,
+                f(V, 3) if need_campos else none, f(V, 3, 4) if (need_points_transform and points_transform.numel() > 0) else none]
+
     @torch.library.register_fake("gsr::rasterize_backward_fused")
     def _(means3D, sh, sh_rest, opacities, scales, rotations, viewmatrix, projmatrix, campos, bg, points_transform, geom, image, binning,
           meta, grad_color, grad_depth, grad_alpha, image_height, image_width, tanfovx, tanfovy, scale_modifier, sh_degree,
@@ -166,6 +179,10 @@ def _register_fakes():
         return None
 
     @torch.library.register_fake("gsr::pose_step")
+    def _(delta, exp_avg, exp_avg_sq, d_xf, base, xf, lr, beta1, beta2, eps, step):
+        return None
+
+    @torch.library.register_fake("gsr::pose_step_many")
     def _(delta, exp_avg, exp_avg_sq, d_xf, base, xf, lr, beta1, beta2, eps, step):
         return None
 

@@ -126,6 +126,7 @@ EXPORTS = [
     "gsr_select_scratch_bytes", "gsr_select_smallest", "gsr_merge_apply",
     "gsr_resize_scratch_bytes_batched", "gsr_resize_plan_batched", "gsr_resize_apply_batched",
     "gsr_geom_bytes_views", "gsr_forward_views", "gsr_importance_scratch_bytes_views", "gsr_importance_accumulate_views",
+    "gsr_backward_scratch_bytes_views", "gsr_backward_views", "gsr_pose_step_many",
 ]
 GSR_FWD_FLAG_VIEWS, GSR_MAX_VIEWS = 1 << 15, 16     # version 123: V views of one model
 GSR_DEPTH_LOSS_L1, GSR_DEPTH_LOSS_INVARIANT = 0, 1
@@ -268,6 +269,13 @@ def load():
     lib.gsr_importance_accumulate_views.restype = C.c_int
     lib.gsr_importance_accumulate_views.argtypes = [C.POINTER(GsrForwardArgs), C.c_int32, C.POINTER(GsrForwardOut), C.c_void_p, C.c_void_p,
                                                     C.c_void_p]
+    # version 124: the frozen call over such a forward -- (args, V, stream); V pose steps in one launch
+    lib.gsr_backward_scratch_bytes_views.restype = C.c_size_t
+    lib.gsr_backward_scratch_bytes_views.argtypes = [C.c_int32, C.c_int32]
+    lib.gsr_backward_views.restype = C.c_int
+    lib.gsr_backward_views.argtypes = [C.POINTER(GsrBackwardArgs), C.c_int32, C.c_void_p]
+    lib.gsr_pose_step_many.restype = C.c_int
+    lib.gsr_pose_step_many.argtypes = [C.c_void_p] * 6 + [C.c_int32] + [C.c_float] * 4 + [C.c_int64, C.c_void_p]
     lib.gsr_mark_visible.restype = C.c_int
     lib.gsr_mark_visible.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.gsr_last_error.restype = C.c_char_p

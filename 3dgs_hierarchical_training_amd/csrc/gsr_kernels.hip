@@ -3477,7 +3477,12 @@ __device__ __forceinline__ void culled_handover(const PrepOut& po, int i, int ba
 // RETIRE TABLE (rt, with ADAM; GsrBackwardArgs::retired_at): a block of a model retired BEFORE this step issues none of its parameter, moment or
 // gradient-row streams -- it writes zero d_means2D rows, a zero camera partial (k_cam_reduce expects one from every block) and, with PREP,
 // culled hand-over records, and leaves.  A model retired AT this step (or earlier) gets culled hand-over records behind its update.
-template <int DEG, bool RAW, bool CAM, bool ADAM, int PREP, bool SHO = false, bool FROZEN = false>
+//
+// VIEWS (with FROZEN; gsr_backward_views): the blocks run over V views of ONE model, view_nb = ceil(N / 128) blocks each -- N is the model's
+// size, so the count needs no argument of its own.  `i` stays the model's row (parameters, N, the SH staging); the blend-gradient row, the
+// d_means2D row and the camera partial's block are the record's, io = i + v Npad.  A view's padding records (i >= N) read no parameter row,
+// add nothing to the block's partial and get a zero d_means2D row.
+template <int DEG, bool RAW, bool CAM, bool ADAM, int PREP, bool SHO = false, bool FROZEN = false, bool VIEWS = false>
 __global__ __launch_bounds__(kPreThreads) void k_preprocess_bwd(CamParams cp, int N, const float* means,
                                                                 const float* scales, const float* rots,
                                                                 const float* __restrict__ cov_pre, const float* shs,
@@ -3493,6 +3498,7 @@ __global__ __launch_bounds__(kPreThreads) void k_preprocess_bwd(CamParams cp, in
 {
     static_assert(!SHO || PREP < 0, "sh_origin is not served together with a next view");
     static_assert(!FROZEN || (CAM && !ADAM && PREP < 0 && !SHO), "the frozen variant: camera gradients, no Adam, no next view, no sh_origin");
+    static_assert(!VIEWS || FROZEN, "views of one model: the frozen variant only");
     constexpr int NC3 = 3 * (DEG + 1) * (DEG + 1);
     constexpr bool kStageSh = !(FROZEN && DEG == 0);   // (FROZEN at degree 0 touches no SH row)
     __shared__ float s_sh[kStageSh ? kPreThreads * kShStride : 1];
@@ -3504,14 +3510,20 @@ __global__ __launch_bounds__(kPreThreads) void k_preprocess_bwd(CamParams cp, in
     OwnMoments<4> om_rq;
     float own_g[11];                // their gradients: mean 3 | opacity 1 | scale 3 | rotation 4
     const int tid = threadIdx.x;
-    const int base = blockIdx.x * kPreThreads;
+    int row_ofs = 0, base_;   // VIEWS: row_ofs = v Npad, what separates a record from its model row (block-uniform)
+    if constexpr (VIEWS) {
+        select_view_of_model(cp, (int)blockIdx.x, (N + kPreThreads - 1) / kPreThreads, row_ofs);
+        base_ = (int)blockIdx.x * kPreThreads - row_ofs;
+    } else
+        base_ = blockIdx.x * kPreThreads;
+    const int base = base_;
     const int i = base + tid;
     const int nG = min(kPreThreads, N - base);
 #ifdef GSR_K9_TIMING
     unsigned long long k9t[8] = {0, 0, 0, 0, 0, 0, 0, 0}, k9t_last = __builtin_readcyclecounter();
     k9t[6] = k9t_last;   // start stamp (k9t[7] = end stamp)
 #endif
-    const int model = select_view(cp, (int)blockIdx.x);   // batched render: this block's model and its camera
+    const int model = select_view(cp, (int)blockIdx.x);   // batched render: this block's model and its camera (VIEWS: the host hands over B = 1)
     CamGrads cg;
     float xg[12];   // dL/d(points_transform) share of this thread
     if (CAM) {
@@ -3633,7 +3645,8 @@ __global__ __launch_bounds__(kPreThreads) void k_preprocess_bwd(CamParams cp, in
         // radius > 0 test, and the 48-byte splat record is not read by this kernel at all (the activated opacity the
         // sigmoid chain needs is recomputed from the logit exactly as the forward computed it).
         float4 g0 = e_g0, g1 = e_g1, g2 = e_g2;   // gx gy gA gB | gC gop gr gg | gb gz - -
-        if constexpr (!ADAM) load_ggrad(ggrad + (size_t)i * kGG, g0, g1, g2);
+        if constexpr (VIEWS) load_ggrad(ggrad + ((size_t)i + (size_t)row_ofs) * kGG, g0, g1, g2);   // (the record's row)
+        else if constexpr (!ADAM) load_ggrad(ggrad + (size_t)i * kGG, g0, g1, g2);
         const bool live = g0.x != 0.f || g0.y != 0.f || g0.z != 0.f || g0.w != 0.f || g1.x != 0.f || g1.y != 0.f || g1.z != 0.f ||
                           g1.w != 0.f || g2.x != 0.f || g2.y != 0.f;
         if (live) {
@@ -3728,6 +3741,10 @@ __global__ __launch_bounds__(kPreThreads) void k_preprocess_bwd(CamParams cp, in
         }
         K9_T(1);
         if constexpr (FROZEN) {   // the only per-Gaussian row of a frozen call, and only when somebody wants it
+            if constexpr (VIEWS) {
+                const size_t io = (size_t)i + (size_t)row_ofs;
+                if (d_means2d) { d_means2d[3 * io] = m2d[0]; d_means2d[3 * io + 1] = m2d[1]; d_means2d[3 * io + 2] = 0.f; }
+            } else
             if (d_means2d) { d_means2d[3 * (size_t)i] = m2d[0]; d_means2d[3 * (size_t)i + 1] = m2d[1]; d_means2d[3 * (size_t)i + 2] = 0.f; }
         } else {
         d_means2d[3 * (size_t)i] = m2d[0]; d_means2d[3 * (size_t)i + 1] = m2d[1]; d_means2d[3 * (size_t)i + 2] = 0.f;
@@ -3775,6 +3792,9 @@ __global__ __launch_bounds__(kPreThreads) void k_preprocess_bwd(CamParams cp, in
         }
         }
         }
+    } else if constexpr (VIEWS) {   // a view's padding record: no parameter row behind it, a zero row for whoever reads d_means2D whole
+        const size_t io = (size_t)i + (size_t)row_ofs;
+        if (d_means2d) { d_means2d[3 * io] = 0.f; d_means2d[3 * io + 1] = 0.f; d_means2d[3 * io + 2] = 0.f; }
     }
     K9_T(2);
     if (CAM) {
@@ -4346,7 +4366,7 @@ size_t gsr_prepared_bytes(int32_t N) { return prep_layout(N).bytes; }
 size_t gsr_prepared_radii_offset(int32_t N) { return prep_layout(N).radii; }
 int gsr_prepare_supported(int32_t M, int32_t D, int32_t raw_params) { return (raw_params && M == 16 && D >= 0 && D <= 3) ? 1 : 0; }
 const char* gsr_last_error(void) { return g_err; }
-int gsr_version(void) { return 123; }
+int gsr_version(void) { return 124; }
 size_t gsr_struct_bytes(int32_t which)
 {
     return which == 0 ? sizeof(GsrForwardArgs) : which == 1 ? sizeof(GsrBackwardArgs) : which == 2 ? sizeof(GsrForwardOut) : 0;
@@ -5117,7 +5137,10 @@ static int blend_bwd_resident(int has_da)
     return cached[has_da] = per_cu * cus;
 }
 
-int gsr_backward(const GsrBackwardArgs* a, void* stream_)
+// views > 0: gsr_backward_views, the frozen call over the output of a gsr_forward_views -- a->N is the MODEL's size and every rule of that entry
+// has been checked; the chain runs over N = views * Npad records as a batch of `views` images (as forward_impl), and only the per-Gaussian
+// kernel (k_preprocess_bwd<..., VIEWS>) knows that the records of all views share one set of parameter rows.
+static int backward_impl(const GsrBackwardArgs* a, void* stream_, int views)
 {
     CallTimer call_timer(g_bwd_calls, g_bwd_ns);
     hipStream_t st = (hipStream_t)stream_;
@@ -5125,16 +5148,23 @@ int gsr_backward(const GsrBackwardArgs* a, void* stream_)
     const Options opt = options_snapshot();
     if (a->forward_flags & GSR_FWD_FLAG_RENDER_ONLY)
         return fail(GSR_ERR_ARG, "gsr_backward: forward_flags come from a render-only forward, which keeps nothing a backward could read%s");
-    if (a->forward_flags & GSR_FWD_FLAG_VIEWS)
+    if (views == 0 && (a->forward_flags & GSR_FWD_FLAG_VIEWS))
         return fail(GSR_ERR_ARG, "gsr_backward: forward_flags come from a views forward (gsr_forward_views): a backward over views is not served%s");
     int rc = check_common(a->N, a->M, a->D, a->W, a->H);
     if (rc) return rc;
-    const int N = a->N, W = a->W, H = a->H;
+    const int view_nb = views > 0 ? (int)(views_npad(a->N) / kPreThreads) : 0;
+    const int N = views > 0 ? views * view_nb * kPreThreads : a->N, W = a->W, H = a->H;
     BatchDev bt;
-    rc = batch_dev(a->batch, N, H, bt);
-    if (rc) return rc;
+    if (views > 0) {
+        bt = BatchDev{};
+        bt.B = views;
+        for (int q = 0; q <= kMaxBatch; q++) bt.first_block[q] = std::min(q, views) * view_nb;
+    } else {
+        rc = batch_dev(a->batch, N, H, bt);
+        if (rc) return rc;
+    }
     const int NB = bt.B;
-    if (a->sh_origin && (!a->shs || NB > 1 || a->next_view))
+    if (a->sh_origin && (!a->shs || (NB > 1 && views == 0) || a->next_view))
         return fail(GSR_ERR_ARG, "sh_origin needs shs and is not served with a batch of B > 1 or a next_view%s");
     // which gradients the caller wants (GsrBackwardArgs, "frozen call"): decided and checked here, in front of the first launch or memset
     // of the call -- a refused call enqueues nothing
@@ -5367,6 +5397,13 @@ int gsr_backward(const GsrBackwardArgs* a, void* stream_)
     } while (0)
 #define GSR_PREB(DEG) GSR_PREB_SO(DEG, false)
 #define GSR_PREB_FROZEN(DEG) do { if (a->raw_params) GSR_PREB_SF(DEG, true, true, false, -1, false, true); else GSR_PREB_SF(DEG, false, true, false, -1, false, true); } while (0)
+    // the frozen call over views: the grid covers the V Npad records, the kernel gets the MODEL's size and finds a block's view from it
+#define GSR_PREB_VIEWS_(DEG, RAW)                                                                                                           \
+    hipLaunchKernelGGL((k_preprocess_bwd<DEG, RAW, true, false, -1, false, true, true>), dim3(grid), dim3(kPreThreads), 0, st, cp_views, a->N, \
+                       a->means3D, a->scales, a->rotations, a->cov3D_precomp, a->shs, a->shs_rest, a->opacities, ad, splat, gg,             \
+                       (float*)nullptr, a->d_means2D, (float*)nullptr, (float*)nullptr, (float*)nullptr, (float*)nullptr, (float*)nullptr,  \
+                       (float*)nullptr, (float*)nullptr, cam_partial, po, ds, (const float*)nullptr, rt)
+#define GSR_PREB_VIEWS(DEG) do { if (a->raw_params) GSR_PREB_VIEWS_(DEG, true); else GSR_PREB_VIEWS_(DEG, false); } while (0)
 #define GSR_PREB_NEXT(DEG, NDEG) do { if (want_cam) GSR_PREB_(DEG, true, true, true, NDEG); else GSR_PREB_(DEG, true, false, true, NDEG); } while (0)
 #define GSR_PRE_TAIL(NDEG)                                                                                                               \
     hipLaunchKernelGGL((k_preprocess<NDEG, true>), dim3(1), dim3(kPreThreads), 0, st, po.cp, N, a->means3D, a->scales, a->rotations,       \
@@ -5401,6 +5438,17 @@ int gsr_backward(const GsrBackwardArgs* a, void* stream_)
             // the colour's share of dL/dmean reaches the camera and the transform only where the colour depends on the POSED mean: not at
             // degree 0, not with colors_precomp and not with sh_origin (whose share goes to d_means3D alone) -- those run the degree-0 variant
             g_frozen_bwd_calls.fetch_add(1, std::memory_order_relaxed);   // (gsr_get_counter "frozen_backward_calls": which route a caller took)
+            if (views > 0) {
+                CamParams cp_views = cp;   // (the kernel takes a block's view from its number: no table of models for select_view)
+                cp_views.bt = BatchDev{};
+                cp_views.bt.B = 1;
+                switch ((a->shs && !a->sh_origin) ? a->D : 0) {
+                    case 0: GSR_PREB_VIEWS(0); break;
+                    case 1: GSR_PREB_VIEWS(1); break;
+                    case 2: GSR_PREB_VIEWS(2); break;
+                    default: GSR_PREB_VIEWS(3); break;
+                }
+            } else
             switch ((a->shs && !a->sh_origin) ? a->D : 0) {
                 case 0: GSR_PREB_FROZEN(0); break;
                 case 1: GSR_PREB_FROZEN(1); break;
@@ -5425,6 +5473,8 @@ int gsr_backward(const GsrBackwardArgs* a, void* stream_)
     }
 #undef GSR_PRE_TAIL
 #undef GSR_PREB_NEXT
+#undef GSR_PREB_VIEWS
+#undef GSR_PREB_VIEWS_
 #undef GSR_PREB_FROZEN
 #undef GSR_PREB
 #undef GSR_PREB_SO
@@ -5436,6 +5486,40 @@ int gsr_backward(const GsrBackwardArgs* a, void* stream_)
                            a->d_points_transform, bt);
     GSR_HIP(hipGetLastError());
     return GSR_OK;
+}
+
+int gsr_backward(const GsrBackwardArgs* a, void* stream_) { return backward_impl(a, stream_, 0); }
+
+// ---- the frozen call over V views of one model, behind gsr_forward_views (include/gsr.h) -------------------------------------------
+size_t gsr_backward_scratch_bytes_views(int32_t N, int32_t V)
+{
+    const int64_t rec = (int64_t)(V > 0 ? V : 1) * views_npad(N > 0 ? N : 1);
+    return rec < ((int64_t)1 << 31) ? gsr_backward_scratch_bytes((int32_t)rec) : 0;
+}
+
+int gsr_backward_views(const GsrBackwardArgs* a, int32_t V, void* stream_)
+{
+    if (!a) return fail(GSR_ERR_ARG, "null args%s");
+    if (V < 1 || V > GSR_MAX_VIEWS) return fail(GSR_ERR_ARG, "backward over views: 1..16 views expected%s");
+    if (a->N < 1) return fail(GSR_ERR_ARG, "backward over views: at least one Gaussian expected%s");
+    if ((int64_t)V * views_npad(a->N) >= ((int64_t)1 << 31)) return fail(GSR_ERR_RANGE, "backward over views: V * Npad must stay below 2^31 records%s");
+    if (a->forward_flags & GSR_FWD_FLAG_RENDER_ONLY)
+        return fail(GSR_ERR_ARG, "backward over views: forward_flags come from a render-only forward, which keeps nothing a backward could read%s");
+    if (!(a->forward_flags & GSR_FWD_FLAG_VIEWS))
+        return fail(GSR_ERR_ARG, "backward over views: forward_flags do not come from gsr_forward_views%s");
+    if (a->fused_adam || a->d_means3D || a->d_opacities || a->d_colors_precomp || a->d_shs || a->d_shs_rest || a->d_scales || a->d_rotations ||
+        a->d_cov3D_precomp)
+        return fail(GSR_ERR_ARG, "a backward over views serves the frozen call only: no per-Gaussian gradient pointer and no fused_adam (a full "
+                                 "backward over views is not served)%s");
+    if (a->next_view || a->prepared_out) return fail(GSR_ERR_ARG, "backward over views: next_view / prepared_out are not served%s");
+    if (a->densify_stats) return fail(GSR_ERR_ARG, "backward over views: densify_stats are not served%s");
+    if (a->retired_at) return fail(GSR_ERR_ARG, "backward over views: retired_at (a retire table) is not served%s");
+    if (a->batch) return fail(GSR_ERR_ARG, "backward over views: not served with a batch (views of a GsrBatch are out of scope)%s");
+    if (!a->d_viewmatrix && !a->d_projmatrix && !a->d_campos && !a->d_points_transform)
+        return fail(GSR_ERR_ARG, "backward over views: no gradient output -- d_viewmatrix, d_projmatrix, d_campos and d_points_transform are all NULL%s");
+    if (!a->geom || !a->image || !a->binning || !a->scratch) return fail(GSR_ERR_ARG, "backward over views: missing workspace pointer%s");
+    if (a->H > 0 && (long long)V * ((a->H + kTile - 1) / kTile) > 4095) return fail(GSR_ERR_RANGE, "backward over views: more than 4095 tile rows in total%s");
+    return backward_impl(a, stream_, V);
 }
 
 // ---- merge-time colour importance of one view, from the forward alone (include/gsr.h) --------------------------------------------

@@ -189,10 +189,21 @@ __device__ inline void pose_grad_and_adam(double* d /*6, lane-uniform copy*/, co
     for (int k = 0; k < 6; k++) d[k] = (double)s_g[k];
 }
 
+// MANY (gsr_pose_step_many): P poses, one workgroup each -- pose p at p * 6 / p * 12 floats; the poses share nothing but the hyper-parameters.
+// One statement of the step for both, so that a pose gets the same bits from either; MANY = false is the kernel as it was.
+template <bool MANY = false>
 __global__ __launch_bounds__(64) void k_pose_adam(float* __restrict__ delta, float* __restrict__ m, float* __restrict__ v,
                                                    const float* __restrict__ d_xf, const float* __restrict__ base, float* __restrict__ xf_out,
                                                    float lr, float b1, float b2, float eps, float bc1, float bc2_sqrt, int do_step)
 {
+    if constexpr (MANY) {
+        const size_t p = blockIdx.x;
+        delta += 6 * p; xf_out += 12 * p;
+        if (m) m += 6 * p;
+        if (v) v += 6 * p;
+        if (d_xf) d_xf += 12 * p;
+        if (base) base += 12 * p;
+    }
     __shared__ double s_M[12][12];
     __shared__ float s_g[6];
     double d[6], B[12], G[12];
@@ -213,6 +224,19 @@ __global__ __launch_bounds__(64) void k_pose_adam(float* __restrict__ delta, flo
 
 }  // namespace gsr
 
+extern "C" int gsr_pose_step_many(float* delta6, float* exp_avg6, float* exp_avg_sq6, const float* d_points_transform12, const float* base12,
+                                  float* points_transform_out12, int32_t P, float lr, float beta1, float beta2, float eps, int64_t step,
+                                  void* stream)
+{
+    if (!delta6 || !points_transform_out12 || step < 0 || P < 1 || P > 65535) return GSR_ERR_ARG;
+    if (step > 0 && (!exp_avg6 || !exp_avg_sq6 || !d_points_transform12)) return GSR_ERR_ARG;
+    const float bc1 = step > 0 ? (float)(1.0 - pow((double)beta1, (double)step)) : 1.f;
+    const float bc2s = step > 0 ? (float)sqrt(1.0 - pow((double)beta2, (double)step)) : 1.f;
+    hipLaunchKernelGGL(gsr::k_pose_adam<true>, dim3(P), dim3(64), 0, (hipStream_t)stream, delta6, exp_avg6, exp_avg_sq6, d_points_transform12,
+                       base12, points_transform_out12, lr, beta1, beta2, eps, bc1, bc2s, step > 0 ? 1 : 0);
+    return hipGetLastError() == hipSuccess ? GSR_OK : GSR_ERR_HIP;
+}
+
 extern "C" int gsr_pose_step(float* delta6, float* exp_avg6, float* exp_avg_sq6, const float* d_points_transform12, const float* base12,
                              float* points_transform_out12, float lr, float beta1, float beta2, float eps, int64_t step, void* stream)
 {
@@ -220,7 +244,7 @@ extern "C" int gsr_pose_step(float* delta6, float* exp_avg6, float* exp_avg_sq6,
     if (step > 0 && (!exp_avg6 || !exp_avg_sq6 || !d_points_transform12)) return GSR_ERR_ARG;
     const float bc1 = step > 0 ? (float)(1.0 - pow((double)beta1, (double)step)) : 1.f;
     const float bc2s = step > 0 ? (float)sqrt(1.0 - pow((double)beta2, (double)step)) : 1.f;
-    hipLaunchKernelGGL(gsr::k_pose_adam, dim3(1), dim3(64), 0, (hipStream_t)stream, delta6, exp_avg6, exp_avg_sq6, d_points_transform12, base12,
+    hipLaunchKernelGGL(gsr::k_pose_adam<false>, dim3(1), dim3(64), 0, (hipStream_t)stream, delta6, exp_avg6, exp_avg_sq6, d_points_transform12, base12,
                        points_transform_out12, lr, beta1, beta2, eps, bc1, bc2s, step > 0 ? 1 : 0);
     return hipGetLastError() == hipSuccess ? GSR_OK : GSR_ERR_HIP;
 }

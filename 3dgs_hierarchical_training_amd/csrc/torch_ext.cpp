@@ -10,6 +10,7 @@
 //   gsr::rasterize_forward    -> gsr_forward   (buffers come from at::empty inside the allocator callback: no Python)
 //   gsr::rasterize_backward   -> gsr_backward
 //   gsr::rasterize_backward_frozen -> gsr_backward, the frozen call: camera / points_transform gradients alone
+//   gsr::rasterize_backward_views  -> gsr_backward_views, that call over the output of rasterize_forward_views (V views of one model)
 //   gsr::rasterize_backward_fused  -> gsr_backward with the in-kernel Adam step (parameters / moments updated in place)
 //   gsr::render               -> gsr_forward, the render-only call: an image, nothing kept, no autograd
 //   gsr::mark_visible         -> gsr_mark_visible
@@ -22,6 +23,7 @@
 //   gsr::batch_retire         -> gsr_batch_retire (the per-model exit decision of a launch chain, written into the retire table)
 //   gsr::retire_attach        attaches a retire table + step to the NEXT gsr::rasterize / render / importance_accumulate of the calling thread
 //   gsr::pose_step            -> gsr_pose_step (stage A: tangent-space Adam + exponential map between two renders)
+//   gsr::pose_step_many       -> gsr_pose_step_many (P such steps in one launch)
 //   gsr::knn_mean_dist2       -> gsr_knn_mean_dist2
 //   gsr::depth_to_points      -> gsr_depth_to_points (a depth map's pixels un-projected, colours gathered beside them)
 //   gsr::voxel_down_sample    -> gsr_voxel_down_sample (voxel-grid means; its read of `meta` is the one host synchronisation)
@@ -295,7 +297,7 @@ std::vector<Tensor> importance_accumulate(
 // gsr::rasterize_forward_views -> gsr_forward_views (include/gsr.h, version 123): ONE model under V cameras in one launch chain.
 // viewmatrix / projmatrix are [V,4,4], campos [V,3], points_transform [V,3,4] and sh_origin [V,3] when given; V = viewmatrix.size(0).
 // Returns {color [V,3,H,W], radii [V Npad], depth, alpha [V,1,H,W], geom, image, binning, meta, clamped, visible [V Npad]}; extras as in
-// rasterize_forward.  No autograd: there is no backward over a views forward.
+// rasterize_forward.  No autograd key: rasterizer.rasterize_views pairs it with rasterize_backward_views (the frozen call over views).
 std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> rasterize_forward_views(
     const Tensor& means3D_, const Tensor& sh_, const Tensor& colors_, const Tensor& opacities_, const Tensor& scales_,
     const Tensor& rotations_, const Tensor& cov3D_, const Tensor& sh_rest_, const Tensor& viewmatrix_, const Tensor& projmatrix_,
@@ -512,6 +514,60 @@ std::vector<Tensor> rasterize_backward_frozen(
     const RetirePending retire = take_retire();   // (refused by the library: no update to gate on the frozen backward)
     if (retire.table.defined()) { a.retired_at = retire.table.data_ptr<int32_t>(); a.retire_step = retire.step; }
     check(gsr_backward(&a, c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream()), "gsr_backward");
+    return {d_means2D, d_vm, d_pm, d_cp, d_xf};
+}
+
+// gsr::rasterize_backward_views -> gsr_backward_views (include/gsr.h, version 124): the frozen call over the output of a
+// rasterize_forward_views -- geom / image / binning / meta are that op's.  viewmatrix / projmatrix [V,4,4], campos [V,3], points_transform
+// [V,3,4] and sh_origin [V,3] as in the forward; grad_color [V,3,H,W], grad_depth / grad_alpha [V,1,H,W] (or empty).  Returns
+// {d_means2D [V Npad,3], d_viewmatrix [V,4,4], d_projmatrix [V,4,4], d_campos [V,3], d_points_transform [V,3,4]}, an empty tensor where
+// the output is not wanted.  No autograd key: rasterizer.rasterize_views is the autograd node over the two ops.
+std::vector<Tensor> rasterize_backward_views(
+    const Tensor& means3D_, const Tensor& sh_, const Tensor& colors_, const Tensor& opac_, const Tensor& scales_, const Tensor& rots_,
+    const Tensor& cov_, const Tensor& rest_, const Tensor& vm_, const Tensor& pm_, const Tensor& campos_, const Tensor& bg_, const Tensor& xf_,
+    const Tensor& geom, const Tensor& image, const Tensor& binning, const Tensor& meta, const Tensor& grad_color, const Tensor& grad_depth,
+    const Tensor& grad_alpha, int64_t H, int64_t W, double tanfovx, double tanfovy, double scale_modifier, int64_t sh_degree,
+    bool raw_params, bool need_means2D, bool need_vm, bool need_pm, bool need_campos, bool need_xf, const c10::optional<Tensor>& sh_origin_)
+{
+    TORCH_CHECK(means3D_.is_cuda(), "rasterize_backward_views: tensors must be on a ROCm/HIP device (no CPU fallback)");
+    TORCH_CHECK(!take_retire().table.defined(), "rasterize_backward_views: a retire table (retired_at) is not served with views");
+    TORCH_CHECK(vm_.dim() == 3 && vm_.size(1) == 4 && vm_.size(2) == 4, "views: viewmatrix must be [V,4,4]");
+    const int64_t V = vm_.size(0);
+    TORCH_CHECK(V >= 1 && V <= GSR_MAX_VIEWS, "views: 1..16 views expected");
+    const c10::hip::HIPGuardMasqueradingAsCUDA guard(means3D_.device());
+    BwdCommon b{f32c(means3D_), f32c(sh_), f32c(colors_), f32c(opac_), f32c(scales_), f32c(rots_), f32c(cov_), f32c(rest_), f32c(vm_), f32c(pm_),
+                f32c(campos_), f32c(bg_), f32c(xf_), f32c(grad_color), f32c(grad_depth), f32c(grad_alpha)};
+    Tensor sh_origin;
+    if (sh_origin_.has_value() && sh_origin_->defined()) {
+        TORCH_CHECK(sh_origin_->numel() == 3 * V && sh_origin_->is_cuda(), "views: sh_origin must be [V,3] on the device of the model");
+        sh_origin = f32c(sh_origin_->reshape({V, 3}));
+    }
+    TORCH_CHECK(b.pm.numel() == 16 * V && (!has(b.campos) || b.campos.numel() == 3 * V) && (!has(b.xf) || b.xf.numel() == 12 * V),
+                "views: projmatrix must be [V,4,4], campos [V,3], points_transform [V,3,4]");
+    TORCH_CHECK((!has(b.gc) || b.gc.numel() == V * 3 * H * W) && (!has(b.gd) || b.gd.numel() == V * H * W) && (!has(b.ga) || b.ga.numel() == V * H * W),
+                "views: grad_color must be [V,3,H,W], grad_depth and grad_alpha [V,1,H,W]");
+    TORCH_CHECK(meta.defined() && !meta.is_cuda() && meta.scalar_type() == at::kLong && meta.numel() == 3, "views: meta must be the forward's");
+    const int64_t N = b.means3D.size(0);
+    TORCH_CHECK(N >= 1, "views: at least one Gaussian expected");
+    const int64_t Npad = (N + 127) / 128 * 128;
+    TORCH_CHECK(V * Npad < ((int64_t)1 << 31), "views: V * Npad must stay below 2^31 records");
+    const auto fo = b.means3D.options().dtype(at::kFloat);
+    const Tensor none = at::empty({0}, fo);
+    const bool want_xf = need_xf && has(b.xf);
+    TORCH_CHECK(need_vm || need_pm || need_campos || want_xf,
+                "rasterize_backward_views: no camera or points_transform gradient is wanted -- nothing to compute");
+    Tensor d_means2D = need_means2D ? at::empty({V * Npad, 3}, fo) : none;
+    Tensor d_vm = need_vm ? at::empty({V, 4, 4}, fo) : none, d_pm = need_pm ? at::empty({V, 4, 4}, fo) : none;
+    Tensor d_cp = need_campos ? at::empty({V, 3}, fo) : none;
+    Tensor d_xf = want_xf ? at::zeros({V, 3, 4}, fo) : none;
+    Tensor scratch = at::empty({(int64_t)gsr_backward_scratch_bytes_views((int32_t)N, (int32_t)V)}, b.means3D.options().dtype(at::kByte));
+    GsrBackwardArgs a{};
+    fill_backward_args(a, b, geom, image, binning, meta, H, W, tanfovx, tanfovy, scale_modifier, sh_degree, raw_params);
+    a.sh_origin = fp(sh_origin);
+    a.d_means2D = fpm(d_means2D);
+    a.d_viewmatrix = fpm(d_vm); a.d_projmatrix = fpm(d_pm); a.d_campos = fpm(d_cp); a.d_points_transform = fpm(d_xf);
+    a.scratch = scratch.data_ptr();
+    check(gsr_backward_views(&a, (int32_t)V, c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream()), "gsr_backward_views");
     return {d_means2D, d_vm, d_pm, d_cp, d_xf};
 }
 
@@ -1222,6 +1278,28 @@ void pose_step(Tensor delta, Tensor exp_avg, Tensor exp_avg_sq, const Tensor& d_
     torch::autograd::impl::bump_version(delta);
 }
 
+// pose_step for P poses in ONE launch (gsr_pose_step_many): delta / exp_avg / exp_avg_sq [P,6], d_xf [P,3,4] (what rasterize_backward_views
+// returns for points_transform), base [P,3,4] or empty (identity), xf [P,3,4] -- the tensor the next rasterize_forward_views reads.
+void pose_step_many(Tensor delta, Tensor exp_avg, Tensor exp_avg_sq, const Tensor& d_xf, const Tensor& base, Tensor xf, double lr,
+                    double beta1, double beta2, double eps, int64_t step)
+{
+    TORCH_CHECK(delta.is_cuda(), "pose_step_many: tensors must be on a ROCm/HIP device (no CPU fallback)");
+    const c10::hip::HIPGuardMasqueradingAsCUDA guard(delta.device());
+    TORCH_CHECK(delta.dim() == 2 && delta.size(1) == 6 && delta.size(0) >= 1, "pose_step_many: delta must be [P,6]");
+    const int64_t P = delta.size(0);
+    auto ok6 = [P](const Tensor& t) { return t.is_contiguous() && t.scalar_type() == at::kFloat && t.numel() == 6 * P; };
+    TORCH_CHECK(ok6(delta) && (step == 0 || (ok6(exp_avg) && ok6(exp_avg_sq))), "pose_step_many: delta / moments must be contiguous float32 [P,6]");
+    TORCH_CHECK(xf.is_contiguous() && xf.scalar_type() == at::kFloat && xf.numel() == 12 * P, "pose_step_many: xf must be contiguous float32 [P,3,4]");
+    Tensor g = has(d_xf) ? f32c(d_xf) : d_xf, b = has(base) ? f32c(base) : base;
+    TORCH_CHECK(step == 0 || (has(g) && g.numel() == 12 * P), "pose_step_many: d_xf must hold dL/dM of every pose ([P,3,4])");
+    TORCH_CHECK(!has(b) || b.numel() == 12 * P, "pose_step_many: base must be [P,3,4]");
+    check(gsr_pose_step_many(delta.data_ptr<float>(), step ? exp_avg.data_ptr<float>() : nullptr, step ? exp_avg_sq.data_ptr<float>() : nullptr,
+                             fp(g), fp(b), xf.data_ptr<float>(), (int32_t)P, (float)lr, (float)beta1, (float)beta2, (float)eps, step,
+                             c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream()), "gsr_pose_step_many");
+    torch::autograd::impl::bump_version(xf);   // (as pose_step)
+    torch::autograd::impl::bump_version(delta);
+}
+
 // The pose matrix as an autograd node (round 6; what gsr_autopatch puts where the unmodified trainer evaluates `P[k].retr()`,
 // /root/reference/scene/gaussian_model_ht.py:135-148): M = Exp(delta) * base as a [3,4] tensor from the pose's six tangent numbers,
 // one one-wave kernel forward (gsr_pose_step with step 0), one backward (gsr_pose_grad: dL/dM -> dL/d(delta)); `delta` keeps its own
@@ -1751,6 +1829,12 @@ TORCH_LIBRARY(gsr, m)
           "int image_height, int image_width, float tanfovx, float tanfovy, float scale_modifier, int sh_degree, bool raw_params, "
           "bool need_means2D, bool need_viewmatrix, bool need_projmatrix, bool need_campos, bool need_points_transform, int[] batch_first_block, "
           "Tensor? sh_origin=None) -> Tensor[]");
+    m.def("rasterize_backward_views(Tensor means3D, Tensor sh, Tensor colors_precomp, Tensor opacities, Tensor scales, Tensor rotations, "
+          "Tensor cov3D_precomp, Tensor sh_rest, Tensor viewmatrix, Tensor projmatrix, Tensor campos, Tensor bg, Tensor points_transform, "
+          "Tensor geom, Tensor image, Tensor binning, Tensor meta, Tensor grad_color, Tensor grad_depth, Tensor grad_alpha, "
+          "int image_height, int image_width, float tanfovx, float tanfovy, float scale_modifier, int sh_degree, bool raw_params, "
+          "bool need_means2D, bool need_viewmatrix, bool need_projmatrix, bool need_campos, bool need_points_transform, "
+          "Tensor? sh_origin=None) -> Tensor[]");
     m.def("rasterize_backward_fused(Tensor(a!) means3D, Tensor(b!) sh, Tensor(c!) sh_rest, Tensor(d!) opacities, Tensor(e!) scales, "
           "Tensor(f!) rotations, Tensor viewmatrix, Tensor projmatrix, Tensor campos, Tensor bg, Tensor points_transform, Tensor geom, "
           "Tensor image, Tensor binning, Tensor meta, Tensor grad_color, Tensor grad_depth, Tensor grad_alpha, int image_height, "
@@ -1801,6 +1885,8 @@ TORCH_LIBRARY(gsr, m)
           "float beta2, float eps, int step) -> ()");
     m.def("pose_step(Tensor(a!) delta, Tensor(b!) exp_avg, Tensor(c!) exp_avg_sq, Tensor d_xf, Tensor base, Tensor(d!) xf, float lr, "
           "float beta1, float beta2, float eps, int step) -> ()");
+    m.def("pose_step_many(Tensor(a!) delta, Tensor(b!) exp_avg, Tensor(c!) exp_avg_sq, Tensor d_xf, Tensor base, Tensor(d!) xf, float lr, "
+          "float beta1, float beta2, float eps, int step) -> ()");
     m.def("pose_step_camera(Tensor(a!) delta, Tensor(b!) exp_avg, Tensor(c!) exp_avg_sq, Tensor d_viewmatrix, Tensor d_projmatrix, "
           "Tensor d_campos, Tensor projection_T, Tensor base, Tensor(d!) viewmatrix, Tensor(e!) projmatrix, Tensor(f!) campos, float lr, "
           "float beta1, float beta2, float eps, int step) -> ()");
@@ -1836,6 +1922,7 @@ TORCH_LIBRARY_IMPL(gsr, CUDA, m)   // the dispatch key of HIP tensors on a ROCm 
     m.impl("rasterize_backward", &rasterize_backward);
     m.impl("rasterize_backward_fused", &rasterize_backward_fused);
     m.impl("rasterize_backward_frozen", &rasterize_backward_frozen);
+    m.impl("rasterize_backward_views", &rasterize_backward_views);
     m.impl("render", &render);
     m.impl("importance_accumulate", &importance_accumulate);
     m.impl("importance_pass", &importance_pass);
@@ -1846,6 +1933,7 @@ TORCH_LIBRARY_IMPL(gsr, CUDA, m)   // the dispatch key of HIP tensors on a ROCm 
     m.impl("photometric_loss_backward", &photometric_loss_backward);
     m.impl("adam_step", &adam_step);
     m.impl("pose_step", &pose_step);
+    m.impl("pose_step_many", &pose_step_many);
     m.impl("pose_step_camera", &pose_step_camera);
     m.impl("pose_matrix_forward", &pose_matrix_forward);
     m.impl("pose_matrix_backward", &pose_matrix_backward);

@@ -828,7 +828,7 @@ def forward_views(means3D, sh, opacities, scales, rotations, view_settings, sh_r
     preprocess reads the model's one set of parameter rows for every view, behind it the chain is a batched forward's.
     view_settings: what batched.batch_settings returns for the V settings (cameras [V,4,4], [V,4,4], [V,3]; image size, field of view,
     background, degree and scale modifier shared); points_transform [V,3,4] / [V,4,4] and sh_origin [V,3] are per view.  No autograd --
-    there is no backward over a views forward -- and inputs are detached.  extras: bit 0 = the clamped colour, bit 1 = the visibility
+    rasterize_views is the node with a backward (the frozen call over views) -- and inputs are detached.  extras: bit 0 = the clamped colour, bit 1 = the visibility
     bytes.  Returns (color [V,3,H,W], radii [V,N], depth [V,1,H,W], alpha [V,1,H,W], clamped [V,3,H,W] | None, visible [V,N] | None);
     every view's outputs are bit-identical with rendering that view alone."""
     V, vm, pm, cp, xf, sh_origin = _views_inputs("forward_views", means3D, view_settings, points_transform, sh_origin, sh)
@@ -885,6 +885,112 @@ def importance_accumulate_views(acc, means3D, sh, opacities, scales, rotations, 
             L.check(lib.gsr_importance_accumulate_views(C.byref(f.a), V, C.byref(f.out), acc.data_ptr(), scratch.data_ptr(), C.c_void_p(stream)),
                     "gsr_importance_accumulate_views")
         return f.color, rows(f.radii), f.depth, f.alpha
+
+
+class _ViewsCall:
+    """What one rasterize_views call carries past autograd's tensor arguments: the frozen model's (detached) tensors, the settings, the
+    device copies of the cameras and, after the forward, what the backward needs of it."""
+    __slots__ = ("params", "rs", "raw_params", "V", "vm", "pm", "cp", "xf", "sh_origin", "xf_shape", "ext", "ctypes")
+
+
+class _RasterizeViews(torch.autograd.Function):
+    """rasterize_forward_views + rasterize_backward_views (gsr_forward_views + gsr_backward_views over ctypes) as one autograd node: the
+    tensor inputs are the cameras and the transforms, the only things a backward over views differentiates."""
+
+    @staticmethod
+    def forward(ctx, viewmatrix, projmatrix, campos, points_transform, call):
+        means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, sh_rest = call.params
+        rs, V = call.rs, call.V
+        dev = means3D.device
+        if not E.use_ctypes():
+            ops = E.load()
+            e = _e(dev)
+            pick = lambda t: e if (t is None or t.numel() == 0) else t
+            call.ext = [pick(means3D), pick(sh), pick(colors_precomp), pick(opacities), pick(scales), pick(rotations), pick(cov3Ds_precomp),
+                        pick(sh_rest), call.vm, call.pm, call.cp, rs.bg.detach().to(dev), pick(call.xf)]
+            color, radii, depth, alpha, geom, image, binning, meta, _cl, _vis = ops.rasterize_forward_views(
+                *call.ext, int(rs.image_height), int(rs.image_width), float(rs.tanfovx), float(rs.tanfovy), float(rs.scale_modifier),
+                int(rs.sh_degree), bool(call.raw_params), 0, call.sh_origin)
+            call.ext += [geom, image, binning, meta]
+        else:
+            f = _ctypes_forward_views(means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, rs, sh_rest, call.raw_params, V,
+                                      call.vm, call.pm, call.cp, call.xf, call.sh_origin, 0)
+            call.ctypes = f
+            color, radii, depth, alpha = f.color, f.radii, f.depth, f.alpha
+        ctx.call = call
+        ctx.mark_non_differentiable(radii)
+        ctx.set_materialize_grads(False)   # unused depth / alpha outputs arrive as None
+        return color, radii, depth, alpha
+
+    @staticmethod
+    def backward(ctx, grad_color, grad_radii, grad_depth, grad_alpha):
+        call = ctx.call
+        if grad_color is None and grad_depth is None and grad_alpha is None:
+            return (None,) * 5
+        rs, V = call.rs, call.V
+        need_vm, need_pm, need_cp, need_xf = ctx.needs_input_grad[:4]
+        dev = call.vm.device
+        if call.ext is not None:
+            ops = E.load()
+            e = _e(dev)
+            g = lambda t: e if t is None else t
+            _m2d, d_vm, d_pm, d_cp, d_xf = ops.rasterize_backward_views(
+                *call.ext, g(grad_color), g(grad_depth), g(grad_alpha), int(rs.image_height), int(rs.image_width), float(rs.tanfovx),
+                float(rs.tanfovy), float(rs.scale_modifier), int(rs.sh_degree), bool(call.raw_params), False, bool(need_vm), bool(need_pm),
+                bool(need_cp), bool(need_xf), call.sh_origin)
+        else:
+            lib = L.load()
+            f = call.ctypes
+            grad_color, grad_depth, grad_alpha = _f32c(grad_color), _f32c(grad_depth), _f32c(grad_alpha)
+            new = lambda *s: torch.zeros(s, dtype=torch.float32, device=dev)
+            d_vm, d_pm = (new(V, 4, 4) if need_vm else None), (new(V, 4, 4) if need_pm else None)
+            d_cp, d_xf = (new(V, 3) if need_cp else None), (new(V, 3, 4) if need_xf else None)
+            scratch = torch.empty(lib.gsr_backward_scratch_bytes_views(f.N, V), dtype=torch.uint8, device=dev)
+            a = L.GsrBackwardArgs()
+            for name in ("N", "M", "D", "W", "H", "scale_modifier", "tanfovx", "tanfovy", "means3D", "scales", "rotations", "cov3D_precomp",
+                         "opacities", "shs", "colors_precomp", "viewmatrix", "projmatrix", "campos", "bg", "geom", "image", "shs_rest",
+                         "raw_params", "points_transform", "sh_origin"):
+                setattr(a, name, getattr(f.a, name))
+            a.binning, a.num_rendered = f.out.binning, f.out.num_rendered
+            a.binning_capacity, a.forward_flags = f.out.binning_capacity, f.out.forward_flags
+            a.grad_color, a.grad_depth, a.grad_alpha = _ptr(grad_color), _ptr(grad_depth), _ptr(grad_alpha)
+            a.d_viewmatrix, a.d_projmatrix, a.d_campos, a.d_points_transform = _ptr(d_vm), _ptr(d_pm), _ptr(d_cp), _ptr(d_xf)
+            a.scratch = scratch.data_ptr()
+            with torch.cuda.device(dev):
+                stream = torch.cuda.current_stream(dev).cuda_stream
+                L.check(lib.gsr_backward_views(C.byref(a), V, C.c_void_p(stream)), "gsr_backward_views")
+        if need_xf and call.xf_shape[1] == 4:     # a [V,4,4] input: the last row takes no part in the render
+            d_xf = torch.cat([d_xf, torch.zeros((V, 1, 4), dtype=torch.float32, device=dev)], dim=1)
+        return (d_vm if need_vm else None, d_pm if need_pm else None, d_cp if need_cp else None, d_xf if need_xf else None, None)
+
+
+def rasterize_views(means3D, sh, opacities, scales, rotations, view_settings, sh_rest=None, raw_params=False, cov3Ds_precomp=None,
+                    colors_precomp=None, points_transform=None, sh_origin=None):
+    """ONE frozen model under V cameras in one launch chain, WITH a backward (include/gsr.h gsr_forward_views + gsr_backward_views): a
+    torch.autograd.Function over torch.ops.gsr.rasterize_forward_views and rasterize_backward_views.  Gradients reach points_transform
+    ([V,3,4] or [V,4,4]) and those of view_settings.viewmatrix / projmatrix / campos that require grad -- per view, nothing is summed
+    across views.  The model's tensors take no gradient: only the frozen call is served over views.  Arguments as in forward_views.
+    Returns (color [V,3,H,W], radii [V,N], depth [V,1,H,W], alpha [V,1,H,W]).  Raises RuntimeError before a device is touched when a
+    parameter tensor requires grad or nothing differentiable does."""
+    rs = view_settings
+    params = (means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, sh_rest)
+    if any(torch.is_tensor(t) and t.requires_grad for t in params):
+        raise RuntimeError("rasterize_views: a parameter tensor requires grad, and only the frozen call is served over views (camera and "
+                           "points_transform gradients; a full backward over views is not served) -- detach the model")
+    diff = (rs.viewmatrix, rs.projmatrix, rs.campos, points_transform)
+    if not any(torch.is_tensor(t) and t.requires_grad for t in diff):
+        raise RuntimeError("rasterize_views: nothing differentiable requires grad (points_transform, viewmatrix, projmatrix, campos): use "
+                           "forward_views for a render without a backward")
+    call = _ViewsCall()
+    call.V, call.vm, call.pm, call.cp, call.xf, call.sh_origin = _views_inputs("rasterize_views", means3D, rs, points_transform, sh_origin, sh)
+    call.params = tuple(None if t is None else t.detach() for t in params)
+    call.rs, call.raw_params = rs, bool(raw_params)
+    call.xf_shape = tuple(points_transform.shape) if points_transform is not None else None
+    call.ext = call.ctypes = None
+    N = int(means3D.shape[0])
+    Npad = (N + 127) // 128 * 128
+    color, radii, depth, alpha = _RasterizeViews.apply(rs.viewmatrix, rs.projmatrix, rs.campos, points_transform, call)
+    return color, radii.view(call.V, Npad)[:, :N], depth, alpha
 
 
 class GaussianRasterizer(nn.Module):

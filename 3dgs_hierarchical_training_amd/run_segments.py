@@ -56,11 +56,13 @@ if __package__ in (None, ""):      # executed as a script: make the oddly named 
     host_mod = importlib.import_module("3dgs_hierarchical_training_amd.host")
     stage_a = importlib.import_module("3dgs_hierarchical_training_amd.stage_a")
     cameras = importlib.import_module("3dgs_hierarchical_training_amd.cameras")
+    pose_fit = importlib.import_module("3dgs_hierarchical_training_amd.pose_fit")
 else:
     from . import cameras, densify, hierarchy, segments, sequence
     from . import host as host_mod
     from . import stage_a
     from . import pose as pose_mod
+    from . import pose_fit
     from . import train_step as ts
 
 
@@ -89,6 +91,9 @@ class HTConfig:
     phase2_iters_per_frame: List[int] = field(default_factory=lambda: [10, 10, 10])   # num_iterations_per_frame_each_level
     prune_ratio: float = 0.5                    # Ballroom.yml:44
     importance_views: int = 0                   # 0 = all of the child's frames (the reference), k = every (len/k)-th
+    eval_pose_iters: int = 0                    # evaluate(): Adam iterations of a test-time pose fit of every frame before it is rendered (pose_fit.fit_poses;
+                                                # the start is the pose the run ended with); 0 = render at the run's poses, as ever
+    eval_views_per_call: int = 1                # frames of that fit that share a launch chain (1 = frame by frame)
     importance_views_per_call: int = 1          # views of a model one launch chain of the merge's importance takes (hierarchy.group_views):
                                                 # 1 = a forward and a pass per view (default), 2..16 = gsr_importance_accumulate_views
     densify: bool = False
@@ -362,14 +367,39 @@ class RankRunner:
                     "gaussians": seg.params.num_points, "ms": 1e3 * (time.perf_counter() - t0)})
 
     def evaluate(self) -> float:
-        """Mean PSNR of the final model over its frames."""
+        """Mean PSNR of the final model over its frames.  cfg.eval_pose_iters > 0: every frame's pose is first fitted against the frozen
+        model (pose_fit.fit_poses from the pose the run ended with, cfg.eval_views_per_call frames per launch chain -- the reference's
+        test-time fit of eval_nvs); an 'eval' record carries the PSNR before and after, the PSNR after is returned.  The segment keeps
+        the poses it had."""
         seg, tot = self.seg, 0.0
         with torch.no_grad():
             for f in seg.frames:
                 img = ts.render_image(seg.params, self._settings(seg, f))[0]     # (the render-only forward: nothing kept behind the image)
                 mse = ((img - self.seq.target(f)) ** 2).mean().clamp_min(1e-12)
                 tot += float(-10.0 * torch.log10(mse))
-        return tot / len(seg.frames)
+        before = tot / len(seg.frames)
+        n = int(self.cfg.eval_pose_iters)
+        if n <= 0:
+            return before
+        t0 = time.perf_counter()
+        start = torch.stack([seg.poses[f].detach().float().cpu() for f in seg.frames])      # [F,4,4] world-to-camera
+        origin = -(start[:, :3, :3].transpose(1, 2) @ start[:, :3, 3:]).squeeze(-1)         # the cameras' centres: the SH view origin
+        ident = ts.with_sh_degree(self.seq.settings_for_pose(torch.eye(4)), seg.params.active_sh_degree)
+        M, info = pose_fit.fit_poses(seg.params.raw(), ident, torch.stack([self.seq.target(f) for f in seg.frames]), init=start.to(self.dev),
+                                     iters=n, lr=float(self.cfg.pose_lr), views_per_call=int(self.cfg.eval_views_per_call),
+                                     sh_origin=origin.to(self.dev) if seg.params.active_sh_degree > 0 else None)
+        fitted, tot = M.detach().cpu(), 0.0
+        with torch.no_grad():
+            for k, f in enumerate(seg.frames):
+                pose = torch.eye(4)
+                pose[:3] = fitted[k]
+                img = ts.render_image(seg.params, self.seq.settings_for_pose(pose))[0]
+                mse = ((img - self.seq.target(f)) ** 2).mean().clamp_min(1e-12)
+                tot += float(-10.0 * torch.log10(mse))
+        after = tot / len(seg.frames)
+        self._emit({"phase": "eval", "pose_iters": n, "views_per_call": info["views_per_call"], "launch_chains": info["launch_chains"],
+                    "psnr_before": before, "psnr_after": after, "ms": 1e3 * (time.perf_counter() - t0)})
+        return after
 
     # ---- one rank's whole run (distributed) ----------------------------------------------------------------------------
     def link_selftest(self, all_ok=None) -> bool:
@@ -415,6 +445,13 @@ def check_importance_views_per_call(cfg: HTConfig):
     n = int(cfg.importance_views_per_call)
     if not 1 <= n <= hierarchy.MAX_VIEWS_PER_CALL:
         raise ValueError(f"importance_views_per_call: 1..{hierarchy.MAX_VIEWS_PER_CALL} views share a launch chain, got {n}")
+
+
+def check_eval_pose(cfg: HTConfig):
+    """`eval_pose_iters` >= 0 and `eval_views_per_call` in 1 .. 16, refused before a device is touched."""
+    if int(cfg.eval_pose_iters) < 0:
+        raise ValueError(f"eval_pose_iters must not be negative, got {cfg.eval_pose_iters}")
+    pose_fit.check_views_per_call(int(cfg.eval_views_per_call))
 
 
 def check_leaf_batch(cfg: HTConfig, local: bool):
@@ -632,6 +669,12 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--importance-views-per-call", type=int, default=1,
                     help="views of a model that one launch chain of the merge's importance takes: 1 = a forward and a pass per view "
                          "(default); 2..16 = runs of views go through the views entry, one host wait per run")
+    ap.add_argument("--eval-pose-iters", type=int, default=0,
+                    help="fit every frame's pose against the final model for this many Adam iterations before the evaluation renders it "
+                         "(from the pose the run ended with); the PSNR before and after goes into an 'eval' record.  0 = off (default)")
+    ap.add_argument("--eval-views-per-call", type=int, default=1,
+                    help="frames of that fit that share one launch chain: 1 = frame by frame (default); 2..16 = chunks of frames through the "
+                         "views entries (one render, one loss, one backward and one pose step per chunk and iteration)")
     ap.add_argument("--densify", action="store_true")
     ap.add_argument("--pose-lr", type=float, default=None)
     ap.add_argument("--fit-pose", action="store_true", help="refine every frame's pose while training on it (the reference's "
@@ -683,6 +726,10 @@ def parse_args(argv=None):
     a = ap.parse_args(argv)
     if not 1 <= a.importance_views_per_call <= hierarchy.MAX_VIEWS_PER_CALL:
         ap.error(f"--importance-views-per-call: 1..{hierarchy.MAX_VIEWS_PER_CALL} expected, got {a.importance_views_per_call}")
+    if a.eval_pose_iters < 0:
+        ap.error(f"--eval-pose-iters: a non-negative count expected, got {a.eval_pose_iters}")
+    if not 1 <= a.eval_views_per_call <= 16:
+        ap.error(f"--eval-views-per-call: 1..16 expected, got {a.eval_views_per_call}")
     return a
 
 
@@ -695,8 +742,10 @@ def main():
     cfg = HTConfig(frames=a.frames, width=a.width, height=a.height, gt_gaussians=a.gt_gaussians, leaf_gaussians=a.leaf_gaussians,
                    leaf_iters_per_frame=a.leaf_iters, phase1_iters_per_frame=a.phase1_iters, phase2_iters_per_frame=[a.phase2_iters] * 3,
                    importance_views=a.importance_views, importance_views_per_call=a.importance_views_per_call, densify=a.densify, fit_pose=a.fit_pose, stage_a_batch=a.stage_a_batch, stage_a_lambda_depth=a.stage_a_lambda_depth, stage_a_early_exit=a.stage_a_early_exit, stage_a_init=a.stage_a_init, densify_route=a.densify_route, merge_route=a.merge_route, sh_up_every=a.sh_up_every,
-                   device_cameras=a.device_cameras, leaf_batch=a.leaf_batch)
+                   device_cameras=a.device_cameras, leaf_batch=a.leaf_batch, eval_pose_iters=a.eval_pose_iters,
+                   eval_views_per_call=a.eval_views_per_call)
     check_leaf_batch(cfg, local=a.local)
+    check_eval_pose(cfg)
     if a.pose_lr is not None:
         cfg.pose_lr = a.pose_lr
     if not torch.cuda.is_available():

@@ -383,7 +383,7 @@ int gsr_importance_accumulate(const GsrForwardArgs* fwd, const GsrForwardOut* ou
  * rendering that view alone, and the list-building routes, the early instance count, capacity hints, speculative binning and the balanced
  * placement behave as a batched forward of V images treats them.  V = 1 is served: one view through the same front.
  * forward_flags carries GSR_FWD_FLAG_VIEWS: gsr_backward and the single-view gsr_importance_accumulate refuse such flags (GSR_ERR_ARG)
- * before anything is enqueued -- there is no backward over a views forward.
+ * before anything is enqueued -- the backward over a views forward is gsr_backward_views (version 124, below), the frozen call only.
  * Refused before a device is touched, the rule in gsr_last_error(): V outside [1, 16]; a->batch set; `prepared`; `render_only`;
  * V Npad >= 2^31 (GSR_ERR_RANGE).  colors_precomp IS served by the forward.
  *
@@ -399,6 +399,27 @@ int gsr_forward_views(const GsrForwardArgs* args, int32_t V, GsrForwardOut* out,
 size_t gsr_importance_scratch_bytes_views(int32_t N, int32_t V);
 int gsr_importance_accumulate_views(const GsrForwardArgs* fwd, int32_t V, const GsrForwardOut* out, float* acc /* [N,M,3], += */,
                                     void* scratch, void* stream);
+
+/* ---- version 124: the FROZEN CALL over V views of one model (fitting V poses against a model that does not move).
+ * gsr_backward_views is the frozen call of gsr_backward (camera and transform gradients alone) over the output of a gsr_forward_views of the
+ * same N, V, cameras and transforms.  GsrBackwardArgs keeps its layout; the count travels beside it.  N is the MODEL's size;
+ *   viewmatrix / projmatrix / campos, and points_transform / sh_origin when given, are arrays of V entries, as in the forward;
+ *   grad_color is [V,3,H,W], grad_depth and grad_alpha [V,1,H,W], any subset;
+ *   geom, image, binning, num_rendered, binning_capacity and forward_flags come from the forward; scratch holds
+ *     gsr_backward_scratch_bytes_views(N, V) bytes;
+ *   outputs, any subset, at least one: d_viewmatrix [V,16], d_projmatrix [V,16], d_campos [V,3], d_points_transform [V,12]; optionally
+ *     d_means2D [V Npad,3] -- record v Npad + n is Gaussian n under view v, the rows n >= N are written as zeros.
+ * Nothing is summed across views: every view's outputs are what a single-view gsr_forward + frozen gsr_backward of that view gives, the
+ * same bits under the deterministic_backward option.  The per-Gaussian kernel reads the model's ONE set of parameter rows; a view's padding
+ * records read no parameter row.  Accepted: whatever the single-view frozen call accepts (raw or activated parameters, shs alone or shs +
+ * shs_rest, colors_precomp, cov3D_precomp, sh_origin, any D <= 3 with any stored M).  Counted once by the "frozen_backward_calls" counter.
+ * Refused with GSR_ERR_ARG before anything is enqueued or a device is touched, the rule in gsr_last_error(): V outside [1, 16];
+ * V Npad >= 2^31 (GSR_ERR_RANGE); forward_flags without GSR_FWD_FLAG_VIEWS or with the render-only flag; any per-Gaussian gradient pointer
+ * or fused_adam (a backward over views serves the frozen call only: a full backward over views is not served); next_view / prepared_out;
+ * densify_stats; retired_at; batch; no camera or transform output at all; a missing workspace pointer.  gsr_backward itself keeps refusing
+ * the flags of a views forward. */
+size_t gsr_backward_scratch_bytes_views(int32_t N, int32_t V);
+int gsr_backward_views(const GsrBackwardArgs* args, int32_t V, void* stream);
 
 const char* gsr_last_error(void);
 /* 100 * major + minor.  110 (round 6): GsrForwardArgs ends with view_id, out_color_clamped, visible (appended in round 5 under
@@ -418,7 +439,8 @@ const char* gsr_last_error(void);
  * 122: gsr_resize_plan_batched, gsr_resize_apply_batched, gsr_resize_scratch_bytes_batched (GsrResizeBatch and GsrResizeBatchTensor are
  *      new); no existing struct or entry changes.
  * 123: gsr_forward_views, gsr_geom_bytes_views, gsr_importance_accumulate_views, gsr_importance_scratch_bytes_views
- *      (GSR_FWD_FLAG_VIEWS); no struct changes. */
+ *      (GSR_FWD_FLAG_VIEWS); no struct changes.
+ * 124: gsr_backward_views, gsr_backward_scratch_bytes_views, gsr_pose_step_many; no struct changes. */
 int gsr_version(void);
 size_t gsr_struct_bytes(int32_t which); /* 0 GsrForwardArgs, 1 GsrBackwardArgs, 2 GsrForwardOut; anything else 0 */
 
@@ -652,6 +674,12 @@ int gsr_adam_step(const GsrAdamTensor* tensors, int32_t count, float beta1, floa
  * step = 0: only evaluates M for the current delta.  base12 = NULL: identity.  All pointers device; one one-thread kernel. */
 int gsr_pose_step(float* delta6, float* exp_avg6, float* exp_avg_sq6, const float* d_points_transform12, const float* base12,
                   float* points_transform_out12, float lr, float beta1, float beta2, float eps, int64_t step, void* stream);
+/* gsr_pose_step for P >= 1 independent poses in ONE launch (one 64-lane workgroup per pose): pose p lives at p * 6 floats of delta6 /
+ * exp_avg6 / exp_avg_sq6 and p * 12 floats of d_points_transform12 (as gsr_backward_views writes it), base12 ([P,12] or NULL) and
+ * points_transform_out12.  Every pose gets, bit for bit, what gsr_pose_step gives it alone, step = 0 included. */
+int gsr_pose_step_many(float* delta6, float* exp_avg6, float* exp_avg_sq6, const float* d_points_transform12,
+                       const float* base12 /* [P,12] or NULL */, float* points_transform_out12, int32_t P, float lr, float beta1, float beta2,
+                       float eps, int64_t step, void* stream);
 
 /* The chain of gsr_pose_step alone (round 6): d_delta6_out = dL/d(delta) of M = Exp(delta) * base given dL/dM
  * (d_points_transform12, as written by gsr_backward), nothing updated.  It is the backward of the autograd node that stands where the
